@@ -35,11 +35,23 @@ Other workloads (one JSON line each, same keys):
   --config 5share  one GPU's share of configs[4]: the 64-term wide statement, 32,768 proofs per step (prove + batch verify)
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4share|5share] [--batch n] [--batches-per-call K] [--streams S]
+                  [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 
-Prints ONE JSON line (rank 0).  Everything in it is measured in this run, except the PMC-derived fields (roofline.traffic,
-*_valu_busy, step_valu), which need a rocprofv3 --pmc pass: they are taken from --pmc-json only when that file was
-collected from exactly these kernel sources (sha256 of zkp_amd/csrc), and say so in "pmc_source"; otherwise they are null.
+Prints ONE JSON line (rank 0).  A plain run does what the headline needs and nothing else: set-up, warm-up, the --steps timed
+steps, the checks that every timed batch verified, and the line (metric, value, unit, ms_per_step, higher_is_better, dtype,
+the workload's shape).  --full adds everything else the line used to carry: the single-flow lines, per-kernel HIP-event timing
+and the roofline, the tampered-proof check, e2e_host_buffers, lone_call, sustained, ct, the multi-GPU sub-records and the CPU
+baseline with its parity check against the oracle.  Everything in it is measured in this run, except the PMC-derived fields
+(roofline.traffic, *_valu_busy, step_valu), which need a rocprofv3 --pmc pass: they are taken from --pmc-json only when that
+file was collected from exactly these kernel sources (sha256 of zkp_amd/csrc), and say so in "pmc_source"; otherwise they are null.
+
+--dump-outputs DIR: after the timed steps, what the last timed step handed back, as DIR/<name>.npy (float32, one element per byte of a
+challenge, response, commitment or verdict; statuses and sample indices float64): per part of the workload the proofs of the last batch where the step
+proves (challenges, responses, commitments, prove_status) and that batch's verdict where it batch-verifies (batch_check = the
+identity test's 32 bytes, zero when the batch verified; batch_status).  At most OUTPUT_BUDGET bytes in all: a larger batch is
+represented by a fixed, seeded sample of its proofs (<part>sample_rows.npy holds their indices).  The inputs depend on the
+arguments alone (numpy default_rng(seed + rank)), so two builds can be compared output for output.
 """
 import argparse
 import datetime
@@ -378,6 +390,57 @@ def init_distributed(world, rank, local_rank):
     return dist, group, info
 
 
+OUTPUT_BUDGET = 60 * 10 ** 6   # --dump-outputs: bytes of array data in all (under 64 MB with the .npy headers)
+OUTPUT_SAMPLE_SEED = 7
+
+
+def sample_rows(n, row_bytes, budget):
+    """the proofs of a batch --dump-outputs writes: None (all n) when they fit the budget, else the sorted indices of a fixed, seeded
+    sample of as many as fit"""
+    import numpy as np
+    fit = max(1, budget // max(1, row_bytes))
+    if n <= fit:
+        return None
+    return np.sort(np.random.default_rng(OUTPUT_SAMPLE_SEED).choice(n, size=fit, replace=False))
+
+
+def last_step_outputs(ps, k, K, prefixed):
+    """what the last timed step (batch K - 1 of the call chain on stream k) handed back, per part of the workload, as host arrays:
+    float32 bytes of the proofs and of the identity test, float64 statuses and sample indices"""
+    import numpy as np
+    import torch
+    f32 = lambda x: x.cpu().numpy().astype(np.float32)
+    f64 = lambda x: x.cpu().numpy().astype(np.float64)
+    budget = (OUTPUT_BUDGET - (64 << 10)) // len(ps)   # (room for the verdicts)
+    out = {}
+    for i, p in enumerate(ps):
+        pre = "part%d_" % i if prefixed else ""
+        b = p.bufs[k]
+        if "prove" in p.flows:
+            lo = (K - 1) * p.n_each
+            rows = sample_rows(p.n_each, 4 * 32 * (1 + p.m + p.nc) + 8 * (p.nc + 1), budget)
+            sel = slice(lo, lo + p.n_each) if rows is None else torch.from_numpy(rows.astype(np.int64) + lo).to(b["chal"].device)
+            out[pre + "challenges"] = f32(b["chal"][sel])
+            out[pre + "responses"] = f32(b["resp"][sel])
+            out[pre + "commitments"] = f32(b["coms"][sel])
+            out[pre + "prove_status"] = f64(b["st"].view(p.n, p.nc)[sel])
+            if rows is not None:
+                out[pre + "sample_rows"] = rows.astype(np.float64)
+        if "batch_verify" in p.flows:
+            out[pre + "batch_check"] = f32(b["out"][K - 1])
+            out[pre + "batch_status"] = f64(b["bst"][K - 1])
+    return out
+
+
+def write_outputs(d, outputs):
+    """--dump-outputs: one DIR/<name>.npy per array"""
+    import numpy as np
+    assert sum(a.nbytes for a in outputs.values()) <= OUTPUT_BUDGET
+    os.makedirs(d, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 class Ctx:
     """what every workload of a run shares: the rank's device, the process groups"""
     pass
@@ -578,9 +641,10 @@ def run_workload(cx, args, cfg, n, steps, warmup, K, n_streams, primary):
             if "batch_verify" in p.flows:
                 assert batches_ok(b), "a batch of fresh proofs did not verify"
         assert all(bool((b["chal"] == p.bufs[0]["chal"]).all().item()) and bool((b["resp"] == p.bufs[0]["resp"]).all().item()) for b in p.bufs), "streams disagree"
+    outputs = last_step_outputs(ps, (calls - 1) % n_streams, K, len(ps) > 1) if primary and args.dump_outputs else None
     # the proofs must be REAL proofs: a flipped response bit makes its batch check fail -- and only that one
     for p in ps:
-        if "batch_verify" not in p.flows:
+        if "batch_verify" not in p.flows or not args.full:
             continue
         b = p.bufs[0]
         kb = p.K // 2
@@ -599,8 +663,8 @@ def run_workload(cx, args, cfg, n, steps, warmup, K, n_streams, primary):
 
     total_n = sum(p.n_each for p in ps)                # proofs per step
     res = {"elapsed": elapsed, "own_elapsed": own_elapsed, "ms_per_step": elapsed * 1e3 / steps, "value": world * total_n * steps / elapsed,
-           "host_enqueue_ms_per_step": t_enqueued * 1e3 / steps, "streams": n_streams, "ps": ps, "total_n": total_n}
-    if not primary:
+           "host_enqueue_ms_per_step": t_enqueued * 1e3 / steps, "streams": n_streams, "ps": ps, "total_n": total_n, "outputs": outputs}
+    if not primary or not args.full:
         for e_ in engines:
             e_.close()
         return res
@@ -902,6 +966,10 @@ def main():
     ap.add_argument("--sustained-steps", type=int, default=4000, help="steps of the `sustained` sub-record (a multiple of 50: >= 2 s of GPU time at the default)")
     ap.add_argument("--engine-opt", action="append", default=[], metavar="ID=VALUE",
                     help="zkp_ctx_set_option(ID, VALUE) on every engine context (tuning experiments; results never depend on it)")
+    ap.add_argument("--full", action="store_true", help="also run every measurement and check beyond the headline figure (single-flow lines, per-kernel timing and "
+                    "roofline, tampered-proof check, e2e_host_buffers, lone_call, sustained, ct, multi-GPU sub-records, CPU baseline and oracle parity); "
+                    "the --no-* options above apply to these")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "RANK" not in os.environ and not args.in_process:
@@ -1016,6 +1084,20 @@ def rank_main(args, desc, n, K, n_streams, rank_, local_rank_, world_, thread_gr
     rank, world, dist = cx.rank, cx.world, cx.dist
 
     r = run_workload(cx, args, args.config, n, args.steps, args.warmup, K, n_streams, primary=True)
+    user_lookup = next((int(kv.split("=")[1]) for kv in args.engine_opt if int(kv.split("=")[0]) == 9), 0)
+    if not args.full:
+        # a plain run: the headline figure alone (--full measures and checks the rest)
+        if rank == 0:
+            out = headline(args, desc, n, K, r, dinfo, user_lookup, world)
+            out["source_sha256"] = source_sha256()
+            if user_lookup in (0, 1):
+                out["value_ct_by_construction"] = r["value"]
+            if args.dump_outputs:
+                write_outputs(args.dump_outputs, r["outputs"])
+            print(json.dumps(out))
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     ps, kms, flow_lines, total_n = r["ps"], r["kms"], r["flow_lines"], r["total_n"]
     eng = r["engines"][0]
 
@@ -1046,7 +1128,6 @@ def rank_main(args, desc, n, K, n_streams, rank_, local_rank_, world_, thread_gr
         torch.cuda.empty_cache()
     # ---- what the short timed region cannot show, under the same clock: the steady-state rate, and the same steps on the other look-ups ----
     sustained, ct = None, None
-    user_lookup = next((int(kv.split("=")[1]) for kv in args.engine_opt if int(kv.split("=")[0]) == 9), 0)
     if args.config == "2" and not args.no_sustained and not args.no_flow_lines:
         import copy
         torch.cuda.empty_cache()
@@ -1238,24 +1319,12 @@ def rank_main(args, desc, n, K, n_streams, rank_, local_rank_, world_, thread_gr
                                              "the chip's VALU issue slots in the timed region that executed a multiplication's product; peak = every SIMD issuing a mad every slot at 2.4 GHz"}
         except Exception:                       # noqa: BLE001 -- a reported extra, never the measurement
             pmc_source = None
-    out = {
-        "metric": METRIC, "value": value, "unit": "proofs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32x9 (29-bit limbs, u64 accumulate)",
-        "data": "synthetic", "seed": 1000,                                      # numpy default_rng(seed + rank) drives every witness, point, entropy and weight
-        "config": {"workload": desc % n, "baseline_config": args.config, "w64_form": args.w64_form if args.config == "5share" else None, "batch_per_gpu": n, "batches_per_call": K, "calls": args.steps // K,
-                   "streams": r["streams"], "hip_graphs": not args.no_graphs,
-                   "ct_schedule": CT_SCHEDULES[user_lookup],
-                   "gpu_max_hw_queues": int(os.environ["GPU_MAX_HW_QUEUES"]), "sharding": "independent proof ranges per GPU, AND of verdict bits",
-                   "collective": dinfo["collective"], "backend_world_size": dinfo["backend_world_size"],
-                   "excluded_from_value": "per-proof entropy (prover.rs:82 thread_rng) and batch weights (batch_verifier.rs:179) are fixed arrays resident in HBM, "
-                                          "so every step re-proves the same proofs; host-side RNG / weight generation is not timed (see e2e_host_buffers)"},
-        "host_enqueue_ms_per_step": r["host_enqueue_ms_per_step"],
+    out = headline(args, desc, n, K, r, dinfo, user_lookup, world)
+    out.update({
         "pipelined_proofs_per_s": flow_lines,                                   # same loop, one flow only
         "single_stream_proofs_per_s": {f: world * K * sum(p.n_each for p in ps if f in ("verify_compact", "verify_batchable") or f in p.flows) / (kms[f]["total"] * 1e-3) for f in kms},
         "kernel_ms_per_call": kms, "roofline": roof, "pmc_source": pmc_source, "source_sha256": sha,
-    }
-    if dinfo.get("rccl_error"):
-        out["config"]["rccl_error"] = dinfo["rccl_error"]
+    })
     if step_valu:
         out["step_valu"] = step_valu
     if roof_valu:
@@ -1304,9 +1373,31 @@ def rank_main(args, desc, n, K, n_streams, rank_, local_rank_, world_, thread_gr
         assert equal, "GPU proofs differ from the oracle's"
         if args.config == "2":
             out["cpu_baseline_all_cores"] = cpu_baseline_all_cores()
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, r["outputs"])
     print(json.dumps(out))
     if dist is not None:
         dist.destroy_process_group()
+
+
+def headline(args, desc, n, K, r, dinfo, user_lookup, world):
+    """the keys of the JSON line that a plain run and a --full run share: the headline figure and the workload's shape"""
+    out = {
+        "metric": METRIC, "value": r["value"], "unit": "proofs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": r["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32x9 (29-bit limbs, u64 accumulate)",
+        "data": "synthetic", "seed": 1000,                                      # numpy default_rng(seed + rank) drives every witness, point, entropy and weight
+        "config": {"workload": desc % n, "baseline_config": args.config, "w64_form": args.w64_form if args.config == "5share" else None, "batch_per_gpu": n, "batches_per_call": K, "calls": args.steps // K,
+                   "streams": r["streams"], "hip_graphs": not args.no_graphs,
+                   "ct_schedule": CT_SCHEDULES[user_lookup],
+                   "gpu_max_hw_queues": int(os.environ["GPU_MAX_HW_QUEUES"]), "sharding": "independent proof ranges per GPU, AND of verdict bits",
+                   "collective": dinfo["collective"], "backend_world_size": dinfo["backend_world_size"],
+                   "excluded_from_value": "per-proof entropy (prover.rs:82 thread_rng) and batch weights (batch_verifier.rs:179) are fixed arrays resident in HBM, "
+                                          "so every step re-proves the same proofs; host-side RNG / weight generation is not timed (see e2e_host_buffers)"},
+        "host_enqueue_ms_per_step": r["host_enqueue_ms_per_step"],
+    }
+    if dinfo.get("rccl_error"):
+        out["config"]["rccl_error"] = dinfo["rccl_error"]
+    return out
 
 
 def cpu_baseline(ps, label, sample):

@@ -73,3 +73,41 @@ def test_workload_table_is_consistent():
             secrets, points, cons = st_fn()
             assert all(f in ("prove", "batch_verify") for f in flows) and len(cons) >= 1
             assert sum(1 for _, c in points if c) <= 64          # every common point gets a fixed-base table slot
+
+
+def test_dump_sample_is_fixed_and_fits_the_budget():
+    """--dump-outputs: a batch too large for the budget is written as a fixed, seeded sample of its proofs"""
+    row = 4 * 32 * (1 + 21 + 11) + 8 * (11 + 1)                     # one CMZ proof as float32, its statuses and its sample index
+    assert bench.sample_rows(4096, row, bench.OUTPUT_BUDGET) is None
+    a = bench.sample_rows(1 << 19, row, bench.OUTPUT_BUDGET)
+    assert a is not None and (a == bench.sample_rows(1 << 19, row, bench.OUTPUT_BUDGET)).all()
+    assert len(a) * row <= bench.OUTPUT_BUDGET and (np.diff(a) > 0).all() and 0 <= a[0] and a[-1] < 1 << 19
+
+
+def test_last_step_outputs_take_the_last_batch_of_the_call(monkeypatch):
+    """the arrays --dump-outputs writes are the proofs and the verdict of batch K - 1 of the call chain named, as float32 / float64, within
+    the budget (here shrunk so that the batch is sampled)"""
+    import torch
+
+    class P:
+        pass
+    K, n_each, m, nc = 3, 500, 2, 3
+    p = P()
+    p.flows, p.n_each, p.n, p.m, p.nc = ("prove", "batch_verify"), n_each, K * n_each, m, nc
+    row = torch.arange(p.n, dtype=torch.int64) % 251
+    mk = lambda *shape: row.reshape((p.n,) + (1,) * len(shape)).expand((p.n,) + shape).to(torch.uint8).contiguous()
+    good = dict(chal=mk(32), resp=mk(m, 32), coms=mk(nc, 32), st=mk(nc).reshape(-1), out=torch.zeros((K, 32), dtype=torch.uint8),
+                bst=torch.zeros((K, 2), dtype=torch.int32))
+    other = {k: torch.full_like(v, 7) for k, v in good.items()}
+    p.bufs = [other, good]
+    full = bench.last_step_outputs([p], 1, K, False)
+    assert sorted(full) == ["batch_check", "batch_status", "challenges", "commitments", "prove_status", "responses"]
+    want = (np.arange((K - 1) * n_each, K * n_each) % 251).astype(np.float32)
+    assert full["challenges"].dtype == np.float32 and full["challenges"].shape == (n_each, 32) and (full["challenges"] == want[:, None]).all()
+    assert full["responses"].shape == (n_each, m, 32) and full["commitments"].shape == (n_each, nc, 32) and full["prove_status"].shape == (n_each, nc)
+    assert full["batch_status"].dtype == np.float64 and not full["batch_check"].any()
+    monkeypatch.setattr(bench, "OUTPUT_BUDGET", (64 << 10) + 20000)
+    small = bench.last_step_outputs([p], 1, K, False)
+    rows = small["sample_rows"].astype(np.int64)
+    assert 0 < len(rows) < n_each and sum(a.nbytes for a in small.values()) <= bench.OUTPUT_BUDGET
+    assert (small["responses"][:, 1, 5] == want[rows]).all()

@@ -90,7 +90,7 @@ def test_bench_eight_rank_control_flow_on_one_gpu():
     env.pop("GPU_MAX_HW_QUEUES", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=8", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "4", "--warmup", "1",
-           "--batch", "256", "--batches-per-call", "2", "--streams", "2", "--no-flow-lines", "--multi-total4", "2048", "--multi-total5", "1024"]
+           "--batch", "256", "--batches-per-call", "2", "--streams", "2", "--full", "--no-flow-lines", "--multi-total4", "2048", "--multi-total5", "1024"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -120,7 +120,7 @@ def test_bench_in_process_multi_gpu_control_flow_on_one_gpu():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--in-process", "--steps", "4", "--warmup", "1", "--batch", "256", "--batches-per-call", "2",
-           "--streams", "2", "--multi-total4", "1536", "--multi-total5", "768", "--no-cpu-baseline"]
+           "--streams", "2", "--full", "--multi-total4", "1536", "--multi-total5", "768", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

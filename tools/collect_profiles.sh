@@ -12,7 +12,7 @@ export TMPDIR=/tmp
 O=gpurun_out
 S=${TAG}_cfg${CFG}
 mkdir -p $O
-B="python bench.py --config $CFG --steps $STEPS --warmup 1 --no-cpu-baseline --no-flow-lines $*"
+B="python bench.py --full --config $CFG --steps $STEPS --warmup 1 --no-cpu-baseline --no-flow-lines $*"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${S}_prof -o kt -- $B > $O/${S}_kt.log 2>&1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/${S}_prof -o fetch -- $B > $O/${S}_fetch.log 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/${S}_prof -o write -- $B > $O/${S}_write.log 2>&1

@@ -15,7 +15,7 @@ cp $O/r06_pmc_counters_cfg*.json profiles/
 # latency schedule's two streams show as one chain -- its concurrent timing is lone_call.latency_schedule of the bench line)
 for sched in throughput latency; do
   opt=""; [ $sched = latency ] && opt="--engine-opt 5=2"
-  B="python bench.py --config 2 --steps 20 --warmup 2 --no-cpu-baseline --no-flow-lines --no-sustained --streams 1 --max-hw-queues 1 --batches-per-call 1 $opt"
+  B="python bench.py --full --config 2 --steps 20 --warmup 2 --no-cpu-baseline --no-flow-lines --no-sustained --streams 1 --max-hw-queues 1 --batches-per-call 1 $opt"
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/r06_k1_prof -o k1 -- $B > $O/r06_k1_$sched.log 2>&1
   python - <<PY > $O/r06_kernel_stats_cfg2_k1_${sched}_schedule_one_stream.txt
 import csv, sys
@@ -33,7 +33,7 @@ done
 bash tools/x/sync_call_timeline.sh > $O/r06_sync_call_timeline.txt 2>&1
 # the pipe against the resident loop
 rocprofv3 --hip-trace --kernel-trace --memory-copy-trace --output-format csv -d $O/r06_gap_pipe -o p -- python tools/e2e_pipe_bench.py --shapes 10x6 --order pinned --jobs 36 > $O/r06_gap_pipe.log 2>&1
-rocprofv3 --hip-trace --kernel-trace --memory-copy-trace --output-format csv -d $O/r06_gap_res -o r -- python bench.py --steps 200 --batches-per-call 5 --streams 4 --warmup 2 --no-cpu-baseline --no-flow-lines --no-sustained > $O/r06_gap_res.log 2>&1
+rocprofv3 --hip-trace --kernel-trace --memory-copy-trace --output-format csv -d $O/r06_gap_res -o r -- python bench.py --full --steps 200 --batches-per-call 5 --streams 4 --warmup 2 --no-cpu-baseline --no-flow-lines --no-sustained > $O/r06_gap_res.log 2>&1
 python tools/pipe_gap_trace.py $O/r06_gap_pipe $O/r06_gap_res > $O/r06_pipe_gap_trace.txt 2>&1
 rm -rf $O/r06_gap_pipe $O/r06_gap_res
 # Keccak-f[1600] on a lone wavefront: the shipped lane-pair layout, unrolled, and one word per lane over the crossbar
@@ -50,12 +50,12 @@ rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_VALU_INT64 SQ_ACTIVE_INST_
 python tools/verify_compact_profile.py --summarise $(ls $O/r06_vc/*vc_kernel_trace.csv | head -1) $(ls $O/r06_vc/*vcp_counter_collection.csv | head -1) > $O/r06_verify_compact_accounting.txt 2>&1
 rm -rf $O/r06_vc
 python tools/e2e_toolbox_bench.py 4096 16384 > $O/r06_e2e_toolbox_host_included.txt 2>&1
-python bench.py --steps 20 --warmup 5 > $O/r06_bench_1gpu_steps20.json 2> $O/err1.log
-python bench.py > $O/r06_bench_1gpu.json 2> $O/err2.log
-python bench.py --config 3 > $O/r06_bench_cfg3.json 2> $O/err3.log
-python bench.py --config 4share > $O/r06_bench_cfg4share.json 2> $O/err4.log
-python bench.py --config 5share > $O/r06_bench_cfg5share.json 2> $O/err5.log
-python bench.py --config 5share --w64-form constraints --no-cpu-baseline > $O/r06_bench_cfg5share_constraints.json 2> $O/err6.log
+python bench.py --full --steps 20 --warmup 5 > $O/r06_bench_1gpu_steps20.json 2> $O/err1.log
+python bench.py --full > $O/r06_bench_1gpu.json 2> $O/err2.log
+python bench.py --full --config 3 > $O/r06_bench_cfg3.json 2> $O/err3.log
+python bench.py --full --config 4share > $O/r06_bench_cfg4share.json 2> $O/err4.log
+python bench.py --full --config 5share > $O/r06_bench_cfg5share.json 2> $O/err5.log
+python bench.py --full --config 5share --w64-form constraints --no-cpu-baseline > $O/r06_bench_cfg5share_constraints.json 2> $O/err6.log
 tail -2 $O/err*.log | grep -v "^$" | head -20
 python - <<'PY'
 import json

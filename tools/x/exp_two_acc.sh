@@ -7,7 +7,7 @@ cp zkp_amd/libzkp_mi355x.so /tmp/shipped.so
 cp tools/x/variants/libzkp_two_acc.so zkp_amd/libzkp_mi355x.so
 echo "== parity with the variant library"
 python -m pytest tests/test_gpu_toolbox.py tests/test_gpu_device_entry.py tests/test_gpu_fused.py tests/test_gpu_fullsize.py -m gpu -x -q 2>&1 | tail -3
-B="python bench.py --no-cpu-baseline --no-flow-lines"
+B="python bench.py --full --no-cpu-baseline --no-flow-lines"
 val() { $B "$@" 2>/dev/null | tail -1 | python -c "import json,sys; j=json.loads(sys.stdin.read()); k=j['kernel_ms_per_call']['prove']; print('%.3f M/s   lone prove call: terms %.3f ms, total %.3f ms' % (j['value']/1e6, k['terms'], k['total']))"; }
 for r in 1 2 3; do
   cp /tmp/shipped.so zkp_amd/libzkp_mi355x.so;                       echo "shipped  20: $(val --steps 20 --warmup 5)";  echo "shipped 200: $(val --steps 200)"

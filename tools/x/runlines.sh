@@ -9,7 +9,7 @@ for r in $(seq 1 $R); do
   while IFS='|' read -r label args; do
     [ -z "$label" ] && continue
     case "$label" in \#*) continue;; esac
-    line=$(timeout 300 python bench.py --no-cpu-baseline --no-flow-lines $args 2>gpurun_out/runlines_err.log | tail -1 | python -c "
+    line=$(timeout 300 python bench.py --full --no-cpu-baseline --no-flow-lines $args 2>"$OUT.err" | tail -1 | python -c "
 import json,sys
 try:
     j=json.loads(sys.stdin.read())
@@ -20,6 +20,6 @@ except Exception as e:
     print('ERR', e)
 ")
     echo "$label |$args | $line" | tee -a $OUT
-    if echo "$line" | grep -q ERR; then tail -3 gpurun_out/runlines_err.log | tee -a $OUT; fi
+    if echo "$line" | grep -q ERR; then tail -3 "$OUT.err" | tee -a $OUT; fi
   done < $IN
 done
