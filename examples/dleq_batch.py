@@ -5,6 +5,7 @@
 
 Everything that is arithmetic -- transcripts included for batches of 32 proofs or more -- runs on the GPU behind the C ABI
 of include/zkp_mi355x.h; this script only prepares inputs and checks verdicts.  Needs a gfx950 device.
+H = s G with a random s keeps the example short; a real DLEQ / VRF hashes H so that nobody knows log_G(H): examples/vrf_batch.py.
 
     python examples/dleq_batch.py [N]"""
 import hashlib

@@ -441,6 +441,21 @@ int zkp_decode_check(zkp_ctx* ctx, uint64_t n, const uint8_t* points /*[n][32]*/
  *     32-byte little-endian field element (need not be reduced below p, bit 255 ignored). */
 int zkp_encode_many(zkp_ctx* ctx, uint64_t n, const uint8_t* xyzt /*[n][128]*/, uint8_t* out /*[n][32]*/);
 
+/* (5) Hash to the group, batched: RFC 9496 section 4.3.4 FROM_UNIFORM_BYTES, which is curve25519-dalek's
+ *     `RistrettoPoint::from_uniform_bytes` (and, behind SHA-512 on the host, `hash_from_bytes::<Sha512>`).  out[i] = the
+ *     canonical encoding of the map of in[i].  Each 32-byte half is read little-endian with bit 255 cleared and need not be
+ *     below p.  The map never fails: there is no status.  Constant time: no branch or address depends on the input.
+ *     n = 0 is a no-op; a NULL buffer with n > 0 is ZKP_ERR_ARG; at most 2^31 - 1 outputs per call.  Timed under ZKP_K_DECODE.
+ *     zkp_from_uniform_bytes takes host pointers and synchronises; zkp_from_uniform_bytes_dev takes device pointers (16-byte
+ *     aligned), enqueues on the context's stream without synchronising, and may be recorded between zkp_ctx_capture_begin / _end. */
+int zkp_from_uniform_bytes(zkp_ctx* ctx, uint64_t n, const uint8_t* in /*[n][64]*/, uint8_t* out /*[n][32]*/);
+int zkp_from_uniform_bytes_dev(zkp_ctx* ctx, uint64_t n, const uint8_t* d_in /*[n][64]*/, uint8_t* d_out /*[n][32]*/);
+/*     N x { transcript.challenge_bytes(label, 64) ; from_uniform_bytes }, the `hash_to_group` of the reference's VRF example
+ *     (tests/sig_and_vrf_example.rs:36-40), with the transcripts on the device: all N blobs must stand at one STROBE position
+ *     (ZKP_ERR_ARG otherwise), and they are advanced in place exactly as merlin advances them.  Host pointers, synchronous.
+ *     The squeeze is timed under ZKP_K_TRANSCRIPT, the map under ZKP_K_DECODE. */
+int zkp_fused_hash_to_group(zkp_ctx* ctx, uint32_t N, uint8_t* transcripts /*[N][208]*/, const char* label, uint8_t* out /*[N][32]*/);
+
 /* Timing of the last *_dev / host call on this context, measured with HIP events on the stream the
  * kernels were launched on.  kernel_ms[] is indexed by ZKP_K_*; returns the number of entries. */
 enum {

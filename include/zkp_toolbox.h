@@ -248,6 +248,17 @@ void zkp_toolbox_set_host_max_terms(uint32_t n);
 uint32_t zkp_toolbox_get_host_max_terms(void);
 uint32_t zkp_toolbox_get_fused_min_batch(void);
 
+/* Hash to the group (RFC 9496 section 4.3.4; zkp_mi355x.h (5)).
+ * zkp_from_uniform_bytes_batch: n x RistrettoPoint::from_uniform_bytes, in [n][64] -> canonical encodings out [n][32].  ctx == NULL or
+ *   n <= zkp_toolbox_get_host_max_terms() runs on the host backend (n_threads threads), anything else on the device.
+ * zkp_hash_to_group_batch: N x { transcript.challenge_bytes(label, 64) ; from_uniform_bytes } -- the `hash_to_group` of
+ *   tests/sig_and_vrf_example.rs:36-40 -- with the transcripts [N][208] advanced in place as merlin advances them.  With a context, batches
+ *   of at least fused_min_batch transcripts that stand at one STROBE position squeeze on the device (zkp_fused_hash_to_group); the others
+ *   squeeze on the host threads and map as zkp_from_uniform_bytes_batch does.  Same bytes on every route.
+ * Both: n = 0 is a no-op; a NULL buffer (with n > 0) or a NULL label is ZKP_TB_BAD_STATEMENT; the map never fails. */
+int zkp_from_uniform_bytes_batch(zkp_ctx* ctx, uint64_t n, const uint8_t* in /*[n][64]*/, int n_threads, uint8_t* out /*[n][32]*/);
+int zkp_hash_to_group_batch(zkp_ctx* ctx, uint32_t N, uint8_t* transcripts /*[N][208]*/, const char* label, int n_threads, uint8_t* out /*[N][32]*/);
+
 /* The ChaCha20 block function (RFC 8439 section 2.3; state words 12-13 = counter, 14-15 = nonce) behind the default
  * entropy / weights of the calls above (`entropy == NULL`, `weights16 == NULL`): like the reference's `thread_rng()`, a
  * ChaCha stream keyed from the operating system.  Exposed for the known-answer test. */

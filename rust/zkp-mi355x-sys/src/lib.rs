@@ -187,6 +187,10 @@ extern "C" {
     // ---- (3), (4) stand-alone codec: verifier.rs:87-92, mod.rs:180 -------------------------------------------------------
     pub fn zkp_decode_check(ctx: *mut zkp_ctx, n: u64, points: *const u8, status: *mut u8, xyzt: *mut u8) -> c_int;
     pub fn zkp_encode_many(ctx: *mut zkp_ctx, n: u64, xyzt: *const u8, out: *mut u8) -> c_int;
+    // ---- (5) hash to the group: RistrettoPoint::from_uniform_bytes (RFC 9496 4.3.4), sig_and_vrf_example.rs:36-40 --------
+    pub fn zkp_from_uniform_bytes(ctx: *mut zkp_ctx, n: u64, input: *const u8, out: *mut u8) -> c_int;
+    pub fn zkp_from_uniform_bytes_dev(ctx: *mut zkp_ctx, n: u64, d_in: *const u8, d_out: *mut u8) -> c_int;
+    pub fn zkp_fused_hash_to_group(ctx: *mut zkp_ctx, n: u32, transcripts: *mut u8, label: *const c_char, out: *mut u8) -> c_int;
     pub fn zkp_ctx_last_timing(ctx: *mut zkp_ctx, kernel_ms: *mut f32, total_ms: *mut f32) -> c_int;
     pub fn zkp_ctx_last_kernels(ctx: *mut zkp_ctx, kind: c_int, buf: *mut c_char, cap: usize) -> c_int;
     pub fn zkp_ctx_set_profiling(ctx: *mut zkp_ctx, enabled: c_int) -> c_int;
@@ -281,6 +285,9 @@ extern "C" {
     pub fn zkp_toolbox_get_host_max_terms() -> u32;
     pub fn zkp_toolbox_set_fused_min_batch(n: u32);
     pub fn zkp_toolbox_get_fused_min_batch() -> u32;
+    // hash to the group on the host backend (ctx NULL or n <= host_max_terms) or the device
+    pub fn zkp_from_uniform_bytes_batch(ctx: *mut zkp_ctx, n: u64, input: *const u8, n_threads: c_int, out: *mut u8) -> c_int;
+    pub fn zkp_hash_to_group_batch(ctx: *mut zkp_ctx, n: u32, transcripts: *mut u8, label: *const c_char, n_threads: c_int, out: *mut u8) -> c_int;
     pub fn zkp_chacha20_block(key: *const u8, counter: u64, nonce: u64, out: *mut u8);
     // ---- proof wire format (proofs.rs:14-32 under bincode 1.x) ------------------------------------------------------------
     pub fn zkp_proof_compact_size(m: u32) -> usize;

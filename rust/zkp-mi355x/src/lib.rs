@@ -120,6 +120,38 @@ pub mod multiscalar {
     }
 }
 
+/// Hashing to the group, batched (`zkp_toolbox.h`; RFC 9496 section 4.3.4).  `engine = None` runs on the host backend.
+pub mod hash_to_group {
+    use super::*;
+
+    fn ctx(engine: Option<&Engine>) -> *mut sys::zkp_ctx {
+        engine.map_or(ptr::null_mut(), |e| e.0)
+    }
+
+    /// `RistrettoPoint::from_uniform_bytes(&wide[i]).compress()` for every i (the map never fails).
+    pub fn from_uniform_bytes(engine: Option<&Engine>, wide: &[[u8; 64]]) -> Result<Vec<CompressedRistretto>, Error> {
+        let flat: Vec<u8> = wide.iter().flat_map(|w| w.iter().copied()).collect();
+        let mut out = vec![0u8; 32 * wide.len()];
+        check(unsafe { sys::zkp_from_uniform_bytes_batch(ctx(engine), wide.len() as u64, flat.as_ptr(), 0, out.as_mut_ptr()) })?;
+        Ok(out.chunks(32).map(|c| { let mut b = [0u8; 32]; b.copy_from_slice(c); CompressedRistretto(b) }).collect())
+    }
+
+    /// The VRF example's `hash_to_group` (tests/sig_and_vrf_example.rs:36-40) for every transcript: `challenge_bytes(label, 64)`, then
+    /// `from_uniform_bytes`.  The transcripts are advanced as merlin advances them.
+    pub fn hash_to_group(engine: Option<&Engine>, transcripts: &mut [Transcript], label: &[u8]) -> Result<Vec<CompressedRistretto>, Error> {
+        let label = CString::new(label).map_err(|_| Error::Shape("label must not contain NUL bytes"))?;
+        let mut flat: Vec<u8> = transcripts.iter().flat_map(|t| t.0.iter().copied()).collect();
+        let mut out = vec![0u8; 32 * transcripts.len()];
+        check(unsafe {
+            sys::zkp_hash_to_group_batch(ctx(engine), transcripts.len() as u32, flat.as_mut_ptr(), label.as_ptr(), 0, out.as_mut_ptr())
+        })?;
+        for (t, s) in transcripts.iter_mut().zip(flat.chunks(sys::ZKP_TRANSCRIPT_BYTES)) {
+            t.0.copy_from_slice(s);
+        }
+        Ok(out.chunks(32).map(|c| { let mut b = [0u8; 32]; b.copy_from_slice(c); CompressedRistretto(b) }).collect())
+    }
+}
+
 /// A Merlin transcript as the 208-byte state the C ABI works on (merlin keeps its fields private, so the state machine
 /// lives on the C side: `zkp_transcript_*` are byte-identical to merlin 2.x -- Merlin's published test vector is a test).
 #[derive(Clone)]

@@ -1696,4 +1696,54 @@ int zkp_fused_verify_batchable_dev(zkp_ctx* c, const zkp_fused_statement* st, ui
   return each_core(c, *pl, o, d_transcripts, d_table, d_responses, d_weights16, d_results, /*overlap=*/c->dev_overlap);
 }
 
+// ---- hash to the group: N x { challenge_bytes(label, 64) ; from_uniform_bytes } -----------------------------------------
+// A one-step transcript program (nothing but the squeeze, compiled per call: a few dozen operations) writes the 64-byte strings
+// to the workspace, and k_from_uniform maps them there.  The program has no SAVE / RESTORE and no identity check, so the
+// interpreter touches neither clone slots nor rejection flags (both NULL).
+int zkp_fused_hash_to_group(zkp_ctx* c, uint32_t N, uint8_t* transcripts, const char* label, uint8_t* out) {
+  if (!c) return fail(ZKP_ERR_ARG, "ctx is NULL");
+  if (N == 0) return ZKP_OK;
+  if (!transcripts || !label || !out) return fail(ZKP_ERR_ARG, "NULL pointer");
+  if (N > 0x7fffffffu) return fail(ZKP_ERR_ARG, "N too large");
+  uint32_t pos = 0;
+  int rc = common_tail(transcripts, N, &pos);
+  if (rc) return rc;
+  TrCompiler tc((uint8_t)pos, (uint8_t)(pos >> 8), (uint8_t)(pos >> 16));
+  tc.challenge_bytes(label, tr_ref{0, 64, 0}, 64);
+  uint8_t tail[3];
+  const std::vector<tr_op> ops = tc.finish(tail);
+  const std::vector<uint64_t>& tables = tc.tables();
+  HIP_TRY(hipSetDevice(c->device));
+  carve cv;
+  const size_t o_ts = cv.take((size_t)N * 208);
+  const size_t o_wide = cv.take((size_t)N * 64);
+  const size_t o_out = cv.take((size_t)N * 32);
+  const size_t o_ops = cv.take(ops.size() * sizeof(tr_op));
+  const size_t o_tab = cv.take(tables.size() * 8);
+  rc = ensure_ws(c, cv.off);
+  if (rc) return rc;
+  char* base = static_cast<char*>(c->ws);
+  HIP_TRY(hipMemcpyAsync(base + o_ts, transcripts, (size_t)N * 208, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(base + o_ops, ops.data(), ops.size() * sizeof(tr_op), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(base + o_tab, tables.data(), tables.size() * 8, hipMemcpyHostToDevice, c->stream));
+  prof_begin(c);
+  prog_dev p;
+  p.ops = reinterpret_cast<const tr_op*>(base + o_ops);
+  p.n = (uint32_t)ops.size();
+  p.tail = tail[0] | (uint32_t)tail[1] << 8 | (uint32_t)tail[2] << 16;
+  p.tables = reinterpret_cast<const uint64_t*>(base + o_tab);
+  tr_bufs bufs{};
+  bufs.dst[0] = reinterpret_cast<uint8_t*>(base + o_wide);
+  uint8_t* d_ts = reinterpret_cast<uint8_t*>(base + o_ts);
+  run_program(c, p, N, bufs, d_ts, nullptr, nullptr, /*throughput=*/false, /*d_img=*/nullptr);
+  prof_mark(c, ZKP_K_TRANSCRIPT);
+  HIP_TRY(hipGetLastError());
+  rc = launch_from_uniform(c, N, reinterpret_cast<uint8_t*>(base + o_wide), reinterpret_cast<uint8_t*>(base + o_out));
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(transcripts, d_ts, (size_t)N * 208, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)N * 32, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return ZKP_OK;
+}
+
 }  // extern "C"

@@ -245,6 +245,48 @@ ZKP_HD uint32_t fe_invsqrt(fe& r, const fe& v) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// SQRT_RATIO_M1(u, v), the general form of RFC 9496 section 4.2 (the Elligator map needs it; decode and encode keep
+// fe_invsqrt above).  u, v tight.  Returns was_square; r = |sqrt(u / v)| or |sqrt(i u / v)|, tight and non-negative.
+// u = 0 gives (1, 0).  Selects only: nothing branches on u or v.
+// ---------------------------------------------------------------------------------------------
+ZKP_HD uint32_t fe_words_eq(const uint32_t a[8], const uint32_t b[8]) {
+  uint32_t x = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) x |= a[i] ^ b[i];
+  return (uint32_t)(x == 0);
+}
+
+ZKP_HD uint32_t fe_sqrt_ratio_m1(fe& r, const fe& u, const fe& v) {
+  fe t, v3, c;
+  fe_sq(t, v);
+  fe_mul(v3, t, v);              // v^3
+  fe_sq(t, v3);
+  fe_mul(t, t, v);               // v^7
+  fe_mul(t, t, u);               // u v^7
+  fe_pow22523(t, t);             // (u v^7)^((p-5)/8)
+  fe_mul(r, u, v3);
+  fe_mul(r, r, t);               // r = u v^3 (u v^7)^((p-5)/8)
+  fe_sq(t, r);
+  fe_mul(t, t, v);               // check = v r^2
+  uint32_t cw[8], w[8];
+  fe_towords(cw, t);
+  fe_towords(w, u);
+  const uint32_t correct = fe_words_eq(cw, w);
+  fe_neg(t, u);                  // -u  (limbs <= bias2p)
+  fe_towords(w, t);
+  const uint32_t flipped = fe_words_eq(cw, w);
+  fe_from_const(c, FE_SQRT_M1);
+  fe_mul(t, t, c);               // -u i
+  fe_towords(w, t);
+  const uint32_t flipped_i = fe_words_eq(cw, w);
+  fe_mul(t, r, c);
+  fe_cmov(r, t, flipped | flipped_i);
+  fe_abs(r, r);
+  fe_carry(r, r);
+  return correct | flipped;
+}
+
+// ---------------------------------------------------------------------------------------------
 // ristretto255 decode: 32 bytes (as 8 LE words) -> extended point with Z = 1; returns 1 if valid.
 // On failure the output is the identity (so downstream arithmetic stays defined).
 // ---------------------------------------------------------------------------------------------
@@ -321,6 +363,80 @@ ZKP_HD void ristretto_encode(uint32_t w[8], const ge_p3& p) {
   fe_mul(t, dinv, t);
   fe_abs(t, t);
   fe_towords(w, t);
+}
+
+// ---- hash to the group: RFC 9496 section 4.3.4 (curve25519-dalek's RistrettoPoint::from_uniform_bytes) --------------------------
+// MAP (the Elligator 2 variant of the RFC) of one field element t (tight) to an extended point with tight coordinates.
+// was_square picks its two cases by select only: in a VRF or OPRF the input can be secret.
+ZKP_HD void ristretto_elligator(ge_p3& r, const fe& t0) {
+  fe rr, u, v, s, sp, c, n, w0, w1, w2, w3, t, one, k;
+  fe_1(one);
+  fe_from_const(k, FE_SQRT_M1);
+  fe_sq(t, t0);
+  fe_mul(rr, t, k);              // r = i t^2
+  fe_add(t, rr, one);            // sum
+  fe_from_const(k, FE_ONE_MINUS_D_SQ);
+  fe_mul(u, t, k);               // u = (r + 1) (1 - d^2)
+  fe_from_const(k, FE_D);
+  fe_mul(t, rr, k);
+  fe_neg(t, t);
+  fe_sub(t, t, one);
+  fe_carry(t, t);                // -1 - r d
+  fe_add(v, rr, k);              // r + d  (sum)
+  fe_mul(v, t, v);               // v = (-1 - r d) (r + d)
+  const uint32_t was_square = fe_sqrt_ratio_m1(s, u, v);
+  fe_mul(sp, s, t0);
+  fe_abs(sp, sp);
+  fe_neg(sp, sp);
+  fe_carry(sp, sp);              // s' = -|s t|
+  fe_cmov(s, sp, was_square ^ 1u);
+  fe_neg(t, one);
+  fe_carry(t, t);                // -1
+  c = rr;
+  fe_cmov(c, t, was_square);     // c = was_square ? -1 : r
+  fe_sub(t, rr, one);            // r - 1  (diff)
+  fe_mul(n, c, t);
+  fe_from_const(k, FE_D_MINUS_ONE_SQ);
+  fe_mul(n, n, k);
+  fe_sub(n, n, v);               // N = c (r - 1) (d - 1)^2 - v  (diff)
+  fe_mul(t, s, v);
+  fe_add(w0, t, t);              // w0 = 2 s v  (sum)
+  fe_from_const(k, FE_SQRT_AD_MINUS_ONE);
+  fe_mul(w1, n, k);              // w1 = N sqrt(a d - 1)
+  fe_sq(t, s);
+  fe_sub(w2, one, t);            // w2 = 1 - s^2  (diff)
+  fe_add(w3, one, t);            // w3 = 1 + s^2  (sum)
+  fe_mul(r.X, w0, w3);
+  fe_mul(r.Y, w2, w1);
+  fe_mul(r.Z, w1, w3);
+  fe_mul(r.T, w0, w2);
+}
+
+// FROM_UNIFORM_BYTES: w = the 64 bytes as 16 little-endian words.  Each half is read with bit 255 cleared and is not required
+// to be below p (dalek's FieldElement::from_bytes); the two maps are added with the unified addition.  A rolled loop over the halves:
+// one copy of the map in the code, and on gfx950 one map's registers live at a time (written out, the two maps are interleaved and
+// k_from_uniform spills 46 VGPRs at 256).
+ZKP_HD void ristretto_from_uniform_words(ge_p3& r, const uint32_t w[16]) {
+  ge_cached q;
+#pragma unroll 1
+  for (int h = 0; h < 2; ++h) {
+    uint32_t x[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) x[i] = h ? w[i] : w[8 + i];
+    fe t;
+    fe_fromwords(t, x);
+    ge_p3 p;
+    ristretto_elligator(p, t);
+    if (h == 0) ge_to_cached(q, p);      // the second half's map ...
+    else ge_add_cached(r, p, q);         // ... plus the first's
+  }
+}
+ZKP_HD void ristretto_from_uniform_bytes(ge_p3& r, const uint8_t b[64]) {
+  uint32_t w[16];
+#pragma unroll
+  for (int i = 0; i < 16; ++i)
+    w[i] = (uint32_t)b[4 * i] | (uint32_t)b[4 * i + 1] << 8 | (uint32_t)b[4 * i + 2] << 16 | (uint32_t)b[4 * i + 3] << 24;
+  ristretto_from_uniform_words(r, w);
 }
 
 // ---- encode(2 P) with a plain inversion instead of an inverse square root ---------------------------------------------------

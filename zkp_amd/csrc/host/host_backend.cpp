@@ -15,6 +15,7 @@
 //                 curve25519-dalek's constant-time multiscalar_mul does, prover.rs:94); ZKP_VARTIME: indexed, zeros skipped.
 //   msm_optional  the same walk over n points with decode-or-None (verifier.rs:162-166, batch_verifier.rs:219-228).
 //   decode_check  ristretto decode.
+//   from_uniform_bytes  RFC 9496 section 4.3.4 (ristretto_from_uniform_bytes of ge25519.h: selects only, constant time), then the encoder.
 #include "host_backend.hpp"
 
 #include <cstring>
@@ -162,6 +163,16 @@ int decode_check(uint64_t n, const uint8_t* points, uint8_t* status) {
   for (uint64_t i = 0; i < n; ++i) {
     ge_p3 p;
     status[i] = decode(p, points + 32 * i) ? 0 : 1;
+  }
+  return ZKP_OK;
+}
+
+int from_uniform_bytes(uint64_t n, const uint8_t* in, uint8_t* out) {
+  if (n && (!in || !out)) return ZKP_ERR_ARG;
+  for (uint64_t i = 0; i < n; ++i) {
+    ge_p3 p;
+    ristretto_from_uniform_bytes(p, in + 64 * i);
+    encode(out + 32 * i, p);
   }
   return ZKP_OK;
 }

@@ -12,5 +12,6 @@ int msm_many(uint32_t n_msm, const uint32_t* off, const uint8_t* scalars, const 
              uint8_t* out, uint8_t* status);
 int msm_optional(uint64_t n, const uint8_t* scalars, const uint8_t* points, uint8_t out_point[32], int* status);
 int decode_check(uint64_t n, const uint8_t* points, uint8_t* status);
+int from_uniform_bytes(uint64_t n, const uint8_t* in /*[n][64]*/, uint8_t* out /*[n][32]*/);      // zkp_from_uniform_bytes (5)
 }  // namespace hostbk
 }  // namespace zkp

@@ -805,6 +805,35 @@ int zkp_batch_verify_many(zkp_ctx* ctx, const zkp_statement* stp, uint32_t K, ui
   return ZKP_TB_OK;
 }
 
+// ---- hash to the group (RFC 9496 section 4.3.4) ----------------------------------------------------------------------
+int zkp_from_uniform_bytes_batch(zkp_ctx* ctx, uint64_t n, const uint8_t* in, int n_threads, uint8_t* out) {
+  if (n == 0) return ZKP_TB_OK;
+  if (!in || !out) return ZKP_TB_BAD_STATEMENT;
+  if (!on_host(ctx, n)) return zkp_from_uniform_bytes(ctx, n, in, out);
+  if (n > 0xffffffffull) return ZKP_TB_BAD_STATEMENT;
+  parallel_for((uint32_t)n, n_threads, [&](uint32_t lo, uint32_t hi) { zkp::hostbk::from_uniform_bytes(hi - lo, in + 64 * (size_t)lo, out + 32 * (size_t)lo); });
+  return ZKP_TB_OK;
+}
+
+// tests/sig_and_vrf_example.rs:36-40 for N transcripts.  Aligned batches of fused_min_batch or more squeeze on the device and map there
+// (zkp_fused_hash_to_group); otherwise host Merlin on the host threads, then the map on the backend zkp_from_uniform_bytes_batch picks.
+int zkp_hash_to_group_batch(zkp_ctx* ctx, uint32_t N, uint8_t* ts, const char* label, int n_threads, uint8_t* out) {
+  if (!label) return ZKP_TB_BAD_STATEMENT;
+  if (N == 0) return ZKP_TB_OK;
+  if (!ts || !out) return ZKP_TB_BAD_STATEMENT;
+  if (!fits_u32(std::strlen(label))) return ZKP_TB_TOO_LONG;
+  if (ctx && use_fused(ts, N)) return zkp_fused_hash_to_group(ctx, N, ts, label, out);
+  std::vector<uint8_t> wide(64 * (size_t)N);
+  parallel_for(N, n_threads, [&](uint32_t lo, uint32_t hi) {
+    for (uint32_t j = lo; j < hi; ++j) {
+      Transcript x = Transcript::from_bytes(ts + TB * (size_t)j);
+      x.challenge_bytes(label, wide.data() + 64 * (size_t)j, 64);
+      x.to_bytes(ts + TB * (size_t)j);
+    }
+  });
+  return zkp_from_uniform_bytes_batch(ctx, N, wide.data(), n_threads, out);
+}
+
 int zkp_batch_verify_locate(zkp_ctx* ctx, const zkp_statement* st, uint32_t N, uint32_t n_transcripts, uint8_t* ts, const uint8_t* inst,
                             const uint8_t* common, const uint8_t* commitments, const uint8_t* responses, const uint8_t* weights16,
                             int n_threads, uint8_t* results) {

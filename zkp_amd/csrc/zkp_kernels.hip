@@ -1279,6 +1279,21 @@ k_encode_many(uint32_t n, const uint8_t* __restrict__ xyzt, uint8_t* __restrict_
   store_vec<2>(out + 32 * (size_t)i, o);
 }
 
+// hash to the group (RFC 9496 section 4.3.4, RistrettoPoint::from_uniform_bytes): 64 bytes in, the canonical 32-byte encoding out, one
+// lane per output over a grid-stride loop.  No input-dependent branch or address (ristretto_elligator selects).
+__global__ void __launch_bounds__(256, 2)
+k_from_uniform(uint32_t n, const uint8_t* __restrict__ in, uint8_t* __restrict__ out) {
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    uint32_t w[16];
+    load_vec<4>(w, in + 64 * (size_t)i);
+    ge_p3 p;
+    ristretto_from_uniform_words(p, w);
+    uint32_t o[8];
+    ristretto_encode(o, p);
+    store_vec<2>(out + 32 * (size_t)i, o);
+  }
+}
+
 // =============================================================================================
 // host side: context, workspace, C ABI
 // =============================================================================================
@@ -1910,6 +1925,17 @@ terms_cfg host_terms_cfg(const zkp_ctx* c, uint32_t n_terms, const uint32_t* pid
   return k;
 }
 
+// k_from_uniform over n outputs on the context's stream (device pointers).  The grid stops at 2,048 blocks of 256 lanes (8 per CU
+// of an MI355X); larger calls loop.
+int launch_from_uniform(zkp_ctx* c, uint64_t n, const uint8_t* d_in, uint8_t* d_out) {
+  constexpr uint64_t kMaxBlocks = 2048;
+  const unsigned blocks = (unsigned)std::min<uint64_t>(kMaxBlocks, (n + 255) / 256);
+  hipLaunchKernelGGL(k_from_uniform, dim3(blocks), dim3(256), 0, c->stream, (uint32_t)n, d_in, d_out);
+  prof_mark(c, ZKP_K_DECODE);
+  HIP_TRY(hipGetLastError());
+  return ZKP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2420,6 +2446,38 @@ int zkp_decode_check(zkp_ctx* c, uint64_t n, const uint8_t* points, uint8_t* sta
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(status, base + o_st, (size_t)n, hipMemcpyDeviceToHost, c->stream));
   if (xyzt) HIP_TRY(hipMemcpyAsync(xyzt, base + o_xyzt, (size_t)n * 128, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return ZKP_OK;
+}
+
+int zkp_from_uniform_bytes_dev(zkp_ctx* c, uint64_t n, const uint8_t* d_in, uint8_t* d_out) {
+  if (!c) return fail(ZKP_ERR_ARG, "ctx is NULL");
+  if (n == 0) return ZKP_OK;
+  if (!d_in || !d_out) return fail(ZKP_ERR_ARG, "NULL device pointer");
+  if (n > 0x7fffffffull) return fail(ZKP_ERR_ARG, "n too large");
+  if (!aligned16(d_in) || !aligned16(d_out)) return fail(ZKP_ERR_ARG, "device buffers must be 16-byte aligned");
+  HIP_TRY(hipSetDevice(c->device));
+  prof_begin(c);
+  return launch_from_uniform(c, n, d_in, d_out);
+}
+
+int zkp_from_uniform_bytes(zkp_ctx* c, uint64_t n, const uint8_t* in, uint8_t* out) {
+  if (!c) return fail(ZKP_ERR_ARG, "ctx is NULL");
+  if (n == 0) return ZKP_OK;
+  if (!in || !out) return fail(ZKP_ERR_ARG, "NULL pointer");
+  if (n > 0x7fffffffull) return fail(ZKP_ERR_ARG, "n too large");
+  HIP_TRY(hipSetDevice(c->device));
+  carve cv;
+  const size_t o_in = cv.take((size_t)n * 64);
+  const size_t o_out = cv.take((size_t)n * 32);
+  int rc = ensure_ws(c, cv.off);
+  if (rc) return rc;
+  char* base = static_cast<char*>(c->ws);
+  HIP_TRY(hipMemcpyAsync(base + o_in, in, (size_t)n * 64, hipMemcpyHostToDevice, c->stream));
+  prof_begin(c);
+  rc = launch_from_uniform(c, n, reinterpret_cast<uint8_t*>(base + o_in), reinterpret_cast<uint8_t*>(base + o_out));
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return ZKP_OK;
 }

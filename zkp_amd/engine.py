@@ -34,7 +34,7 @@ EXPORTS = (
     "zkp_fused_verify_batchable_coeffs", "zkp_fused_batch_verify_many", "zkp_fused_batch_verify_many_dev", "zkp_ctx_capture_begin", "zkp_ctx_capture_end", "zkp_ctx_capture_abort", "zkp_graph_launch", "zkp_graph_destroy",
     "zkp_fused_prove_submit", "zkp_fused_verify_compact_submit", "zkp_fused_batch_verify_many_submit", "zkp_fused_verify_batchable_submit",
     "zkp_fused_prove_seeded", "zkp_fused_batch_verify_many_seeded", "zkp_ctx_job_wait", "zkp_ctx_job_poll", "zkp_ctx_job_pending", "zkp_ctx_job_discard", "zkp_ctx_job_timing", "zkp_ctx_last_kernels", "zkp_host_alloc", "zkp_host_alloc_on", "zkp_host_numa_node", "zkp_host_node_of", "zkp_host_free", "zkp_host_register", "zkp_host_unregister",
-    "zkp_host_is_pinned", "zkp_chacha20_fill_dev",
+    "zkp_host_is_pinned", "zkp_chacha20_fill_dev", "zkp_from_uniform_bytes", "zkp_from_uniform_bytes_dev", "zkp_fused_hash_to_group",
 )
 TEST_HOOK_EXPORTS = ("zkp_debug_quad_selftest", "zkp_debug_row_selftest", "zkp_debug_wave_cycles")      # only in libzkp_mi355x_testhooks.so
 
@@ -74,6 +74,9 @@ def load_library(test_hooks: bool = False) -> ctypes.CDLL:
     lib.zkp_msm_optional_dev.argtypes = [vp, ctypes.c_uint64, u8p, u8p, u8p, u32p]
     lib.zkp_decode_check.argtypes = [vp, ctypes.c_uint64, u8p, u8p, u8p]
     lib.zkp_encode_many.argtypes = [vp, ctypes.c_uint64, u8p, u8p]
+    lib.zkp_from_uniform_bytes.argtypes = [vp, ctypes.c_uint64, u8p, u8p]
+    lib.zkp_from_uniform_bytes_dev.argtypes = [vp, ctypes.c_uint64, u8p, u8p]
+    lib.zkp_fused_hash_to_group.argtypes = [vp, ctypes.c_uint32, u8p, ctypes.c_char_p, u8p]
     lib.zkp_ctx_last_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
     lib.zkp_ctx_set_profiling.argtypes = [vp, i32]
     lib.zkp_ctx_capture_begin.argtypes = [vp]
@@ -178,6 +181,13 @@ class Engine:
         _check(self._lib.zkp_encode_many(self._h, len(xyzt), _ptr(xyzt), _ptr(out)), "zkp_encode_many")
         return out
 
+    def from_uniform_bytes(self, inp) -> np.ndarray:
+        """RistrettoPoint::from_uniform_bytes (RFC 9496 section 4.3.4) of every 64-byte row: [n][64] -> canonical encodings [n][32]"""
+        inp = _u8(inp, 64) if len(inp) else np.zeros((0, 64), np.uint8)
+        out = np.zeros((len(inp), 32), np.uint8)
+        _check(self._lib.zkp_from_uniform_bytes(self._h, len(inp), _ptr(inp), _ptr(out)), "zkp_from_uniform_bytes")
+        return out
+
     def debug_quad_selftest(self, pairs) -> np.ndarray:
         pairs = _u8(pairs, 64)
         out = np.zeros((len(pairs), 4, 32), np.uint8)
@@ -225,6 +235,10 @@ class Engine:
 
     def msm_optional_dev(self, n, d_scalars, d_points, d_out, d_status) -> None:
         _check(self._lib.zkp_msm_optional_dev(self._h, n, d_scalars, d_points, d_out, d_status), "zkp_msm_optional_dev")
+
+    def from_uniform_bytes_dev(self, n, d_in, d_out) -> None:
+        """zkp_from_uniform_bytes_dev: d_in [n][64] -> d_out [n][32], device pointers (16-byte aligned), queued on the context's stream"""
+        _check(self._lib.zkp_from_uniform_bytes_dev(self._h, n, d_in, d_out), "zkp_from_uniform_bytes_dev")
 
     # ---- fused statement flows on device-resident buffers (include/zkp_mi355x.h section 2c) -------------
     def fused_prove_dev(self, fst: "FusedStatement", n, strobe_pos, d_ts, d_secrets, d_table, d_entropy, d_chal, d_resp, d_coms, d_status) -> None:

@@ -18,6 +18,7 @@ marshals buffers.  Points are 32-byte ristretto255 encodings, scalars 32-byte li
 from __future__ import annotations
 
 import ctypes
+import hashlib
 import weakref
 import os
 from dataclasses import dataclass
@@ -46,6 +47,7 @@ EXPORTS = (
     "zkp_verify_batchable_each_submit", "zkp_batch_verify_many_submit", "zkp_job_done", "zkp_job_wait", "zkp_job_context_index", "zkp_pipe_prove_batch",
     "zkp_pipe_verify_compact_batch", "zkp_pipe_verify_batchable_each", "zkp_pipe_batch_verify", "zkp_pipe_batch_verify_many",
     "zkp_pipe_batch_verify_locate", "zkp_toolbox_set_host_max_terms", "zkp_toolbox_get_host_max_terms",
+    "zkp_from_uniform_bytes_batch", "zkp_hash_to_group_batch",
 )
 ZKP_JOB_SHARED_TRANSCRIPT = 1
 ZKP_TB_PIPE_FULL = 3
@@ -120,6 +122,8 @@ def lib() -> ctypes.CDLL:
         _lib.zkp_pipe_batch_verify.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp, vp, vp]
         _lib.zkp_pipe_batch_verify_many.argtypes = [vp, vp, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp]
         _lib.zkp_pipe_batch_verify_locate.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp]
+        _lib.zkp_from_uniform_bytes_batch.argtypes = [vp, ctypes.c_uint64, vp, i32, vp]
+        _lib.zkp_hash_to_group_batch.argtypes = [vp, u32, vp, ctypes.c_char_p, i32, vp]
     return _lib
 
 
@@ -474,6 +478,42 @@ def batch_verify_build(st, transcripts, inst, common, commitments, responses, we
                                       _p(np.ascontiguousarray(weights16)), threads, _p(ms), _p(mp))
     _raise(rc, "zkp_batch_verify_build")
     return ms, mp
+
+
+# ---- hash to the group (RFC 9496 section 4.3.4) ------------------------------------------------------------------------
+def from_uniform_bytes(eng, inp, threads: int = 0) -> np.ndarray:
+    """RistrettoPoint::from_uniform_bytes of every 64-byte row: [n][64] -> canonical encodings [n][32].  eng = None (or a HostEngine)
+    maps on the host threads; with an Engine, calls above get_host_max_terms() outputs map on the GPU."""
+    inp = np.ascontiguousarray(inp, dtype=np.uint8).reshape(-1, 64) if len(inp) else np.zeros((0, 64), np.uint8)
+    out = np.zeros((len(inp), 32), np.uint8)
+    rc = lib().zkp_from_uniform_bytes_batch(None if eng is None else eng._h, ctypes.c_uint64(len(inp)), _p(inp), threads, _p(out))
+    _raise(rc, "zkp_from_uniform_bytes_batch")
+    return out
+
+
+def hash_to_group(eng, transcripts, label: bytes = b"output", threads: int = 0) -> np.ndarray:
+    """N x { challenge_bytes(label, 64) ; from_uniform_bytes } -- the `hash_to_group` of the reference's VRF example
+    (tests/sig_and_vrf_example.rs:36-40) -- -> encodings [N][32].  transcripts: a list of Transcript objects or a [N][208] uint8
+    array (C-contiguous); either is advanced in place exactly as merlin advances it."""
+    objs = None
+    if len(transcripts) and isinstance(transcripts[0], Transcript):
+        objs, arr = transcripts, _transcripts_array(transcripts)
+    else:
+        arr = transcripts if len(transcripts) else np.zeros((0, TRANSCRIPT_BYTES), np.uint8)
+        if not (isinstance(arr, np.ndarray) and arr.dtype == np.uint8 and arr.ndim == 2 and arr.shape[1] == TRANSCRIPT_BYTES and arr.flags["C_CONTIGUOUS"]):
+            raise ValueError("transcripts must be Transcript objects or a C-contiguous uint8 array of shape [N][%d]" % TRANSCRIPT_BYTES)
+    out = np.zeros((len(arr), 32), np.uint8)
+    rc = lib().zkp_hash_to_group_batch(None if eng is None else eng._h, ctypes.c_uint32(len(arr)), _p(arr), label, threads, _p(out))
+    _raise(rc, "zkp_hash_to_group_batch")
+    if objs is not None:
+        _store_transcripts(objs, arr)
+    return out
+
+
+def hash_from_bytes_sha512(eng, messages, threads: int = 0) -> np.ndarray:
+    """RistrettoPoint::hash_from_bytes::<Sha512> (reference tests/zkp.rs:35) of every message: SHA-512 on the host, then the batched map."""
+    wide = np.frombuffer(b"".join(hashlib.sha512(bytes(m)).digest() for m in messages), np.uint8).reshape(-1, 64)
+    return from_uniform_bytes(eng, wide, threads)
 
 
 
