@@ -455,6 +455,21 @@ int zkp_from_uniform_bytes_dev(zkp_ctx* ctx, uint64_t n, const uint8_t* d_in /*[
  *     (ZKP_ERR_ARG otherwise), and they are advanced in place exactly as merlin advances them.  Host pointers, synchronous.
  *     The squeeze is timed under ZKP_K_TRANSCRIPT, the map under ZKP_K_DECODE. */
 int zkp_fused_hash_to_group(zkp_ctx* ctx, uint32_t N, uint8_t* transcripts /*[N][208]*/, const char* label, uint8_t* out /*[N][32]*/);
+/*     n x RistrettoPoint::hash_from_bytes::<Sha512>(message) (reference tests/zkp.rs:34): SHA-512 (FIPS 180-4) of each message,
+ *     then from_uniform_bytes above.  The messages are a CSR batch: message i = msgs[offsets[i], offsets[i + 1]), of any length
+ *     and at any byte offset.  Lengths are public: branches depend on them, never on message bytes.  One lane hashes one message,
+ *     so a batch runs at the pace of its longest message.  n = 0 is a no-op; n > 2^31 - 1 is ZKP_ERR_ARG.  The SHA-512 stage is
+ *     timed under ZKP_K_TRANSCRIPT, the map under ZKP_K_DECODE.
+ *     zkp_hash_from_bytes_sha512 takes host pointers: offsets must be non-decreasing (ZKP_ERR_ARG otherwise, and for a NULL buffer);
+ *     it uploads msgs[offsets[0], offsets[n]) and the offsets rebased to 0, and synchronises.
+ *     zkp_hash_from_bytes_sha512_dev takes device pointers (d_offsets 8-byte aligned, d_out 16-byte aligned, d_msgs any alignment;
+ *     d_msgs may be NULL when msgs_len = 0), enqueues on the context's stream and may be recorded between zkp_ctx_capture_begin /
+ *     _end once the same call has run outside the capture.  It does not check d_offsets: every range is clamped to [0, msgs_len)
+ *     and hi < lo is empty, so a bad offset gives a wrong point, never a read outside d_msgs.  d_out may point at a row of a fused
+ *     flow's d_table, so that an instance point such as H is hashed in place ahead of zkp_fused_prove_dev / _batch_verify_dev. */
+int zkp_hash_from_bytes_sha512(zkp_ctx* ctx, uint64_t n, const uint8_t* msgs, const uint64_t* offsets /*[n+1]*/, uint8_t* out /*[n][32]*/);
+int zkp_hash_from_bytes_sha512_dev(zkp_ctx* ctx, uint64_t n, const uint8_t* d_msgs, uint64_t msgs_len, const uint64_t* d_offsets /*[n+1]*/,
+                                   uint8_t* d_out /*[n][32]*/);
 
 /* Timing of the last *_dev / host call on this context, measured with HIP events on the stream the
  * kernels were launched on.  kernel_ms[] is indexed by ZKP_K_*; returns the number of entries. */
@@ -495,10 +510,12 @@ int zkp_ctx_set_profiling(zkp_ctx* ctx, int enabled);
  *   k_stmt_classify;
  *   ZKP_TESTOPT_WAVE_CYCLES = 1 switches on a per-wavefront cycle recorder in the term kernel (s_memtime at entry and exit);
  * zkp_debug_wave_cycles copies out (and clears) up to cap records, [block][wavefront 0..3] = block class << 56 | cycles (class 1 =
- *   ladder, 2 = comb scan, 3 = grouped comb walk, 4 = fixed-base; 0 = no record): the timing side of the constant-time evidence. */
+ *   ladder, 2 = comb scan, 3 = grouped comb walk, 4 = fixed-base; 0 = no record): the timing side of the constant-time evidence.
+ * zkp_debug_sha512: the SHA-512 stage of zkp_hash_from_bytes_sha512 alone (same arguments and checks): out = [n][64] digests. */
 int zkp_debug_quad_selftest(zkp_ctx* ctx, uint32_t n, const uint8_t* pairs /*[n][64]*/, uint8_t* out /*[n][128]*/);
 int zkp_debug_row_selftest(zkp_ctx* ctx, uint32_t n, const uint8_t* pairs /*[n][64]*/, uint8_t* out /*[n][96]*/);
 int zkp_debug_wave_cycles(zkp_ctx* ctx, uint64_t* out, uint32_t cap);     /* returns the number of records copied */
+int zkp_debug_sha512(zkp_ctx* ctx, uint64_t n, const uint8_t* msgs, const uint64_t* offsets /*[n+1]*/, uint8_t* out /*[n][64]*/);
 enum { ZKP_TESTOPT_DUMMY_LAUNCHES = 1001, ZKP_TESTOPT_GENERIC_CLASSIFIER = 1002, ZKP_TESTOPT_WAVE_CYCLES = 1003 };
 #endif
 

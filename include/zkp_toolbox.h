@@ -258,6 +258,13 @@ uint32_t zkp_toolbox_get_fused_min_batch(void);
  * Both: n = 0 is a no-op; a NULL buffer (with n > 0) or a NULL label is ZKP_TB_BAD_STATEMENT; the map never fails. */
 int zkp_from_uniform_bytes_batch(zkp_ctx* ctx, uint64_t n, const uint8_t* in /*[n][64]*/, int n_threads, uint8_t* out /*[n][32]*/);
 int zkp_hash_to_group_batch(zkp_ctx* ctx, uint32_t N, uint8_t* transcripts /*[N][208]*/, const char* label, int n_threads, uint8_t* out /*[N][32]*/);
+/* zkp_hash_from_bytes_sha512_batch: n x RistrettoPoint::hash_from_bytes::<Sha512>(message) (reference tests/zkp.rs:34) over a CSR batch,
+ *   message i = msgs[offsets[i], offsets[i + 1]) (any lengths, any byte offsets), -> canonical encodings out [n][32].  Routes as
+ *   zkp_from_uniform_bytes_batch: ctx == NULL or n <= zkp_toolbox_get_host_max_terms() on the host backend (n_threads threads), anything
+ *   else on the device (zkp_hash_from_bytes_sha512).  Same bytes on every route.  n = 0 is a no-op; a NULL buffer (with n > 0) or
+ *   decreasing offsets are ZKP_TB_BAD_STATEMENT. */
+int zkp_hash_from_bytes_sha512_batch(zkp_ctx* ctx, uint64_t n, const uint8_t* msgs, const uint64_t* offsets /*[n+1]*/, int n_threads,
+                                     uint8_t* out /*[n][32]*/);
 
 /* The ChaCha20 block function (RFC 8439 section 2.3; state words 12-13 = counter, 14-15 = nonce) behind the default
  * entropy / weights of the calls above (`entropy == NULL`, `weights16 == NULL`): like the reference's `thread_rng()`, a

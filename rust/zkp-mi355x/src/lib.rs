@@ -150,6 +150,24 @@ pub mod hash_to_group {
         }
         Ok(out.chunks(32).map(|c| { let mut b = [0u8; 32]; b.copy_from_slice(c); CompressedRistretto(b) }).collect())
     }
+
+    /// `RistrettoPoint::hash_from_bytes::<Sha512>(messages[i]).compress()` for every i (reference tests/zkp.rs:34): SHA-512, then
+    /// `from_uniform_bytes`, on the host backend or the GPU as `from_uniform_bytes` routes.
+    pub fn hash_from_bytes_sha512(engine: Option<&Engine>, messages: &[&[u8]]) -> Result<Vec<CompressedRistretto>, Error> {
+        let mut offsets = Vec::with_capacity(messages.len() + 1);
+        offsets.push(0u64);
+        let mut data = Vec::with_capacity(messages.iter().map(|m| m.len()).sum::<usize>().max(1));
+        for m in messages {
+            data.extend_from_slice(m);
+            offsets.push(data.len() as u64);
+        }
+        data.push(0);                                   // never an empty buffer: its pointer is not NULL
+        let mut out = vec![0u8; 32 * messages.len()];
+        check(unsafe {
+            sys::zkp_hash_from_bytes_sha512_batch(ctx(engine), messages.len() as u64, data.as_ptr(), offsets.as_ptr(), 0, out.as_mut_ptr())
+        })?;
+        Ok(out.chunks(32).map(|c| { let mut b = [0u8; 32]; b.copy_from_slice(c); CompressedRistretto(b) }).collect())
+    }
 }
 
 /// A Merlin transcript as the 208-byte state the C ABI works on (merlin keeps its fields private, so the state machine

@@ -16,6 +16,7 @@
 //   msm_optional  the same walk over n points with decode-or-None (verifier.rs:162-166, batch_verifier.rs:219-228).
 //   decode_check  ristretto decode.
 //   from_uniform_bytes  RFC 9496 section 4.3.4 (ristretto_from_uniform_bytes of ge25519.h: selects only, constant time), then the encoder.
+//   hash_from_bytes_sha512  sha512_range of sha512.h (the kernel's SHA-512, byte loads on the host), then from_uniform_bytes.
 #include "host_backend.hpp"
 
 #include <cstring>
@@ -23,6 +24,7 @@
 
 #define ZKP_HOST_FE51 1        // this translation unit (and no other of the library) gets the 5 x 51-bit field under the device's point formulas
 #include "../ge25519.h"
+#include "../sha512.h"
 
 namespace zkp {
 namespace hostbk {
@@ -172,6 +174,20 @@ int from_uniform_bytes(uint64_t n, const uint8_t* in, uint8_t* out) {
   for (uint64_t i = 0; i < n; ++i) {
     ge_p3 p;
     ristretto_from_uniform_bytes(p, in + 64 * i);
+    encode(out + 32 * i, p);
+  }
+  return ZKP_OK;
+}
+
+int hash_from_bytes_sha512(uint64_t n, const uint8_t* msgs, const uint64_t* offsets, uint8_t* out) {
+  if (n && (!msgs || !offsets || !out)) return ZKP_ERR_ARG;
+  for (uint64_t i = 0; i < n; ++i) {
+    uint64_t H[8];
+    uint32_t w[16];
+    sha512_range(H, msgs, offsets[n], offsets[i], offsets[i + 1]);
+    sha512_digest_words(w, H);
+    ge_p3 p;
+    ristretto_from_uniform_words(p, w);
     encode(out + 32 * i, p);
   }
   return ZKP_OK;

@@ -815,6 +815,20 @@ int zkp_from_uniform_bytes_batch(zkp_ctx* ctx, uint64_t n, const uint8_t* in, in
   return ZKP_TB_OK;
 }
 
+// RistrettoPoint::hash_from_bytes::<Sha512> of n messages (CSR: message i = msgs[offsets[i], offsets[i + 1])).  The offsets are checked
+// here, whichever backend runs: non-decreasing, or ZKP_TB_BAD_STATEMENT.
+int zkp_hash_from_bytes_sha512_batch(zkp_ctx* ctx, uint64_t n, const uint8_t* msgs, const uint64_t* offsets, int n_threads, uint8_t* out) {
+  if (n == 0) return ZKP_TB_OK;
+  if (!msgs || !offsets || !out) return ZKP_TB_BAD_STATEMENT;
+  for (uint64_t i = 0; i < n; ++i)
+    if (offsets[i + 1] < offsets[i]) return ZKP_TB_BAD_STATEMENT;
+  if (!on_host(ctx, n)) return zkp_hash_from_bytes_sha512(ctx, n, msgs, offsets, out);
+  if (n > 0xffffffffull) return ZKP_TB_BAD_STATEMENT;
+  // a thread's slice [lo, hi) is a CSR batch of its own (offsets + lo), whose buffer msgs[0, offsets[hi]) holds all of its messages
+  parallel_for((uint32_t)n, n_threads, [&](uint32_t lo, uint32_t hi) { zkp::hostbk::hash_from_bytes_sha512(hi - lo, msgs, offsets + lo, out + 32 * (size_t)lo); });
+  return ZKP_TB_OK;
+}
+
 // tests/sig_and_vrf_example.rs:36-40 for N transcripts.  Aligned batches of fused_min_batch or more squeeze on the device and map there
 // (zkp_fused_hash_to_group); otherwise host Merlin on the host threads, then the map on the backend zkp_from_uniform_bytes_batch picks.
 int zkp_hash_to_group_batch(zkp_ctx* ctx, uint32_t N, uint8_t* ts, const char* label, int n_threads, uint8_t* out) {

@@ -70,6 +70,7 @@ __device__ __forceinline__ uint32_t sel8(const uint32_t w[8], int j) {
 #include "comb_tables.h"
 #include "sc25519.h"
 #include "transcript_kernels.h"
+#include "sha512.h"
 
 // =============================================================================================
 // (A) small-MSM path
@@ -1294,6 +1295,21 @@ k_from_uniform(uint32_t n, const uint8_t* __restrict__ in, uint8_t* __restrict__
   }
 }
 
+// SHA-512 over a CSR batch of messages (the first half of RistrettoPoint::hash_from_bytes::<Sha512>): message i = msgs[offsets[i],
+// offsets[i + 1]) clamped to [0, msgs_len) (sha512_clamp: whatever the offsets hold, no read leaves the buffer), its 64-byte digest to
+// out + 64 i.  One lane per message over a grid-stride loop; a lane runs ceil((len + 17) / 128) compressions, so a wave runs at the pace
+// of its longest message.  Branches and addresses depend on the lengths only.
+__global__ void __launch_bounds__(256)
+k_sha512_csr(uint32_t n, const uint8_t* __restrict__ msgs, uint64_t msgs_len, const uint64_t* __restrict__ offsets, uint8_t* __restrict__ out) {
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    uint64_t H[8];
+    sha512_range(H, msgs, msgs_len, offsets[i], offsets[i + 1]);
+    uint32_t w[16];
+    sha512_digest_words(w, H);
+    store_vec<4>(out + 64 * (size_t)i, w);
+  }
+}
+
 // =============================================================================================
 // host side: context, workspace, C ABI
 // =============================================================================================
@@ -1936,6 +1952,54 @@ int launch_from_uniform(zkp_ctx* c, uint64_t n, const uint8_t* d_in, uint8_t* d_
   return ZKP_OK;
 }
 
+// k_sha512_csr over n messages on the context's stream (device pointers; d_out 16-byte aligned), grid as launch_from_uniform.
+int launch_sha512(zkp_ctx* c, uint64_t n, const uint8_t* d_msgs, uint64_t msgs_len, const uint64_t* d_offsets, uint8_t* d_out) {
+  constexpr uint64_t kMaxBlocks = 2048;
+  const unsigned blocks = (unsigned)std::min<uint64_t>(kMaxBlocks, (n + 255) / 256);
+  hipLaunchKernelGGL(k_sha512_csr, dim3(blocks), dim3(256), 0, c->stream, (uint32_t)n, d_msgs, msgs_len, d_offsets, d_out);
+  prof_mark(c, ZKP_K_TRANSCRIPT);
+  HIP_TRY(hipGetLastError());
+  return ZKP_OK;
+}
+
+// zkp_hash_from_bytes_sha512 and zkp_debug_sha512: checks the offsets on the host (non-decreasing), uploads msgs[offsets[0], offsets[n])
+// and the offsets rebased to 0, hashes, and (map) maps the digests in place of the workspace.  out: [n][32] encodings, or [n][64] digests.
+int hash_from_bytes_host(zkp_ctx* c, uint64_t n, const uint8_t* msgs, const uint64_t* offsets, uint8_t* out, bool map) {
+  if (!c) return fail(ZKP_ERR_ARG, "ctx is NULL");
+  if (n == 0) return ZKP_OK;
+  if (!msgs || !offsets || !out) return fail(ZKP_ERR_ARG, "NULL pointer");
+  if (n > 0x7fffffffull) return fail(ZKP_ERR_ARG, "n too large");
+  for (uint64_t i = 0; i < n; ++i)
+    if (offsets[i + 1] < offsets[i]) return fail(ZKP_ERR_ARG, "offsets must be non-decreasing");
+  const uint64_t base_off = offsets[0], total = offsets[n] - offsets[0];
+  std::vector<uint64_t> rebased(n + 1);
+  for (uint64_t i = 0; i <= n; ++i) rebased[i] = offsets[i] - base_off;
+  HIP_TRY(hipSetDevice(c->device));
+  carve cv;
+  const size_t o_msgs = cv.take((size_t)total);
+  const size_t o_off = cv.take((size_t)(n + 1) * 8);
+  const size_t o_wide = cv.take((size_t)n * 64);
+  const size_t o_out = cv.take((size_t)n * 32);
+  int rc = ensure_ws(c, cv.off);
+  if (rc) return rc;
+  char* base = static_cast<char*>(c->ws);
+  if (total) HIP_TRY(hipMemcpyAsync(base + o_msgs, msgs + base_off, (size_t)total, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(base + o_off, rebased.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+  prof_begin(c);
+  uint8_t* d_wide = reinterpret_cast<uint8_t*>(base + o_wide);
+  rc = launch_sha512(c, n, reinterpret_cast<const uint8_t*>(base + o_msgs), total, reinterpret_cast<const uint64_t*>(base + o_off), d_wide);
+  if (rc) return rc;
+  if (map) {
+    rc = launch_from_uniform(c, n, d_wide, reinterpret_cast<uint8_t*>(base + o_out));
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
+  } else {
+    HIP_TRY(hipMemcpyAsync(out, d_wide, (size_t)n * 64, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return ZKP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2481,6 +2545,37 @@ int zkp_from_uniform_bytes(zkp_ctx* c, uint64_t n, const uint8_t* in, uint8_t* o
   HIP_TRY(hipStreamSynchronize(c->stream));
   return ZKP_OK;
 }
+
+int zkp_hash_from_bytes_sha512(zkp_ctx* c, uint64_t n, const uint8_t* msgs, const uint64_t* offsets, uint8_t* out) {
+  return hash_from_bytes_host(c, n, msgs, offsets, out, /*map=*/true);
+}
+
+// The digests go to the workspace (which must not grow under capture: run the call once first), then k_from_uniform maps them to d_out.
+// The device offsets are not validated: the kernel clamps every range to [0, msgs_len).
+int zkp_hash_from_bytes_sha512_dev(zkp_ctx* c, uint64_t n, const uint8_t* d_msgs, uint64_t msgs_len, const uint64_t* d_offsets, uint8_t* d_out) {
+  if (!c) return fail(ZKP_ERR_ARG, "ctx is NULL");
+  if (n == 0) return ZKP_OK;
+  if ((!d_msgs && msgs_len) || !d_offsets || !d_out) return fail(ZKP_ERR_ARG, "NULL device pointer");
+  if (n > 0x7fffffffull) return fail(ZKP_ERR_ARG, "n too large");
+  if ((reinterpret_cast<uintptr_t>(d_offsets) & 7) || !aligned16(d_out))
+    return fail(ZKP_ERR_ARG, "d_offsets must be 8-byte and d_out 16-byte aligned");
+  HIP_TRY(hipSetDevice(c->device));
+  carve cv;
+  const size_t o_wide = cv.take((size_t)n * 64);
+  int rc = ensure_ws(c, cv.off);
+  if (rc) return rc;
+  uint8_t* d_wide = static_cast<uint8_t*>(c->ws) + o_wide;
+  prof_begin(c);
+  rc = launch_sha512(c, n, d_msgs, msgs_len, d_offsets, d_wide);
+  if (rc) return rc;
+  return launch_from_uniform(c, n, d_wide, d_out);
+}
+
+#ifdef ZKP_BUILD_TEST_HOOKS
+int zkp_debug_sha512(zkp_ctx* c, uint64_t n, const uint8_t* msgs, const uint64_t* offsets, uint8_t* out) {
+  return hash_from_bytes_host(c, n, msgs, offsets, out, /*map=*/false);
+}
+#endif  // ZKP_BUILD_TEST_HOOKS
 
 #ifdef ZKP_BUILD_TEST_HOOKS
 int zkp_debug_quad_selftest(zkp_ctx* c, uint32_t n, const uint8_t* pairs, uint8_t* out) {

@@ -35,8 +35,9 @@ EXPORTS = (
     "zkp_fused_prove_submit", "zkp_fused_verify_compact_submit", "zkp_fused_batch_verify_many_submit", "zkp_fused_verify_batchable_submit",
     "zkp_fused_prove_seeded", "zkp_fused_batch_verify_many_seeded", "zkp_ctx_job_wait", "zkp_ctx_job_poll", "zkp_ctx_job_pending", "zkp_ctx_job_discard", "zkp_ctx_job_timing", "zkp_ctx_last_kernels", "zkp_host_alloc", "zkp_host_alloc_on", "zkp_host_numa_node", "zkp_host_node_of", "zkp_host_free", "zkp_host_register", "zkp_host_unregister",
     "zkp_host_is_pinned", "zkp_chacha20_fill_dev", "zkp_from_uniform_bytes", "zkp_from_uniform_bytes_dev", "zkp_fused_hash_to_group",
+    "zkp_hash_from_bytes_sha512", "zkp_hash_from_bytes_sha512_dev",
 )
-TEST_HOOK_EXPORTS = ("zkp_debug_quad_selftest", "zkp_debug_row_selftest", "zkp_debug_wave_cycles")      # only in libzkp_mi355x_testhooks.so
+TEST_HOOK_EXPORTS = ("zkp_debug_quad_selftest", "zkp_debug_row_selftest", "zkp_debug_wave_cycles", "zkp_debug_sha512")      # only in libzkp_mi355x_testhooks.so
 
 
 class ZkpError(RuntimeError):
@@ -77,6 +78,8 @@ def load_library(test_hooks: bool = False) -> ctypes.CDLL:
     lib.zkp_from_uniform_bytes.argtypes = [vp, ctypes.c_uint64, u8p, u8p]
     lib.zkp_from_uniform_bytes_dev.argtypes = [vp, ctypes.c_uint64, u8p, u8p]
     lib.zkp_fused_hash_to_group.argtypes = [vp, ctypes.c_uint32, u8p, ctypes.c_char_p, u8p]
+    lib.zkp_hash_from_bytes_sha512.argtypes = [vp, ctypes.c_uint64, u8p, ctypes.c_void_p, u8p]
+    lib.zkp_hash_from_bytes_sha512_dev.argtypes = [vp, ctypes.c_uint64, u8p, ctypes.c_uint64, ctypes.c_void_p, u8p]
     lib.zkp_ctx_last_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
     lib.zkp_ctx_set_profiling.argtypes = [vp, i32]
     lib.zkp_ctx_capture_begin.argtypes = [vp]
@@ -90,6 +93,7 @@ def load_library(test_hooks: bool = False) -> ctypes.CDLL:
         lib.zkp_debug_quad_selftest.argtypes = [vp, ctypes.c_uint32, u8p, u8p]
         lib.zkp_debug_row_selftest.argtypes = [vp, ctypes.c_uint32, u8p, u8p]
         lib.zkp_debug_wave_cycles.argtypes = [vp, ctypes.c_void_p, ctypes.c_uint32]
+        lib.zkp_debug_sha512.argtypes = [vp, ctypes.c_uint64, u8p, ctypes.c_void_p, u8p]
         _hooks_lib = lib
     else:
         _lib = lib
@@ -110,6 +114,28 @@ def _u8(a, shape_last: int) -> np.ndarray:
 
 def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+
+def messages_csr(messages) -> Tuple[np.ndarray, np.ndarray]:
+    """A list of byte strings as a CSR batch: (data uint8, offsets uint64 [n + 1]), message i = data[offsets[i]:offsets[i + 1]].  data
+    has at least one byte, so that its pointer is never NULL."""
+    msgs = [bytes(m) for m in messages]
+    offsets = np.zeros(len(msgs) + 1, np.uint64)
+    offsets[1:] = np.cumsum([len(m) for m in msgs], dtype=np.uint64)
+    data = np.frombuffer(b"".join(msgs) or b"\0", np.uint8).copy()
+    return data, offsets
+
+
+def _csr_args(data, offsets) -> Tuple[np.ndarray, np.ndarray]:
+    data = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+    if len(offsets) < 1:
+        raise ValueError("offsets must hold n + 1 entries")
+    if len(offsets) > 1 and (np.any(offsets[1:] < offsets[:-1]) or int(offsets[-1]) > len(data)):
+        raise ValueError("offsets must be non-decreasing and end within data")
+    if len(data) == 0:
+        data = np.zeros(1, np.uint8)
+    return data, offsets
 
 
 class Engine:
@@ -188,6 +214,28 @@ class Engine:
         _check(self._lib.zkp_from_uniform_bytes(self._h, len(inp), _ptr(inp), _ptr(out)), "zkp_from_uniform_bytes")
         return out
 
+    def hash_from_bytes_sha512(self, messages) -> np.ndarray:
+        """RistrettoPoint::hash_from_bytes::<Sha512> of every message (a list of byte strings) on the GPU -> encodings [n][32]"""
+        return self.hash_from_bytes_sha512_csr(*messages_csr(messages))
+
+    def hash_from_bytes_sha512_csr(self, data, offsets) -> np.ndarray:
+        """the same for a CSR batch held in numpy buffers: message i = data[offsets[i]:offsets[i + 1]]"""
+        data, offsets = _csr_args(data, offsets)
+        n = len(offsets) - 1
+        out = np.zeros((n, 32), np.uint8)
+        _check(self._lib.zkp_hash_from_bytes_sha512(self._h, n, _ptr(data), _ptr(offsets), _ptr(out)), "zkp_hash_from_bytes_sha512")
+        return out
+
+    def debug_sha512(self, data, offsets) -> np.ndarray:
+        """the SHA-512 stage alone (test-hook build): CSR batch -> digests [n][64]"""
+        if not self.test_hooks:
+            raise ZkpError("zkp_debug_sha512 exists in the test-hook build only: Engine(device, test_hooks=True)")
+        data, offsets = _csr_args(data, offsets)
+        n = len(offsets) - 1
+        out = np.zeros((n, 64), np.uint8)
+        _check(self._lib.zkp_debug_sha512(self._h, n, _ptr(data), _ptr(offsets), _ptr(out)), "zkp_debug_sha512")
+        return out
+
     def debug_quad_selftest(self, pairs) -> np.ndarray:
         pairs = _u8(pairs, 64)
         out = np.zeros((len(pairs), 4, 32), np.uint8)
@@ -239,6 +287,11 @@ class Engine:
     def from_uniform_bytes_dev(self, n, d_in, d_out) -> None:
         """zkp_from_uniform_bytes_dev: d_in [n][64] -> d_out [n][32], device pointers (16-byte aligned), queued on the context's stream"""
         _check(self._lib.zkp_from_uniform_bytes_dev(self._h, n, d_in, d_out), "zkp_from_uniform_bytes_dev")
+
+    def hash_from_bytes_sha512_dev(self, n, d_msgs, msgs_len, d_offsets, d_out) -> None:
+        """zkp_hash_from_bytes_sha512_dev: message i = d_msgs[d_offsets[i], d_offsets[i + 1]) (u64 offsets, 8-byte aligned) -> d_out [n][32]
+        (16-byte aligned), device pointers, queued on the context's stream"""
+        _check(self._lib.zkp_hash_from_bytes_sha512_dev(self._h, n, d_msgs, msgs_len, d_offsets, d_out), "zkp_hash_from_bytes_sha512_dev")
 
     # ---- fused statement flows on device-resident buffers (include/zkp_mi355x.h section 2c) -------------
     def fused_prove_dev(self, fst: "FusedStatement", n, strobe_pos, d_ts, d_secrets, d_table, d_entropy, d_chal, d_resp, d_coms, d_status) -> None:

@@ -18,7 +18,6 @@ marshals buffers.  Points are 32-byte ristretto255 encodings, scalars 32-byte li
 from __future__ import annotations
 
 import ctypes
-import hashlib
 import weakref
 import os
 from dataclasses import dataclass
@@ -47,7 +46,7 @@ EXPORTS = (
     "zkp_verify_batchable_each_submit", "zkp_batch_verify_many_submit", "zkp_job_done", "zkp_job_wait", "zkp_job_context_index", "zkp_pipe_prove_batch",
     "zkp_pipe_verify_compact_batch", "zkp_pipe_verify_batchable_each", "zkp_pipe_batch_verify", "zkp_pipe_batch_verify_many",
     "zkp_pipe_batch_verify_locate", "zkp_toolbox_set_host_max_terms", "zkp_toolbox_get_host_max_terms",
-    "zkp_from_uniform_bytes_batch", "zkp_hash_to_group_batch",
+    "zkp_from_uniform_bytes_batch", "zkp_hash_to_group_batch", "zkp_hash_from_bytes_sha512_batch",
 )
 ZKP_JOB_SHARED_TRANSCRIPT = 1
 ZKP_TB_PIPE_FULL = 3
@@ -124,6 +123,7 @@ def lib() -> ctypes.CDLL:
         _lib.zkp_pipe_batch_verify_locate.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp]
         _lib.zkp_from_uniform_bytes_batch.argtypes = [vp, ctypes.c_uint64, vp, i32, vp]
         _lib.zkp_hash_to_group_batch.argtypes = [vp, u32, vp, ctypes.c_char_p, i32, vp]
+        _lib.zkp_hash_from_bytes_sha512_batch.argtypes = [vp, ctypes.c_uint64, vp, vp, i32, vp]
     return _lib
 
 
@@ -511,9 +511,23 @@ def hash_to_group(eng, transcripts, label: bytes = b"output", threads: int = 0) 
 
 
 def hash_from_bytes_sha512(eng, messages, threads: int = 0) -> np.ndarray:
-    """RistrettoPoint::hash_from_bytes::<Sha512> (reference tests/zkp.rs:35) of every message: SHA-512 on the host, then the batched map."""
-    wide = np.frombuffer(b"".join(hashlib.sha512(bytes(m)).digest() for m in messages), np.uint8).reshape(-1, 64)
-    return from_uniform_bytes(eng, wide, threads)
+    """RistrettoPoint::hash_from_bytes::<Sha512> (reference tests/zkp.rs:35) of every message (a list of byte strings) -> encodings
+    [n][32].  eng = None (or a HostEngine) hashes and maps on the host threads; with an Engine, calls above get_host_max_terms()
+    messages run both on the GPU."""
+    from .engine import messages_csr
+    return hash_from_bytes_sha512_csr(eng, *messages_csr(messages), threads=threads)
+
+
+def hash_from_bytes_sha512_csr(eng, data, offsets, threads: int = 0) -> np.ndarray:
+    """hash_from_bytes_sha512 of a CSR batch already held in numpy buffers: message i = data[offsets[i]:offsets[i + 1]] (offsets: n + 1
+    entries, non-decreasing, uint64)."""
+    from .engine import _csr_args
+    data, offsets = _csr_args(data, offsets)
+    n = len(offsets) - 1
+    out = np.zeros((n, 32), np.uint8)
+    rc = lib().zkp_hash_from_bytes_sha512_batch(None if eng is None else eng._h, ctypes.c_uint64(n), _p(data), _p(offsets), threads, _p(out))
+    _raise(rc, "zkp_hash_from_bytes_sha512_batch")
+    return out
 
 
 
