@@ -511,11 +511,18 @@ int zkp_ctx_set_profiling(zkp_ctx* ctx, int enabled);
  *   ZKP_TESTOPT_WAVE_CYCLES = 1 switches on a per-wavefront cycle recorder in the term kernel (s_memtime at entry and exit);
  * zkp_debug_wave_cycles copies out (and clears) up to cap records, [block][wavefront 0..3] = block class << 56 | cycles (class 1 =
  *   ladder, 2 = comb scan, 3 = grouped comb walk, 4 = fixed-base; 0 = no record): the timing side of the constant-time evidence.
- * zkp_debug_sha512: the SHA-512 stage of zkp_hash_from_bytes_sha512 alone (same arguments and checks): out = [n][64] digests. */
+ * zkp_debug_sha512: the SHA-512 stage of zkp_hash_from_bytes_sha512 alone (same arguments and checks): out = [n][64] digests.
+ * zkp_debug_last_schedule: the size-driven choices the last call on ctx made, as "key=value" pairs separated by spaces (only the keys the
+ *   call decided): batch_encode (k_encode_* against k_reduce_encode), enc_groups (k_encode_invert blocks), opt_pip (zkp_msm_optional: Pippenger
+ *   against the term path), pip_c, pip_part, status_shared (batch verification's status words without memsets), lat_split, grouped, comb_min,
+ *   ladder_interleave, riders, straus_lanes, straus_wins, tr_lanes, tr_steps, fuse_tt (tables + transcript in one launch), terms_split (the
+ *   classified term path against one k_terms_r4 lane per term).  Writes a
+ *   NUL-terminated string of at most cap - 1 characters and returns the untruncated length. */
 int zkp_debug_quad_selftest(zkp_ctx* ctx, uint32_t n, const uint8_t* pairs /*[n][64]*/, uint8_t* out /*[n][128]*/);
 int zkp_debug_row_selftest(zkp_ctx* ctx, uint32_t n, const uint8_t* pairs /*[n][64]*/, uint8_t* out /*[n][96]*/);
 int zkp_debug_wave_cycles(zkp_ctx* ctx, uint64_t* out, uint32_t cap);     /* returns the number of records copied */
 int zkp_debug_sha512(zkp_ctx* ctx, uint64_t n, const uint8_t* msgs, const uint64_t* offsets /*[n+1]*/, uint8_t* out /*[n][64]*/);
+int zkp_debug_last_schedule(zkp_ctx* ctx, char* buf, size_t cap);
 enum { ZKP_TESTOPT_DUMMY_LAUNCHES = 1001, ZKP_TESTOPT_GENERIC_CLASSIFIER = 1002, ZKP_TESTOPT_WAVE_CYCLES = 1003 };
 #endif
 

@@ -967,6 +967,8 @@ void run_program(zkp_ctx* c, const prog_dev& p_in, uint32_t N, const tr_bufs& bu
   if (!p_in.n) return;
   prog_dev p = p_in;
   if (owns_failed) p.tail |= 0x80000000u;          // the kernel writes every proof's rejection flag, 0 included
+  ZKP_SCHED(c, TR_LANES, transcript_single_lane(c, N, throughput) ? 1 : 2);
+  ZKP_SCHED(c, TR_STEPS, transcript_steps(c, p, N, throughput, d_img));
   if (transcript_steps(c, p, N, throughput, d_img)) {
     prof_note(c, ZKP_K_TRANSCRIPT, "zkp::k_transcript_chain");
     tr_steps_dev sd = p.sd;
@@ -1002,10 +1004,15 @@ void offer_program(zkp_ctx* c, const prog_dev& p, uint32_t N, const tr_bufs& buf
   t.ops = p.ops; t.n_ops = p.n; t.tables = p.tables; t.N = N; t.bufs = bufs; t.ts = d_ts; t.saved = reinterpret_cast<uint32_t*>(d_saved); t.failed = d_failed; t.tail = p.tail;
   t.steps = transcript_steps(c, p, N, throughput, d_img);
   t.sd = p.sd; t.sd.tail = p.tail; t.img = d_img;
+  if (p.n) {
+    ZKP_SCHED(c, TR_LANES, transcript_single_lane(c, N, throughput) ? 1 : 2);
+    ZKP_SCHED(c, TR_STEPS, t.steps);
+  }
 }
 void run_program_pending(zkp_ctx* c, const prog_dev& p, uint32_t N, const tr_bufs& bufs, uint8_t* d_ts, uint64_t* d_saved, uint32_t* d_failed, bool throughput,
                          uint64_t* d_img) {
   const bool taken = c->pending_tr.offered && !c->pending_tr.active;      // the term path launched it with its tables
+  if (p.n) ZKP_SCHED(c, FUSE_TT, taken);
   c->pending_tr.offered = c->pending_tr.active = false;
   if (!taken) run_program(c, p, N, bufs, d_ts, d_saved, d_failed, throughput, d_img);
 }
@@ -1075,7 +1082,12 @@ prove_inter prove_carve(const fused_plan& pl, size_t start) {
   o.end = cv.off;
   return o;
 }
-int prove_core(zkp_ctx* c, const fused_plan& pl, const prove_inter& o, uint8_t* d_ts, const uint8_t* d_sec, const uint8_t* d_tbl,
+// the term-path configuration a prove call runs (its callers size the workspace with the same one)
+terms_cfg prove_terms_cfg(const zkp_ctx* c, const fused_plan& pl, bool throughput) {
+  return cfg_from_terms(pl.tpt.data(), pl.T1, pl.s.ns, pl.s.np, pl.N, c->ct_comb_min(throughput, (size_t)pl.N * pl.T1));
+}
+// ws_bound: the workspace bytes the caller ensured (o.end + terms_path_ws of prove_terms_cfg(c, pl, throughput))
+int prove_core(zkp_ctx* c, const fused_plan& pl, const prove_inter& o, size_t ws_bound, uint8_t* d_ts, const uint8_t* d_sec, const uint8_t* d_tbl,
                const uint8_t* d_ent, uint8_t* d_chal, uint8_t* d_resp, uint8_t* d_coms, uint8_t* d_st8, bool overlap, bool throughput,
                const std::function<int()>* late_inputs = nullptr, const std::function<int()>* early_outputs = nullptr, bool late_early = false) {
   const uint32_t N = pl.N, m = pl.s.m, nc = pl.s.nc, T = pl.T1, n_points = pl.s.ns + pl.s.ni * N;
@@ -1086,7 +1098,9 @@ int prove_core(zkp_ctx* c, const fused_plan& pl, const prove_inter& o, uint8_t* 
   uint64_t* d_saved = reinterpret_cast<uint64_t*>(w.base + o.saved);
   prof_begin(c);
   const size_t lanes = std::max<size_t>((size_t)N * T, (size_t)N * nc) + 1;
-  terms_cfg tk = cfg_from_terms(pl.tpt.data(), T, pl.s.ns, pl.s.np, N, c->ct_comb_min(throughput, (size_t)N * T));
+  terms_cfg tk = prove_terms_cfg(c, pl, throughput);
+  if (o.end + terms_path_ws(n_points, N * T, N * nc, tk) > ws_bound)
+    return fail(ZKP_ERR_ARG, "internal: prove_core's term path does not fit the workspace its caller sized");
   tk.throughput = throughput;
   if (pl.d_order) { tk.map.N = N; tk.map.nc = nc; tk.map.order = pl.d_order; }
   tk.stmt.toff = pl.d_tarr; tk.stmt.tpt = pl.d_tarr + nc + 1 + T; tk.stmt.N = N; tk.stmt.T = T; tk.stmt.nc = nc; tk.stmt.ns = pl.s.ns; tk.stmt.np = pl.s.np;
@@ -1180,8 +1194,10 @@ verify_inter verify_carve(const fused_plan& pl, size_t start) {
 // the verifier's CSR job: bounds, statement structure and -- where the statement classifier runs -- the pairs of terms that share a doubling chain
 // riders: tables of multiples for points whose terms all ride (stmt_rider).  A table is a chain of 127 additions on one lane: worth it where calls are wide or
 // overlap (throughput schedule, or >= kRiderLatencyProofs proofs) -- a lone synchronous call of 4096 CMZ proofs takes 1.89 ms with them and 1.55 ms without,
-// 16,384 proofs 4.14 - 4.21 against 4.18 - 4.20 ms.  Workspace bounds are taken with riders = true (the larger layout).
+// 16,384 proofs 4.14 - 4.21 against 4.18 - 4.20 ms.  The callers size the workspace with the configuration verify_core runs (verify_riders), and
+// verify_core checks that bound before it launches anything.
 constexpr uint32_t kRiderLatencyProofs = 16384;
+inline bool verify_riders(uint32_t N, bool throughput) { return throughput || N >= kRiderLatencyProofs; }
 terms_cfg verify_terms_cfg(const zkp_ctx* c, const fused_plan& pl, bool riders = true) {
   const uint32_t N = pl.N, nc = pl.s.nc, T1 = pl.T1;
   terms_cfg tk = cfg_from_terms(pl.tpt.data(), T1, pl.s.ns, pl.s.np, N, 2);
@@ -1196,9 +1212,13 @@ terms_cfg verify_terms_cfg(const zkp_ctx* c, const fused_plan& pl, bool riders =
   }
   return tk;
 }
-int verify_core(zkp_ctx* c, const fused_plan& pl, const verify_inter& o, uint8_t* d_ts, const uint8_t* d_tbl, const uint8_t* d_claim,
+// ws_bound: the workspace bytes the caller ensured (o.end + terms_path_ws of verify_terms_cfg(c, pl, verify_riders(N, throughput)))
+int verify_core(zkp_ctx* c, const fused_plan& pl, const verify_inter& o, size_t ws_bound, uint8_t* d_ts, const uint8_t* d_tbl, const uint8_t* d_claim,
                 const uint8_t* d_resp, uint8_t* d_results, bool overlap, bool throughput, const std::function<int()>* late_inputs = nullptr, bool late_early = false) {
   const uint32_t N = pl.N, m = pl.s.m, nc = pl.s.nc, T1 = pl.T1, n_points = pl.s.ns + pl.s.ni * N;
+  terms_cfg tk = verify_terms_cfg(c, pl, verify_riders(N, throughput));
+  if (o.end + terms_path_ws(n_points, N * T1, N * nc, tk) > ws_bound)
+    return fail(ZKP_ERR_ARG, "internal: verify_core's term path does not fit the workspace its caller sized");
   const ws_view w{static_cast<char*>(c->ws)};
   tr_bufs hb{};
   hb.src[SRC_TABLE] = d_tbl; hb.src[SRC_COMS] = w.u8(o.coms);
@@ -1206,7 +1226,6 @@ int verify_core(zkp_ctx* c, const fused_plan& pl, const verify_inter& o, uint8_t
   HIP_TRY(hipMemsetAsync(w.base + o.failed, 0, (size_t)N * 4, c->stream));
   prof_begin(c);
   const size_t lanes = std::max<size_t>((size_t)N * T1, (size_t)N * nc) + 1;
-  terms_cfg tk = verify_terms_cfg(c, pl, throughput || N >= kRiderLatencyProofs);
   tk.throughput = throughput;
   if (pl.d_order) { tk.map.N = N; tk.map.nc = nc; tk.map.order = pl.d_order; }
   tk.stmt.off = w.u32(o.off); tk.stmt.pidx = w.u32(o.pidx);
@@ -1299,6 +1318,7 @@ int batch_core(zkp_ctx* c, const fused_plan& pl, const batch_inter& o, uint8_t* 
   }
   if (!shared) HIP_TRY(hipMemsetAsync(d_status, 0, 8, c->stream));
   prof_begin(c);
+  ZKP_SCHED(c, STATUS_SHARED, shared != nullptr);
   uint64_t* d_img = pl.img_bytes ? reinterpret_cast<uint64_t*>(w.base + o.img) : nullptr;
   // Latency schedule (one call in flight: the synchronous entry points, ZKP_OPT_DEV_OVERLAP = 2): the point half of the MSM's prepare step -- 24 N + 12
   // decompressions, batch_verifier.rs:226, which no scalar enters -- runs on the side stream next to the transcript chain (0.13 of a lone call's 0.85 ms
@@ -1467,6 +1487,8 @@ int each_core(zkp_ctx* c, const fused_plan& pl, const each_inter& o, uint8_t* d_
   if (straus) {
     dev_ext* spart = reinterpret_cast<dev_ext*>(w.base + so.spart);
     const uint32_t Wn = straus_win_parts(c, pl), L = Wn ? 1 : straus_lanes(c, pl);
+    ZKP_SCHED(c, STRAUS_WINS, Wn);
+    ZKP_SCHED(c, STRAUS_LANES, L);
     if (Wn) hipLaunchKernelGGL(k_straus_recode, grid1((size_t)N * K, 256), dim3(256), 0, c->stream, N * K, w.u8(o.sc), w.u32(so.digits));
     const int rcj = side_join(c, overlap);
     if (rcj) return rcj;
@@ -1588,9 +1610,10 @@ int zkp_fused_prove_dev(zkp_ctx* c, const zkp_fused_statement* st, uint32_t N, u
     return fail(ZKP_ERR_ARG, "NULL device pointer");
   if ((uint64_t)N * s.T > 0x7fffffffull || (uint64_t)s.ns + (uint64_t)s.ni * N > 0x7fffffffull) return fail(ZKP_ERR_ARG, "batch too large");
   const prove_inter o = prove_carve(*pl, 0);
-  rc = ensure_ws(c, o.end + terms_path_ws(s.ns + s.ni * N, N * s.T, N * s.nc, cfg_from_terms(pl->tpt.data(), s.T, s.ns, s.np, N, c->ct_comb_min(!c->dev_latency, (size_t)N * s.T))));
+  const size_t ws_need = o.end + terms_path_ws(s.ns + s.ni * N, N * s.T, N * s.nc, prove_terms_cfg(c, *pl, !c->dev_latency));
+  rc = ensure_ws(c, ws_need);
   if (rc) return rc;
-  return prove_core(c, *pl, o, d_transcripts, d_secrets, d_table, d_entropy, d_challenges, d_responses, d_commitments, d_status, /*overlap=*/c->dev_overlap, /*throughput=*/!c->dev_latency);
+  return prove_core(c, *pl, o, ws_need, d_transcripts, d_secrets, d_table, d_entropy, d_challenges, d_responses, d_commitments, d_status, /*overlap=*/c->dev_overlap, /*throughput=*/!c->dev_latency);
 }
 
 // ---- verify_compact --------------------------------------------------------------------------------------------------
@@ -1606,9 +1629,10 @@ int zkp_fused_verify_compact_dev(zkp_ctx* c, const zkp_fused_statement* st, uint
   if (!d_transcripts || !d_challenges || !d_results || (s.m && !d_responses) || (s.np && !d_table)) return fail(ZKP_ERR_ARG, "NULL device pointer");
   if ((uint64_t)N * pl->T1 > 0x7fffffffull || (uint64_t)s.ns + (uint64_t)s.ni * N > 0x7fffffffull) return fail(ZKP_ERR_ARG, "batch too large");
   const verify_inter o = verify_carve(*pl, 0);
-  rc = ensure_ws(c, o.end + terms_path_ws(s.ns + s.ni * N, N * pl->T1, N * s.nc, verify_terms_cfg(c, *pl)));
+  const size_t ws_need = o.end + terms_path_ws(s.ns + s.ni * N, N * pl->T1, N * s.nc, verify_terms_cfg(c, *pl, verify_riders(N, !c->dev_latency)));
+  rc = ensure_ws(c, ws_need);
   if (rc) return rc;
-  return verify_core(c, *pl, o, d_transcripts, d_table, d_challenges, d_responses, d_results, /*overlap=*/c->dev_overlap, /*throughput=*/!c->dev_latency);
+  return verify_core(c, *pl, o, ws_need, d_transcripts, d_table, d_challenges, d_responses, d_results, /*overlap=*/c->dev_overlap, /*throughput=*/!c->dev_latency);
 }
 
 // ---- batch verification ----------------------------------------------------------------------------------------------

@@ -215,7 +215,8 @@ int prove_job(zkp_ctx* c, const zkp_fused_statement* st, uint32_t N, uint32_t fl
   const size_t o_blob = cv.take(256);
   const size_t o_flag = cv.take(16);
   const prove_inter o = prove_carve(*pl, cv.off);
-  rc = ensure_ws(c, o.end + terms_path_ws(n_points, N * s.T, N * s.nc, cfg_from_terms(pl->tpt.data(), s.T, s.ns, s.np, N, c->ct_comb_min(!sync_variant, (size_t)N * s.T))));
+  const size_t ws_need = o.end + terms_path_ws(n_points, N * s.T, N * s.nc, prove_terms_cfg(c, *pl, !sync_variant));
+  rc = ensure_ws(c, ws_need);
   if (rc) return rc;
   rc = job_begin(c, 16);
   if (rc) return rc;
@@ -240,7 +241,7 @@ int prove_job(zkp_ctx* c, const zkp_fused_statement* st, uint32_t N, uint32_t fl
   };
   if (!sync_variant) ZKP_JOB_TRY(rest());
   job_mark(c, 1);
-  ZKP_JOB_TRY(prove_core(c, *pl, o, w.u8(o_ts), w.u8(o_sec), w.u8(o_tbl), w.u8(o_ent), w.u8(o_chal), w.u8(o_resp), w.u8(o_coms), w.u8(o_st), /*overlap=*/sync_variant,
+  ZKP_JOB_TRY(prove_core(c, *pl, o, ws_need, w.u8(o_ts), w.u8(o_sec), w.u8(o_tbl), w.u8(o_ent), w.u8(o_chal), w.u8(o_resp), w.u8(o_coms), w.u8(o_st), /*overlap=*/sync_variant,
                          /*throughput=*/!sync_variant, sync_variant ? &rest : nullptr, sync_variant ? &early : nullptr,
                          /*late_early=*/zkp_host_is_pinned(transcripts) && (!m || zkp_host_is_pinned(secrets)) && (!entropy || zkp_host_is_pinned(entropy))));
   job_mark(c, 2);
@@ -283,7 +284,8 @@ int verify_compact_job(zkp_ctx* c, const zkp_fused_statement* st, uint32_t N, ui
   const size_t o_res = cv.take((size_t)N);
   const size_t o_blob = cv.take(256);
   const verify_inter o = verify_carve(*pl, cv.off);
-  rc = ensure_ws(c, o.end + terms_path_ws(n_points, N * pl->T1, N * s.nc, verify_terms_cfg(c, *pl)));
+  const size_t ws_need = o.end + terms_path_ws(n_points, N * pl->T1, N * s.nc, verify_terms_cfg(c, *pl, verify_riders(N, !sync_variant)));
+  rc = ensure_ws(c, ws_need);
   if (rc) return rc;
   rc = job_begin(c, 16);
   if (rc) return rc;
@@ -300,7 +302,7 @@ int verify_compact_job(zkp_ctx* c, const zkp_fused_statement* st, uint32_t N, ui
   };
   if (!sync_variant) ZKP_JOB_TRY(rest());
   job_mark(c, 1);
-  ZKP_JOB_TRY(verify_core(c, *pl, o, w.u8(o_ts), w.u8(o_tbl), w.u8(o_claim), w.u8(o_resp), w.u8(o_res), /*overlap=*/sync_variant, /*throughput=*/!sync_variant,
+  ZKP_JOB_TRY(verify_core(c, *pl, o, ws_need, w.u8(o_ts), w.u8(o_tbl), w.u8(o_claim), w.u8(o_resp), w.u8(o_res), /*overlap=*/sync_variant, /*throughput=*/!sync_variant,
                           sync_variant ? &rest : nullptr, /*late_early=*/zkp_host_is_pinned(transcripts) && zkp_host_is_pinned(challenges) && (!m || zkp_host_is_pinned(responses))));
   job_mark(c, 2);
   ZKP_JOB_TRY(d2h(c, results, w.base + o_res, (size_t)N));

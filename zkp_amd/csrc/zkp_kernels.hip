@@ -210,6 +210,8 @@ k_terms_split(const uint8_t* __restrict__ scalars, const uint32_t* __restrict__ 
         const uint32_t pi = pidx[t];                              // < n_points (out-of-range indices are classed with the comb terms)
         uint4* tbl = reinterpret_cast<uint4*>(ladder_rw) + (size_t)(i >> 6) * LADDER_GROUP_UINT4 + (i & 63u);
         bool joint = false;
+        // a variable-time paired job must never compile without the joint ladder below (its second terms would be dropped)
+        static_assert(CT || terms_lds_uint4<LOOKUP>() >= 1024, "variable-time ladder blocks need LDS for two recoded scalars");
         if constexpr (!CT && terms_lds_uint4<LOOKUP>() >= 1024) {  // (16 words of LDS per lane for the two recoded scalars)
           // pair (variable-time statement jobs): this term carries another term of its MSM through its doublings; the tables of the second points lie behind
           // those of the first ones
@@ -1376,6 +1378,10 @@ struct zkp_ctx {
 #ifdef ZKP_BUILD_TEST_HOOKS
   uint64_t* wave_cycles = nullptr;   // ZKP_TESTOPT_WAVE_CYCLES: per-wavefront cycle recorder of the term kernel
   static constexpr uint32_t kWaveCyclesCap = 1u << 20;
+  // zkp_debug_last_schedule: the size-driven choices the last call made (cleared by prof_begin; -1 = the call did not make it)
+  enum { SCH_BATCH_ENCODE, SCH_ENC_GROUPS, SCH_OPT_PIP, SCH_PIP_C, SCH_PIP_PART, SCH_STATUS_SHARED, SCH_LAT_SPLIT, SCH_GROUPED, SCH_COMB_MIN,
+         SCH_LADDER_INTERLEAVE, SCH_RIDERS, SCH_STRAUS_LANES, SCH_STRAUS_WINS, SCH_TR_LANES, SCH_TR_STEPS, SCH_FUSE_TT, SCH_TERMS_SPLIT, SCH_COUNT };
+  int64_t sched[SCH_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
 #endif
   static constexpr size_t kGroupedCombTerms = 400000;
   static constexpr size_t kSplitCombTerms = 8192;   // narrow constant-time calls on the latency schedule from this many terms on: grouped walk + quad-split scans (ZKP_OPT_COMB_SPLIT)
@@ -1489,7 +1495,16 @@ void prof_note(zkp_ctx* c, int kind, const std::string& name) {
   std::string& s = c->kernel_names[kind];
   if ((";" + s + ";").find(";" + name + ";") == std::string::npos) s += (s.empty() ? "" : ";") + name;
 }
+// test-hook builds: note a size-driven choice of the running call for zkp_debug_last_schedule (the shipped library records nothing)
+#ifdef ZKP_BUILD_TEST_HOOKS
+#define ZKP_SCHED(c, key, v) ((c)->sched[zkp_ctx::SCH_##key] = (int64_t)(v))
+#else
+#define ZKP_SCHED(c, key, v) ((void)0)
+#endif
 void prof_begin(zkp_ctx* c) {
+#ifdef ZKP_BUILD_TEST_HOOKS
+  for (int64_t& v : c->sched) v = -1;
+#endif
   c->n_ev = 0;
   if (c->profiling && !c->capturing) for (auto& s : c->kernel_names) s.clear();
   if (c->profiling && !c->capturing) { hipEventRecord(c->ev[0], c->stream); c->ev_kind[0] = -1; c->n_ev = 1; }
@@ -1587,7 +1602,9 @@ void launch_terms_split(zkp_ctx* c, dim3 grid, bool ladder, const uint8_t* d_sca
   // ladder blocks spread over the first half of the grid (ZKP_OPT_LADDER_INTERLEAVE), or all at the front
   uint32_t stride = 0;
   const uint32_t lb = (max_ladder + 255) / 256;
-  if (ladder && lb && (c->ladder_interleave < 0 ? lb >= zkp_ctx::kInterleaveLadderBlocks : c->ladder_interleave != 0)) {
+  const bool interleave = ladder && lb && (c->ladder_interleave < 0 ? lb >= zkp_ctx::kInterleaveLadderBlocks : c->ladder_interleave != 0);
+  if (ladder && lb) ZKP_SCHED(c, LADDER_INTERLEAVE, interleave);
+  if (interleave) {
     stride = (grid.x / 2) / lb;
     // ODD: workgroups go to the 8 XCDs round robin by their index, so an even stride puts every ladder block -- the long ones, 1.65 M cycles each -- on half, a
     // stride of 16 on ONE of the XCDs, and the launch ends in a tail on 32 CUs (round 5: 524,288 CMZ proofs 34 -> 87 ms when a 3 % larger grid moved the stride
@@ -1626,10 +1643,17 @@ int msm_terms_path(zkp_ctx* c, uint32_t n_msm, const uint32_t* d_off, const uint
   const uint32_t enc_blocks = (n_msm + ENC_BLOCK - 1) / ENC_BLOCK;
   // ensure_ws was done by the caller for ws_reserved + this much; recompute defensively
   if (o.end > c->ws_bytes) return fail(ZKP_ERR_ARG, "internal: workspace too small");
+  const bool terms_split = n_terms >= 1024;                          // classified terms (k_terms_split) against one k_terms_r4 lane per term
+  const uint32_t enc_groups = (enc_blocks + ENC_BLOCK - 1) / ENC_BLOCK;  // k_encode_invert blocks of the batched encoder
+  if (phase & PH_SCALARS) {
+    ZKP_SCHED(c, TERMS_SPLIT, terms_split);
+    ZKP_SCHED(c, BATCH_ENCODE, batched_encode);
+    if (batched_encode) ZKP_SCHED(c, ENC_GROUPS, enc_groups);
+  }
   char* base = static_cast<char*>(c->ws);
   dev_affine* pts = reinterpret_cast<dev_affine*>(base + o.pts);
   dev_ext* part = reinterpret_cast<dev_ext*>(base + o.part);
-  if (n_terms >= 1024) {
+  if (terms_split) {
     // split the terms: those on a registered fixed-base point (grouped by table) / those on a point with a comb table
     // built here (two or more cold uses) / single-use points on a ladder
     int32_t* hotmap = reinterpret_cast<int32_t*>(base + o.hot);
@@ -1653,6 +1677,9 @@ int msm_terms_path(zkp_ctx* c, uint32_t n_msm, const uint32_t* d_off, const uint
                           : c->grouped_comb < 0 ? (n_terms >= (k.throughput ? zkp_ctx::kWideCallTerms : zkp_ctx::kGroupedCombTerms) || lat_split) : c->grouped_comb != 0;
     const bool comb_split = lat_split && flags == ZKP_CT && k.teeth == 16 && !(HOT_LDS_ROWS && c->ct_lookup != LOOKUP_XBAR);
     const uint32_t group_min = (flags == ZKP_CT && k.teeth == 16 && group_on && k.max_tables) ? GROUP_MIN_USES : 0xffffffffu;
+    ZKP_SCHED(c, LAT_SPLIT, lat_split);
+    ZKP_SCHED(c, GROUPED, group_on);
+    ZKP_SCHED(c, COMB_MIN, comb_min);
     // (a caller that pairs terms sized its bounds for the pairs: it only does so where the statement classifier runs)
     const bool pair_on = k.stmt.pair && flags == ZKP_VARTIME && stmt_classify_applies(k, n_terms);
     if (k.stmt.pair && !pair_on) return fail(ZKP_ERR_ARG, "paired terms outside the statement classifier");
@@ -1660,6 +1687,7 @@ int msm_terms_path(zkp_ctx* c, uint32_t n_msm, const uint32_t* d_off, const uint
     if (pair_on && !decode_all) return fail(ZKP_ERR_ARG, "paired terms need decode_all");
     // riders whose point has no other term get a table of multiples in a 16-teeth comb table's place (stmt_pairs.h: stmt_rider; the plan's bounds count them)
     const bool rider_ok = pair_on && k.teeth == 16 && k.rider_tables;
+    if (pair_on) ZKP_SCHED(c, RIDERS, rider_ok);
     uint32_t* gstart = reinterpret_cast<uint32_t*>(base + o.gstart);
     uint32_t* gfill = reinterpret_cast<uint32_t*>(base + o.gfill);
     if ((phase & PH_POINTS) && stmt_classify_applies(k, n_terms)) {
@@ -1763,7 +1791,7 @@ int msm_terms_path(zkp_ctx* c, uint32_t n_msm, const uint32_t* d_off, const uint
       hipLaunchKernelGGL(k_encode_prepare<uint8_t>, dim3(enc_blocks), dim3(ENC_BLOCK), 0, c->stream, n_msm, d_off, d_pidx, n_points, pts, part, states, xs, bprod, zflag, d_status8, k.map);
     else
       hipLaunchKernelGGL(k_encode_prepare<uint32_t>, dim3(enc_blocks), dim3(ENC_BLOCK), 0, c->stream, n_msm, d_off, d_pidx, n_points, pts, part, states, xs, bprod, zflag, d_status32, k.map);
-    hipLaunchKernelGGL(k_encode_invert, dim3((enc_blocks + ENC_BLOCK - 1) / ENC_BLOCK), dim3(ENC_BLOCK), 0, c->stream, enc_blocks, bprod, binv);
+    hipLaunchKernelGGL(k_encode_invert, dim3(enc_groups), dim3(ENC_BLOCK), 0, c->stream, enc_blocks, bprod, binv);
     hipLaunchKernelGGL(k_encode_finish, dim3(enc_blocks), dim3(ENC_BLOCK), 0, c->stream, n_msm, d_off, d_pidx, n_points, pts, part, states, xs, binv, zflag,
                        (const uint8_t*)d_status8, (const uint32_t*)d_status32, d_out, k.map);
   } else if (n_msm) {
@@ -1829,6 +1857,8 @@ int pip_run(zkp_ctx* c, uint32_t n, const uint8_t* d_scalars, const uint8_t* d_p
   uint32_t* tilehist = reinterpret_cast<uint32_t*>(base + cv.take(WK * tiles * cfg::B1 * 4));
   const uint32_t L = pip_part_len(n);
   const size_t vmax = pip_vmax<C>(n);
+  ZKP_SCHED(c, PIP_C, C);
+  ZKP_SCHED(c, PIP_PART, L);
   dev_ext* parts = reinterpret_cast<dev_ext*>(base + cv.take(WK * vmax * sizeof(dev_ext)));
   uint32_t* vmap = reinterpret_cast<uint32_t*>(base + cv.take(WK * vmax * 4));
   uint32_t* invalid = reinterpret_cast<uint32_t*>(base + cv.take((size_t)K * 4 + 256));
@@ -2402,6 +2432,7 @@ int zkp_msm_many(zkp_ctx* c, uint32_t n_msm, const uint32_t* off, const uint8_t*
 // whose bit 1 the caller may have set; the last kernel then writes status[0] = bit 0 and status[1] = bit 1 (no memsets)
 static int msm_optional_impl(zkp_ctx* c, uint64_t n, const uint8_t* d_scalars, const uint8_t* d_points,
                              uint8_t* d_out, uint32_t* d_status, size_t reserved, uint32_t* shared_flags = nullptr, int phases = 3) {
+  ZKP_SCHED(c, OPT_PIP, n > kSmallOptional);
   if (n <= kSmallOptional) {
     if (shared_flags) return fail(ZKP_ERR_ARG, "internal: shared flags with a small MSM");
     carve cv;
@@ -2572,6 +2603,19 @@ int zkp_hash_from_bytes_sha512_dev(zkp_ctx* c, uint64_t n, const uint8_t* d_msgs
 }
 
 #ifdef ZKP_BUILD_TEST_HOOKS
+int zkp_debug_last_schedule(zkp_ctx* c, char* buf, size_t cap) {
+  if (!c || !buf || !cap) return fail(ZKP_ERR_ARG, "bad argument");
+  static const char* const names[zkp_ctx::SCH_COUNT] = {"batch_encode", "enc_groups", "opt_pip", "pip_c", "pip_part", "status_shared", "lat_split", "grouped", "comb_min",
+                                                        "ladder_interleave", "riders", "straus_lanes", "straus_wins", "tr_lanes", "tr_steps", "fuse_tt", "terms_split"};
+  std::string s;
+  for (int i = 0; i < zkp_ctx::SCH_COUNT; ++i)
+    if (c->sched[i] >= 0) s += (s.empty() ? "" : " ") + std::string(names[i]) + "=" + std::to_string(c->sched[i]);
+  const size_t n = std::min(s.size(), cap - 1);
+  memcpy(buf, s.data(), n);
+  buf[n] = 0;
+  return (int)s.size();
+}
+
 int zkp_debug_sha512(zkp_ctx* c, uint64_t n, const uint8_t* msgs, const uint64_t* offsets, uint8_t* out) {
   return hash_from_bytes_host(c, n, msgs, offsets, out, /*map=*/false);
 }

@@ -37,7 +37,7 @@ EXPORTS = (
     "zkp_host_is_pinned", "zkp_chacha20_fill_dev", "zkp_from_uniform_bytes", "zkp_from_uniform_bytes_dev", "zkp_fused_hash_to_group",
     "zkp_hash_from_bytes_sha512", "zkp_hash_from_bytes_sha512_dev",
 )
-TEST_HOOK_EXPORTS = ("zkp_debug_quad_selftest", "zkp_debug_row_selftest", "zkp_debug_wave_cycles", "zkp_debug_sha512")      # only in libzkp_mi355x_testhooks.so
+TEST_HOOK_EXPORTS = ("zkp_debug_quad_selftest", "zkp_debug_row_selftest", "zkp_debug_wave_cycles", "zkp_debug_sha512", "zkp_debug_last_schedule")      # only in libzkp_mi355x_testhooks.so
 
 
 class ZkpError(RuntimeError):
@@ -94,6 +94,7 @@ def load_library(test_hooks: bool = False) -> ctypes.CDLL:
         lib.zkp_debug_row_selftest.argtypes = [vp, ctypes.c_uint32, u8p, u8p]
         lib.zkp_debug_wave_cycles.argtypes = [vp, ctypes.c_void_p, ctypes.c_uint32]
         lib.zkp_debug_sha512.argtypes = [vp, ctypes.c_uint64, u8p, ctypes.c_void_p, u8p]
+        lib.zkp_debug_last_schedule.argtypes = [vp, ctypes.c_char_p, ctypes.c_size_t]
         _hooks_lib = lib
     else:
         _lib = lib
@@ -264,6 +265,17 @@ class Engine:
         buf = buf[:n]
         buf = buf[buf != 0]
         return (buf >> np.uint64(56)).astype(np.int64), (buf & np.uint64((1 << 56) - 1)).astype(np.int64)
+
+    def last_schedule(self) -> dict:
+        """(test-hook build) {choice: value} of the size-driven choices the last call made (zkp_debug_last_schedule), e.g.
+        {"batch_encode": 1, "enc_groups": 2}; choices the call did not make are absent"""
+        if not self.test_hooks:
+            raise ZkpError("zkp_debug_last_schedule exists in the test-hook build only: Engine(device, test_hooks=True)")
+        buf = ctypes.create_string_buffer(1024)
+        n = self._lib.zkp_debug_last_schedule(self._h, buf, 1024)
+        if n < 0:
+            _check(n, "zkp_debug_last_schedule")
+        return {k: int(v) for k, v in (kv.split("=") for kv in buf.value.decode().split())}
 
     def prepare_fixed_points(self, encodings) -> None:
         """Hint: these points (the statement's common / static points) will be referenced by many terms."""
