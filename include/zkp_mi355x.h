@@ -319,6 +319,21 @@ int zkp_fused_verify_batchable_coeffs(zkp_ctx* ctx, const zkp_fused_statement* s
                                       const uint8_t* responses, const uint8_t* weights16, uint8_t* results,
                                       uint8_t* debug_scalars);
 
+/* Ragged batches: the calls above for transcripts at different STROBE positions (aligned batches are accepted too).  Synchronous, host
+ * pointers, ZKP_ERR_ARG during graph capture.  Prove takes entropy [N][32] or a 40-byte seed, batch verification weights16 or a seed: exactly one. */
+int zkp_fused_prove_ragged(zkp_ctx* ctx, const zkp_fused_statement* st, uint32_t N, uint8_t* transcripts, const uint8_t* secrets,
+                           const uint8_t* inst, const uint8_t* common, const uint8_t* entropy, const uint8_t seed[40], uint8_t* challenges,
+                           uint8_t* responses, uint8_t* commitments, int* invalid_point);
+int zkp_fused_verify_compact_ragged(zkp_ctx* ctx, const zkp_fused_statement* st, uint32_t N, uint8_t* transcripts,
+                                    const uint8_t* inst, const uint8_t* common, const uint8_t* challenges,
+                                    const uint8_t* responses, uint8_t* results);
+int zkp_fused_verify_batchable_ragged(zkp_ctx* ctx, const zkp_fused_statement* st, uint32_t N, uint8_t* transcripts,
+                                      const uint8_t* inst, const uint8_t* common, const uint8_t* commitments,
+                                      const uint8_t* responses, const uint8_t* weights16, uint8_t* results);
+int zkp_fused_batch_verify_many_ragged(zkp_ctx* ctx, const zkp_fused_statement* st, uint32_t n_batches, uint32_t N_each, uint8_t* transcripts,
+                                       const uint8_t* inst, const uint8_t* common, const uint8_t* commitments, const uint8_t* responses,
+                                       const uint8_t* weights16, const uint8_t seed[40], int* verdicts);
+
 /*     Device-resident variants: every buffer is a device pointer (16-byte aligned), nothing is copied and the call
  *     returns as soon as the work is queued on the context's stream (zkp_ctx_synchronize to wait).  strobe_pos =
  *     pos | pos_begin << 8 | cur_flags << 16, the three trailing bytes every one of the N transcript blobs holds.
@@ -455,6 +470,8 @@ int zkp_from_uniform_bytes_dev(zkp_ctx* ctx, uint64_t n, const uint8_t* d_in /*[
  *     (ZKP_ERR_ARG otherwise), and they are advanced in place exactly as merlin advances them.  Host pointers, synchronous.
  *     The squeeze is timed under ZKP_K_TRANSCRIPT, the map under ZKP_K_DECODE. */
 int zkp_fused_hash_to_group(zkp_ctx* ctx, uint32_t N, uint8_t* transcripts /*[N][208]*/, const char* label, uint8_t* out /*[N][32]*/);
+/*     The same for transcripts at any mix of STROBE positions. */
+int zkp_fused_hash_to_group_ragged(zkp_ctx* ctx, uint32_t N, uint8_t* transcripts /*[N][208]*/, const char* label, uint8_t* out /*[N][32]*/);
 /*     n x RistrettoPoint::hash_from_bytes::<Sha512>(message) (reference tests/zkp.rs:34): SHA-512 (FIPS 180-4) of each message,
  *     then from_uniform_bytes above.  The messages are a CSR batch: message i = msgs[offsets[i], offsets[i + 1]), of any length
  *     and at any byte offset.  Lengths are public: branches depend on them, never on message bytes.  One lane hashes one message,
@@ -516,13 +533,17 @@ int zkp_ctx_set_profiling(zkp_ctx* ctx, int enabled);
  *   call decided): batch_encode (k_encode_* against k_reduce_encode), enc_groups (k_encode_invert blocks), opt_pip (zkp_msm_optional: Pippenger
  *   against the term path), pip_c, pip_part, status_shared (batch verification's status words without memsets), lat_split, grouped, comb_min,
  *   ladder_interleave, riders, straus_lanes, straus_wins, tr_lanes, tr_steps, fuse_tt (tables + transcript in one launch), terms_split (the
- *   classified term path against one k_terms_r4 lane per term).  Writes a
+ *   classified term path against one k_terms_r4 lane per term), ragged_classes, ragged_compiled, ragged_base and fused_plans (the _ragged calls:
+ *   position classes, class programs compiled by this call, 1 if it built its position-free base plan, the size of the aligned plan cache).  Writes a
  *   NUL-terminated string of at most cap - 1 characters and returns the untruncated length. */
 int zkp_debug_quad_selftest(zkp_ctx* ctx, uint32_t n, const uint8_t* pairs /*[n][64]*/, uint8_t* out /*[n][128]*/);
 int zkp_debug_row_selftest(zkp_ctx* ctx, uint32_t n, const uint8_t* pairs /*[n][64]*/, uint8_t* out /*[n][96]*/);
 int zkp_debug_wave_cycles(zkp_ctx* ctx, uint64_t* out, uint32_t cap);     /* returns the number of records copied */
 int zkp_debug_sha512(zkp_ctx* ctx, uint64_t n, const uint8_t* msgs, const uint64_t* offsets /*[n+1]*/, uint8_t* out /*[n][64]*/);
 int zkp_debug_last_schedule(zkp_ctx* ctx, char* buf, size_t cap);
+/* zkp_debug_ragged_blocks: the class grouping the _ragged calls launch: idx [N] = proof indices sorted stably by class, blocks [cap][3] =
+ * (class, first, count) per wavefront, classes in order of first appearance.  Returns the number of blocks. */
+int zkp_debug_ragged_blocks(const uint8_t* transcripts, uint32_t N, uint32_t* idx, uint32_t* blocks, uint32_t cap);
 enum { ZKP_TESTOPT_DUMMY_LAUNCHES = 1001, ZKP_TESTOPT_GENERIC_CLASSIFIER = 1002, ZKP_TESTOPT_WAVE_CYCLES = 1003 };
 #endif
 

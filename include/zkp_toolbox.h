@@ -45,6 +45,10 @@ void zkp_transcript_init(uint8_t t[ZKP_TRANSCRIPT_BYTES], const uint8_t* label, 
  * silently truncated length prefix.  Returns ZKP_TB_OK otherwise. */
 int zkp_transcript_append_message(uint8_t t[ZKP_TRANSCRIPT_BYTES], const char* label, const uint8_t* msg, size_t len);
 int zkp_transcript_challenge_bytes(uint8_t t[ZKP_TRANSCRIPT_BYTES], const char* label, uint8_t* out, size_t len);
+/* N x append_message(label, msgs[offsets[j], offsets[j + 1])) on host threads; shared_initial != 0: every transcript starts from ts[0].  The
+ * ZKP_TB_TOO_LONG rule above per message; decreasing offsets or NULL buffers are ZKP_TB_BAD_STATEMENT; nothing changes on an error. */
+int zkp_transcripts_append_message_batch(uint8_t* ts /*[N][208]*/, uint32_t N, int shared_initial, const char* label, const uint8_t* msgs,
+                                         const uint64_t* offsets /*[N + 1]*/, int n_threads);
 
 /* ---- scalars mod l (curve25519_dalek::scalar::Scalar) -------------------------------------------- */
 void zkp_scalar_from_wide(uint8_t out[32], const uint8_t in[64]);   /* from_bytes_mod_order_wide */
@@ -232,9 +236,9 @@ int zkp_pipe_batch_verify_locate(zkp_pipe* pipe, const zkp_statement* st, uint32
                                  const uint8_t* inst_points, const uint8_t* common_points, const uint8_t* commitments,
                                  const uint8_t* responses, const uint8_t* weights16, uint8_t* results);
 
-/* Batches of at least this many proofs whose transcripts stand at one STROBE position run entirely on the device
- * (zkp_mi355x.h section 2c: transcripts, scalars and MSMs); smaller or ragged batches hash their transcripts on the
- * host threads and use the GPU for the group arithmetic only.  Both routes produce the same bytes.  Default 32 (the measured crossover for the CMZ statement);
+/* Batches of at least this many proofs run entirely on the device (zkp_mi355x.h section 2c: transcripts, scalars and MSMs); ragged
+ * batches (transcripts at different STROBE positions) through the _ragged calls, except zkp_batch_verify_coeffs.  Smaller batches hash
+ * their transcripts on the host threads and use the GPU for the group arithmetic only.  Both routes produce the same bytes.  Default 32 (the measured crossover for the CMZ statement);
  * 0 = always fused, UINT32_MAX = never. */
 void zkp_toolbox_set_fused_min_batch(uint32_t n);
 /* Host backend (zkp_amd/csrc/host/host_backend.cpp: the kernels' own point formulas and ristretto codec compiled for the host over a
@@ -254,7 +258,8 @@ uint32_t zkp_toolbox_get_fused_min_batch(void);
  * zkp_hash_to_group_batch: N x { transcript.challenge_bytes(label, 64) ; from_uniform_bytes } -- the `hash_to_group` of
  *   tests/sig_and_vrf_example.rs:36-40 -- with the transcripts [N][208] advanced in place as merlin advances them.  With a context, batches
  *   of at least fused_min_batch transcripts that stand at one STROBE position squeeze on the device (zkp_fused_hash_to_group); the others
- *   squeeze on the host threads and map as zkp_from_uniform_bytes_batch does.  Same bytes on every route.
+ *   squeeze on the host threads and map as zkp_from_uniform_bytes_batch does; batches of transcripts at different positions squeeze on the
+ *   device per position class (zkp_fused_hash_to_group_ragged).  Same bytes on every route.
  * Both: n = 0 is a no-op; a NULL buffer (with n > 0) or a NULL label is ZKP_TB_BAD_STATEMENT; the map never fails. */
 int zkp_from_uniform_bytes_batch(zkp_ctx* ctx, uint64_t n, const uint8_t* in /*[n][64]*/, int n_threads, uint8_t* out /*[n][32]*/);
 int zkp_hash_to_group_batch(zkp_ctx* ctx, uint32_t N, uint8_t* transcripts /*[N][208]*/, const char* label, int n_threads, uint8_t* out /*[N][32]*/);

@@ -191,6 +191,18 @@ extern "C" {
     pub fn zkp_from_uniform_bytes(ctx: *mut zkp_ctx, n: u64, input: *const u8, out: *mut u8) -> c_int;
     pub fn zkp_from_uniform_bytes_dev(ctx: *mut zkp_ctx, n: u64, d_in: *const u8, d_out: *mut u8) -> c_int;
     pub fn zkp_fused_hash_to_group(ctx: *mut zkp_ctx, n: u32, transcripts: *mut u8, label: *const c_char, out: *mut u8) -> c_int;
+    // ragged batches: transcripts at different STROBE positions (synchronous, host pointers; aligned batches accepted too)
+    pub fn zkp_fused_hash_to_group_ragged(ctx: *mut zkp_ctx, n: u32, transcripts: *mut u8, label: *const c_char, out: *mut u8) -> c_int;
+    pub fn zkp_fused_prove_ragged(ctx: *mut zkp_ctx, st: *const zkp_fused_statement, n: u32, transcripts: *mut u8, secrets: *const u8, inst: *const u8,
+                                  common: *const u8, entropy: *const u8, seed: *const u8, challenges: *mut u8, responses: *mut u8, commitments: *mut u8,
+                                  invalid_point: *mut c_int) -> c_int;
+    pub fn zkp_fused_verify_compact_ragged(ctx: *mut zkp_ctx, st: *const zkp_fused_statement, n: u32, transcripts: *mut u8, inst: *const u8,
+                                           common: *const u8, challenges: *const u8, responses: *const u8, results: *mut u8) -> c_int;
+    pub fn zkp_fused_verify_batchable_ragged(ctx: *mut zkp_ctx, st: *const zkp_fused_statement, n: u32, transcripts: *mut u8, inst: *const u8,
+                                             common: *const u8, commitments: *const u8, responses: *const u8, weights16: *const u8, results: *mut u8) -> c_int;
+    pub fn zkp_fused_batch_verify_many_ragged(ctx: *mut zkp_ctx, st: *const zkp_fused_statement, n_batches: u32, n_each: u32, transcripts: *mut u8,
+                                              inst: *const u8, common: *const u8, commitments: *const u8, responses: *const u8, weights16: *const u8,
+                                              seed: *const u8, verdicts: *mut c_int) -> c_int;
     // hash_from_bytes::<Sha512> over a CSR batch of messages (zkp.rs:34): SHA-512, then from_uniform_bytes
     pub fn zkp_hash_from_bytes_sha512(ctx: *mut zkp_ctx, n: u64, msgs: *const u8, offsets: *const u64, out: *mut u8) -> c_int;
     pub fn zkp_hash_from_bytes_sha512_dev(ctx: *mut zkp_ctx, n: u64, d_msgs: *const u8, msgs_len: u64, d_offsets: *const u64, d_out: *mut u8) -> c_int;
@@ -202,6 +214,8 @@ extern "C" {
     pub fn zkp_transcript_init(t: *mut u8, label: *const u8, label_len: usize);
     pub fn zkp_transcript_append_message(t: *mut u8, label: *const c_char, msg: *const u8, len: usize) -> c_int;
     pub fn zkp_transcript_challenge_bytes(t: *mut u8, label: *const c_char, out: *mut u8, len: usize) -> c_int;
+    pub fn zkp_transcripts_append_message_batch(ts: *mut u8, n: u32, shared_initial: c_int, label: *const c_char, msgs: *const u8, offsets: *const u64,
+                                                n_threads: c_int) -> c_int;
     pub fn zkp_scalar_from_wide(out: *mut u8, input: *const u8);
     pub fn zkp_scalar_muladd(out: *mut u8, a: *const u8, b: *const u8, c: *const u8);
     pub fn zkp_scalar_neg(out: *mut u8, a: *const u8);

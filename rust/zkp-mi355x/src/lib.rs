@@ -192,6 +192,31 @@ impl Transcript {
         let rc = unsafe { sys::zkp_transcript_challenge_bytes(self.0.as_mut_ptr(), l.as_ptr(), dest.as_mut_ptr(), dest.len()) };
         assert_eq!(rc, 0, "zkp_transcript_challenge_bytes: code {}", rc);
     }
+    /// `transcripts[j].append_message(label, messages[j])` for every j, on the library's host threads.  Messages of different lengths
+    /// leave the transcripts at different STROBE positions; prove_batch / verify_* / batch_verify then run them on the device per
+    /// position class.
+    pub fn append_messages(transcripts: &mut [Transcript], label: &'static [u8], messages: &[&[u8]]) -> Result<(), Error> {
+        if transcripts.len() != messages.len() {
+            return Err(Error::Shape("one message per transcript"));
+        }
+        let l = CString::new(label).map_err(|_| Error::Shape("label must not contain NUL bytes"))?;
+        let mut offsets = Vec::with_capacity(messages.len() + 1);
+        offsets.push(0u64);
+        let mut data = Vec::with_capacity(messages.iter().map(|m| m.len()).sum::<usize>().max(1));
+        for m in messages {
+            data.extend_from_slice(m);
+            offsets.push(data.len() as u64);
+        }
+        data.push(0);                                   // never an empty buffer: its pointer is not NULL
+        let mut ts: Vec<u8> = transcripts.iter().flat_map(|t| t.0.iter().copied()).collect();
+        check(unsafe {
+            sys::zkp_transcripts_append_message_batch(ts.as_mut_ptr(), transcripts.len() as u32, 0, l.as_ptr(), data.as_ptr(), offsets.as_ptr(), 0)
+        })?;
+        for (t, chunk) in transcripts.iter_mut().zip(ts.chunks(sys::ZKP_TRANSCRIPT_BYTES)) {
+            t.0.copy_from_slice(chunk);
+        }
+        Ok(())
+    }
 }
 
 #[derive(Copy, Clone)]

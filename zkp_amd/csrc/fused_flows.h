@@ -633,7 +633,9 @@ enum fused_flow : char { FLOW_PROVE = 'P', FLOW_VERIFY = 'V', FLOW_BATCH = 'B' }
 
 // sd / steps: the same program in step form (assemble + chain, transcript_kernels.h); steps = false when the plan could not build it (a step with more
 // than 64 PRF-output operations, more image words than a grid has rows) or the call is wide enough for the one-lane interpreter
-struct prog_dev { const tr_op* ops = nullptr; uint32_t n = 0; uint32_t tail = 0; const uint64_t* tables = nullptr; tr_steps_dev sd; bool steps = false; };
+// rg != nullptr: a ragged program (ragged_transcripts.h), one class program per block of rg[rg_blocks] over the proofs rg_idx[]
+struct prog_dev { const tr_op* ops = nullptr; uint32_t n = 0; uint32_t tail = 0; const uint64_t* tables = nullptr; tr_steps_dev sd; bool steps = false;
+                  const tr_rg_block* rg = nullptr; const uint32_t* rg_idx = nullptr; uint32_t rg_blocks = 0; };
 struct fused_plan {
   fused_shape s;
   uint32_t N = 0, T1 = 0;          // T1 = terms per proof of the flow's CSR job
@@ -782,23 +784,10 @@ void dump_program(char flow, const char* which, const std::vector<tr_op>& ops, u
   fprintf(stderr, "[transcript program] %u Keccak-f permutations per proof\n", perms);
 }
 
-int get_plan(zkp_ctx* c, char flow, const zkp_fused_statement* st, uint32_t N, uint32_t pos, fused_plan** out) {
-  fused_shape s;
-  int rc = check_fused_statement(st, s);
-  if (rc) return rc;
-  if ((pos & 0xff) >= 166) return fail(ZKP_ERR_ARG, "corrupt transcript blob (STROBE position out of range)");
-  const std::string key = plan_key(flow, st, s, N, pos);
-  auto it = c->fused_plans.find(key);
-  if (it != c->fused_plans.end()) { *out = static_cast<fused_plan*>(it->second); return ZKP_OK; }
-  if (c->capturing) return fail(ZKP_ERR_ARG, "graph capture: this statement has no compiled plan yet -- run the same call once before capturing it");
-  std::unique_ptr<fused_plan> pl(new fused_plan());
-  pl->s = s;
-  pl->N = N;
+// The transcript programs of a flow at one STROBE position: A, and B (prove, verify_compact) from A's trailing position
+void compile_programs(char flow, const zkp_fused_statement* st, const fused_shape& s, uint32_t N, uint32_t pos, std::vector<tr_op>& pa, std::vector<uint64_t>& tbl_a,
+                      uint8_t tailA[3], std::vector<tr_op>& pb, std::vector<uint64_t>& tbl_b, uint8_t tailB[3]) {
   const uint32_t m = s.m, nc = s.nc;
-  uint8_t tailA[3], tailB[3];
-  std::vector<tr_op> pa, pb;
-  std::vector<uint64_t> tbl_a, tbl_b;
-  std::vector<uint32_t> tarr;
   TrCompiler ta((uint8_t)pos, (uint8_t)(pos >> 8), (uint8_t)(pos >> 16));
   if (flow == FLOW_PROVE) {
     // program A: allocations, then the blinding factors from a clone of the transcript (prover.rs:78-89)
@@ -817,12 +806,6 @@ int get_plan(zkp_ctx* c, char flow, const zkp_fused_statement* st, uint32_t N, u
     tb.get_challenge_wide("chal", tr_ref{DST_CHAL, 64, 0});
     pb = tb.finish(tailB);
     tbl_b = tb.tables();
-    // prover.rs:94-97 operand lists
-    tarr.assign(nc + 1, 0);
-    for (uint32_t k = 0; k < nc; ++k) tarr[k + 1] = st->shape.cons_off[k + 1];
-    if (s.T) { tarr.insert(tarr.end(), st->shape.cons_sc, st->shape.cons_sc + s.T); tarr.insert(tarr.end(), st->shape.cons_pt, st->shape.cons_pt + s.T); }
-    pl->T1 = s.T;
-    pl->tpt.assign(st->shape.cons_pt, st->shape.cons_pt + s.T);
   } else if (flow == FLOW_VERIFY) {
     compile_allocations(ta, st, s, N, true);                            // verifier.rs:61-77 validating appends
     pa = ta.finish(tailA);
@@ -833,6 +816,28 @@ int get_plan(zkp_ctx* c, char flow, const zkp_fused_statement* st, uint32_t N, u
     tb.get_challenge_wide("chal", tr_ref{DST_CHAL, 64, 0});
     pb = tb.finish(tailB);
     tbl_b = tb.tables();
+  } else {
+    compile_allocations(ta, st, s, N, true);                            // batch_verifier.rs:92-94, :105-107, :125-128
+    for (uint32_t k = 0; k < nc; ++k)                                    // :152-160 validating
+      ta.append_blinding_commitment_var(st->point_labels[st->shape.cons_lhs[k]], tr_ref{SRC_COMS, 32 * nc, 32ull * k}, true);
+    ta.get_challenge_wide("chal", tr_ref{DST_CHAL, 64, 0});              // :163-167
+    pa = ta.finish(tailA);
+    tbl_a = ta.tables();
+  }
+}
+
+// The position-free half of a plan: the term arrays of the flow's MSMs (tarr: offsets | scalars | points | unref | pairs | order), T1, tpt, pair
+void plan_operands(char flow, const zkp_fused_statement* st, const fused_shape& s, fused_plan& pl, std::vector<uint32_t>& tarr, size_t& order_at,
+                   size_t& pair_at) {
+  const uint32_t nc = s.nc;
+  if (flow == FLOW_PROVE) {
+    // prover.rs:94-97 operand lists
+    tarr.assign(nc + 1, 0);
+    for (uint32_t k = 0; k < nc; ++k) tarr[k + 1] = st->shape.cons_off[k + 1];
+    if (s.T) { tarr.insert(tarr.end(), st->shape.cons_sc, st->shape.cons_sc + s.T); tarr.insert(tarr.end(), st->shape.cons_pt, st->shape.cons_pt + s.T); }
+    pl.T1 = s.T;
+    pl.tpt.assign(st->shape.cons_pt, st->shape.cons_pt + s.T);
+  } else if (flow == FLOW_VERIFY) {
     // verifier.rs:95-106: per constraint the rhs terms with the responses, then (-c) on the lhs point
     std::vector<uint32_t> vsc, vpt;
     tarr.assign(nc + 1, 0);
@@ -842,22 +847,15 @@ int get_plan(zkp_ctx* c, char flow, const zkp_fused_statement* st, uint32_t N, u
       vpt.push_back(st->shape.cons_lhs[k]);
       tarr[k + 1] = (uint32_t)vsc.size();
     }
-    pl->T1 = (uint32_t)vsc.size();
-    pl->tpt = vpt;
+    pl.T1 = (uint32_t)vsc.size();
+    pl.tpt = vpt;
     tarr.insert(tarr.end(), vsc.begin(), vsc.end());
     tarr.insert(tarr.end(), vpt.begin(), vpt.end());
     tarr.insert(tarr.end(), s.unref.begin(), s.unref.end());
-    pl->pair = pair_terms(tarr.data(), vpt.data(), pl->T1, nc, s.ns, s.np);
-  } else {
-    compile_allocations(ta, st, s, N, true);                            // batch_verifier.rs:92-94, :105-107, :125-128
-    for (uint32_t k = 0; k < nc; ++k)                                    // :152-160 validating
-      ta.append_blinding_commitment_var(st->point_labels[st->shape.cons_lhs[k]], tr_ref{SRC_COMS, 32 * nc, 32ull * k}, true);
-    ta.get_challenge_wide("chal", tr_ref{DST_CHAL, 64, 0});              // :163-167
-    pa = ta.finish(tailA);
-    tbl_a = ta.tables();
+    pl.pair = pair_terms(tarr.data(), vpt.data(), pl.T1, nc, s.ns, s.np);
   }
-  size_t order_at = 0, pair_at = 0;
-  if (!pl->pair.empty()) { pair_at = tarr.size(); tarr.insert(tarr.end(), pl->pair.begin(), pl->pair.end()); }
+  order_at = pair_at = 0;
+  if (!pl.pair.empty()) { pair_at = tarr.size(); tarr.insert(tarr.end(), pl.pair.begin(), pl.pair.end()); }
   if (flow != FLOW_BATCH && nc) {       // tarr[0 .. nc] = term offsets of the flow's MSMs
     std::vector<uint32_t> order(nc);
     for (uint32_t k = 0; k < nc; ++k) order[k] = k;
@@ -865,6 +863,27 @@ int get_plan(zkp_ctx* c, char flow, const zkp_fused_statement* st, uint32_t N, u
     order_at = tarr.size();
     tarr.insert(tarr.end(), order.begin(), order.end());
   }
+}
+
+int get_plan(zkp_ctx* c, char flow, const zkp_fused_statement* st, uint32_t N, uint32_t pos, fused_plan** out) {
+  fused_shape s;
+  int rc = check_fused_statement(st, s);
+  if (rc) return rc;
+  if ((pos & 0xff) >= 166) return fail(ZKP_ERR_ARG, "corrupt transcript blob (STROBE position out of range)");
+  const std::string key = plan_key(flow, st, s, N, pos);
+  auto it = c->fused_plans.find(key);
+  if (it != c->fused_plans.end()) { *out = static_cast<fused_plan*>(it->second); return ZKP_OK; }
+  if (c->capturing) return fail(ZKP_ERR_ARG, "graph capture: this statement has no compiled plan yet -- run the same call once before capturing it");
+  std::unique_ptr<fused_plan> pl(new fused_plan());
+  pl->s = s;
+  pl->N = N;
+  uint8_t tailA[3], tailB[3];
+  std::vector<tr_op> pa, pb;
+  std::vector<uint64_t> tbl_a, tbl_b;
+  std::vector<uint32_t> tarr;
+  compile_programs(flow, st, s, N, pos, pa, tbl_a, tailA, pb, tbl_b, tailB);
+  size_t order_at = 0, pair_at = 0;
+  plan_operands(flow, st, s, *pl, tarr, order_at, pair_at);
   if (debug_transcript_enabled()) {
     dump_program(flow, flow == FLOW_BATCH ? "program (allocations, commitments, challenge)" : "program A (allocations ...)", pa, N);
     if (!pb.empty()) dump_program(flow, "program B (commitments, challenge)", pb, N);
@@ -965,6 +984,14 @@ void launch_assemble(zkp_ctx* c, const tr_steps_dev& sd, uint32_t N, const tr_bu
 void run_program(zkp_ctx* c, const prog_dev& p_in, uint32_t N, const tr_bufs& bufs, uint8_t* d_ts, uint64_t* d_saved, uint32_t* d_failed, bool throughput,
                  uint64_t* d_img, bool owns_failed = false, int phase = 3) {
   if (!p_in.n) return;
+  if (p_in.rg) {                                   // a ragged program: always the segmented interpreter, a launch of its own
+    ZKP_SCHED(c, TR_LANES, 2);
+    ZKP_SCHED(c, TR_STEPS, 0);
+    prof_note(c, ZKP_K_TRANSCRIPT, "zkp::k_transcript_run_ragged");
+    hipLaunchKernelGGL(k_transcript_run_ragged, dim3(p_in.rg_blocks), dim3(TR_BLOCK), 0, c->stream, p_in.rg, p_in.rg_idx, N, bufs, d_ts,
+                       reinterpret_cast<uint32_t*>(d_saved), d_failed, owns_failed ? 0x80000000u : 0u);
+    return;
+  }
   prog_dev p = p_in;
   if (owns_failed) p.tail |= 0x80000000u;          // the kernel writes every proof's rejection flag, 0 included
   ZKP_SCHED(c, TR_LANES, transcript_single_lane(c, N, throughput) ? 1 : 2);
@@ -1000,7 +1027,7 @@ void offer_program(zkp_ctx* c, const prog_dev& p, uint32_t N, const tr_bufs& buf
                    uint64_t* d_img) {
   auto& t = c->pending_tr;
   const bool fuse = c->fuse_tables_transcript < 0 ? N < zkp_ctx::kVeryWideCallProofs : c->fuse_tables_transcript != 0;
-  t.offered = t.active = fuse && p.n != 0 && throughput && !overlap && !transcript_single_lane(c, N, throughput);
+  t.offered = t.active = fuse && p.n != 0 && !p.rg && throughput && !overlap && !transcript_single_lane(c, N, throughput);
   t.ops = p.ops; t.n_ops = p.n; t.tables = p.tables; t.N = N; t.bufs = bufs; t.ts = d_ts; t.saved = reinterpret_cast<uint32_t*>(d_saved); t.failed = d_failed; t.tail = p.tail;
   t.steps = transcript_steps(c, p, N, throughput, d_img);
   t.sd = p.sd; t.sd.tail = p.tail; t.img = d_img;

@@ -233,6 +233,29 @@ int zkp_transcript_append_message(uint8_t* t, const char* label, const uint8_t* 
   x.to_bytes(t);
   return ZKP_TB_OK;
 }
+// merlin append_message over a CSR batch on host threads (about one Keccak-f per 166 bytes: nothing the device would gain on).  Every
+// argument is checked before any transcript changes.
+int zkp_transcripts_append_message_batch(uint8_t* ts, uint32_t N, int shared_initial, const char* label, const uint8_t* msgs, const uint64_t* offsets,
+                                         int n_threads) {
+  if (!label) return ZKP_TB_BAD_STATEMENT;
+  if (!fits_u32(std::strlen(label))) return ZKP_TB_TOO_LONG;
+  if (N == 0) return ZKP_TB_OK;
+  if (!ts || !offsets || (offsets[N] > offsets[0] && !msgs)) return ZKP_TB_BAD_STATEMENT;
+  for (uint32_t j = 0; j < N; ++j) {
+    if (offsets[j + 1] < offsets[j]) return ZKP_TB_BAD_STATEMENT;
+    if (!fits_u32(offsets[j + 1] - offsets[j])) return ZKP_TB_TOO_LONG;
+  }
+  uint8_t init[TB];
+  if (shared_initial) std::memcpy(init, ts, TB);
+  parallel_for(N, n_threads, [&](uint32_t lo, uint32_t hi) {
+    for (uint32_t j = lo; j < hi; ++j) {
+      Transcript x = Transcript::from_bytes(shared_initial ? init : ts + TB * (size_t)j);
+      x.append_message(label, msgs + offsets[j], offsets[j + 1] - offsets[j]);
+      x.to_bytes(ts + TB * (size_t)j);
+    }
+  });
+  return ZKP_TB_OK;
+}
 int zkp_transcript_challenge_bytes(uint8_t* t, const char* label, uint8_t* out, size_t len) {
   if (!t || !label || (len && !out)) return ZKP_TB_BAD_STATEMENT;
   if (!fits_u32(len) || !fits_u32(std::strlen(label))) return ZKP_TB_TOO_LONG;
@@ -439,6 +462,16 @@ int zkp_prove_batch(zkp_ctx* ctx, const zkp_statement* st, uint32_t N, uint8_t* 
     if (rc) return rc;
     return invalid ? ZKP_TB_INVALID_POINT : ZKP_TB_OK;
   }
+  if (ctx && ts && use_ragged(ts, N)) {                                  // the same on the device, one transcript program per position class
+    uint8_t seed[40];
+    if (!entropy && !os_entropy(seed, sizeof(seed))) return ZKP_TB_NO_ENTROPY;
+    if (st->ns && N >= 32) { const int rc = zkp_ctx_prepare_fixed_points(ctx, st->ns, common); if (rc) return rc; }
+    FusedView fv(*st);
+    int invalid = 0;
+    const int rc = zkp_fused_prove_ragged(ctx, &fv.fs, N, ts, secrets, inst, common, entropy, entropy ? nullptr : seed, challenges, responses, commitments, &invalid);
+    if (rc) return rc;
+    return invalid ? ZKP_TB_INVALID_POINT : ZKP_TB_OK;
+  }
   const uint32_t m = (uint32_t)st->secrets.size(), nc = (uint32_t)st->cons.size(), T = st->terms;
   std::vector<uint8_t> blind(32 * (size_t)N * m), scalars(32 * (size_t)N * T), status((size_t)N * nc);
   std::vector<uint32_t> off((size_t)N * nc + 1), pidx((size_t)N * T);
@@ -479,6 +512,11 @@ int zkp_verify_compact_batch(zkp_ctx* ctx, const zkp_statement* stp, uint32_t N,
     if (st.ns && N >= 32) { const int rc = zkp_ctx_prepare_fixed_points(ctx, st.ns, common); if (rc) return rc; }
     FusedView fv(st);
     return zkp_fused_verify_compact(ctx, &fv.fs, N, ts, inst, common, challenges, responses, results);
+  }
+  if (ctx && use_ragged(ts, N)) {
+    if (st.ns && N >= 32) { const int rc = zkp_ctx_prepare_fixed_points(ctx, st.ns, common); if (rc) return rc; }
+    FusedView fv(st);
+    return zkp_fused_verify_compact_ragged(ctx, &fv.fs, N, ts, inst, common, challenges, responses, results);
   }
   const uint32_t m = (uint32_t)st.secrets.size(), nc = (uint32_t)st.cons.size(), T1 = st.terms + nc;
   std::memset(results, 0, N);
@@ -562,6 +600,11 @@ int zkp_verify_batchable_each(zkp_ctx* ctx, const zkp_statement* stp, uint32_t N
     if (st.ns && N >= 32) { const int rc = zkp_ctx_prepare_fixed_points(ctx, st.ns, common); if (rc) return rc; }
     FusedView fv(st);
     return zkp_fused_verify_batchable(ctx, &fv.fs, N, ts, inst, common, commitments, responses, weights16, results);
+  }
+  if (ctx && use_ragged(ts, N)) {
+    if (st.ns && N >= 32) { const int rc = zkp_ctx_prepare_fixed_points(ctx, st.ns, common); if (rc) return rc; }
+    FusedView fv(st);
+    return zkp_fused_verify_batchable_ragged(ctx, &fv.fs, N, ts, inst, common, commitments, responses, weights16, results);
   }
   std::memset(results, 0, N);
   flag_noncanonical(N, m, responses, results);                         // proofs.rs:27-32 through serde
@@ -758,9 +801,26 @@ int zkp_batch_verify_coeffs(zkp_ctx* ctx, const zkp_statement* stp, uint32_t N, 
   return std::memcmp(out, zero, 32) == 0 ? ZKP_TB_OK : ZKP_TB_VERIFICATION_FAILURE;   // :230-234
 }
 
+// K batch verifications of a ragged batch on the device (K = 1: zkp_batch_verify); weights16 == NULL: drawn there from 40 bytes of getrandom()
+static int batch_verify_ragged(zkp_ctx* ctx, const zkp_statement& st, uint32_t K, uint32_t N_each, uint8_t* ts, const uint8_t* inst, const uint8_t* common,
+                               const uint8_t* commitments, const uint8_t* responses, const uint8_t* weights16, int* verdicts) {
+  uint8_t seed[40];
+  if (!weights16 && !st.cons.empty() && !os_entropy(seed, sizeof(seed))) return ZKP_TB_NO_ENTROPY;
+  FusedView fv(st);
+  const int rc = zkp_fused_batch_verify_many_ragged(ctx, &fv.fs, K, N_each, ts, inst, common, commitments, responses, weights16, weights16 ? nullptr : seed, verdicts);
+  if (rc) return rc;
+  for (uint32_t b = 0; b < K; ++b) verdicts[b] = verdicts[b] ? ZKP_TB_VERIFICATION_FAILURE : ZKP_TB_OK;
+  return ZKP_TB_OK;
+}
+
 int zkp_batch_verify(zkp_ctx* ctx, const zkp_statement* st, uint32_t N, uint32_t n_transcripts, uint8_t* ts, const uint8_t* inst,
                      const uint8_t* common, const uint8_t* commitments, const uint8_t* responses, const uint8_t* weights16,
                      int n_threads) {
+  if (st && ctx && ts && n_transcripts == N && !on_host(ctx, (uint64_t)st->ns + ((uint64_t)st->ni + st->cons.size()) * N) && use_ragged(ts, N)) {
+    int verdict = ZKP_TB_VERIFICATION_FAILURE;
+    const int rc = batch_verify_ragged(ctx, *st, 1, N, ts, inst, common, commitments, responses, weights16, &verdict);
+    return rc ? rc : verdict;
+  }
   return zkp_batch_verify_coeffs(ctx, st, N, n_transcripts, ts, inst, common, commitments, responses, weights16, n_threads, nullptr);
 }
 
@@ -773,6 +833,7 @@ int zkp_batch_verify_many(zkp_ctx* ctx, const zkp_statement* stp, uint32_t K, ui
   if (!ts) return ZKP_TB_BAD_STATEMENT;
   const zkp_statement& st = *stp;
   const uint32_t m = (uint32_t)st.secrets.size(), nc = (uint32_t)st.cons.size(), ni = st.ni;
+  if (ctx && use_ragged(ts, N)) return batch_verify_ragged(ctx, st, K, N_each, ts, inst, common, commitments, responses, weights16, verdicts);
   std::vector<uint8_t> own_w;
   if (!weights16 && ctx && nc && use_fused(ts, N)) {                   // weights drawn on the device from 40 bytes of getrandom() (see zkp_batch_verify)
     uint8_t seed[40];
@@ -837,6 +898,7 @@ int zkp_hash_to_group_batch(zkp_ctx* ctx, uint32_t N, uint8_t* ts, const char* l
   if (!ts || !out) return ZKP_TB_BAD_STATEMENT;
   if (!fits_u32(std::strlen(label))) return ZKP_TB_TOO_LONG;
   if (ctx && use_fused(ts, N)) return zkp_fused_hash_to_group(ctx, N, ts, label, out);
+  if (ctx && use_ragged(ts, N)) return zkp_fused_hash_to_group_ragged(ctx, N, ts, label, out);
   std::vector<uint8_t> wide(64 * (size_t)N);
   parallel_for(N, n_threads, [&](uint32_t lo, uint32_t hi) {
     for (uint32_t j = lo; j < hi; ++j) {

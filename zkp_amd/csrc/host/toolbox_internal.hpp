@@ -155,6 +155,14 @@ inline bool use_fused(const uint8_t* ts, uint32_t N) {
 }
 
 
+// transcripts at different STROBE positions (a ragged batch): the device runs one program per position class (zkp_fused_*_ragged)
+inline bool use_ragged(const uint8_t* ts, uint32_t N) {
+  if (N < zkp_toolbox_get_fused_min_batch() || N == 0) return false;
+  for (uint32_t j = 1; j < N; ++j)
+    if (std::memcmp(ts + TB * (size_t)j + 200, ts + 200, 3) != 0) return true;
+  return false;
+}
+
 // getrandom() until `len` bytes are there; false = the operating system gave none (callers fail closed: ZKP_TB_NO_ENTROPY)
 bool os_entropy(uint8_t* out, size_t len);
 // what `thread_rng()` is to the reference: a ChaCha20 stream keyed from the operating system (toolbox.cpp)

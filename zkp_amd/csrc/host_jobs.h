@@ -185,17 +185,17 @@ int job_tail(const uint8_t* transcripts, uint32_t N, bool shared, uint32_t* pos)
 // sync_variant: the schedule of the synchronous entry point (side stream, quad tables: one call's latency is what the caller sees)
 int prove_job(zkp_ctx* c, const zkp_fused_statement* st, uint32_t N, uint32_t flags, const uint8_t* transcripts, const uint8_t* secrets,
               const uint8_t* inst, uint32_t inst_stride, const uint8_t* common, const uint8_t* entropy, const uint8_t* rng_seed,
-              uint8_t* transcripts_out, uint8_t* challenges, uint8_t* responses, uint8_t* commitments, int* invalid_point, bool sync_variant) {
+              uint8_t* transcripts_out, uint8_t* challenges, uint8_t* responses, uint8_t* commitments, int* invalid_point, bool sync_variant, rg_call* rg = nullptr) {
   if (!c) return fail(ZKP_ERR_ARG, "ctx is NULL");
   if (N == 0) { if (invalid_point) *invalid_point = 0; return ZKP_OK; }
   if (!transcripts) return fail(ZKP_ERR_ARG, "NULL pointer");
   const bool shared = (flags & ZKP_JOB_SHARED_TRANSCRIPT) != 0;
   uint32_t pos = 0;
-  int rc = job_tail(transcripts, N, shared, &pos);
+  int rc = rg ? ZKP_OK : job_tail(transcripts, N, shared, &pos);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(c->device));
-  fused_plan* pl = nullptr;
-  rc = get_plan(c, FLOW_PROVE, st, N, pos, &pl);
+  fused_plan* pl = rg ? &rg->view : nullptr;       // (rg: a ragged call, rg_prepare made its plan)
+  rc = rg ? ZKP_OK : get_plan(c, FLOW_PROVE, st, N, pos, &pl);
   if (rc) return rc;
   const fused_shape& s = pl->s;
   if ((!entropy && !rng_seed) || !challenges || !invalid_point || (s.m && (!secrets || !responses)) || (s.nc && !commitments) || (s.ni && !inst) || (s.ns && !common))
@@ -214,6 +214,7 @@ int prove_job(zkp_ctx* c, const zkp_fused_statement* st, uint32_t N, uint32_t fl
   const size_t o_resp = cv.take((size_t)N * m * 32 + 32);
   const size_t o_blob = cv.take(256);
   const size_t o_flag = cv.take(16);
+  const size_t o_rg = cv.take(rg_bytes(rg));
   const prove_inter o = prove_carve(*pl, cv.off);
   const size_t ws_need = o.end + terms_path_ws(n_points, N * s.T, N * s.nc, prove_terms_cfg(c, *pl, !sync_variant));
   rc = ensure_ws(c, ws_need);
@@ -222,6 +223,7 @@ int prove_job(zkp_ctx* c, const zkp_fused_statement* st, uint32_t N, uint32_t fl
   if (rc) return rc;
   const ws_view w{static_cast<char*>(c->ws)};
   c->job.inline_out = sync_variant;
+  if (rg) ZKP_JOB_TRY(rg_upload(c, *rg, w.u8(o_rg)));
   // The points go first: decode, classification and comb tables (side stream of the latency schedule) need nothing else.  What only the transcripts read --
   // states, witnesses, entropy, two thirds of the bytes -- follows once that work is queued (a copy from pageable memory holds the host thread until it is
   // staged), so it crosses the link under those kernels.  The asynchronous jobs keep everything in front: their copies ride under OTHER jobs' kernels.
@@ -258,17 +260,18 @@ int prove_job(zkp_ctx* c, const zkp_fused_statement* st, uint32_t N, uint32_t fl
 
 // ---- verify_compact -----------------------------------------------------------------------------------------------------------
 int verify_compact_job(zkp_ctx* c, const zkp_fused_statement* st, uint32_t N, uint32_t flags, const uint8_t* transcripts, const uint8_t* inst, uint32_t inst_stride,
-                       const uint8_t* common, const uint8_t* challenges, const uint8_t* responses, uint8_t* transcripts_out, uint8_t* results, bool sync_variant) {
+                       const uint8_t* common, const uint8_t* challenges, const uint8_t* responses, uint8_t* transcripts_out, uint8_t* results, bool sync_variant,
+                       rg_call* rg = nullptr) {
   if (!c) return fail(ZKP_ERR_ARG, "ctx is NULL");
   if (N == 0) return ZKP_OK;
   if (!transcripts) return fail(ZKP_ERR_ARG, "NULL pointer");
   const bool shared = (flags & ZKP_JOB_SHARED_TRANSCRIPT) != 0;
   uint32_t pos = 0;
-  int rc = job_tail(transcripts, N, shared, &pos);
+  int rc = rg ? ZKP_OK : job_tail(transcripts, N, shared, &pos);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(c->device));
-  fused_plan* pl = nullptr;
-  rc = get_plan(c, FLOW_VERIFY, st, N, pos, &pl);
+  fused_plan* pl = rg ? &rg->view : nullptr;
+  rc = rg ? ZKP_OK : get_plan(c, FLOW_VERIFY, st, N, pos, &pl);
   if (rc) return rc;
   const fused_shape& s = pl->s;
   if (!challenges || !results || (s.m && !responses) || (s.ni && !inst) || (s.ns && !common)) return fail(ZKP_ERR_ARG, "NULL pointer");
@@ -283,6 +286,7 @@ int verify_compact_job(zkp_ctx* c, const zkp_fused_statement* st, uint32_t N, ui
   const size_t o_resp = cv.take((size_t)N * m * 32 + 32);
   const size_t o_res = cv.take((size_t)N);
   const size_t o_blob = cv.take(256);
+  const size_t o_rg = cv.take(rg_bytes(rg));
   const verify_inter o = verify_carve(*pl, cv.off);
   const size_t ws_need = o.end + terms_path_ws(n_points, N * pl->T1, N * s.nc, verify_terms_cfg(c, *pl, verify_riders(N, !sync_variant)));
   rc = ensure_ws(c, ws_need);
@@ -292,6 +296,7 @@ int verify_compact_job(zkp_ctx* c, const zkp_fused_statement* st, uint32_t N, ui
   job_results(c, results, N);
   const ws_view w{static_cast<char*>(c->ws)};
   c->job.inline_out = sync_variant;
+  if (rg) ZKP_JOB_TRY(rg_upload(c, *rg, w.u8(o_rg)));
   if (s.ns) ZKP_JOB_TRY(h2d(c, w.base + o_tbl, common, (size_t)s.ns * 32));
   ZKP_JOB_TRY(h2d_rows(c, w.base + o_tbl + 32 * (size_t)s.ns, inst, s.ni, (size_t)N * 32, (size_t)inst_stride * 32));
   const std::function<int()> rest = [&]() -> int {            // (see prove_job: the points first, the rest under the side stream's kernels)
@@ -314,7 +319,7 @@ int verify_compact_job(zkp_ctx* c, const zkp_fused_statement* st, uint32_t N, ui
 // ---- K batch verifications --------------------------------------------------------------------------------------------------
 int batch_verify_job(zkp_ctx* c, const zkp_fused_statement* st, uint32_t K, uint32_t N_each, uint32_t flags, const uint8_t* transcripts, const uint8_t* inst,
                      uint32_t inst_stride, const uint8_t* common, const uint8_t* commitments, const uint8_t* responses, const uint8_t* weights16, uint32_t w_stride,
-                     const uint8_t* rng_seed, uint8_t* transcripts_out, int* verdicts, uint8_t* debug_scalars, bool sync_variant) {
+                     const uint8_t* rng_seed, uint8_t* transcripts_out, int* verdicts, uint8_t* debug_scalars, bool sync_variant, rg_call* rg = nullptr) {
   if (!c) return fail(ZKP_ERR_ARG, "ctx is NULL");
   if (!verdicts) return fail(ZKP_ERR_ARG, "NULL pointer");
   fused_shape s0;
@@ -327,11 +332,11 @@ int batch_verify_job(zkp_ctx* c, const zkp_fused_statement* st, uint32_t K, uint
   if (N && !transcripts) return fail(ZKP_ERR_ARG, "NULL pointer");
   const bool shared = (flags & ZKP_JOB_SHARED_TRANSCRIPT) != 0;
   uint32_t pos = 0;
-  rc = N ? job_tail(transcripts, N, shared, &pos) : ZKP_OK;
+  rc = N && !rg ? job_tail(transcripts, N, shared, &pos) : ZKP_OK;
   if (rc) return rc;
   HIP_TRY(hipSetDevice(c->device));
-  fused_plan* pl = nullptr;
-  rc = get_plan(c, FLOW_BATCH, st, N, pos, &pl);
+  fused_plan* pl = rg ? &rg->view : nullptr;
+  rc = rg ? ZKP_OK : get_plan(c, FLOW_BATCH, st, N, pos, &pl);
   if (rc) return rc;
   const fused_shape& s = pl->s;
   if (N && ((s.nc && (!commitments || (!weights16 && !rng_seed))) || (s.m && !responses) || (s.ni && !inst))) return fail(ZKP_ERR_ARG, "NULL pointer");
@@ -348,6 +353,7 @@ int batch_verify_job(zkp_ctx* c, const zkp_fused_statement* st, uint32_t K, uint
   const size_t o_resp = cv.take((size_t)N * m * 32 + 32);
   const size_t o_w = cv.take((size_t)nc * N * 16 + 64);
   const size_t o_blob = cv.take(256);
+  const size_t o_rg = cv.take(rg_bytes(rg));
   const batch_inter o = batch_carve(*pl, cv.off, K);
   rc = ensure_ws(c, o.end + (K == 1 ? optional_ws(n_each) : optional_many_ws(n_each, K)));
   if (rc) return rc;
@@ -355,6 +361,7 @@ int batch_verify_job(zkp_ctx* c, const zkp_fused_statement* st, uint32_t K, uint
   if (rc) return rc;
   const ws_view w{static_cast<char*>(c->ws)};
   c->job.inline_out = sync_variant;
+  if (rg) ZKP_JOB_TRY(rg_upload(c, *rg, w.u8(o_rg)));
   // points and commitments first (the assemble pass and the decoder on the side stream read them); transcript states once that work is queued; responses and
   // weights (nobody reads them before the coefficient build) once the chain is on its stream -- see prove_job
   if (ns) ZKP_JOB_TRY(h2d(c, w.base + o_pts, common, (size_t)ns * 32));
@@ -387,17 +394,17 @@ int batch_verify_job(zkp_ctx* c, const zkp_fused_statement* st, uint32_t K, uint
 // ---- verify_batchable, one verdict per proof ----------------------------------------------------------------------------------
 int verify_batchable_job(zkp_ctx* c, const zkp_fused_statement* st, uint32_t N, uint32_t flags, const uint8_t* transcripts, const uint8_t* inst, uint32_t inst_stride,
                          const uint8_t* common, const uint8_t* commitments, const uint8_t* responses, const uint8_t* weights16, const uint8_t* rng_seed,
-                         uint8_t* transcripts_out, uint8_t* results, uint8_t* debug_scalars, bool sync_variant) {
+                         uint8_t* transcripts_out, uint8_t* results, uint8_t* debug_scalars, bool sync_variant, rg_call* rg = nullptr) {
   if (!c) return fail(ZKP_ERR_ARG, "ctx is NULL");
   if (N == 0) return ZKP_OK;
   if (!transcripts || !results) return fail(ZKP_ERR_ARG, "NULL pointer");
   const bool shared = (flags & ZKP_JOB_SHARED_TRANSCRIPT) != 0;
   uint32_t pos = 0;
-  int rc = job_tail(transcripts, N, shared, &pos);
+  int rc = rg ? ZKP_OK : job_tail(transcripts, N, shared, &pos);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(c->device));
-  fused_plan* pl = nullptr;
-  rc = get_plan(c, FLOW_BATCH, st, N, pos, &pl);          // same transcript program as the batch verifier (:134-142 = :152-167)
+  fused_plan* pl = rg ? &rg->view : nullptr;
+  rc = rg ? ZKP_OK : get_plan(c, FLOW_BATCH, st, N, pos, &pl);          // same transcript program as the batch verifier (:134-142 = :152-167)
   if (rc) return rc;
   const fused_shape& s = pl->s;
   if ((s.nc && (!commitments || (!weights16 && !rng_seed))) || (s.m && !responses) || (s.ni && !inst) || (s.ns && !common)) return fail(ZKP_ERR_ARG, "NULL pointer");
@@ -413,6 +420,7 @@ int verify_batchable_job(zkp_ctx* c, const zkp_fused_statement* st, uint32_t N, 
   const size_t o_w = cv.take((size_t)N * nc * 16 + 64);
   const size_t o_res = cv.take((size_t)N + 4);
   const size_t o_blob = cv.take(256);
+  const size_t o_rg = cv.take(rg_bytes(rg));
   const each_inter o = each_carve(*pl, cv.off);
   rc = ensure_ws(c, each_uses_straus(c, *pl) ? straus_carve(c, *pl, o.end).end : o.end + terms_path_ws((uint32_t)n_points, (uint32_t)(N * K), N, each_terms_cfg(*pl)));
   if (rc) return rc;
@@ -420,6 +428,7 @@ int verify_batchable_job(zkp_ctx* c, const zkp_fused_statement* st, uint32_t N, 
   if (rc) return rc;
   job_results(c, results, N);
   const ws_view w{static_cast<char*>(c->ws)};
+  if (rg) ZKP_JOB_TRY(rg_upload(c, *rg, w.u8(o_rg)));
   ZKP_JOB_TRY(put_transcripts(c, N, shared, transcripts, w.u8(o_ts), w.u8(o_blob)));
   if (ns) ZKP_JOB_TRY(h2d(c, w.base + o_tbl, common, (size_t)ns * 32));
   ZKP_JOB_TRY(h2d_rows(c, w.base + o_tbl + 32 * (size_t)ns, inst, ni, (size_t)N * 32, (size_t)inst_stride * 32));
@@ -595,6 +604,70 @@ int zkp_fused_verify_batchable_coeffs(zkp_ctx* c, const zkp_fused_statement* st,
 int zkp_fused_verify_batchable(zkp_ctx* c, const zkp_fused_statement* st, uint32_t N, uint8_t* transcripts, const uint8_t* inst, const uint8_t* common,
                                const uint8_t* commitments, const uint8_t* responses, const uint8_t* weights16, uint8_t* results) {
   return zkp_fused_verify_batchable_coeffs(c, st, N, transcripts, inst, common, commitments, responses, weights16, results, nullptr);
+}
+
+// ---- the same synchronous entry points over ragged batches (ragged_transcripts.h): aligned batches take the calls above ----------------
+// prepare: the class programs and the ragged view of the plan; rg == nullptr on return = the batch is aligned
+static int rg_begin(zkp_ctx* c, char flow, const zkp_fused_statement* st, uint32_t N, const uint8_t* transcripts, std::unique_ptr<rg_call>& rg) {
+  if (!c) return fail(ZKP_ERR_ARG, "ctx is NULL");
+  if (c->capturing) return fail(ZKP_ERR_ARG, "graph capture: the _ragged entry points cannot be recorded");
+  if (!N || !transcripts || rg_aligned(transcripts, N)) return ZKP_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  rg.reset(new rg_call());
+  const int rc = rg_prepare(c, flow, st, N, transcripts, *rg);
+  if (rc) rg.reset();
+  return rc;
+}
+static int rg_finish(zkp_ctx* c, const std::unique_ptr<rg_call>& rg, int rc) {
+  (void)c;
+  if (!rc && rg) {
+    ZKP_SCHED(c, RAGGED_CLASSES, rg->n_classes);
+    ZKP_SCHED(c, RAGGED_COMPILED, rg->compiled);
+    ZKP_SCHED(c, RAGGED_BASE, rg->base_built);
+    ZKP_SCHED(c, FUSED_PLANS, c->fused_plans.size());
+  }
+  return rc;
+}
+int zkp_fused_prove_ragged(zkp_ctx* c, const zkp_fused_statement* st, uint32_t N, uint8_t* transcripts, const uint8_t* secrets, const uint8_t* inst, const uint8_t* common,
+                           const uint8_t* entropy, const uint8_t seed[40], uint8_t* challenges, uint8_t* responses, uint8_t* commitments, int* invalid_point) {
+  if (c && N && (!entropy) == (!seed)) return fail(ZKP_ERR_ARG, "exactly one of entropy and seed must be given");
+  std::unique_ptr<rg_call> rg;
+  int rc = rg_begin(c, FLOW_PROVE, st, N, transcripts, rg);
+  if (rc) return rc;
+  rc = job_finish(c, prove_job(c, st, N, 0, transcripts, secrets, inst, N, common, entropy, seed, transcripts, challenges, responses, commitments, invalid_point,
+                               sync_latency(c), rg.get()));
+  return rg_finish(c, rg, rc);
+}
+int zkp_fused_verify_compact_ragged(zkp_ctx* c, const zkp_fused_statement* st, uint32_t N, uint8_t* transcripts, const uint8_t* inst, const uint8_t* common,
+                                    const uint8_t* challenges, const uint8_t* responses, uint8_t* results) {
+  std::unique_ptr<rg_call> rg;
+  int rc = rg_begin(c, FLOW_VERIFY, st, N, transcripts, rg);
+  if (rc) { if (results && N) memset(results, 1, N); return rc; }
+  rc = job_finish(c, verify_compact_job(c, st, N, 0, transcripts, inst, N, common, challenges, responses, transcripts, results, sync_latency(c), rg.get()));
+  return rg_finish(c, rg, rc);
+}
+int zkp_fused_verify_batchable_ragged(zkp_ctx* c, const zkp_fused_statement* st, uint32_t N, uint8_t* transcripts, const uint8_t* inst, const uint8_t* common,
+                                      const uint8_t* commitments, const uint8_t* responses, const uint8_t* weights16, uint8_t* results) {
+  if (c && N && st && st->shape.n_constraints && !weights16) return fail(ZKP_ERR_ARG, "NULL pointer");
+  std::unique_ptr<rg_call> rg;
+  int rc = rg_begin(c, FLOW_BATCH, st, N, transcripts, rg);
+  if (rc) { if (results && N) memset(results, 1, N); return rc; }
+  rc = job_finish(c, verify_batchable_job(c, st, N, 0, transcripts, inst, N, common, commitments, responses, weights16, nullptr, transcripts, results, nullptr, sync_latency(c),
+                                          rg.get()));
+  return rg_finish(c, rg, rc);
+}
+int zkp_fused_batch_verify_many_ragged(zkp_ctx* c, const zkp_fused_statement* st, uint32_t K, uint32_t N_each, uint8_t* transcripts, const uint8_t* inst,
+                                       const uint8_t* common, const uint8_t* commitments, const uint8_t* responses, const uint8_t* weights16, const uint8_t seed[40],
+                                       int* verdicts) {
+  if (c && (K == 0 || N_each == 0)) return fail(ZKP_ERR_ARG, "n_batches and N_each must be positive");
+  if (c && st && st->shape.n_constraints && (!weights16) == (!seed)) return fail(ZKP_ERR_ARG, "exactly one of weights16 and seed must be given");
+  if ((uint64_t)K * N_each > 0x7fffffffull) return fail(ZKP_ERR_ARG, "batch too large");
+  std::unique_ptr<rg_call> rg;
+  int rc = rg_begin(c, FLOW_BATCH, st, K * N_each, transcripts, rg);
+  if (rc) { if (verdicts) for (uint32_t b = 0; b < K; ++b) verdicts[b] = 1; return rc; }
+  rc = job_finish(c, batch_verify_job(c, st, K, N_each, 0, transcripts, inst, K * N_each, common, commitments, responses, weights16, K * N_each, weights16 ? nullptr : seed,
+                                      transcripts, verdicts, nullptr, sync_latency(c), rg.get()));
+  return rg_finish(c, rg, rc);
 }
 
 int zkp_ctx_job_timing(zkp_ctx* c, float ms[3]) {

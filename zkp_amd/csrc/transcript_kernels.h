@@ -76,13 +76,12 @@ constexpr int TR_BLOCK = 64;       // lanes per workgroup (one wavefront) = 32 p
 // The operation list is fetched 64 operations at a time: lane i loads operation base + i (one coalesced 1 KiB load), and
 // the wavefront then walks them with v_readlane -- no scalar-memory latency inside the loop (an s_load per operation
 // would be waited for at every LDS access, since both count on lgkmcnt).
-__device__ __forceinline__ void transcript_pair_block(uint32_t bid, uint32_t* S /*LDS [25 * TR_BLOCK]*/, const tr_op* __restrict__ prog, uint32_t n_ops,
-                                                      const uint64_t* __restrict__ tables, uint32_t N, const tr_bufs& bufs, uint8_t* __restrict__ ts,
-                                                      uint32_t* __restrict__ saved /*[25][2N]*/, uint32_t* __restrict__ failed, uint32_t tail) {
+// Lane pair (lane >> 1) serves proof j; !live = a shadow of a proof of the same program that stores nothing; spare = the one pair that
+// clears the flow's status word failed[N]
+__device__ __forceinline__ void transcript_pair_run(uint32_t j, bool live, bool spare, uint32_t* S /*LDS [25 * TR_BLOCK]*/, const tr_op* __restrict__ prog,
+                                                    uint32_t n_ops, const uint64_t* __restrict__ tables, uint32_t N, const tr_bufs& bufs, uint8_t* __restrict__ ts,
+                                                    uint32_t* __restrict__ saved /*[25][2N]*/, uint32_t* __restrict__ failed, uint32_t tail) {
   const uint32_t lane = threadIdx.x & (TR_BLOCK - 1), h = lane & 1;     // (one wavefront per transcript block; k_tables_transcript_pc runs two in a workgroup)
-  const uint32_t j_raw = bid * (TR_BLOCK / 2) + (lane >> 1);
-  const bool live = j_raw < N;                          // lanes past the end shadow the last proof (they must stay in the
-  const uint32_t j = live ? j_raw : N - 1;              // wavefront: they carry operations for v_readlane) and store nothing
   uint32_t* col = S + lane;
   uint32_t* blob = reinterpret_cast<uint32_t*>(ts + 208 * (size_t)j);
 #pragma unroll
@@ -156,7 +155,15 @@ __device__ __forceinline__ void transcript_pair_block(uint32_t bid, uint32_t* S 
   if (h == 0) { blob[50] = tail & 0xffffffu; blob[51] = 0; }
   // bit 31 of `tail`: this program owns the rejection flags (it writes 0 too, so that nobody has to clear them first)
   if (h == 0 && (bad || (tail >> 31))) failed[j] = bad;
-  if ((tail >> 31) && j_raw == 0 && h == 0) failed[N] = 0;      // the spare word behind the flags: the flow's shared status bits
+  if ((tail >> 31) && spare && h == 0) failed[N] = 0;         // the spare word behind the flags: the flow's shared status bits
+}
+__device__ __forceinline__ void transcript_pair_block(uint32_t bid, uint32_t* S /*LDS [25 * TR_BLOCK]*/, const tr_op* __restrict__ prog, uint32_t n_ops,
+                                                      const uint64_t* __restrict__ tables, uint32_t N, const tr_bufs& bufs, uint8_t* __restrict__ ts,
+                                                      uint32_t* __restrict__ saved /*[25][2N]*/, uint32_t* __restrict__ failed, uint32_t tail) {
+  const uint32_t j_raw = bid * (TR_BLOCK / 2) + ((threadIdx.x & (TR_BLOCK - 1)) >> 1);
+  const bool live = j_raw < N;                          // lanes past the end shadow the last proof (they must stay in the
+  const uint32_t j = live ? j_raw : N - 1;              // wavefront: they carry operations for v_readlane) and store nothing
+  transcript_pair_run(j, live, j_raw == 0, S, prog, n_ops, tables, N, bufs, ts, saved, failed, tail);
 }
 
 __global__ void __launch_bounds__(TR_BLOCK)
@@ -164,6 +171,22 @@ k_transcript_run(const tr_op* __restrict__ prog, uint32_t n_ops, const uint64_t*
                  uint8_t* __restrict__ ts, uint32_t* __restrict__ saved /*[25][2N]*/, uint32_t* __restrict__ failed, uint32_t tail) {
   __shared__ uint32_t S[25 * TR_BLOCK];
   transcript_pair_block(blockIdx.x, S, prog, n_ops, tables, N, bufs, ts, saved, failed, tail);
+}
+
+// ---- ragged batches: transcripts at different STROBE positions (ragged_transcripts.h) ----------------------------------------
+// One entry per wavefront: the program of one position class and up to 32 of its proofs, idx[first .. first + count).  The op walk stays
+// wave-uniform; lane pair p serves proof idx[first + p] everywhere (blob, sources, outputs, clone slots, flags), so nothing moves in memory.
+struct tr_rg_block { const tr_op* ops; const uint64_t* tables; uint32_t n_ops, tail, first, count; };
+static_assert(sizeof(tr_rg_block) == 32, "tr_rg_block layout");
+__global__ void __launch_bounds__(TR_BLOCK)
+k_transcript_run_ragged(const tr_rg_block* __restrict__ blocks, const uint32_t* __restrict__ idx, uint32_t N, const tr_bufs bufs, uint8_t* __restrict__ ts,
+                        uint32_t* __restrict__ saved /*[25][2N]*/, uint32_t* __restrict__ failed, uint32_t owns_failed /*0 or bit 31*/) {
+  __shared__ uint32_t S[25 * TR_BLOCK];
+  const tr_rg_block b = blocks[blockIdx.x];
+  const uint32_t p = (threadIdx.x & (TR_BLOCK - 1)) >> 1;
+  const bool live = p < b.count;
+  const uint32_t j = idx[b.first + (live ? p : b.count - 1)];
+  transcript_pair_run(j, live, blockIdx.x == 0 && p == 0, S, b.ops, b.n_ops, b.tables, N, bufs, ts, saved, failed, b.tail | owns_failed);
 }
 
 // ---- round 6: assemble + chain (the step form of a program, merlin_prog.h) ------------------------------------------------

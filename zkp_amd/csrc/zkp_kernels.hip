@@ -1380,8 +1380,9 @@ struct zkp_ctx {
   static constexpr uint32_t kWaveCyclesCap = 1u << 20;
   // zkp_debug_last_schedule: the size-driven choices the last call made (cleared by prof_begin; -1 = the call did not make it)
   enum { SCH_BATCH_ENCODE, SCH_ENC_GROUPS, SCH_OPT_PIP, SCH_PIP_C, SCH_PIP_PART, SCH_STATUS_SHARED, SCH_LAT_SPLIT, SCH_GROUPED, SCH_COMB_MIN,
-         SCH_LADDER_INTERLEAVE, SCH_RIDERS, SCH_STRAUS_LANES, SCH_STRAUS_WINS, SCH_TR_LANES, SCH_TR_STEPS, SCH_FUSE_TT, SCH_TERMS_SPLIT, SCH_COUNT };
-  int64_t sched[SCH_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+         SCH_LADDER_INTERLEAVE, SCH_RIDERS, SCH_STRAUS_LANES, SCH_STRAUS_WINS, SCH_TR_LANES, SCH_TR_STEPS, SCH_FUSE_TT, SCH_TERMS_SPLIT,
+         SCH_RAGGED_CLASSES, SCH_RAGGED_COMPILED, SCH_RAGGED_BASE, SCH_FUSED_PLANS, SCH_COUNT };
+  int64_t sched[SCH_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
 #endif
   static constexpr size_t kGroupedCombTerms = 400000;
   static constexpr size_t kSplitCombTerms = 8192;   // narrow constant-time calls on the latency schedule from this many terms on: grouped walk + quad-split scans (ZKP_OPT_COMB_SPLIT)
@@ -1428,6 +1429,10 @@ struct zkp_ctx {
   uint32_t hot_nreg = 0;
   // fused flows (fused_flows.h): compiled transcript programs and operand templates per (flow, statement, N, position)
   std::map<std::string, void*> fused_plans;
+  // ragged calls (ragged_transcripts.h): uploaded class programs per (flow, statement, N, position) and position-free base plans per
+  // (flow, statement, N), each least recently used first out (apart from fused_plans: a ragged call never touches those)
+  std::map<std::string, void*> ragged_progs, ragged_bases;
+  uint64_t ragged_tick = 0;
   // asynchronous host-buffer jobs (host_jobs.h): at most one in flight per context
   struct job_t {
     char kind = 0;                     // 0 = none pending; 'P' prove, 'V' verify_compact, 'E' verify_batchable (each), 'B' batch verification(s)
@@ -1457,6 +1462,7 @@ struct zkp_ctx {
   bool hot_registry_uploaded = false;  // the device copy of the fixed-base registry matches hot_key[]
 };
 void free_fused_plans(zkp_ctx* c);
+void free_ragged_progs(zkp_ctx* c);
 
 namespace {
 
@@ -2087,6 +2093,7 @@ void zkp_ctx_destroy(zkp_ctx* c) {
   if (c->wave_cycles) { uint64_t* z = nullptr; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_wave_cycles), &z, sizeof(z)); hipFree(c->wave_cycles); }
 #endif
   free_fused_plans(c);
+  free_ragged_progs(c);
   if (c->side_stream) hipStreamDestroy(c->side_stream);
   if (c->ev_fork) hipEventDestroy(c->ev_fork);
   if (c->ev_join) hipEventDestroy(c->ev_join);
@@ -2606,7 +2613,8 @@ int zkp_hash_from_bytes_sha512_dev(zkp_ctx* c, uint64_t n, const uint8_t* d_msgs
 int zkp_debug_last_schedule(zkp_ctx* c, char* buf, size_t cap) {
   if (!c || !buf || !cap) return fail(ZKP_ERR_ARG, "bad argument");
   static const char* const names[zkp_ctx::SCH_COUNT] = {"batch_encode", "enc_groups", "opt_pip", "pip_c", "pip_part", "status_shared", "lat_split", "grouped", "comb_min",
-                                                        "ladder_interleave", "riders", "straus_lanes", "straus_wins", "tr_lanes", "tr_steps", "fuse_tt", "terms_split"};
+                                                        "ladder_interleave", "riders", "straus_lanes", "straus_wins", "tr_lanes", "tr_steps", "fuse_tt", "terms_split",
+                                                        "ragged_classes", "ragged_compiled", "ragged_base", "fused_plans"};
   std::string s;
   for (int i = 0; i < zkp_ctx::SCH_COUNT; ++i)
     if (c->sched[i] >= 0) s += (s.empty() ? "" : " ") + std::string(names[i]) + "=" + std::to_string(c->sched[i]);
@@ -2699,4 +2707,5 @@ int zkp_encode_many(zkp_ctx* c, uint64_t n, const uint8_t* xyzt, uint8_t* out) {
 }  // extern "C"
 
 #include "fused_flows.h"
+#include "ragged_transcripts.h"
 #include "host_jobs.h"

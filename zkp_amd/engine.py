@@ -36,8 +36,11 @@ EXPORTS = (
     "zkp_fused_prove_seeded", "zkp_fused_batch_verify_many_seeded", "zkp_ctx_job_wait", "zkp_ctx_job_poll", "zkp_ctx_job_pending", "zkp_ctx_job_discard", "zkp_ctx_job_timing", "zkp_ctx_last_kernels", "zkp_host_alloc", "zkp_host_alloc_on", "zkp_host_numa_node", "zkp_host_node_of", "zkp_host_free", "zkp_host_register", "zkp_host_unregister",
     "zkp_host_is_pinned", "zkp_chacha20_fill_dev", "zkp_from_uniform_bytes", "zkp_from_uniform_bytes_dev", "zkp_fused_hash_to_group",
     "zkp_hash_from_bytes_sha512", "zkp_hash_from_bytes_sha512_dev",
+    "zkp_fused_prove_ragged", "zkp_fused_verify_compact_ragged", "zkp_fused_verify_batchable_ragged", "zkp_fused_batch_verify_many_ragged",
+    "zkp_fused_hash_to_group_ragged",
 )
-TEST_HOOK_EXPORTS = ("zkp_debug_quad_selftest", "zkp_debug_row_selftest", "zkp_debug_wave_cycles", "zkp_debug_sha512", "zkp_debug_last_schedule")      # only in libzkp_mi355x_testhooks.so
+TEST_HOOK_EXPORTS = ("zkp_debug_quad_selftest", "zkp_debug_row_selftest", "zkp_debug_wave_cycles", "zkp_debug_sha512", "zkp_debug_last_schedule",
+                     "zkp_debug_ragged_blocks")      # only in libzkp_mi355x_testhooks.so
 
 
 class ZkpError(RuntimeError):
@@ -95,6 +98,7 @@ def load_library(test_hooks: bool = False) -> ctypes.CDLL:
         lib.zkp_debug_wave_cycles.argtypes = [vp, ctypes.c_void_p, ctypes.c_uint32]
         lib.zkp_debug_sha512.argtypes = [vp, ctypes.c_uint64, u8p, ctypes.c_void_p, u8p]
         lib.zkp_debug_last_schedule.argtypes = [vp, ctypes.c_char_p, ctypes.c_size_t]
+        lib.zkp_debug_ragged_blocks.argtypes = [vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32]
         _hooks_lib = lib
     else:
         _lib = lib
@@ -125,6 +129,20 @@ def messages_csr(messages) -> Tuple[np.ndarray, np.ndarray]:
     offsets[1:] = np.cumsum([len(m) for m in msgs], dtype=np.uint64)
     data = np.frombuffer(b"".join(msgs) or b"\0", np.uint8).copy()
     return data, offsets
+
+
+def ragged_blocks(transcripts) -> Tuple[np.ndarray, np.ndarray]:
+    """(test-hook build, no GPU needed) the class grouping the _ragged calls launch for transcripts [N][208]: (idx [N] = proof indices
+    sorted stably by class, blocks [n][3] = (class, first, count) per wavefront, classes in order of first appearance)."""
+    lib = load_library(test_hooks=True)
+    ts = _u8(transcripts, 208)
+    idx = np.zeros(len(ts), np.uint32)
+    cap = len(ts) + 1
+    blocks = np.zeros((cap, 3), np.uint32)
+    n = lib.zkp_debug_ragged_blocks(_ptr(ts), len(ts), _ptr(idx), _ptr(blocks), cap)
+    if n < 0:
+        _check(n, "zkp_debug_ragged_blocks")
+    return idx, blocks[:n]
 
 
 def _csr_args(data, offsets) -> Tuple[np.ndarray, np.ndarray]:
@@ -354,6 +372,68 @@ class Engine:
         transcripts[...] = arrs[0]
         v = np.array(list(verdicts), np.int32)
         return (v, co) if want_coeffs else v
+
+    # ---- ragged batches: transcripts at different STROBE positions (synchronous, host arrays; transcripts [N][208] advanced in place) ----
+    @staticmethod
+    def _ragged_call(transcripts, *args):
+        ts = np.ascontiguousarray(transcripts, dtype=np.uint8)
+        if ts.ndim != 2 or ts.shape[1] != 208:
+            raise ValueError("transcripts must be [N][208] uint8")
+        arrs = [None if a is None else np.ascontiguousarray(a, dtype=np.uint8) for a in args]
+        return ts, arrs, [_ptr(a) for a in arrs]
+
+    def fused_prove_ragged(self, fst: "FusedStatement", transcripts, secrets, inst, common, entropy=None, seed: Optional[bytes] = None):
+        """zkp_fused_prove_ragged -> (challenges [N][32], responses [N][m][32], commitments [N][nc][32], invalid_point); entropy [N][32]
+        or a 40-byte seed, exactly one."""
+        n, m, nc = len(transcripts), fst.c.shape.n_secrets, len(fst._lhs)
+        chal, resp, coms = np.zeros((n, 32), np.uint8), np.zeros((n, m, 32), np.uint8), np.zeros((n, nc, 32), np.uint8)
+        sd = None if seed is None else np.frombuffer(bytes(seed), np.uint8).copy()
+        ts, _, p = self._ragged_call(transcripts, secrets, inst, common, entropy, sd)
+        inv = ctypes.c_int(1)
+        _check(self._lib.zkp_fused_prove_ragged(self._h, ctypes.byref(fst.c), ctypes.c_uint32(n), _ptr(ts), *p, _ptr(chal), _ptr(resp), _ptr(coms), ctypes.byref(inv)),
+               "zkp_fused_prove_ragged")
+        transcripts[...] = ts
+        return chal, resp, coms, inv.value
+
+    def fused_verify_compact_ragged(self, fst: "FusedStatement", transcripts, inst, common, challenges, responses) -> np.ndarray:
+        """zkp_fused_verify_compact_ragged -> results [N] (0 = accepted)"""
+        n = len(transcripts)
+        res = np.ones(n, np.uint8)
+        ts, _, p = self._ragged_call(transcripts, inst, common, challenges, responses)
+        _check(self._lib.zkp_fused_verify_compact_ragged(self._h, ctypes.byref(fst.c), ctypes.c_uint32(n), _ptr(ts), *p, _ptr(res)), "zkp_fused_verify_compact_ragged")
+        transcripts[...] = ts
+        return res
+
+    def fused_verify_batchable_ragged(self, fst: "FusedStatement", transcripts, inst, common, commitments, responses, weights16) -> np.ndarray:
+        """zkp_fused_verify_batchable_ragged -> results [N] (0 = accepted); weights16 [N][nc][16]"""
+        n = len(transcripts)
+        res = np.ones(n, np.uint8)
+        ts, _, p = self._ragged_call(transcripts, inst, common, commitments, responses, weights16)
+        _check(self._lib.zkp_fused_verify_batchable_ragged(self._h, ctypes.byref(fst.c), ctypes.c_uint32(n), _ptr(ts), *p, _ptr(res)), "zkp_fused_verify_batchable_ragged")
+        transcripts[...] = ts
+        return res
+
+    def fused_batch_verify_many_ragged(self, fst: "FusedStatement", n_batches: int, transcripts, inst, common, commitments, responses, weights16=None,
+                                       seed: Optional[bytes] = None) -> np.ndarray:
+        """zkp_fused_batch_verify_many_ragged -> verdicts [n_batches] (0 = the batch verifies); weights16 [nc][N][16] or a 40-byte seed"""
+        n = len(transcripts)
+        if n_batches <= 0 or n % n_batches:
+            raise ValueError("the number of proofs must be a multiple of n_batches")
+        verdicts = (ctypes.c_int * n_batches)(*([1] * n_batches))
+        sd = None if seed is None else np.frombuffer(bytes(seed), np.uint8).copy()
+        ts, _, p = self._ragged_call(transcripts, inst, common, commitments, responses, weights16, sd)
+        _check(self._lib.zkp_fused_batch_verify_many_ragged(self._h, ctypes.byref(fst.c), ctypes.c_uint32(n_batches), ctypes.c_uint32(n // n_batches), _ptr(ts), *p,
+                                                            verdicts), "zkp_fused_batch_verify_many_ragged")
+        transcripts[...] = ts
+        return np.array(list(verdicts), np.int32)
+
+    def fused_hash_to_group_ragged(self, transcripts, label: bytes = b"output") -> np.ndarray:
+        """zkp_fused_hash_to_group_ragged -> encodings [N][32]; transcripts [N][208] advanced in place"""
+        ts = np.ascontiguousarray(transcripts, dtype=np.uint8)
+        out = np.zeros((len(ts), 32), np.uint8)
+        _check(self._lib.zkp_fused_hash_to_group_ragged(self._h, ctypes.c_uint32(len(ts)), _ptr(ts), bytes(label), _ptr(out)), "zkp_fused_hash_to_group_ragged")
+        transcripts[...] = ts
+        return out
 
     def fused_verify_batchable_coeffs(self, fst: "FusedStatement", transcripts, inst, common, commitments, responses, weights16):
         """zkp_fused_verify_batchable_coeffs on host arrays -> (results[N], coefficient vectors [N][np + nc][32]); the

@@ -46,7 +46,7 @@ EXPORTS = (
     "zkp_verify_batchable_each_submit", "zkp_batch_verify_many_submit", "zkp_job_done", "zkp_job_wait", "zkp_job_context_index", "zkp_pipe_prove_batch",
     "zkp_pipe_verify_compact_batch", "zkp_pipe_verify_batchable_each", "zkp_pipe_batch_verify", "zkp_pipe_batch_verify_many",
     "zkp_pipe_batch_verify_locate", "zkp_toolbox_set_host_max_terms", "zkp_toolbox_get_host_max_terms",
-    "zkp_from_uniform_bytes_batch", "zkp_hash_to_group_batch", "zkp_hash_from_bytes_sha512_batch",
+    "zkp_from_uniform_bytes_batch", "zkp_hash_to_group_batch", "zkp_hash_from_bytes_sha512_batch", "zkp_transcripts_append_message_batch",
 )
 ZKP_JOB_SHARED_TRANSCRIPT = 1
 ZKP_TB_PIPE_FULL = 3
@@ -124,6 +124,7 @@ def lib() -> ctypes.CDLL:
         _lib.zkp_from_uniform_bytes_batch.argtypes = [vp, ctypes.c_uint64, vp, i32, vp]
         _lib.zkp_hash_to_group_batch.argtypes = [vp, u32, vp, ctypes.c_char_p, i32, vp]
         _lib.zkp_hash_from_bytes_sha512_batch.argtypes = [vp, ctypes.c_uint64, vp, vp, i32, vp]
+        _lib.zkp_transcripts_append_message_batch.argtypes = [vp, u32, i32, ctypes.c_char_p, vp, vp, i32]
     return _lib
 
 
@@ -508,6 +509,33 @@ def hash_to_group(eng, transcripts, label: bytes = b"output", threads: int = 0) 
     if objs is not None:
         _store_transcripts(objs, arr)
     return out
+
+
+def append_messages(ts_or_label, label: bytes, messages, threads: int = 0) -> np.ndarray:
+    """merlin append_message(label, messages[j]) for every transcript j on the host threads.  ts_or_label: a [N][208] uint8 array (C-contiguous,
+    advanced in place) or a bytes label (N fresh Transcript(label) states).  Returns the [N][208] states."""
+    from .engine import messages_csr
+    return append_messages_csr(ts_or_label, label, *messages_csr(messages), threads=threads)
+
+
+def append_messages_csr(ts_or_label, label: bytes, data, offsets, threads: int = 0) -> np.ndarray:
+    """append_messages over a CSR batch: message j = data[offsets[j]:offsets[j + 1]] (offsets: N + 1 entries, non-decreasing, uint64)"""
+    from .engine import _csr_args
+    data, offsets = _csr_args(data, offsets)
+    n = len(offsets) - 1
+    shared = isinstance(ts_or_label, (bytes, bytearray))
+    if shared:
+        ts = np.zeros((max(n, 1), TRANSCRIPT_BYTES), np.uint8)
+        ts[0] = Transcript(bytes(ts_or_label)).state
+        ts = ts[:n] if n else ts[:0]
+    else:
+        ts = ts_or_label
+        if not (isinstance(ts, np.ndarray) and ts.dtype == np.uint8 and ts.shape == (n, TRANSCRIPT_BYTES) and ts.flags["C_CONTIGUOUS"]):
+            raise ValueError("transcripts must be a C-contiguous uint8 array of shape [N][%d] with N = len(offsets) - 1" % TRANSCRIPT_BYTES)
+    rc = lib().zkp_transcripts_append_message_batch(_p(ts), ctypes.c_uint32(n), int(shared), bytes(label), _p(data), _p(offsets), threads)
+    if rc != 0:
+        raise ValueError("zkp_transcripts_append_message_batch: code %d (messages and labels are limited to 2^32 - 1 bytes, as in merlin)" % rc)
+    return ts
 
 
 def hash_from_bytes_sha512(eng, messages, threads: int = 0) -> np.ndarray:
