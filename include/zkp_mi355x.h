@@ -252,7 +252,13 @@ int zkp_batch_check(zkp_ctx* ctx, const zkp_batch_statement* st, uint32_t N, con
  *     produced by the same sequence of appends with equal lengths; otherwise ZKP_ERR_ARG (callers then use the
  *     per-proof host transcripts of zkp_toolbox.h).  Layouts: secrets / responses [N][n_secrets][32];
  *     inst [n_instance][N][32]; common [n_static][32]; commitments [N][n_constraints][32]; entropy [N][32] (the 32
- *     bytes the external RNG contributes to each proof's TranscriptRng, prover.rs:82). */
+ *     bytes the external RNG contributes to each proof's TranscriptRng, prover.rs:82).
+ *     Witnesses need not be reduced: `secrets` holds each Scalar's 32 bytes as the caller allocated it, and any 256-bit value is
+ *     accepted (a Rust binding passes Scalar::as_bytes(), also of a Scalar::from_bits value).  As in the reference, the prover's RNG
+ *     is re-keyed with those 32 bytes AS GIVEN (prover.rs:80), so s and s + l draw different blindings and give different -- both
+ *     valid -- proofs; the response is (s mod l) * c + b mod l (prover.rs:107-109).  Every output (challenges, responses,
+ *     commitments) is canonical whatever the witness bytes were.  The same holds for d_secrets of the _dev entry points.
+ *     (tests/degenerate_cases.py: non-canonical witnesses on every route against both oracles, byte for byte.) */
 typedef struct {
   zkp_batch_statement shape;
   const char* label;                  /* the proof label of `domain_sep` (mod.rs:166-169)                                  */

@@ -74,7 +74,8 @@ uint32_t zkp_statement_num_constraints(const zkp_statement* st);
 /* Data layout shared by all batch calls (N = batch size, m = #secrets, ni / ns = #instance / #common
  * points, nc = #constraints; "rank" = position among the points of the same kind, in allocation order):
  *   transcripts   [N][ZKP_TRANSCRIPT_BYTES]  in/out: advanced exactly as the reference advances them
- *   secrets       [N][m][32]
+ *   secrets       [N][m][32]    each witness as the 32 bytes of the caller's Scalar, reduced or not: the prover's RNG is re-keyed
+ *                               with the bytes as given (prover.rs:80), the response is (s mod l) * c + b mod l; outputs are canonical
  *   inst_points   [ni][N][32]   row = variable, column = proof (what allocate_instance_point receives,
  *                               batch_verifier.rs:115-134; Matrix layout util.rs:21-37)
  *   common_points [ns][32]
@@ -85,6 +86,9 @@ uint32_t zkp_statement_num_constraints(const zkp_statement* st);
  * value is >= l (proofs.rs:14-32), so such a proof never verifies there; here a response (or compact challenge) >= l is
  * Err(VerificationFailure) for that proof -- for the whole batch in zkp_batch_verify*.  (The wire codec below applies the
  * same rule when it parses.)
+ * Witnesses are the other way round: zkp_prove_batch / zkp_pipe_prove_batch / zkp_prove_phase_a / _b accept ANY 32 bytes per secret (a
+ * `Scalar::from_bits` value in the reference).  s and s + l prove the same statement with different blindings, hence different proofs,
+ * exactly as two such Scalars do in the reference; the host backend, the device and both oracles agree on them byte for byte.
  */
 
 /* Prove N statements.  entropy = [N][32] bytes replacing the thread_rng contribution of prover.rs:82, or

@@ -509,13 +509,22 @@ class Prover:
         transcript.domain_sep(proof_label)
         self.transcript = transcript
         self.scalars: List[int] = []
+        self.scalar_bytes: List[bytes] = []
         self.points: List[Point] = []
         self.point_labels: List[bytes] = []
         self.constraints: List[Constraint] = []
 
-    def allocate_scalar(self, label: bytes, assignment: int) -> int:  # prover.rs:53-57
+    def allocate_scalar(self, label: bytes, assignment) -> int:       # prover.rs:53-57
+        """assignment: an int means "this value" (reduced, canonical bytes); 32 bytes are the caller's Scalar as allocated, canonical or
+        not (Scalar::from_bits): prover.rs:80 re-keys the RNG with scalar.as_bytes(), the raw bytes, and only s * c + b reduces."""
         self.transcript.append_scalar_var(label)
-        self.scalars.append(assignment % L)
+        if isinstance(assignment, (bytes, bytearray)):
+            assert len(assignment) == 32
+            self.scalar_bytes.append(bytes(assignment))
+            self.scalars.append(int.from_bytes(assignment, "little") % L)
+        else:
+            self.scalars.append(assignment % L)
+            self.scalar_bytes.append(sc_to_bytes(assignment % L))
         return len(self.scalars) - 1
 
     def allocate_point(self, label: bytes, assignment: Point) -> Tuple[int, bytes]:  # prover.rs:64-73
@@ -529,8 +538,8 @@ class Prover:
 
     def _prove_impl(self, entropy32: bytes):                            # prover.rs:76-112
         rng_builder = self.transcript.build_rng()
-        for s in self.scalars:
-            rng_builder = rng_builder.rekey_with_witness_bytes(b"", sc_to_bytes(s))
+        for raw in self.scalar_bytes:
+            rng_builder = rng_builder.rekey_with_witness_bytes(b"", raw)
         rng = rng_builder.finalize(entropy32)
         blindings = [rng.random_scalar() for _ in self.scalars]
         commitments = []

@@ -220,3 +220,115 @@ def w64_constraints_case(n, tpc, rng):
     for i in range(64):
         dlog["Q_%d" % i] = [(secrets_int["x_%d" % i][j] * g[i] + (secrets_int["y_%d" % i][j] * h if tpc == 2 else 0)) % L for j in range(n)]
     return (shape,) + _materialise(shape, n, secrets_int, dlog)
+
+
+# ---- the same flows with the verdicts as an input (tests/degenerate_cases.py) ---------------------------------------------------------------
+# _check_all_flows above asserts "every proof is accepted" and flips one response.  Degenerate inputs (an identity left-hand side, a
+# commitment that is the identity) are refused by the reference, so here the oracle says what each verifier must answer, proof by proof.
+class OracleExpectation:
+    """What oracle/c answers for one batch: the proofs (chal [n][32], resp [n][m][32], coms [n][nc][32]), the per-proof verdicts of
+    verify_compact (vc) and verify_batchable (vb), the verdict of one batch verification over all n (rc_batch) with its operand scalars
+    (coeffs; None for n > 512 or when the transcript protocol already refuses), and the verdicts of two batches in one call (rc_many:
+    n ordinary proofs, then the n proofs of this batch).  entropy, w [nc][n][16], w2 [nc][2n][16] and the ordinary batch are kept for the callers."""
+
+
+def oracle_expectation(shape, n, secrets, inst, common, seed, ordinary, same_entropy=False, tl=b"degenerate", many=True):
+    _, cst = shape.build()
+    rng = np.random.default_rng(seed)
+    E = OracleExpectation()
+    E.tl, E.n = tl, n
+    E.entropy = rng.integers(0, 256, size=(n, 32), dtype=np.uint8)
+    if same_entropy:
+        E.entropy[:] = E.entropy[0]
+    nc, m = len(shape.cons), len(shape.secret_names)
+    E.w = rng.integers(0, 256, size=(nc, n, 16), dtype=np.uint8)
+    E.w_each = np.ascontiguousarray(E.w.transpose(1, 0, 2))
+    inst_names = [p for p, c in shape.points if not c]
+    common_names = [p for p, c in shape.points if c]
+
+    def pts(ins, j):
+        return np.stack([common[common_names.index(p)] if c else ins[inst_names.index(p)][j] for p, c in shape.points])
+
+    E.chal, E.resp, E.coms = np.zeros((n, 32), np.uint8), np.zeros((n, m, 32), np.uint8), np.zeros((n, nc, 32), np.uint8)
+    E.vc, E.vb = np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+    for j in range(n):
+        p = pts(inst, j)
+        E.chal[j], E.resp[j], E.coms[j], _ = C.prove(cst, tl, secrets[j], p, E.entropy[j].tobytes())
+        E.vc[j] = C.verify_compact(cst, tl, p, E.chal[j], E.resp[j]) != 0
+        E.vb[j] = C.verify_batchable(cst, tl, p, E.coms[j], E.resp[j], E.w_each[j]) != 0
+    E.rc_batch = int(C.batch_verify(cst, tl, n, inst, common, E.coms, E.resp, E.w) != 0)
+    E.coeffs = None
+    if n <= 512:
+        rc, osc, _ = C.batch_verify(cst, tl, n, inst, common, E.coms, E.resp, E.w, want_msm_inputs=True)
+        if rc == 0:
+            E.coeffs = osc
+    E.rc_many = None
+    if many:
+        # batch 0: ordinary proofs (the oracle's, over the same common points), batch 1: this batch
+        osec, oinst = ordinary
+        k = len(osec)
+        oe = rng.integers(0, 256, size=(k, 32), dtype=np.uint8)
+        op = [C.prove(cst, tl, osec[i], pts(oinst, i), oe[i].tobytes()) for i in range(k)]
+        sel = np.arange(n) % k
+        E.inst2 = np.ascontiguousarray(np.concatenate([oinst[:, sel], inst], axis=1))
+        E.coms2 = np.ascontiguousarray(np.concatenate([np.stack([op[i][2] for i in sel]), E.coms]))
+        E.resp2 = np.ascontiguousarray(np.concatenate([np.stack([op[i][1] for i in sel]), E.resp]))
+        E.w2 = np.ascontiguousarray(np.concatenate([rng.integers(0, 256, size=(nc, n, 16), dtype=np.uint8), E.w], axis=1))
+        E.rc_many = [int(C.batch_verify(cst, tl, n, np.ascontiguousarray(E.inst2[:, b * n:(b + 1) * n]), common, E.coms2[b * n:(b + 1) * n],
+                                        E.resp2[b * n:(b + 1) * n], np.ascontiguousarray(E.w2[:, b * n:(b + 1) * n])) != 0) for b in range(2)]
+    return E
+
+
+def _first_diff(got, want):
+    bad = np.nonzero((got != want).reshape(len(got), -1).any(axis=1))[0]
+    return None if len(bad) == 0 else int(bad[0])
+
+
+def _check_flows_vs_oracle(eng, shape, n, secrets, inst, common, E, routes=(("host", NEVER), ("fused", 0)), names=None):
+    """prove / verify_compact / verify_batchable (per proof) / batch_verify (with its operand scalars) / batch_verify_many on every route,
+    against E (oracle_expectation): proofs byte for byte, verdicts proof by proof and batch by batch.  names: {index: text} for messages."""
+    st, _ = shape.build()
+    names = names or {}
+    tl = E.tl
+    what = lambda j: "proof %d (%s)" % (j, names.get(j, "ordinary"))
+    out = {}
+    for route, thr in routes:
+        T.set_fused_min_batch(thr)
+        try:
+            ts = _fresh(tl, n)
+            chal, resp, coms = T.prove_batch(eng, st, ts, secrets, inst, common, E.entropy)
+            ts2 = _fresh(tl, n)
+            res = T.verify_compact_batch(eng, st, ts2, inst, common, E.chal, E.resp)
+            ok, coeffs = T.batch_verify_coeffs(eng, st, _fresh(tl, n), inst, common, E.coms, E.resp, E.w)
+            ts4 = _fresh(tl, n)
+            each = T.verify_batchable_each(eng, st, ts4, inst, common, E.coms, E.resp, E.w_each)
+            verd = None
+            if E.rc_many is not None:
+                verd = T.batch_verify_many(eng, st, 2, _fresh(tl, 2 * n), E.inst2, common, E.coms2, E.resp2, E.w2)
+            try:
+                T.batch_verify(eng, st, _fresh(tl, n), inst, common, E.coms, E.resp, E.w)
+                rc = 0
+            except T.VerificationFailure:
+                rc = 1
+        finally:
+            T.set_fused_min_batch(32)
+        for name, got, want in (("challenge", chal, E.chal), ("responses", resp, E.resp), ("commitments", coms, E.coms)):
+            j = _first_diff(got, want)
+            assert j is None, "%s route: %s of %s differ from the oracle's prover" % (route, name, what(j))
+        j = _first_diff(res, E.vc)
+        assert j is None, "%s route: verify_compact says %d for %s, the oracle %d" % (route, res[j], what(j), E.vc[j])
+        j = _first_diff(each, E.vb)
+        assert j is None, "%s route: verify_batchable says %d for %s, the oracle %d" % (route, each[j], what(j), E.vb[j])
+        assert rc == E.rc_batch and ok == (E.rc_batch == 0), "%s route: batch_verify %d / %r, the oracle %d" % (route, rc, ok, E.rc_batch)
+        if E.coeffs is not None:
+            j = _first_diff(coeffs, E.coeffs)
+            assert j is None, "%s route: operand scalar %d of the batch verifier differs from the oracle's" % (route, j)
+        if verd is not None:
+            assert verd.tolist() == E.rc_many, "%s route: batch_verify_many %r, the oracle %r" % (route, verd.tolist(), E.rc_many)
+        acc, acc_b = E.vc == 0, E.vb == 0
+        out[route] = (chal, resp, coms, ts[:, :203], ts2[acc][:, :203], ts4[acc_b][:, :203])
+    first = routes[0][0]
+    for route, _ in routes[1:]:
+        for a, b in zip(out[first], out[route]):
+            assert a.shape == b.shape and (a == b).all(), "%s and %s routes leave different bytes" % (first, route)
+    return out[routes[-1][0]]

@@ -23,6 +23,8 @@ ZKP_OPT_WS_LIMIT_BYTES, ZKP_OPT_JOB_DEFER_D2H, ZKP_OPT_SYNC_SCHEDULE, ZKP_OPT_TR
 ZKP_VARTIME = 0
 ZKP_CT = 1
 ZKP_OPT_BATCH_ENCODE_MIN = 1
+(ZKP_OPT_COMB_TEETH, ZKP_OPT_CT_SINGLE_USE_TABLES, ZKP_OPT_TRANSCRIPT_LANES, ZKP_OPT_DEV_OVERLAP, ZKP_OPT_GROUPED_COMB, ZKP_OPT_TABLES_LANE,
+ ZKP_OPT_FUSE_TABLES_TRANSCRIPT) = 2, 3, 4, 5, 6, 7, 8
 K_NAMES = ("decode", "terms", "reduce", "sort", "bucket", "combine", "transcript", "scalars", "tables")
 
 EXPORTS = (
