@@ -178,7 +178,6 @@ def test_device_randomness_is_the_pinned_chacha_stream(eng):
     import torch
     from zkp_amd.engine import load_library
     hip = load_library()
-    hip.zkp_chacha20_fill_dev.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_size_t]
     key = bytes(range(32))
     nonce, first = 0x0123456789ABCDEF, 0xFFFFFFFE                  # the counter crosses 32 bits inside the run
     blocks = 300
@@ -188,7 +187,6 @@ def test_device_randomness_is_the_pinned_chacha_stream(eng):
     got = d.cpu().numpy().tobytes()
     want = b""
     out = ctypes.create_string_buffer(64)
-    T.lib().zkp_chacha20_block.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_char_p]
     for b in range(blocks):
         T.lib().zkp_chacha20_block(key, first + b, nonce, out)
         want += out.raw
@@ -306,7 +304,6 @@ def test_context_with_a_pending_job_refuses_other_calls(eng, cmz):
     t0 = _t0()
     args = [eng._h, ctypes.cast(ctypes.byref(fst.c), ctypes.c_void_p), n, 1, T._p(t0), T._p(np.ascontiguousarray(secrets[:n])), T._p(inst_n), n, T._p(common), T._p(np.ascontiguousarray(entropy[:n])), None, None,
             T._p(chal), T._p(resp), T._p(coms), ctypes.byref(inv)]
-    hip.zkp_fused_prove_submit.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32] + [ctypes.c_void_p] * 3 + [ctypes.c_uint32] + [ctypes.c_void_p] * 8
     assert hip.zkp_fused_prove_submit(*args) == 0
     assert hip.zkp_ctx_job_pending(eng._h) == 1
     assert hip.zkp_fused_prove_submit(*args) == -2                      # ZKP_ERR_ARG: one job per context
@@ -333,7 +330,6 @@ def test_verdict_words_are_rejected_until_the_job_has_run_and_discard_writes_not
     chal, resp, coms = T.prove_batch(eng, st, _t0(n), secrets[:n], inst_n, common, entropy[:n])
     t0 = _t0()
     results = np.zeros(n, np.uint8)                                     # what a careless caller hands over
-    hip.zkp_fused_verify_compact_submit.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32] + [ctypes.c_void_p] * 2 + [ctypes.c_uint32] + [ctypes.c_void_p] * 5
     args = [eng._h, ctypes.cast(ctypes.byref(fst.c), ctypes.c_void_p), n, 1, T._p(t0), T._p(inst_n), n, T._p(common), T._p(chal), T._p(resp), None, T._p(results)]
     assert hip.zkp_fused_verify_compact_submit(*args) == 0
     assert results.all()                                                # rejected until the job says otherwise
@@ -346,7 +342,6 @@ def test_verdict_words_are_rejected_until_the_job_has_run_and_discard_writes_not
     # discard: the job's kernels run, its outputs never arrive, the verdict words keep what submit put there
     results[:] = 0
     assert hip.zkp_fused_verify_compact_submit(*args) == 0 and hip.zkp_ctx_job_pending(eng._h) == 1
-    hip.zkp_ctx_job_discard.argtypes = [ctypes.c_void_p]
     assert hip.zkp_ctx_job_discard(eng._h) == 0 and hip.zkp_ctx_job_pending(eng._h) == 0
     assert results.all()
     assert hip.zkp_ctx_job_wait(eng._h) == 0                            # nothing pending: OK at once
@@ -385,10 +380,6 @@ def test_pinned_rings_on_the_gpus_numa_node():
     lets us set a memory policy; everywhere else the call is zkp_host_alloc.  Always: usable pinned memory, visible as such."""
     from zkp_amd.engine import load_library
     hip = load_library()
-    hip.zkp_host_alloc_on.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t, ctypes.c_int]
-    hip.zkp_host_node_of.argtypes = [ctypes.c_void_p]
-    hip.zkp_host_free.argtypes = [ctypes.c_void_p]
-    hip.zkp_host_is_pinned.argtypes = [ctypes.c_void_p]
     node = hip.zkp_host_numa_node(0)
     assert node >= -1
     p = ctypes.c_void_p()

@@ -656,7 +656,6 @@ def test_seeded_synchronous_calls_draw_the_pinned_chacha_stream(eng, pinned):
     mod, secrets, inst, common = _cmz_batch(n, 41)
     fst = _cmz_fused_statement()
     seed = bytes(range(7, 47))
-    T.lib().zkp_chacha20_block.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_char_p]
     out, stream = ctypes.create_string_buffer(64), b""
     for b in range((32 * n + 63) // 64):
         T.lib().zkp_chacha20_block(seed[:32], b, int.from_bytes(seed[32:], "little"), out)

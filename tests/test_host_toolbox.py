@@ -43,6 +43,17 @@ def _declared(header, test_hooks=False):
     return sorted(set(re.findall(r"\b(zkp_[a-z0-9_]+)\s*\(", src)))
 
 
+def _prototypes(header, test_hooks=False):
+    """{name: (return type, parameter count)} of the prototypes a header declares, read here independently of zkp_amd.cabi: one
+    prototype per line start, parameters split on commas, (void) = 0"""
+    src = open(os.path.join(ROOT, "include", header)).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    hooks = "".join(re.findall(r"#ifdef ZKP_BUILD_TEST_HOOKS(.*?)#endif", src, flags=re.S))
+    src = hooks if test_hooks else re.sub(r"#ifdef ZKP_BUILD_TEST_HOOKS.*?#endif", "", src, flags=re.S)
+    protos = re.findall(r"^[ \t]*([\w \t*]+?)[ \t]*\b(zkp_\w+)\s*\(([^()]*)\)\s*;", src, flags=re.M)
+    return {name: (" ".join(ret.split()), 0 if params.strip() in ("", "void") else len(params.split(","))) for ret, name, params in protos}
+
+
 def test_c_abi_exports_every_declared_symbol():
     hip = ctypes.CDLL(engine.LIB_PATH)
     for name in _declared("zkp_mi355x.h"):
@@ -60,6 +71,38 @@ def test_c_abi_exports_every_declared_symbol():
     for name in declared:
         assert hasattr(tb, name), name
     assert set(T.EXPORTS) == set(declared)
+    # the EXPORTS lists come from the binding's header reader: it must find what the name regex above finds, section by section
+    from zkp_amd import cabi
+    for header in ("zkp_mi355x.h", "zkp_toolbox.h"):
+        for in_hooks in (False, True):
+            assert set(cabi.signatures(header, test_hooks=in_hooks)) == set(_declared(header, test_hooks=in_hooks)), (header, in_hooks)
+
+
+def test_every_declared_function_is_typed_from_its_header():
+    """The ctypes binding takes argtypes / restype from include/*.h: after loading the three libraries every declared function is typed,
+    with the header's parameter count and return type; the reader refuses a type it has no mapping for."""
+    from zkp_amd import cabi
+    want_res = {"void": None, "int": ctypes.c_int, "uint32_t": ctypes.c_uint32, "size_t": ctypes.c_size_t, "const char*": ctypes.c_char_p}
+    libs = ((engine.load_library(), "zkp_mi355x.h", False), (engine.load_library(test_hooks=True), "zkp_mi355x.h", True),
+            (T.lib(), "zkp_toolbox.h", False))
+    for lib, header, hooks in libs:
+        protos = dict(_prototypes(header))
+        if hooks:
+            protos.update(_prototypes(header, test_hooks=True))
+        assert set(protos) == set(_declared(header)) | (set(_declared(header, test_hooks=True)) if hooks else set())
+        for name, (ret, n_params) in protos.items():
+            f = getattr(lib, name)
+            assert f.argtypes is not None and len(f.argtypes) == n_params, (header, name, f.argtypes, n_params)
+            assert f.restype is want_res.get(ret, ctypes.c_void_p if ret.endswith("*") else "unmapped"), (header, name, ret, f.restype)
+    hip, tb = engine.load_library(), T.lib()
+    assert hip.zkp_hash_from_bytes_sha512_dev.argtypes[3] is ctypes.c_uint64                 # msgs_len
+    assert hip.zkp_last_error.restype is ctypes.c_char_p
+    assert hip.zkp_ctx_destroy.restype is None
+    assert tb.zkp_pipe_context.restype is ctypes.c_void_p
+    assert tb.zkp_proof_compact_size.restype is ctypes.c_size_t
+    assert tb.zkp_transcript_init.argtypes[0] is ctypes.c_void_p
+    with pytest.raises(TypeError, match="zkp_bogus"):
+        cabi.parse("int zkp_ok(uint32_t n);\nint zkp_bogus(zkp_ctx* ctx, float scale);\n")
 
 
 def test_shipped_code_object_has_no_scratch_no_spills_and_no_hook_kernels(tmp_path):
@@ -262,8 +305,6 @@ def test_transcript_lengths_beyond_u32_are_an_error_not_a_truncated_prefix():
     """merlin frames lengths as u32 and asserts that they fit (tests/sig_and_vrf_example.rs:224-241 is the ignored > 4 GiB case): the C
     ABI returns ZKP_TB_TOO_LONG before it reads a byte and leaves the transcript untouched."""
     lib = T.lib()
-    lib.zkp_transcript_append_message.restype = ctypes.c_int
-    lib.zkp_transcript_challenge_bytes.restype = ctypes.c_int
     t = T.Transcript(b"len")
     before = t.state.copy()
     small = ctypes.create_string_buffer(16)
@@ -478,6 +519,11 @@ def test_rust_sys_crate_declares_every_exported_symbol():
     src = open(os.path.join(root, "rust", "zkp-mi355x-sys", "src", "lib.rs")).read()
     declared = set(re.findall(r"pub fn (zkp_\w+)\s*\(", src))
     assert declared == set(engine.EXPORTS) | set(T.EXPORTS), (declared ^ (set(engine.EXPORTS) | set(T.EXPORTS)))
+    # ... with the header's parameter count
+    counts = {name: n for header in ("zkp_mi355x.h", "zkp_toolbox.h") for name, (_, n) in _prototypes(header).items()}
+    assert set(counts) == declared
+    for name, params in re.findall(r"pub fn (zkp_\w+)\s*\(([^)]*)\)", src):
+        assert len([p for p in params.split(",") if p.strip()]) == counts[name], name
     assert "UNBUILT SOURCE" in src and "UNBUILT" in open(os.path.join(root, "rust", "README.md")).read()
 
 

@@ -53,10 +53,8 @@ def run():
     m, nc = len(st[0]), len(st[2])
     z = lambda *s: torch.zeros(s, dtype=torch.uint8, device=dev)
     d_ts, d_chal, d_resp, d_coms, d_st = z(n, 208), z(n, 32), z(n, m, 32), z(n, nc, 32), z(n * nc)
-    import ctypes
     from zkp_amd.engine import load_library
     hip = load_library()
-    hip.zkp_chacha20_fill_dev.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_size_t]
     d_mark = z(64)
     for name, opts in SCHEDULES:
         for k, v in ((5, 0), (15, 1)) + tuple(opts):

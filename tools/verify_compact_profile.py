@@ -15,7 +15,6 @@ K, N_EACH, CALLS = 50, 4096, 3
 
 
 def run():
-    import ctypes
     import torch
     import bench
     from zkp_amd.engine import Engine, FusedStatement, load_library
@@ -40,7 +39,6 @@ def run():
     eng.fused_prove_dev(fst, n, pos, d_ts.data_ptr(), d_sec.data_ptr(), d_tbl.data_ptr(), d_ent.data_ptr(), d_chal.data_ptr(), d_resp.data_ptr(), d_coms.data_ptr(), d_st.data_ptr())
     eng.synchronize()
     hip = load_library()
-    hip.zkp_chacha20_fill_dev.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_size_t]
     d_mark = z(64)
     for _ in range(CALLS + 1):                  # (the first call also registers what a first call registers; the summary reads the calls behind the LAST markers)
         d_ts.copy_(d_ts0)

@@ -11,6 +11,8 @@ from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
+from . import cabi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libzkp_mi355x.so")
 TESTHOOKS_LIB_PATH = os.path.join(_HERE, "libzkp_mi355x_testhooks.so")     # -DZKP_BUILD_TEST_HOOKS build (tests / A-B tools)
@@ -27,22 +29,8 @@ ZKP_OPT_BATCH_ENCODE_MIN = 1
  ZKP_OPT_FUSE_TABLES_TRANSCRIPT) = 2, 3, 4, 5, 6, 7, 8
 K_NAMES = ("decode", "terms", "reduce", "sort", "bucket", "combine", "transcript", "scalars", "tables")
 
-EXPORTS = (
-    "zkp_ctx_create", "zkp_ctx_destroy", "zkp_ctx_set_stream", "zkp_ctx_synchronize", "zkp_last_error",
-    "zkp_version", "zkp_ctx_set_option", "zkp_msm_many", "zkp_msm_many_dev", "zkp_msm_optional", "zkp_msm_optional_dev",
-    "zkp_decode_check", "zkp_encode_many", "zkp_ctx_last_timing", "zkp_ctx_set_profiling",
-    "zkp_ctx_prepare_fixed_points", "zkp_batch_check", "zkp_fused_prove", "zkp_fused_verify_compact", "zkp_fused_batch_verify",
-    "zkp_fused_verify_batchable", "zkp_fused_prove_dev", "zkp_fused_verify_compact_dev", "zkp_fused_verify_batchable_dev", "zkp_fused_batch_verify_dev",
-    "zkp_fused_verify_batchable_coeffs", "zkp_fused_batch_verify_many", "zkp_fused_batch_verify_many_dev", "zkp_ctx_capture_begin", "zkp_ctx_capture_end", "zkp_ctx_capture_abort", "zkp_graph_launch", "zkp_graph_destroy",
-    "zkp_fused_prove_submit", "zkp_fused_verify_compact_submit", "zkp_fused_batch_verify_many_submit", "zkp_fused_verify_batchable_submit",
-    "zkp_fused_prove_seeded", "zkp_fused_batch_verify_many_seeded", "zkp_ctx_job_wait", "zkp_ctx_job_poll", "zkp_ctx_job_pending", "zkp_ctx_job_discard", "zkp_ctx_job_timing", "zkp_ctx_last_kernels", "zkp_host_alloc", "zkp_host_alloc_on", "zkp_host_numa_node", "zkp_host_node_of", "zkp_host_free", "zkp_host_register", "zkp_host_unregister",
-    "zkp_host_is_pinned", "zkp_chacha20_fill_dev", "zkp_from_uniform_bytes", "zkp_from_uniform_bytes_dev", "zkp_fused_hash_to_group",
-    "zkp_hash_from_bytes_sha512", "zkp_hash_from_bytes_sha512_dev",
-    "zkp_fused_prove_ragged", "zkp_fused_verify_compact_ragged", "zkp_fused_verify_batchable_ragged", "zkp_fused_batch_verify_many_ragged",
-    "zkp_fused_hash_to_group_ragged",
-)
-TEST_HOOK_EXPORTS = ("zkp_debug_quad_selftest", "zkp_debug_row_selftest", "zkp_debug_wave_cycles", "zkp_debug_sha512", "zkp_debug_last_schedule",
-                     "zkp_debug_ragged_blocks")      # only in libzkp_mi355x_testhooks.so
+EXPORTS = tuple(cabi.signatures("zkp_mi355x.h"))
+TEST_HOOK_EXPORTS = tuple(cabi.signatures("zkp_mi355x.h", test_hooks=True))      # only in libzkp_mi355x_testhooks.so
 
 
 class ZkpError(RuntimeError):
@@ -54,8 +42,9 @@ _hooks_lib = None
 
 
 def load_library(test_hooks: bool = False) -> ctypes.CDLL:
-    """dlopen the HIP library; raises (never falls back) when it has not been built.  test_hooks = the -DZKP_BUILD_TEST_HOOKS
-    build of the same sources (a second, independent copy of the library: its contexts must not be handed to libzkp_toolbox.so)."""
+    """dlopen the HIP library, every function typed from include/zkp_mi355x.h; raises (never falls back) when it has not been built.
+    test_hooks = the -DZKP_BUILD_TEST_HOOKS build of the same sources (a second, independent copy of the library: its contexts must not
+    be handed to libzkp_toolbox.so), its hook section typed too."""
     global _lib, _hooks_lib
     if test_hooks and _hooks_lib is not None:
         return _hooks_lib
@@ -65,42 +54,8 @@ def load_library(test_hooks: bool = False) -> ctypes.CDLL:
     if not os.path.exists(path):
         raise ZkpError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                        "(hipcc --offload-arch=gfx950); there is no CPU fallback")
-    lib = ctypes.CDLL(path)
-    vp, u8p, u32p, i32 = ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int
-    lib.zkp_ctx_create.argtypes = [ctypes.POINTER(vp), i32]
-    lib.zkp_ctx_destroy.argtypes = [vp]
-    lib.zkp_ctx_destroy.restype = None
-    lib.zkp_ctx_set_stream.argtypes = [vp, vp]
-    lib.zkp_ctx_synchronize.argtypes = [vp]
-    lib.zkp_last_error.restype = ctypes.c_char_p
-    lib.zkp_version.restype = ctypes.c_char_p
-    lib.zkp_msm_many.argtypes = [vp, ctypes.c_uint32, u32p, u8p, u32p, u8p, ctypes.c_uint32, i32, u8p, u8p]
-    lib.zkp_msm_many_dev.argtypes = [vp, ctypes.c_uint32, u32p, u8p, u32p, u8p, ctypes.c_uint32, ctypes.c_uint32, i32, u8p, u8p]
-    lib.zkp_msm_optional.argtypes = [vp, ctypes.c_uint64, u8p, u8p, u8p, ctypes.POINTER(i32)]
-    lib.zkp_msm_optional_dev.argtypes = [vp, ctypes.c_uint64, u8p, u8p, u8p, u32p]
-    lib.zkp_decode_check.argtypes = [vp, ctypes.c_uint64, u8p, u8p, u8p]
-    lib.zkp_encode_many.argtypes = [vp, ctypes.c_uint64, u8p, u8p]
-    lib.zkp_from_uniform_bytes.argtypes = [vp, ctypes.c_uint64, u8p, u8p]
-    lib.zkp_from_uniform_bytes_dev.argtypes = [vp, ctypes.c_uint64, u8p, u8p]
-    lib.zkp_fused_hash_to_group.argtypes = [vp, ctypes.c_uint32, u8p, ctypes.c_char_p, u8p]
-    lib.zkp_hash_from_bytes_sha512.argtypes = [vp, ctypes.c_uint64, u8p, ctypes.c_void_p, u8p]
-    lib.zkp_hash_from_bytes_sha512_dev.argtypes = [vp, ctypes.c_uint64, u8p, ctypes.c_uint64, ctypes.c_void_p, u8p]
-    lib.zkp_ctx_last_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
-    lib.zkp_ctx_set_profiling.argtypes = [vp, i32]
-    lib.zkp_ctx_capture_begin.argtypes = [vp]
-    lib.zkp_ctx_capture_end.argtypes = [vp, ctypes.POINTER(vp)]
-    lib.zkp_graph_launch.argtypes = [vp, vp]
-    lib.zkp_graph_destroy.argtypes = [vp]
-    lib.zkp_graph_destroy.restype = None
-    lib.zkp_ctx_prepare_fixed_points.argtypes = [vp, ctypes.c_uint32, u8p]
-    lib.zkp_ctx_capture_abort.argtypes = [vp]
+    lib = cabi.bind(ctypes.CDLL(path), "zkp_mi355x.h", test_hooks)
     if test_hooks:
-        lib.zkp_debug_quad_selftest.argtypes = [vp, ctypes.c_uint32, u8p, u8p]
-        lib.zkp_debug_row_selftest.argtypes = [vp, ctypes.c_uint32, u8p, u8p]
-        lib.zkp_debug_wave_cycles.argtypes = [vp, ctypes.c_void_p, ctypes.c_uint32]
-        lib.zkp_debug_sha512.argtypes = [vp, ctypes.c_uint64, u8p, ctypes.c_void_p, u8p]
-        lib.zkp_debug_last_schedule.argtypes = [vp, ctypes.c_char_p, ctypes.c_size_t]
-        lib.zkp_debug_ragged_blocks.argtypes = [vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32]
         _hooks_lib = lib
     else:
         _lib = lib
@@ -113,6 +68,8 @@ def _check(rc: int, what: str) -> None:
 
 
 def _u8(a, shape_last: int) -> np.ndarray:
+    if len(a) == 0:
+        return np.zeros((0, shape_last), np.uint8)
     a = np.ascontiguousarray(a, dtype=np.uint8)
     if a.ndim != 2 or a.shape[1] != shape_last:
         raise ValueError(f"expected uint8 array of shape [n][{shape_last}], got {a.shape}")
@@ -185,6 +142,10 @@ class Engine:
     def version(self) -> str:
         return self._lib.zkp_version().decode()
 
+    def _need_hooks(self, fn: str) -> None:
+        if not self.test_hooks:
+            raise ZkpError(f"{fn} exists in the test-hook build only: Engine(device, test_hooks=True)")
+
     # ---- host-buffer entry points (numpy) ---------------------------------------------------
     def msm_many(self, off: Sequence[int], scalars, pidx: Sequence[int], points, flags: int = ZKP_VARTIME
                  ) -> Tuple[np.ndarray, np.ndarray]:
@@ -194,7 +155,7 @@ class Engine:
         pidx = np.ascontiguousarray(pidx, dtype=np.uint32)
         n_terms = int(off[-1]) if n_msm >= 0 and len(off) else 0
         scalars = _u8(scalars, 32) if n_terms else np.zeros((0, 32), np.uint8)
-        points = _u8(points, 32) if len(points) else np.zeros((0, 32), np.uint8)
+        points = _u8(points, 32)
         if len(scalars) != n_terms or len(pidx) != n_terms:
             raise ValueError("scalars / pidx length must equal off[-1]")
         out = np.zeros((max(n_msm, 0), 32), np.uint8)
@@ -205,8 +166,7 @@ class Engine:
 
     def msm_optional(self, scalars, points) -> Optional[bytes]:
         """optional_multiscalar_mul: encoding of sum s_i * decode(P_i), or None if a decode fails."""
-        scalars = _u8(scalars, 32) if len(scalars) else np.zeros((0, 32), np.uint8)
-        points = _u8(points, 32) if len(points) else np.zeros((0, 32), np.uint8)
+        scalars, points = _u8(scalars, 32), _u8(points, 32)
         if len(scalars) != len(points):
             raise ValueError("scalars and points must have equal length")
         out = np.zeros(32, np.uint8)
@@ -216,21 +176,21 @@ class Engine:
         return None if st.value else out.tobytes()
 
     def decode_check(self, points, want_coords: bool = False):
-        points = _u8(points, 32) if len(points) else np.zeros((0, 32), np.uint8)
+        points = _u8(points, 32)
         status = np.zeros(len(points), np.uint8)
         xyzt = np.zeros((len(points), 128), np.uint8) if want_coords else None
         _check(self._lib.zkp_decode_check(self._h, len(points), _ptr(points), _ptr(status), _ptr(xyzt)), "zkp_decode_check")
         return (status, xyzt) if want_coords else status
 
     def encode_many(self, xyzt) -> np.ndarray:
-        xyzt = _u8(xyzt, 128) if len(xyzt) else np.zeros((0, 128), np.uint8)
+        xyzt = _u8(xyzt, 128)
         out = np.zeros((len(xyzt), 32), np.uint8)
         _check(self._lib.zkp_encode_many(self._h, len(xyzt), _ptr(xyzt), _ptr(out)), "zkp_encode_many")
         return out
 
     def from_uniform_bytes(self, inp) -> np.ndarray:
         """RistrettoPoint::from_uniform_bytes (RFC 9496 section 4.3.4) of every 64-byte row: [n][64] -> canonical encodings [n][32]"""
-        inp = _u8(inp, 64) if len(inp) else np.zeros((0, 64), np.uint8)
+        inp = _u8(inp, 64)
         out = np.zeros((len(inp), 32), np.uint8)
         _check(self._lib.zkp_from_uniform_bytes(self._h, len(inp), _ptr(inp), _ptr(out)), "zkp_from_uniform_bytes")
         return out
@@ -249,8 +209,7 @@ class Engine:
 
     def debug_sha512(self, data, offsets) -> np.ndarray:
         """the SHA-512 stage alone (test-hook build): CSR batch -> digests [n][64]"""
-        if not self.test_hooks:
-            raise ZkpError("zkp_debug_sha512 exists in the test-hook build only: Engine(device, test_hooks=True)")
+        self._need_hooks("zkp_debug_sha512")
         data, offsets = _csr_args(data, offsets)
         n = len(offsets) - 1
         out = np.zeros((n, 64), np.uint8)
@@ -260,8 +219,7 @@ class Engine:
     def debug_quad_selftest(self, pairs) -> np.ndarray:
         pairs = _u8(pairs, 64)
         out = np.zeros((len(pairs), 4, 32), np.uint8)
-        if not self.test_hooks:
-            raise ZkpError("zkp_debug_quad_selftest exists in the test-hook build only: Engine(device, test_hooks=True)")
+        self._need_hooks("zkp_debug_quad_selftest")
         _check(self._lib.zkp_debug_quad_selftest(self._h, len(pairs), _ptr(pairs), _ptr(out)), "zkp_debug_quad_selftest")
         return out
 
@@ -269,17 +227,15 @@ class Engine:
         """(test-hook build) one-limb-per-lane point arithmetic (csrc/rowfe.h): [n][64] encodings (P, Q) -> [n][3][32] = enc(2P), enc(P+Q), enc(2^11 P + Q)"""
         pairs = _u8(pairs, 64)
         out = np.zeros((len(pairs), 3, 32), np.uint8)
-        if not self.test_hooks:
-            raise ZkpError("zkp_debug_row_selftest exists in the test-hook build only: Engine(device, test_hooks=True)")
+        self._need_hooks("zkp_debug_row_selftest")
         _check(self._lib.zkp_debug_row_selftest(self._h, len(pairs), _ptr(pairs), _ptr(out)), "zkp_debug_row_selftest")
         return out
 
     def debug_wave_cycles(self, cap: int = 1 << 20):
         """(test-hook build, after set_option(ZKP_TESTOPT_WAVE_CYCLES, 1)) -> (class[n], cycles[n]) of the term kernel's wavefronts since the last read"""
-        if not self.test_hooks:
-            raise ZkpError("zkp_debug_wave_cycles exists in the test-hook build only: Engine(device, test_hooks=True)")
+        self._need_hooks("zkp_debug_wave_cycles")
         buf = np.zeros(cap, np.uint64)
-        n = self._lib.zkp_debug_wave_cycles(self._h, _ptr(buf), ctypes.c_uint32(cap))
+        n = self._lib.zkp_debug_wave_cycles(self._h, _ptr(buf), cap)
         if n < 0:
             _check(n, "zkp_debug_wave_cycles")
         buf = buf[:n]
@@ -289,8 +245,7 @@ class Engine:
     def last_schedule(self) -> dict:
         """(test-hook build) {choice: value} of the size-driven choices the last call made (zkp_debug_last_schedule), e.g.
         {"batch_encode": 1, "enc_groups": 2}; choices the call did not make are absent"""
-        if not self.test_hooks:
-            raise ZkpError("zkp_debug_last_schedule exists in the test-hook build only: Engine(device, test_hooks=True)")
+        self._need_hooks("zkp_debug_last_schedule")
         buf = ctypes.create_string_buffer(1024)
         n = self._lib.zkp_debug_last_schedule(self._h, buf, 1024)
         if n < 0:
@@ -299,12 +254,12 @@ class Engine:
 
     def prepare_fixed_points(self, encodings) -> None:
         """Hint: these points (the statement's common / static points) will be referenced by many terms."""
-        encodings = _u8(encodings, 32) if len(encodings) else np.zeros((0, 32), np.uint8)
+        encodings = _u8(encodings, 32)
         _check(self._lib.zkp_ctx_prepare_fixed_points(self._h, len(encodings), _ptr(encodings)), "zkp_ctx_prepare_fixed_points")
 
     # ---- device-buffer entry points (raw device pointers, e.g. torch tensor .data_ptr()) ----
     def set_stream(self, hip_stream: int) -> None:
-        _check(self._lib.zkp_ctx_set_stream(self._h, ctypes.c_void_p(hip_stream)), "zkp_ctx_set_stream")
+        _check(self._lib.zkp_ctx_set_stream(self._h, hip_stream), "zkp_ctx_set_stream")
 
     def synchronize(self) -> None:
         _check(self._lib.zkp_ctx_synchronize(self._h), "zkp_ctx_synchronize")
@@ -327,31 +282,26 @@ class Engine:
 
     # ---- fused statement flows on device-resident buffers (include/zkp_mi355x.h section 2c) -------------
     def fused_prove_dev(self, fst: "FusedStatement", n, strobe_pos, d_ts, d_secrets, d_table, d_entropy, d_chal, d_resp, d_coms, d_status) -> None:
-        _check(self._lib.zkp_fused_prove_dev(self._h, ctypes.byref(fst.c), ctypes.c_uint32(n), ctypes.c_uint32(strobe_pos),
-                                             *[ctypes.c_void_p(x) for x in (d_ts, d_secrets, d_table, d_entropy, d_chal, d_resp, d_coms, d_status)]),
-               "zkp_fused_prove_dev")
+        _check(self._lib.zkp_fused_prove_dev(self._h, ctypes.byref(fst.c), n, strobe_pos, d_ts, d_secrets, d_table, d_entropy, d_chal, d_resp, d_coms,
+                                             d_status), "zkp_fused_prove_dev")
 
     def fused_verify_batchable_dev(self, fst: "FusedStatement", n, strobe_pos, d_ts, d_table, d_resp, d_w, d_results) -> None:
         """d_table = common || instance rows || commitments [n][nc]; d_w [n][nc][16]; d_results [n] bytes (0 = verified)"""
-        _check(self._lib.zkp_fused_verify_batchable_dev(self._h, ctypes.byref(fst.c), ctypes.c_uint32(n), ctypes.c_uint32(strobe_pos),
-                                                        *[ctypes.c_void_p(x) for x in (d_ts, d_table, d_resp, d_w, d_results)]),
+        _check(self._lib.zkp_fused_verify_batchable_dev(self._h, ctypes.byref(fst.c), n, strobe_pos, d_ts, d_table, d_resp, d_w, d_results),
                "zkp_fused_verify_batchable_dev")
 
     def fused_verify_compact_dev(self, fst: "FusedStatement", n, strobe_pos, d_ts, d_table, d_chal, d_resp, d_results) -> None:
-        _check(self._lib.zkp_fused_verify_compact_dev(self._h, ctypes.byref(fst.c), ctypes.c_uint32(n), ctypes.c_uint32(strobe_pos),
-                                                      *[ctypes.c_void_p(x) for x in (d_ts, d_table, d_chal, d_resp, d_results)]),
+        _check(self._lib.zkp_fused_verify_compact_dev(self._h, ctypes.byref(fst.c), n, strobe_pos, d_ts, d_table, d_chal, d_resp, d_results),
                "zkp_fused_verify_compact_dev")
 
     def fused_batch_verify_dev(self, fst: "FusedStatement", n, strobe_pos, d_ts, d_points, d_coms, d_resp, d_w, d_out, d_status) -> None:
-        _check(self._lib.zkp_fused_batch_verify_dev(self._h, ctypes.byref(fst.c), ctypes.c_uint32(n), ctypes.c_uint32(strobe_pos),
-                                                    *[ctypes.c_void_p(x) for x in (d_ts, d_points, d_coms, d_resp, d_w, d_out, d_status)]),
+        _check(self._lib.zkp_fused_batch_verify_dev(self._h, ctypes.byref(fst.c), n, strobe_pos, d_ts, d_points, d_coms, d_resp, d_w, d_out, d_status),
                "zkp_fused_batch_verify_dev")
 
     def fused_batch_verify_many_dev(self, fst: "FusedStatement", n_batches, n_each, strobe_pos, d_ts, d_points, d_coms, d_resp, d_w, d_out, d_status) -> None:
         """K batch verifications of n_each proofs in one pass; d_out [K][32], d_status [K][2] int32 (zkp_fused_batch_verify_many_dev)."""
-        _check(self._lib.zkp_fused_batch_verify_many_dev(self._h, ctypes.byref(fst.c), ctypes.c_uint32(n_batches), ctypes.c_uint32(n_each), ctypes.c_uint32(strobe_pos),
-                                                         *[ctypes.c_void_p(x) for x in (d_ts, d_points, d_coms, d_resp, d_w, d_out, d_status)]),
-               "zkp_fused_batch_verify_many_dev")
+        _check(self._lib.zkp_fused_batch_verify_many_dev(self._h, ctypes.byref(fst.c), n_batches, n_each, strobe_pos, d_ts, d_points, d_coms, d_resp, d_w,
+                                                         d_out, d_status), "zkp_fused_batch_verify_many_dev")
 
     def fused_batch_verify_many(self, fst: "FusedStatement", n_batches: int, transcripts, inst, common, commitments, responses, weights16, want_coeffs: bool = False):
         """zkp_fused_batch_verify_many on host arrays: the len(transcripts) = n_batches * N_each proofs lie next to each other, batch b =
@@ -368,9 +318,8 @@ class Engine:
         if arrs[1].shape != (fst.n_instance, n, 32) or arrs[2].shape != (fst.n_static, 32) or arrs[3].shape != (n, len(fst._lhs), 32) or \
                 arrs[4].shape[:1] != (n,) or arrs[5].shape != (len(fst._lhs), n, 16) or arrs[0].shape != (n, 208):
             raise ValueError("array shapes do not match the statement / batch sizes")
-        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-        _check(self._lib.zkp_fused_batch_verify_many(self._h, ctypes.byref(fst.c), ctypes.c_uint32(n_batches), ctypes.c_uint32(n_each), ptr(arrs[0]), ptr(arrs[1]),
-                                                     ptr(arrs[2]), ptr(arrs[3]), ptr(arrs[4]), ptr(arrs[5]), verdicts, _ptr(co)), "zkp_fused_batch_verify_many")
+        _check(self._lib.zkp_fused_batch_verify_many(self._h, ctypes.byref(fst.c), n_batches, n_each, *map(_ptr, arrs), verdicts, _ptr(co)),
+               "zkp_fused_batch_verify_many")
         transcripts[...] = arrs[0]
         v = np.array(list(verdicts), np.int32)
         return (v, co) if want_coeffs else v
@@ -392,7 +341,7 @@ class Engine:
         sd = None if seed is None else np.frombuffer(bytes(seed), np.uint8).copy()
         ts, _, p = self._ragged_call(transcripts, secrets, inst, common, entropy, sd)
         inv = ctypes.c_int(1)
-        _check(self._lib.zkp_fused_prove_ragged(self._h, ctypes.byref(fst.c), ctypes.c_uint32(n), _ptr(ts), *p, _ptr(chal), _ptr(resp), _ptr(coms), ctypes.byref(inv)),
+        _check(self._lib.zkp_fused_prove_ragged(self._h, ctypes.byref(fst.c), n, _ptr(ts), *p, _ptr(chal), _ptr(resp), _ptr(coms), ctypes.byref(inv)),
                "zkp_fused_prove_ragged")
         transcripts[...] = ts
         return chal, resp, coms, inv.value
@@ -402,7 +351,7 @@ class Engine:
         n = len(transcripts)
         res = np.ones(n, np.uint8)
         ts, _, p = self._ragged_call(transcripts, inst, common, challenges, responses)
-        _check(self._lib.zkp_fused_verify_compact_ragged(self._h, ctypes.byref(fst.c), ctypes.c_uint32(n), _ptr(ts), *p, _ptr(res)), "zkp_fused_verify_compact_ragged")
+        _check(self._lib.zkp_fused_verify_compact_ragged(self._h, ctypes.byref(fst.c), n, _ptr(ts), *p, _ptr(res)), "zkp_fused_verify_compact_ragged")
         transcripts[...] = ts
         return res
 
@@ -411,7 +360,7 @@ class Engine:
         n = len(transcripts)
         res = np.ones(n, np.uint8)
         ts, _, p = self._ragged_call(transcripts, inst, common, commitments, responses, weights16)
-        _check(self._lib.zkp_fused_verify_batchable_ragged(self._h, ctypes.byref(fst.c), ctypes.c_uint32(n), _ptr(ts), *p, _ptr(res)), "zkp_fused_verify_batchable_ragged")
+        _check(self._lib.zkp_fused_verify_batchable_ragged(self._h, ctypes.byref(fst.c), n, _ptr(ts), *p, _ptr(res)), "zkp_fused_verify_batchable_ragged")
         transcripts[...] = ts
         return res
 
@@ -424,8 +373,8 @@ class Engine:
         verdicts = (ctypes.c_int * n_batches)(*([1] * n_batches))
         sd = None if seed is None else np.frombuffer(bytes(seed), np.uint8).copy()
         ts, _, p = self._ragged_call(transcripts, inst, common, commitments, responses, weights16, sd)
-        _check(self._lib.zkp_fused_batch_verify_many_ragged(self._h, ctypes.byref(fst.c), ctypes.c_uint32(n_batches), ctypes.c_uint32(n // n_batches), _ptr(ts), *p,
-                                                            verdicts), "zkp_fused_batch_verify_many_ragged")
+        _check(self._lib.zkp_fused_batch_verify_many_ragged(self._h, ctypes.byref(fst.c), n_batches, n // n_batches, _ptr(ts), *p, verdicts),
+               "zkp_fused_batch_verify_many_ragged")
         transcripts[...] = ts
         return np.array(list(verdicts), np.int32)
 
@@ -433,7 +382,7 @@ class Engine:
         """zkp_fused_hash_to_group_ragged -> encodings [N][32]; transcripts [N][208] advanced in place"""
         ts = np.ascontiguousarray(transcripts, dtype=np.uint8)
         out = np.zeros((len(ts), 32), np.uint8)
-        _check(self._lib.zkp_fused_hash_to_group_ragged(self._h, ctypes.c_uint32(len(ts)), _ptr(ts), bytes(label), _ptr(out)), "zkp_fused_hash_to_group_ragged")
+        _check(self._lib.zkp_fused_hash_to_group_ragged(self._h, len(ts), _ptr(ts), bytes(label), _ptr(out)), "zkp_fused_hash_to_group_ragged")
         transcripts[...] = ts
         return out
 
@@ -445,9 +394,8 @@ class Engine:
         res = np.ones(n, np.uint8)
         co = np.zeros((n, k, 32), np.uint8)
         arrs = [np.ascontiguousarray(a, dtype=np.uint8) for a in (transcripts, inst, common, commitments, responses, weights16)]
-        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-        _check(self._lib.zkp_fused_verify_batchable_coeffs(self._h, ctypes.byref(fst.c), ctypes.c_uint32(n), ptr(arrs[0]), ptr(arrs[1]), ptr(arrs[2]),
-                                                           ptr(arrs[3]), ptr(arrs[4]), ptr(arrs[5]), ptr(res), ptr(co)), "zkp_fused_verify_batchable_coeffs")
+        _check(self._lib.zkp_fused_verify_batchable_coeffs(self._h, ctypes.byref(fst.c), n, *map(_ptr, arrs), _ptr(res), _ptr(co)),
+               "zkp_fused_verify_batchable_coeffs")
         transcripts[...] = arrs[0]
         return res, co
 
@@ -459,7 +407,7 @@ class Engine:
 
     def set_option(self, option: int, value: int) -> None:
         """Tuning knobs of include/zkp_mi355x.h (ZKP_OPT_*); results never depend on them."""
-        _check(self._lib.zkp_ctx_set_option(self._h, ctypes.c_int(option), ctypes.c_uint64(value)), "zkp_ctx_set_option")
+        _check(self._lib.zkp_ctx_set_option(self._h, option, value), "zkp_ctx_set_option")
 
     def capture_begin(self) -> None:
         """Start recording what is enqueued on this context's stream into a HIP graph (zkp_ctx_capture_begin)."""
@@ -494,7 +442,6 @@ class Engine:
         """{timing kind: [kernel names as rocprofv3 prints them]} for the kinds whose kernel variant the last call picked at run time"""
         out = {}
         buf = ctypes.create_string_buffer(512)
-        self._lib.zkp_ctx_last_kernels.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]
         for i, k in enumerate(K_NAMES):
             if self._lib.zkp_ctx_last_kernels(self._h, i, buf, 512) > 0:
                 out[k] = buf.value.decode().split(";")
@@ -582,9 +529,8 @@ class FusedStatement:
         self._sl = (ctypes.c_char_p * max(1, len(secrets)))(*[bytes(x) for x in secrets])
         self._pl = (ctypes.c_char_p * max(1, len(points)))(*plabels)
         self._label = bytes(proof_label)
-        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-        self.c = _FusedStatementC(_BatchStatementC(len(secrets), k_c, k_i, len(constraints), vp(self._lhs), vp(self._off), vp(self._sc), vp(self._pt)),
-                                  self._label, self._sl, self._pl, vp(self._order), None)
+        self.c = _FusedStatementC(_BatchStatementC(len(secrets), k_c, k_i, len(constraints), _ptr(self._lhs), _ptr(self._off), _ptr(self._sc), _ptr(self._pt)),
+                                  self._label, self._sl, self._pl, _ptr(self._order), None)
         if alloc_seq is not None:
             self._seq = np.array([(0x80000000 | i) if kind == "s" else rank[i] for kind, i in alloc_seq], np.uint32)
-            self.c.alloc_seq = vp(self._seq)
+            self.c.alloc_seq = _ptr(self._seq)

@@ -25,6 +25,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from . import cabi
 from .engine import Engine, load_library
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -32,22 +33,7 @@ LIB_PATH = os.path.join(_HERE, "libzkp_toolbox.so")
 TRANSCRIPT_BYTES = 208
 L = 2**252 + 27742317777372353535851937790883648493
 
-EXPORTS = (
-    "zkp_transcript_init", "zkp_transcript_append_message", "zkp_transcript_challenge_bytes", "zkp_scalar_from_wide",
-    "zkp_scalar_muladd", "zkp_scalar_neg", "zkp_statement_new", "zkp_statement_free", "zkp_statement_add_secret",
-    "zkp_statement_add_point", "zkp_statement_constrain", "zkp_statement_num_secrets", "zkp_statement_num_instance",
-    "zkp_statement_num_common", "zkp_statement_num_constraints", "zkp_statement_num_terms", "zkp_prove_batch",
-    "zkp_verify_compact_batch", "zkp_verify_batchable_each", "zkp_batch_verify", "zkp_batch_verify_coeffs", "zkp_batch_verify_build",
-    "zkp_prove_phase_a", "zkp_prove_phase_b", "zkp_toolbox_set_fused_min_batch", "zkp_toolbox_get_fused_min_batch", "zkp_chacha20_block",
-    "zkp_proof_compact_size", "zkp_proof_batchable_size", "zkp_proof_compact_encode", "zkp_proof_compact_decode",
-    "zkp_proof_batchable_encode", "zkp_proof_batchable_decode", "zkp_batch_verify_locate", "zkp_batch_verify_many",
-    "zkp_pipe_create", "zkp_pipe_destroy", "zkp_pipe_num_contexts", "zkp_pipe_num_devices", "zkp_pipe_context", "zkp_pipe_context_device", "zkp_pipe_shard_plan",
-    "zkp_pipe_jobs_in_flight", "zkp_pipe_set_submit_threads", "zkp_pipe_last_error", "zkp_prove_batch_submit", "zkp_verify_compact_batch_submit",
-    "zkp_verify_batchable_each_submit", "zkp_batch_verify_many_submit", "zkp_job_done", "zkp_job_wait", "zkp_job_context_index", "zkp_pipe_prove_batch",
-    "zkp_pipe_verify_compact_batch", "zkp_pipe_verify_batchable_each", "zkp_pipe_batch_verify", "zkp_pipe_batch_verify_many",
-    "zkp_pipe_batch_verify_locate", "zkp_toolbox_set_host_max_terms", "zkp_toolbox_get_host_max_terms",
-    "zkp_from_uniform_bytes_batch", "zkp_hash_to_group_batch", "zkp_hash_from_bytes_sha512_batch", "zkp_transcripts_append_message_batch",
-)
+EXPORTS = tuple(cabi.signatures("zkp_toolbox.h"))
 ZKP_JOB_SHARED_TRANSCRIPT = 1
 ZKP_TB_PIPE_FULL = 3
 
@@ -73,75 +59,22 @@ def lib() -> ctypes.CDLL:
         load_library()          # libzkp_mi355x.so must exist: no CPU fallback
         if not os.path.exists(LIB_PATH):
             raise RuntimeError(f"{LIB_PATH} is missing: run __graft_entry__.build()")
-        _lib = ctypes.CDLL(LIB_PATH)
-        _lib.zkp_statement_new.restype = ctypes.c_void_p
-        _lib.zkp_statement_new.argtypes = [ctypes.c_char_p]
-        _lib.zkp_statement_free.argtypes = [ctypes.c_void_p]
-        _lib.zkp_statement_free.restype = None
-        _lib.zkp_statement_add_secret.argtypes = [ctypes.c_void_p, ctypes.c_char_p]
-        _lib.zkp_statement_add_point.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int]
-        _lib.zkp_statement_constrain.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
-        for f in ("num_secrets", "num_instance", "num_common", "num_constraints", "num_terms"):
-            getattr(_lib, "zkp_statement_" + f).argtypes = [ctypes.c_void_p]
-            getattr(_lib, "zkp_statement_" + f).restype = ctypes.c_uint32
-        vp, u32, sz = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_size_t
-        _lib.zkp_proof_compact_size.restype = sz
-        _lib.zkp_proof_compact_size.argtypes = [u32]
-        _lib.zkp_proof_batchable_size.restype = sz
-        _lib.zkp_proof_batchable_size.argtypes = [u32, u32]
-        _lib.zkp_proof_compact_encode.argtypes = [ctypes.c_char_p, vp, u32, ctypes.c_char_p, sz]
-        _lib.zkp_proof_compact_decode.argtypes = [ctypes.c_char_p, sz, vp, vp, u32, ctypes.POINTER(u32), ctypes.POINTER(sz)]
-        _lib.zkp_proof_batchable_encode.argtypes = [vp, u32, vp, u32, ctypes.c_char_p, sz]
-        _lib.zkp_proof_batchable_decode.argtypes = [ctypes.c_char_p, sz, vp, u32, ctypes.POINTER(u32), vp, u32, ctypes.POINTER(u32), ctypes.POINTER(sz)]
-        i32 = ctypes.c_int
-        _lib.zkp_pipe_create.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(i32), i32, i32]
-        _lib.zkp_pipe_destroy.argtypes = [vp]
-        _lib.zkp_pipe_destroy.restype = None
-        for f in ("num_contexts", "num_devices", "jobs_in_flight"):
-            getattr(_lib, "zkp_pipe_" + f).argtypes = [vp]
-        _lib.zkp_pipe_context.argtypes = [vp, i32]
-        _lib.zkp_pipe_context.restype = vp
-        _lib.zkp_pipe_context_device.argtypes = [vp, i32]
-        _lib.zkp_pipe_shard_plan.argtypes = [u32, u32, u32, u32, vp, vp]
-        _lib.zkp_pipe_shard_plan.restype = u32
-        _lib.zkp_pipe_set_submit_threads.argtypes = [vp, i32]
-        _lib.zkp_pipe_last_error.argtypes = [vp]
-        _lib.zkp_pipe_last_error.restype = ctypes.c_char_p
-        pj = ctypes.POINTER(vp)
-        _lib.zkp_prove_batch_submit.argtypes = [vp, vp, u32, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, pj]
-        _lib.zkp_verify_compact_batch_submit.argtypes = [vp, vp, u32, u32, vp, vp, u32, vp, vp, vp, vp, vp, pj]
-        _lib.zkp_verify_batchable_each_submit.argtypes = [vp, vp, u32, u32, vp, vp, u32, vp, vp, vp, vp, vp, vp, pj]
-        _lib.zkp_batch_verify_many_submit.argtypes = [vp, vp, u32, u32, u32, vp, vp, u32, vp, vp, vp, vp, u32, vp, vp, pj]
-        _lib.zkp_job_done.argtypes = [vp]
-        _lib.zkp_job_context_index.argtypes = [vp]
-        _lib.zkp_job_wait.argtypes = [vp]
-        _lib.zkp_pipe_prove_batch.argtypes = [vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]
-        _lib.zkp_pipe_verify_compact_batch.argtypes = [vp, vp, u32, vp, vp, vp, vp, vp, vp]
-        _lib.zkp_pipe_verify_batchable_each.argtypes = [vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]
-        _lib.zkp_pipe_batch_verify.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp, vp, vp]
-        _lib.zkp_pipe_batch_verify_many.argtypes = [vp, vp, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp]
-        _lib.zkp_pipe_batch_verify_locate.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp]
-        _lib.zkp_from_uniform_bytes_batch.argtypes = [vp, ctypes.c_uint64, vp, i32, vp]
-        _lib.zkp_hash_to_group_batch.argtypes = [vp, u32, vp, ctypes.c_char_p, i32, vp]
-        _lib.zkp_hash_from_bytes_sha512_batch.argtypes = [vp, ctypes.c_uint64, vp, vp, i32, vp]
-        _lib.zkp_transcripts_append_message_batch.argtypes = [vp, u32, i32, ctypes.c_char_p, vp, vp, i32]
+        _lib = cabi.bind(ctypes.CDLL(LIB_PATH), "zkp_toolbox.h")
     return _lib
 
 
 def set_fused_min_batch(n: int) -> None:
     """Batches of >= n proofs run transcripts, scalars and MSMs on the device; smaller ones hash on the host threads."""
-    lib().zkp_toolbox_set_fused_min_batch(ctypes.c_uint32(n))
+    lib().zkp_toolbox_set_fused_min_batch(n)
 
 
 def set_host_max_terms(n: int) -> None:
     """Calls of at most n (scalar, point) terms run on the host backend even with a GPU context (0 = never); ctx = None always does."""
-    lib().zkp_toolbox_set_host_max_terms(ctypes.c_uint32(n))
+    lib().zkp_toolbox_set_host_max_terms(n)
 
 
 def get_host_max_terms() -> int:
-    f = lib().zkp_toolbox_get_host_max_terms
-    f.restype = ctypes.c_uint32
-    return int(f())
+    return lib().zkp_toolbox_get_host_max_terms()
 
 
 class HostEngine:
@@ -153,9 +86,7 @@ class HostEngine:
 
 
 def get_fused_min_batch() -> int:
-    f = lib().zkp_toolbox_get_fused_min_batch
-    f.restype = ctypes.c_uint32
-    return int(f())
+    return lib().zkp_toolbox_get_fused_min_batch()
 
 
 def pipe_shard_plan(n_items: int, n_contexts: int, unit: int = 1, fused_min_batch: Optional[int] = None):
@@ -199,19 +130,19 @@ class Transcript:
             self.state = _state.copy()
         else:
             self.state = np.zeros(TRANSCRIPT_BYTES, np.uint8)
-            lib().zkp_transcript_init(_p(self.state), label, ctypes.c_size_t(len(label)))
+            lib().zkp_transcript_init(_p(self.state), label, len(label))
 
     def clone(self) -> "Transcript":
         return Transcript(_state=self.state)
 
     def append_message(self, label: bytes, message: bytes) -> None:
-        rc = lib().zkp_transcript_append_message(_p(self.state), label, message, ctypes.c_size_t(len(message)))
+        rc = lib().zkp_transcript_append_message(_p(self.state), label, message, len(message))
         if rc != 0:
             raise ValueError("zkp_transcript_append_message: code %d (messages and labels are limited to 2^32 - 1 bytes, as in merlin)" % rc)
 
     def challenge_bytes(self, label: bytes, n: int) -> bytes:
         out = ctypes.create_string_buffer(n)
-        rc = lib().zkp_transcript_challenge_bytes(_p(self.state), label, out, ctypes.c_size_t(n))
+        rc = lib().zkp_transcript_challenge_bytes(_p(self.state), label, out, n)
         if rc != 0:
             raise ValueError("zkp_transcript_challenge_bytes: code %d" % rc)
         return out.raw
@@ -229,10 +160,9 @@ def _wire_decode(kind: str, buf: bytes, allow_trailing: bool):
     r = np.zeros((cap, 32), np.uint8)
     na, nr, used = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_size_t(0)
     if kind == "compact":
-        rc = lib().zkp_proof_compact_decode(buf, ctypes.c_size_t(len(buf)), _p(a), _p(r), ctypes.c_uint32(cap), ctypes.byref(nr), ctypes.byref(used))
+        rc = lib().zkp_proof_compact_decode(buf, len(buf), _p(a), _p(r), cap, ctypes.byref(nr), ctypes.byref(used))
     else:
-        rc = lib().zkp_proof_batchable_decode(buf, ctypes.c_size_t(len(buf)), _p(a), ctypes.c_uint32(cap), ctypes.byref(na), _p(r), ctypes.c_uint32(cap),
-                                              ctypes.byref(nr), ctypes.byref(used))
+        rc = lib().zkp_proof_batchable_decode(buf, len(buf), _p(a), cap, ctypes.byref(na), _p(r), cap, ctypes.byref(nr), ctypes.byref(used))
     if rc != 0:
         raise ValueError("malformed proof (truncated, or a scalar was not canonically encoded): code %d" % rc)
     if not allow_trailing and used.value != len(buf):
@@ -253,9 +183,9 @@ class CompactProof:            # src/proofs.rs:15-20
     # bincode's own behaviour (its top-level deserialize ignores what follows the value); the default here is strict.
     def to_bytes(self) -> bytes:
         m = len(self.responses)
-        out = ctypes.create_string_buffer(lib().zkp_proof_compact_size(ctypes.c_uint32(m)))
+        out = ctypes.create_string_buffer(lib().zkp_proof_compact_size(m))
         resp = np.frombuffer(b"".join(self.responses), np.uint8) if m else np.zeros(0, np.uint8)
-        rc = lib().zkp_proof_compact_encode(bytes(self.challenge), _p(resp), ctypes.c_uint32(m), out, ctypes.c_size_t(len(out)))
+        rc = lib().zkp_proof_compact_encode(bytes(self.challenge), _p(resp), m, out, len(out))
         if rc != 0:
             raise ValueError("zkp_proof_compact_encode: code %d" % rc)
         return out.raw
@@ -273,10 +203,10 @@ class BatchableProof:          # src/proofs.rs:27-32
 
     def to_bytes(self) -> bytes:
         nc, m = len(self.commitments), len(self.responses)
-        out = ctypes.create_string_buffer(lib().zkp_proof_batchable_size(ctypes.c_uint32(nc), ctypes.c_uint32(m)))
+        out = ctypes.create_string_buffer(lib().zkp_proof_batchable_size(nc, m))
         coms = np.frombuffer(b"".join(self.commitments), np.uint8) if nc else np.zeros(0, np.uint8)
         resp = np.frombuffer(b"".join(self.responses), np.uint8) if m else np.zeros(0, np.uint8)
-        rc = lib().zkp_proof_batchable_encode(_p(coms), ctypes.c_uint32(nc), _p(resp), ctypes.c_uint32(m), out, ctypes.c_size_t(len(out)))
+        rc = lib().zkp_proof_batchable_encode(_p(coms), nc, _p(resp), m, out, len(out))
         if rc != 0:
             raise ValueError("zkp_proof_batchable_encode: code %d" % rc)
         return out.raw
@@ -361,7 +291,7 @@ def prove_batch(eng: Engine, st: Statement, transcripts: np.ndarray, secrets: np
         for name, a, shape in (("challenges", chal, (n, 32)), ("responses", resp, (n, st.m, 32)), ("commitments", coms, (n, st.nc, 32))):
             if tuple(np.shape(a)) != shape or a.dtype != np.uint8 or not a.flags["C_CONTIGUOUS"]:
                 raise ValueError("out: %s must be a C-contiguous uint8 array of shape %r" % (name, shape))
-    rc = lib().zkp_prove_batch(eng._h, st._h, ctypes.c_uint32(n), _p(transcripts), _p(np.ascontiguousarray(secrets)),
+    rc = lib().zkp_prove_batch(eng._h, st._h, n, _p(transcripts), _p(np.ascontiguousarray(secrets)),
                                _p(np.ascontiguousarray(inst)), _p(np.ascontiguousarray(common)),
                                _p(None if entropy is None else np.ascontiguousarray(entropy)), threads, _p(chal), _p(resp), _p(coms))
     _raise(rc, "zkp_prove_batch")
@@ -374,7 +304,7 @@ def verify_compact_batch(eng, st, transcripts, inst, common, challenges, respons
     if tuple(np.shape(challenges)) != (n, 32):
         raise ValueError("challenges must have shape (%d, 32)" % n)
     res = np.ones(n, np.uint8)
-    rc = lib().zkp_verify_compact_batch(eng._h, st._h, ctypes.c_uint32(n), _p(transcripts), _p(np.ascontiguousarray(inst)),
+    rc = lib().zkp_verify_compact_batch(eng._h, st._h, n, _p(transcripts), _p(np.ascontiguousarray(inst)),
                                         _p(np.ascontiguousarray(common)), _p(np.ascontiguousarray(challenges)),
                                         _p(np.ascontiguousarray(responses)), threads, _p(res))
     _raise(rc, "zkp_verify_compact_batch")
@@ -385,7 +315,7 @@ def verify_batchable_each(eng, st, transcripts, inst, common, commitments, respo
     n = len(transcripts)
     _check_batch_shapes(st, n, inst, common, commitments, responses, weights16, per_proof_weights=True)
     res = np.ones(n, np.uint8)
-    rc = lib().zkp_verify_batchable_each(eng._h, st._h, ctypes.c_uint32(n), _p(transcripts), _p(np.ascontiguousarray(inst)),
+    rc = lib().zkp_verify_batchable_each(eng._h, st._h, n, _p(transcripts), _p(np.ascontiguousarray(inst)),
                                          _p(np.ascontiguousarray(common)), _p(np.ascontiguousarray(commitments)),
                                          _p(np.ascontiguousarray(responses)),
                                          _p(None if weights16 is None else np.ascontiguousarray(weights16)), threads, _p(res))
@@ -411,8 +341,7 @@ def batch_verify(eng, st, transcripts, inst, common, commitments, responses, wei
     """Raises VerificationFailure / BatchSizeMismatch like BatchVerifier::verify_batchable."""
     n = len(commitments)
     _check_batch_shapes(st, n, inst, common, commitments, responses, weights16)
-    rc = lib().zkp_batch_verify(eng._h, st._h, ctypes.c_uint32(n if batch_size is None else batch_size),
-                                ctypes.c_uint32(len(transcripts)), _p(transcripts),
+    rc = lib().zkp_batch_verify(eng._h, st._h, n if batch_size is None else batch_size, len(transcripts), _p(transcripts),
                                 _p(np.ascontiguousarray(inst)), _p(np.ascontiguousarray(common)),
                                 _p(np.ascontiguousarray(commitments)), _p(np.ascontiguousarray(responses)),
                                 _p(None if weights16 is None else np.ascontiguousarray(weights16)), threads)
@@ -427,7 +356,7 @@ def batch_verify_many(eng, st, n_batches: int, transcripts, inst, common, commit
         raise ValueError("the number of proofs must be a positive multiple of n_batches")
     _check_batch_shapes(st, n, inst, common, commitments, responses, weights16)
     verdicts = (ctypes.c_int * n_batches)(*([1] * n_batches))
-    rc = lib().zkp_batch_verify_many(eng._h, st._h, ctypes.c_uint32(n_batches), ctypes.c_uint32(n // n_batches), ctypes.c_uint32(len(transcripts)),
+    rc = lib().zkp_batch_verify_many(eng._h, st._h, n_batches, n // n_batches, len(transcripts),
                                      _p(transcripts), _p(np.ascontiguousarray(inst)), _p(np.ascontiguousarray(common)),
                                      _p(np.ascontiguousarray(commitments)), _p(np.ascontiguousarray(responses)),
                                      _p(None if weights16 is None else np.ascontiguousarray(weights16)), threads, verdicts)
@@ -442,7 +371,7 @@ def batch_verify_locate(eng, st, transcripts, inst, common, commitments, respons
     n = len(commitments)
     _check_batch_shapes(st, n, inst, common, commitments, responses, weights16)
     res = np.ones(n, np.uint8)
-    rc = lib().zkp_batch_verify_locate(eng._h, st._h, ctypes.c_uint32(n), ctypes.c_uint32(len(transcripts)), _p(transcripts),
+    rc = lib().zkp_batch_verify_locate(eng._h, st._h, n, len(transcripts), _p(transcripts),
                                        _p(np.ascontiguousarray(inst)), _p(np.ascontiguousarray(common)),
                                        _p(np.ascontiguousarray(commitments)), _p(np.ascontiguousarray(responses)),
                                        _p(None if weights16 is None else np.ascontiguousarray(weights16)), threads, _p(res))
@@ -457,7 +386,7 @@ def batch_verify_coeffs(eng, st, transcripts, inst, common, commitments, respons
     _check_batch_shapes(st, n, inst, common, commitments, responses, weights16)
     total = st.ns + (st.ni + st.nc) * n
     co = np.zeros((total, 32), np.uint8)
-    rc = lib().zkp_batch_verify_coeffs(eng._h, st._h, ctypes.c_uint32(n), ctypes.c_uint32(len(transcripts)), _p(transcripts),
+    rc = lib().zkp_batch_verify_coeffs(eng._h, st._h, n, len(transcripts), _p(transcripts),
                                        _p(np.ascontiguousarray(inst)), _p(np.ascontiguousarray(common)),
                                        _p(np.ascontiguousarray(commitments)), _p(np.ascontiguousarray(responses)),
                                        _p(np.ascontiguousarray(weights16)), threads, _p(co))
@@ -473,7 +402,7 @@ def batch_verify_build(st, transcripts, inst, common, commitments, responses, we
     total = st.ns + (st.ni + st.nc) * n
     ms = np.zeros((total, 32), np.uint8)
     mp = np.zeros((total, 32), np.uint8)
-    rc = lib().zkp_batch_verify_build(st._h, ctypes.c_uint32(n), ctypes.c_uint32(len(transcripts)), _p(transcripts),
+    rc = lib().zkp_batch_verify_build(st._h, n, len(transcripts), _p(transcripts),
                                       _p(np.ascontiguousarray(inst)), _p(np.ascontiguousarray(common)),
                                       _p(np.ascontiguousarray(commitments)), _p(np.ascontiguousarray(responses)),
                                       _p(np.ascontiguousarray(weights16)), threads, _p(ms), _p(mp))
@@ -487,7 +416,7 @@ def from_uniform_bytes(eng, inp, threads: int = 0) -> np.ndarray:
     maps on the host threads; with an Engine, calls above get_host_max_terms() outputs map on the GPU."""
     inp = np.ascontiguousarray(inp, dtype=np.uint8).reshape(-1, 64) if len(inp) else np.zeros((0, 64), np.uint8)
     out = np.zeros((len(inp), 32), np.uint8)
-    rc = lib().zkp_from_uniform_bytes_batch(None if eng is None else eng._h, ctypes.c_uint64(len(inp)), _p(inp), threads, _p(out))
+    rc = lib().zkp_from_uniform_bytes_batch(None if eng is None else eng._h, len(inp), _p(inp), threads, _p(out))
     _raise(rc, "zkp_from_uniform_bytes_batch")
     return out
 
@@ -504,7 +433,7 @@ def hash_to_group(eng, transcripts, label: bytes = b"output", threads: int = 0) 
         if not (isinstance(arr, np.ndarray) and arr.dtype == np.uint8 and arr.ndim == 2 and arr.shape[1] == TRANSCRIPT_BYTES and arr.flags["C_CONTIGUOUS"]):
             raise ValueError("transcripts must be Transcript objects or a C-contiguous uint8 array of shape [N][%d]" % TRANSCRIPT_BYTES)
     out = np.zeros((len(arr), 32), np.uint8)
-    rc = lib().zkp_hash_to_group_batch(None if eng is None else eng._h, ctypes.c_uint32(len(arr)), _p(arr), label, threads, _p(out))
+    rc = lib().zkp_hash_to_group_batch(None if eng is None else eng._h, len(arr), _p(arr), label, threads, _p(out))
     _raise(rc, "zkp_hash_to_group_batch")
     if objs is not None:
         _store_transcripts(objs, arr)
@@ -532,7 +461,7 @@ def append_messages_csr(ts_or_label, label: bytes, data, offsets, threads: int =
         ts = ts_or_label
         if not (isinstance(ts, np.ndarray) and ts.dtype == np.uint8 and ts.shape == (n, TRANSCRIPT_BYTES) and ts.flags["C_CONTIGUOUS"]):
             raise ValueError("transcripts must be a C-contiguous uint8 array of shape [N][%d] with N = len(offsets) - 1" % TRANSCRIPT_BYTES)
-    rc = lib().zkp_transcripts_append_message_batch(_p(ts), ctypes.c_uint32(n), int(shared), bytes(label), _p(data), _p(offsets), threads)
+    rc = lib().zkp_transcripts_append_message_batch(_p(ts), n, int(shared), bytes(label), _p(data), _p(offsets), threads)
     if rc != 0:
         raise ValueError("zkp_transcripts_append_message_batch: code %d (messages and labels are limited to 2^32 - 1 bytes, as in merlin)" % rc)
     return ts
@@ -553,7 +482,7 @@ def hash_from_bytes_sha512_csr(eng, data, offsets, threads: int = 0) -> np.ndarr
     data, offsets = _csr_args(data, offsets)
     n = len(offsets) - 1
     out = np.zeros((n, 32), np.uint8)
-    rc = lib().zkp_hash_from_bytes_sha512_batch(None if eng is None else eng._h, ctypes.c_uint64(n), _p(data), _p(offsets), threads, _p(out))
+    rc = lib().zkp_hash_from_bytes_sha512_batch(None if eng is None else eng._h, n, _p(data), _p(offsets), threads, _p(out))
     _raise(rc, "zkp_hash_from_bytes_sha512_batch")
     return out
 
@@ -564,12 +493,9 @@ def pinned_empty(shape, dtype=np.uint8) -> np.ndarray:
     """A numpy array in pinned host memory (zkp_host_alloc): jobs copy from / to it without staging.  The memory is freed when
     the array (and every view of it) is gone."""
     hip = load_library()
-    hip.zkp_host_alloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
-    hip.zkp_host_free.argtypes = [ctypes.c_void_p]
-    hip.zkp_host_free.restype = None
     nbytes = int(np.prod(shape)) * np.dtype(dtype).itemsize
     ptr = ctypes.c_void_p()
-    rc = hip.zkp_host_alloc(ctypes.byref(ptr), ctypes.c_size_t(max(nbytes, 1)))
+    rc = hip.zkp_host_alloc(ctypes.byref(ptr), max(nbytes, 1))
     if rc != 0:
         _raise(rc, "zkp_host_alloc")
 
@@ -691,18 +617,15 @@ class Pipe:
 
     def job_timing(self, context: int):
         """(ms of host -> device copies, kernels, device -> host copies) of the last job that finished on that context (profiling on)"""
-        hip = load_library()
-        hip.zkp_ctx_job_timing.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
         ms = (ctypes.c_float * 3)()
-        hip.zkp_ctx_job_timing(lib().zkp_pipe_context(self._h, context), ms)
+        load_library().zkp_ctx_job_timing(lib().zkp_pipe_context(self._h, context), ms)
         return tuple(float(x) for x in ms)
 
     def set_option(self, option: int, value: int, context: Optional[int] = None) -> None:
         """zkp_ctx_set_option on one context of the pipe, or on all of them"""
         hip = load_library()
-        hip.zkp_ctx_set_option.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64]
         for i in ([context] if context is not None else range(self.num_contexts)):
-            rc = hip.zkp_ctx_set_option(lib().zkp_pipe_context(self._h, i), option, ctypes.c_uint64(value))
+            rc = hip.zkp_ctx_set_option(lib().zkp_pipe_context(self._h, i), option, value)
             if rc != 0:
                 _raise(rc, "zkp_ctx_set_option")
 
@@ -875,7 +798,7 @@ def prove_phase_a(st, transcripts, secrets, inst, common, entropy, threads: int 
     off = np.zeros(n * st.nc + 1, np.uint32)
     sc = np.zeros((n * st.terms, 32), np.uint8)
     pidx = np.zeros(n * st.terms, np.uint32)
-    rc = lib().zkp_prove_phase_a(st._h, ctypes.c_uint32(n), _p(transcripts), _p(np.ascontiguousarray(secrets)),
+    rc = lib().zkp_prove_phase_a(st._h, n, _p(transcripts), _p(np.ascontiguousarray(secrets)),
                                  _p(np.ascontiguousarray(inst)), _p(np.ascontiguousarray(common)),
                                  _p(np.ascontiguousarray(entropy)), threads, _p(blind), _p(off), _p(sc), _p(pidx))
     _raise(rc, "zkp_prove_phase_a")
@@ -886,7 +809,7 @@ def prove_phase_b(st, transcripts, secrets, blindings, commitments, threads: int
     n = len(transcripts)
     chal = np.zeros((n, 32), np.uint8)
     resp = np.zeros((n, st.m, 32), np.uint8)
-    rc = lib().zkp_prove_phase_b(st._h, ctypes.c_uint32(n), _p(transcripts), _p(np.ascontiguousarray(secrets)),
+    rc = lib().zkp_prove_phase_b(st._h, n, _p(transcripts), _p(np.ascontiguousarray(secrets)),
                                  _p(np.ascontiguousarray(blindings)), _p(np.ascontiguousarray(commitments)), threads, _p(chal), _p(resp))
     _raise(rc, "zkp_prove_phase_b")
     return chal, resp
