@@ -915,9 +915,10 @@ k_rider_tables(const uint32_t* __restrict__ n_slots, uint32_t max_tables, const 
   m = P;
 #pragma unroll 1
   for (int k = 0; k < 128; ++k) {
-    if (k == 1) ge_double<true>(m, P);
-    else if (k > 1) ge_add_cached(m, m, c1);
-    if (k) ge_to_cached(c, m);
+    if (k) {                                                      // (k = 1: P + P through the unified addition, so that P is dead in the loop: 27 VGPRs)
+      ge_add_cached(m, m, c1);
+      ge_to_cached(c, m);
+    }
     store_entries_staged(stage[wave], live[wave], lane, tbl0, comb_cfg<16>::ENTRIES, (uint32_t)k, c);
   }
 }

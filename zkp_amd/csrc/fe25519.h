@@ -4,7 +4,7 @@
 // issues at the same rate as v_add_co_u32 / v_addc_co_u32, and fp64 FMA is no faster.  With 29-bit
 // limbs every 64-bit column accumulator holds the whole column sum  sum_{i+j=k} a_i*b_j  (8 large
 // products < 2^61 each) WITHOUT carry flags, so a field multiplication is a pure chain of
-// v_mad_u64_u32 (81 products + 17 fold mads) followed by one short carry chain.  Additions and
+// v_mad_u64_u32 (81 products + 17 fold mads) with the carries threaded through the accumulators.  Additions and
 // subtractions are limb-wise and lazy (no carry); a "carry" (weak reduction) is inserted only
 // where interval analysis says the next multiplication would overflow 64 bits.
 //
@@ -162,26 +162,94 @@ ZKP_HD void fe_cswap(fe& a, fe& b, uint32_t flag) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// multiplication: 81 + 17 v_mad_u64_u32, one 9-step carry chain
+// multiplication: 81 + 16 + 1 v_mad_u64_u32, the column carries ride in the accumulators
 // ---------------------------------------------------------------------------------------------
-// shared tail: columns c[0..8] (already containing the folded high half) -> tight limbs
-ZKP_HD void fe_reduce_columns(fe& r, uint64_t c[9]) {
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    c[k + 1] += c[k] >> 29;
-    r.v[k] = (uint32_t)c[k] & FE_M29;
-  }
-  r.v[8] = (uint32_t)c[8] & FE_M23;
-  const uint64_t t = c[8] >> 23;                       // < 2^41, weight 2^255 == 19
-  const uint64_t c0 = (uint64_t)r.v[0] + 19ull * (uint32_t)t;   // < 2^37
+// The high columns 9..16 are summed first (row-major, so consecutive mads hit different accumulators).  The low
+// columns 0..8 are then summed IN SEQUENCE, and column k+1's accumulator starts from column k's carry
+// (total >> 29): the 64-bit addend of v_mad_u64_u32 is free, so the carry costs no addition of its own.  Left to
+// itself LLVM re-associates  carry + sum a_i b_j  and adds the carry last with a v_lshl_add_u64 per column, so the
+// device path pins the mads of the low columns with (non-volatile) inline assembly; the host path is plain C++
+// with the same column values.  Column totals are exactly those of "sum everything, then ripple the carries", so
+// the limbs that come out are the same, not only the residue.  Measured on MI355X (tools/microbench/fe_mul_sched.hip,
+// profiles/r07_fe_carry_thread_microbench.txt): 308 against 276 G mul/s at 2 waves/SIMD with four multiplications in
+// flight per wave, 231 against 262 ns per dependent multiplication for a lone wave.
+// -DZKP_FE_PLAIN_MAD compiles the plain C++ on the device too (the A/B switch of that measurement).
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(ZKP_FE_PLAIN_MAD)
+#define ZKP_FE_PINNED 1
+// One low column = ONE asm statement.  Its mads are a dependent chain anyway, and the compiler, which cannot see inside an asm
+// statement, pads each one whose result the next instruction reads with a wait state: one statement per mad cost 39 s_nop per
+// multiplication and lost a third of the gain, one per column costs none.  Every statement is handed all limbs (the same
+// operand list for every column: they are live to the end of the multiplication in any case) and names the ones it uses:
+// acc += the listed products, x0..x8 / y0..y8 = the operands' limbs, k1 * hl and k2 * hh = the folds (1216 and 9728 in SGPRs,
+// one scalar source per VOP3 instruction); vcc is the carry-out the encoding demands (never set: the sums stay below 2^64).
+#define FE_PIN(p, q) "v_mad_u64_u32 %[acc], vcc, %[" #p "], %[" #q "], %[acc]\n\t"
+#define FE_PIN_COLUMN(body, accv, lo, hi, X, xlast, Y)                                                                              \
+  asm(body : [acc] "+v"(accv)                                                                                                       \
+      : [k1] "s"(1216u), [k2] "s"(9728u), [hl] "v"(lo), [hh] "v"(hi), [x0] "v"(X[0]), [x1] "v"(X[1]), [x2] "v"(X[2]), [x3] "v"(X[3]), \
+        [x4] "v"(X[4]), [x5] "v"(X[5]), [x6] "v"(X[6]), [x7] "v"(X[7]), [x8] "v"(xlast), [y0] "v"(Y[0]), [y1] "v"(Y[1]),            \
+        [y2] "v"(Y[2]), [y3] "v"(Y[3]), [y4] "v"(Y[4]), [y5] "v"(Y[5]), [y6] "v"(Y[6]), [y7] "v"(Y[7]), [y8] "v"(Y[8])              \
+      : "vcc")
+// fe_mul, column k: x_i * y_(k-i), i = 0..k (column 0's lone product is left to the compiler: it has no addend yet)
+#define FE_MUL_COL0 FE_PIN(k1, hl)
+#define FE_MUL_COL1 FE_PIN(x0, y1) FE_PIN(x1, y0) FE_PIN(k1, hl) FE_PIN(k2, hh)
+#define FE_MUL_COL2 FE_PIN(x0, y2) FE_PIN(x1, y1) FE_PIN(x2, y0) FE_PIN(k1, hl) FE_PIN(k2, hh)
+#define FE_MUL_COL3 FE_PIN(x0, y3) FE_PIN(x1, y2) FE_PIN(x2, y1) FE_PIN(x3, y0) FE_PIN(k1, hl) FE_PIN(k2, hh)
+#define FE_MUL_COL4 FE_PIN(x0, y4) FE_PIN(x1, y3) FE_PIN(x2, y2) FE_PIN(x3, y1) FE_PIN(x4, y0) FE_PIN(k1, hl) FE_PIN(k2, hh)
+#define FE_MUL_COL5 FE_PIN(x0, y5) FE_PIN(x1, y4) FE_PIN(x2, y3) FE_PIN(x3, y2) FE_PIN(x4, y1) FE_PIN(x5, y0) FE_PIN(k1, hl) FE_PIN(k2, hh)
+#define FE_MUL_COL6 FE_PIN(x0, y6) FE_PIN(x1, y5) FE_PIN(x2, y4) FE_PIN(x3, y3) FE_PIN(x4, y2) FE_PIN(x5, y1) FE_PIN(x6, y0) FE_PIN(k1, hl) FE_PIN(k2, hh)
+#define FE_MUL_COL7 FE_PIN(x0, y7) FE_PIN(x1, y6) FE_PIN(x2, y5) FE_PIN(x3, y4) FE_PIN(x4, y3) FE_PIN(x5, y2) FE_PIN(x6, y1) FE_PIN(x7, y0) FE_PIN(k1, hl) FE_PIN(k2, hh)
+#define FE_MUL_COL8 FE_PIN(x0, y8) FE_PIN(x1, y7) FE_PIN(x2, y6) FE_PIN(x3, y5) FE_PIN(x4, y4) FE_PIN(x5, y3) FE_PIN(x6, y2) FE_PIN(x7, y1) FE_PIN(x8, y0) FE_PIN(k2, hh)
+// fe_sq, column k: x = the doubled limbs, y = the limbs: x_i * y_(k-i) for 2i < k, and y_(k/2)^2 for even k
+#define FE_SQ_COL0 FE_PIN(k1, hl)
+#define FE_SQ_COL1 FE_PIN(x0, y1) FE_PIN(k1, hl) FE_PIN(k2, hh)
+#define FE_SQ_COL2 FE_PIN(x0, y2) FE_PIN(y1, y1) FE_PIN(k1, hl) FE_PIN(k2, hh)
+#define FE_SQ_COL3 FE_PIN(x0, y3) FE_PIN(x1, y2) FE_PIN(k1, hl) FE_PIN(k2, hh)
+#define FE_SQ_COL4 FE_PIN(x0, y4) FE_PIN(x1, y3) FE_PIN(y2, y2) FE_PIN(k1, hl) FE_PIN(k2, hh)
+#define FE_SQ_COL5 FE_PIN(x0, y5) FE_PIN(x1, y4) FE_PIN(x2, y3) FE_PIN(k1, hl) FE_PIN(k2, hh)
+#define FE_SQ_COL6 FE_PIN(x0, y6) FE_PIN(x1, y5) FE_PIN(x2, y4) FE_PIN(y3, y3) FE_PIN(k1, hl) FE_PIN(k2, hh)
+#define FE_SQ_COL7 FE_PIN(x0, y7) FE_PIN(x1, y6) FE_PIN(x2, y5) FE_PIN(x3, y4) FE_PIN(k1, hl) FE_PIN(k2, hh)
+#define FE_SQ_COL8 FE_PIN(x0, y8) FE_PIN(x1, y7) FE_PIN(x2, y6) FE_PIN(x3, y5) FE_PIN(y4, y4) FE_PIN(k2, hh)
+// all nine columns: h = the high columns (hl / hh = the halves folded into this column; where a column has only one fold the
+// other operand repeats it), every finished column but the last gives up its limb and keeps its carry
+#define FE_PIN_COLUMNS(PRE, acc, h, X, xlast, Y, out)                                                           \
+  FE_PIN_COLUMN(PRE##0, acc, (uint32_t)h[0], (uint32_t)h[0], X, xlast, Y); out.v[0] = fe_take_limb(acc);         \
+  FE_PIN_COLUMN(PRE##1, acc, (uint32_t)h[1], (uint32_t)(h[0] >> 32), X, xlast, Y); out.v[1] = fe_take_limb(acc); \
+  FE_PIN_COLUMN(PRE##2, acc, (uint32_t)h[2], (uint32_t)(h[1] >> 32), X, xlast, Y); out.v[2] = fe_take_limb(acc); \
+  FE_PIN_COLUMN(PRE##3, acc, (uint32_t)h[3], (uint32_t)(h[2] >> 32), X, xlast, Y); out.v[3] = fe_take_limb(acc); \
+  FE_PIN_COLUMN(PRE##4, acc, (uint32_t)h[4], (uint32_t)(h[3] >> 32), X, xlast, Y); out.v[4] = fe_take_limb(acc); \
+  FE_PIN_COLUMN(PRE##5, acc, (uint32_t)h[5], (uint32_t)(h[4] >> 32), X, xlast, Y); out.v[5] = fe_take_limb(acc); \
+  FE_PIN_COLUMN(PRE##6, acc, (uint32_t)h[6], (uint32_t)(h[5] >> 32), X, xlast, Y); out.v[6] = fe_take_limb(acc); \
+  FE_PIN_COLUMN(PRE##7, acc, (uint32_t)h[7], (uint32_t)(h[6] >> 32), X, xlast, Y); out.v[7] = fe_take_limb(acc); \
+  FE_PIN_COLUMN(PRE##8, acc, (uint32_t)(h[7] >> 32), (uint32_t)(h[7] >> 32), X, xlast, Y)
+#endif
+
+// the folds of the high columns h[0..7] (= columns 9..16, split into 32-bit halves) into low column k, with
+// 2^261 == 1216 (mod p):   2^(29(k+9)) == 1216 * 2^(29k)   and   2^(29(k+8) + 32) == 9728 * 2^(29k)
+ZKP_HD uint64_t fe_fold_column(uint64_t acc, int k, const uint64_t h[8]) {
+  if (k <= 7) acc += 1216ull * (uint32_t)h[k];
+  if (k >= 1) acc += 9728ull * (uint32_t)(h[k - 1] >> 32);
+  return acc;
+}
+// limb k (< 8) out of its finished column; what is left in acc is the carry that starts column k + 1
+ZKP_HD uint32_t fe_take_limb(uint64_t& acc) {
+  const uint32_t l = (uint32_t)acc & FE_M29;
+  acc >>= 29;
+  return l;
+}
+// shared tail: the finished column 8 (c8 < 2^64) -> limb 8, and what lies above 2^255 (weight 19) back into limbs 0, 1.
+// 19 * t is ONE 64-bit quantity added to limb 0 (t < 2^41, so c0 < 2^46) and split once at bit 29.
+ZKP_HD void fe_reduce_tail(fe& r, uint64_t c8) {
+  r.v[8] = (uint32_t)c8 & FE_M23;
+  const uint64_t t = c8 >> 23;
+  const uint64_t c0 = 19ull * t + r.v[0];
   r.v[0] = (uint32_t)c0 & FE_M29;
-  r.v[1] += (uint32_t)(c0 >> 29) + 152u * (uint32_t)(t >> 32);   // 2^32 * 19 = 152 * 2^29 * ... limb 1
+  r.v[1] += (uint32_t)(c0 >> 29);                       // < 2^17
   FE_TRACK(fe_set_ub_tight(r));
 }
 
 #ifdef ZKP_FE_TRACK
 inline void fe_track_mul(const fe& a, const fe& b) {
-  // full 17-column bound, then the fold, in 128-bit arithmetic
+  // full 17-column bound, then the fold and the carry that enters each low column, in 128-bit arithmetic
   unsigned __int128 col[17];
   for (int k = 0; k < 17; ++k) col[k] = 0;
   for (int i = 0; i < 9; ++i) if (a.ub[i] >= (1ull << 31) || b.ub[i] >= (1ull << 31)) fe_track_fail("fe_mul: limb >= 2^31");
@@ -189,11 +257,14 @@ inline void fe_track_mul(const fe& a, const fe& b) {
     for (int j = 0; j < 9; ++j) col[i + j] += (unsigned __int128)a.ub[i] * b.ub[j];
   const unsigned __int128 lim = ((unsigned __int128)1 << 64) - 1;
   for (int k = 9; k < 17; ++k) if (col[k] > lim) fe_track_fail("fe_mul: high column overflows 64 bits");
+  unsigned __int128 carry = 0;                           // what column k - 1 hands to the START of column k's accumulator
   for (int k = 0; k < 9; ++k) {
     unsigned __int128 t = col[k];
     if (k + 9 <= 16) t += (unsigned __int128)1216 * 0xffffffffull;
     if (k + 8 >= 9) t += (unsigned __int128)9728 * 0xffffffffull;
-    t += (unsigned __int128)1 << 36;   // incoming carry
+    if (carry > ((unsigned __int128)1 << 36)) fe_track_fail("fe_mul: incoming carry exceeds the 2^36 allowance");
+    carry = (t + carry) >> 29;
+    t += (unsigned __int128)1 << 36;   // incoming carry (the allowance, >= the carry itself as just asserted)
     if (t > lim) fe_track_fail("fe_mul: low column overflows 64 bits");
   }
 }
@@ -201,27 +272,38 @@ inline void fe_track_mul(const fe& a, const fe& b) {
 
 ZKP_HD void fe_mul(fe& r, const fe& a, const fe& b) {
   FE_TRACK(fe_track_mul(a, b));
-  // Row-major (operand scanning) issue order: consecutive v_mad_u64_u32 hit nine different 64-bit
-  // accumulators, so no mad waits on the previous one.  Measured on MI355X
-  // (tools/microbench/fe_mul_sched.hip): 234 ns vs 298 ns per dependent multiplication for a lone wave,
-  // 300 vs 293 G mul/s chip-wide at 8 waves/SIMD, against the column-major order.
-  uint64_t c[17];
+  // High columns in row-major (operand scanning) order: consecutive v_mad_u64_u32 hit different 64-bit accumulators,
+  // so no mad waits on the previous one (tools/microbench/fe_mul_sched.hip).
+  uint64_t h[8];
 #pragma unroll
-  for (int k = 0; k < 17; ++k) c[k] = 0;
+  for (int k = 0; k < 8; ++k) h[k] = 0;
 #pragma unroll
-  for (int i = 0; i < 9; ++i) {
+  for (int i = 1; i < 9; ++i) {
 #pragma unroll
-    for (int j = 0; j < 9; ++j) c[i + j] += (uint64_t)a.v[i] * b.v[j];
+    for (int j = 9 - i; j < 9; ++j) h[i + j - 9] += (uint64_t)a.v[i] * b.v[j];
   }
-  // fold the high columns 9..16, split into 32-bit halves, with 2^261 == 1216 (mod p):
-  //   2^(29k)       == 1216 * 2^(29(k-9))
-  //   2^(29k + 32)  == 9728 * 2^(29(k-8))
+  fe out;
+  uint64_t acc;
+#ifdef ZKP_FE_PINNED
+  // A field constant (fe_from_const) is left to the compiler: it multiplies by literals and SGPRs, where the pinned form would hold
+  // the nine limbs in VGPRs, across a whole loop when the constant is hoisted (that cost the table kernels up to 60 VGPRs).
+  if (!__builtin_constant_p(a.v[0]) && !__builtin_constant_p(b.v[0])) {
+    acc = (uint64_t)a.v[0] * b.v[0];
+    FE_PIN_COLUMNS(FE_MUL_COL, acc, h, a.v, a.v[8], b.v, out);
+  } else
+#endif
+  {
+    acc = 0;
 #pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    c[k] += 1216ull * (uint32_t)c[k + 9];
-    c[k + 1] += 9728ull * (uint32_t)(c[k + 9] >> 32);
+    for (int k = 0; k < 9; ++k) {
+#pragma unroll
+      for (int i = 0; i <= k; ++i) acc += (uint64_t)a.v[i] * b.v[k - i];
+      acc = fe_fold_column(acc, k, h);
+      if (k < 8) out.v[k] = fe_take_limb(acc);
+    }
   }
-  fe_reduce_columns(r, c);
+  fe_reduce_tail(out, acc);
+  r = out;
 }
 
 ZKP_HD void fe_sq(fe& r, const fe& a) {
@@ -229,7 +311,6 @@ ZKP_HD void fe_sq(fe& r, const fe& a) {
   uint32_t a2[9];
 #pragma unroll
   for (int i = 0; i < 9; ++i) a2[i] = a.v[i] << 1;    // requires a.v[i] < 2^31 (checked by fe_track_mul)
-  uint64_t c[9];
   uint64_t h[8];
 #pragma unroll
   for (int k = 9; k < 17; ++k) {
@@ -239,24 +320,45 @@ ZKP_HD void fe_sq(fe& r, const fe& a) {
     if ((k & 1) == 0) acc += (uint64_t)a.v[k / 2] * a.v[k / 2];
     h[k - 9] = acc;
   }
+  fe out;
+#ifdef ZKP_FE_PINNED
+  uint64_t acc = (uint64_t)a.v[0] * a.v[0];
+  // x = the doubled limbs: no squaring column names x8 (2i < k <= 8), so the operand list repeats a2[7] there and a2[8] is never computed
+  FE_PIN_COLUMNS(FE_SQ_COL, acc, h, a2, a2[7], a.v, out);
+#else
+  uint64_t acc = 0;
 #pragma unroll
   for (int k = 0; k < 9; ++k) {
-    uint64_t acc = 0;
 #pragma unroll
     for (int i = 0; 2 * i < k; ++i) acc += (uint64_t)a2[i] * a.v[k - i];
     if ((k & 1) == 0) acc += (uint64_t)a.v[k / 2] * a.v[k / 2];
-    if (k <= 7) acc += 1216ull * (uint32_t)h[k];
-    if (k >= 1) acc += 9728ull * (uint32_t)(h[k - 1] >> 32);
-    c[k] = acc;
+    acc = fe_fold_column(acc, k, h);
+    if (k < 8) out.v[k] = fe_take_limb(acc);
   }
-  fe_reduce_columns(r, c);
+#endif
+  fe_reduce_tail(out, acc);
+  r = out;
 }
 
-// r = a^(2^n), n >= 1; a real loop (not unrolled) so the inverse-square-root chain stays small in I-cache
+// r = a^(2^n), n >= 1; a real loop (not unrolled) so the inverse-square-root chain stays small in I-cache.  Long chains do two
+// squarings per trip, x -> y -> x: with one per trip the loop-carried element is copied back every trip (8 - 14 v_mov per
+// squaring).  Short ones (9 of the chain's 251 squarings) keep the one-squaring loop: there a second body per call site costs
+// more I-cache than the copies cost issue slots.
 ZKP_HD void fe_sqn(fe& r, const fe& a, int n) {
-  r = a;
+  fe x, y;
+  if (n < 8) {
+    x = a;
 #pragma unroll 1
-  for (int i = 0; i < n; ++i) fe_sq(r, r);
+    for (int i = 0; i < n; ++i) fe_sq(x, x);
+  } else {
+    if (n & 1) fe_sq(x, a); else x = a;
+#pragma unroll 1
+    for (int i = n >> 1; i > 0; --i) {
+      fe_sq(y, x);
+      fe_sq(x, y);
+    }
+  }
+  r = x;
 }
 
 // ---------------------------------------------------------------------------------------------
