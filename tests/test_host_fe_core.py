@@ -8,6 +8,7 @@ import random
 import pytest
 
 from tests import fe_core_cases as K
+from tests import row_quad_cases as C
 
 L9, L8 = ctypes.c_uint32 * 9, ctypes.c_uint32 * 8
 
@@ -79,3 +80,29 @@ def test_power_chains_against_integers(lib):
             assert words_value(w) == pow(v, (K.P - 5) // 8, K.P), (cls, a)
             lib.t_core_chain(1, L9(*a), L9(*K.CLASSES[cls]), w)
             assert words_value(w) == pow(v, K.P - 2, K.P), (cls, a)
+
+
+@pytest.mark.parametrize("variant", ["plain", "bound-tracked"])
+def test_quad_point_arithmetic_lane_by_lane(variant):
+    """quad.h's point operations as the host build of the header computes them, a fe per lane and quad.h's calls in quad.h's order
+    (t_quad_probe: the reference of tests/test_gpu_row_quad_probe.py), on operands at the edges of the tight class, non-canonical zeros and
+    curve points: values against the formulas over Python integers, every output inside the tight class the comments of quad.h promise.  The
+    bound-tracked build is given the class maxima as bounds and aborts on a violation (run in a child process: an abort fails this test)."""
+    recs = C.quad_records()
+    got = C.quad_expected(variant)
+    count = {}
+    for kind, _, _ in recs:
+        count[kind] = count.get(kind, 0) + 1
+    assert count == {"tight x tight": 96 + C.EDGE_PAIRS, "non-canonical": 25, "points": 18, "points, cached": 16, "points, niels": 16}
+    for (kind, p, s), out in zip(recs, got):
+        assert all(l <= t for rows in (p, s) for row in rows for l, t in zip(row, K.TIGHT))
+        want = C.quad_values([K.value(r) for r in p], [K.value(r) for r in s])
+        for op in range(6):
+            assert [K.value([int(x) for x in out[op, q]]) for q in range(4)] == want[op], (kind, C.QUAD_OPS[op])
+            assert all(int(out[op, q, k]) <= K.TIGHT[k] for q in range(4) for k in range(9)), (kind, C.QUAD_OPS[op])
+        if kind.startswith("points"):                    # ... and where the second operand is a point in the form an operation takes, the sum is one
+            op = {"points": 2, "points, cached": 1, "points, niels": 4}[kind]
+            for o in (0, op) + ((5,) if op == 4 else ()):
+                x, y, z, t = (K.value([int(v) for v in out[o, q]]) for q in range(4))
+                assert x * y % K.P == z * t % K.P and (y * y - x * x - z * z - C.R.D * t * t) % K.P == 0 and z, (kind, C.QUAD_OPS[o])
+    assert (C.quad_expected("plain") == C.quad_expected("bound-tracked")).all()

@@ -1,7 +1,9 @@
 """The one-limb-per-lane field and point arithmetic of the Horner tail (zkp_amd/csrc/rowfe.h) as a lane-level model over Python integers
 (tools/model/rowfe_model.py: the DPP moves, the column sums, the two carry passes, instruction for instruction): values against big-integer
 arithmetic, every intermediate against its register width, outputs inside the "tight" limb class -- the CPU-side half of that file's evidence
-(the GPU half: tests/test_gpu_parity.py::test_row_cooperative_point_ops and every MSM parity test, whose last kernel is this chain)."""
+(the GPU half: tests/test_gpu_row_quad_probe.py, which pushes the records of tests/row_quad_cases.py through the header on the device and wants
+the images this model gives for them, byte for byte; then tests/test_gpu_parity.py::test_row_cooperative_point_ops and every MSM parity test,
+whose last kernel is this chain).  The tests at the end of this file check those very images against big integers."""
 import os
 import random
 import sys
@@ -10,6 +12,7 @@ import pytest
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "model"))
 import rowfe_model as R  # noqa: E402
+from tests import row_quad_cases as C  # noqa: E402
 
 
 def test_model_matches_integers_and_register_widths():
@@ -67,3 +70,114 @@ def test_lane_swaps_of_the_model_are_what_the_hardware_probe_printed():
     assert got == want
     for v in (h0, h1, a, b):
         assert all(v[16 * r + k] == v[16 * r] + k for r in range(4) for k in range(16))
+
+
+# ------------------------------------------------------------------------------------------ the records of the device probe through the model
+TIGHT = C.K.TIGHT
+
+
+def assert_tight_image(img, what):
+    for r in range(4):
+        assert all(int(img[16 * r + k]) <= TIGHT[k] for k in range(9)), ("not tight", what, r)
+        assert all(int(img[16 * r + k]) == 0 for k in range(9, 16)), ("idle lanes not zero", what, r)
+
+
+def test_probe_records_are_admitted_per_class_pair():
+    """the model is the admission rule: it refuses the two deliberately inadmissible records and nothing else, so every class pair keeps its count"""
+    main, refused = C.row_expected()[:2]
+    assert sorted(r["kind"] for r in refused) == ["refused 2^32-1 limbs", "refused diff x diff"]
+    count = {}
+    for rec in main:
+        count[rec["kind"]] = count.get(rec["kind"], 0) + 1
+    want = {"mul %s x %s" % pair: C.PER_PAIR + C.EDGE_PAIRS for pair in C.ROW_MUL_PAIRS}
+    want.update({"tight x tight": C.PER_PAIR + C.EDGE_PAIRS, "non-canonical": 25, "points": 50, "points with edge rows": 16, "carry 32-bit lanes": 64, "lane index": 1})
+    assert count == want and C.PER_PAIR >= 96
+    assert len(main) + len(refused) == len(C.row_candidates())
+    for rec in main:
+        assert all(rec["a"][16 * r + k] == 0 for r in range(4) for k in range(9, 16)) or rec["kind"] == "lane index"
+    assert sum(1 for rec in main if any(rec["b"][16 * r + k] for r in range(4) for k in range(9, 16))) >= len(main) - 1    # garbage beside b's limbs
+    # the operands really sit at the class edges: every multiplication pair has the two class maxima in one row, and a zero row
+    for ca, cb in C.ROW_MUL_PAIRS:
+        rows = [(rec["a"][16 * r:16 * r + 9], rec["b"][16 * r:16 * r + 9]) for rec in main if rec["kind"] == "mul %s x %s" % (ca, cb) for r in range(4)]
+        assert any(a == C.K.CLASSES[ca] for a, _ in rows) and any(b == C.K.CLASSES[cb] for _, b in rows)
+        assert any(a == C.K.CLASSES[ca] and b == C.K.CLASSES[cb] for a, b in rows)                      # ... and the two maxima meet
+        assert any(not any(a) for a, _ in rows) and any(not any(b) for _, b in rows)
+
+
+def test_probe_main_records_against_integers():
+    """every image the device will be asked for: its value from big-integer arithmetic on the raw row values (the point formulas are polynomial
+    identities, so rows that are no curve point are as good), inside the tight class, zero in the idle lanes"""
+    main, _, imgs = C.row_expected()[:3]
+    for rec, out in zip(main, imgs):
+        a, b, mask, what = C.row_values(rec["a"]), C.row_values(rec["b"]), rec["mask"], rec["kind"]
+        vals = [C.row_values([int(x) for x in img]) for img in out]
+        for op, on in ((0, C.OP_MUL_AB), (1, C.OP_MUL_AA), (2, C.OP_CARRY), (3, C.OP_POINT), (4, C.OP_POINT), (5, C.OP_POINT), (6, C.OP_SQN)):
+            if mask & on:
+                assert_tight_image(out[op], (what, C.ROW_OPS[op]))
+            else:
+                assert not out[op].any()
+        if mask & C.OP_MUL_AB:
+            assert vals[0] == [x * y % R.P for x, y in zip(a, b)], what
+        if mask & C.OP_MUL_AA:
+            assert vals[1] == [x * x % R.P for x in a], what
+        if mask & C.OP_CARRY:
+            assert vals[2] == a, what
+        if mask & C.OP_SQN:
+            assert vals[6] == [pow(x, 2 ** 5, R.P) for x in a], what
+        if mask & C.OP_POINT:
+            assert vals[3] == list(R.ext_double(*a)), what
+            assert vals[4] == C.add_cached_values(a, b), what
+            acc = a
+            for _ in range(11):
+                acc = R.ext_double(*acc)
+            assert vals[5] == C.add_cached_values(acc, b), what
+        # the moves between rows: row s of the operand, lane for lane, in front of every row
+        for op, src in ((7, 0), (8, 1), (9, 2), (10, 3), (11, 0), (12, 1), (13, 2), (14, 3)):
+            assert [int(x) for x in out[op]] == rec["a"][16 * src:16 * src + 16] * 4, (what, C.ROW_OPS[op])
+
+
+def test_probe_point_records_are_points():
+    """the records made of curve points give curve points: 2P, P + Q and 2^11 P + Q projectively, the identity, P = Q and P = -Q among them"""
+    main, _, imgs = C.row_expected()[:3]
+    seen = 0
+    for rec, out in zip(main, imgs):
+        if rec["kind"] != "points":
+            continue
+        seen += 1
+        for op in (3, 4, 5):
+            x, y, z, t = C.row_values([int(v) for v in out[op]])
+            assert x * y % R.P == z * t % R.P and (-x * x + y * y - z * z - R.D * t * t) % R.P == 0 and z != 0
+    assert seen == 50
+
+
+def test_probe_inversions_against_integers():
+    _, _, _, inv, imgs = C.row_expected()[:5]
+    assert len(inv) == 64
+    for a, out in zip(inv, imgs):
+        assert_tight_image(out, "row_invert")
+        assert C.row_values([int(x) for x in out]) == [pow(v, R.P - 2, R.P) for v in C.row_values(a)]
+    assert C.K.value(C.ZERO_AS_P) == 0 and all(C.ZERO_AS_P) and inv[0][:9] == C.ZERO_AS_P      # 0 -> 0 from non-zero limbs
+
+
+def test_probe_horner_tails_against_the_extended_formulas():
+    """the whole chain of k_pip_combine at every (windows, doublings per window) pip_run uses, and the 23 x 11 = 253 doublings of a canonical
+    scalar: ext_double / the cached addition over integers, step for step"""
+    hor, imgs = C.row_expected()[5:]
+    assert sorted({(W, Cb) for W, Cb, _, _, _ in hor}) == sorted(C.HORNER_SHAPES) and len(hor) == 16
+    assert set(C.HORNER_SHAPES) == {(-(-256 // c), c) for c in (7, 10, 11, 16)} | {(23, 11)}       # pip_cfg<C>::W for pip_run's four C, and 253 = 23 x 11
+    with_points = 0
+    for (W, Cb, top, cached, pts), out in zip(hor, imgs):
+        acc = C.row_values(top)
+        ref = pts and pts[0]
+        for k in range(W - 1, -1, -1):
+            for _ in range(Cb):
+                acc = R.ext_double(*acc)
+                ref = ref and R.ext_double(*ref)
+            acc = C.add_cached_values(acc, C.row_values(cached[k]))
+            ref = ref and R.ext_add(ref, pts[1 + k])
+        assert_tight_image(out, ("horner", W, Cb))
+        assert C.row_values([int(x) for x in out]) == list(acc), (W, Cb)
+        if pts:
+            with_points += 1
+            assert tuple(acc) == ref, (W, Cb)
+    assert with_points == 11

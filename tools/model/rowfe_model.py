@@ -1,7 +1,7 @@
 """Lane-level model of zkp_amd/csrc/rowfe.h: GF(2^255-19) with ONE LIMB PER LANE (9 limbs in the low lanes of a 16-lane DPP row, one row per
 coordinate of an extended point), the arithmetic of the 253-doubling Horner tail of k_pip_combine.  Every function below is the HIP routine of
 the same name, instruction for instruction, over lists of 64 Python ints with the DPP moves modelled exactly (row_shr / row_shl with
-bound_ctrl = zero fill, row_newbcast) and the gfx950 lane swaps between rows as probed on the hardware (profiles/r05_permlane_probe.txt).  It checks (1) values against big-integer arithmetic
+bound_ctrl = zero fill, row_newbcast) and the gfx950 lane swaps between rows as probed on the hardware (profiles/r05_permlane_probe.txt; tests/test_gpu_row_quad_probe.py pins them, and every function below, to the machine under test).  It checks (1) values against big-integer arithmetic
 and (2) that no intermediate exceeds its register width for operands at the top of the limb classes the callers use.
 Run:  python tools/model/rowfe_model.py     (also imported by tests/test_rowfe_model.py)"""
 import random
@@ -34,6 +34,13 @@ def u64(v, what):
     if not 0 <= v < 2**64:
         raise Overflow("%s does not fit 64 bits: %d" % (what, v))
     return v
+
+
+def umul24(a, b, what):
+    """__umul24: the product of the low 24 bits of each operand -- a carry that does not fit them would be cut"""
+    if a >= 2**24 or b >= 2**24:
+        raise Overflow("%s: operand of __umul24 does not fit 24 bits: %d, %d" % (what, a, b))
+    return a * b
 
 
 def shr(v, n):
@@ -108,7 +115,7 @@ def row_reduce(col):
     c = [u32(n >> SH[l], "c") for l, n in enumerate(new)]
     r = [(n & 0xffffffff) & MASK[l] for l, n in enumerate(new)]
     c1, c8 = shr(c, 1), shl(c, 8)
-    out = [u32(r[l] + c1[l] + G_Y[l] * c8[l], "out") for l in range(64)]
+    out = [u32(r[l] + c1[l] + umul24(G_Y[l], c8[l], "out"), "out") for l in range(64)]
     return [o if K[l] < 9 else 0 for l, o in enumerate(out)]
 
 
@@ -116,7 +123,7 @@ def row_carry(v):
     c = [x >> SH[l] for l, x in enumerate(v)]
     r = [x & MASK[l] for l, x in enumerate(v)]
     c1, c8 = shr(c, 1), shl(c, 8)
-    out = [u32(r[l] + c1[l] + G_Y[l] * c8[l], "carry out") for l in range(64)]
+    out = [u32(r[l] + c1[l] + umul24(G_Y[l], c8[l], "carry out"), "carry out") for l in range(64)]
     return [o if K[l] < 9 else 0 for l, o in enumerate(out)]
 
 
@@ -207,6 +214,17 @@ def row_invert(z):
     t0 = row_mul(t1, t0)
     t0 = row_sqn(t0, 5)
     return row_mul(t0, z11)
+
+
+def row_horner(top, cached, C):
+    """the chain of k_pip_combine: acc = the top window's sum; per window below it, from the highest down, C doublings and one cached addition
+    (cached[0] belongs to window 0, so it is added last)"""
+    acc = top
+    for k in range(len(cached) - 1, -1, -1):
+        for _ in range(C):
+            acc = row_double(acc)
+        acc = row_add_cached(acc, cached[k])
+    return acc
 
 
 # ---------------------------------------------------------------------------------------------- checks against integers

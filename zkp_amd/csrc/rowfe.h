@@ -16,7 +16,9 @@
 //
 // tools/model/rowfe_model.py is this file instruction for instruction over Python integers: values against big-integer
 // arithmetic and every intermediate against its register width at the top of the limb classes used here (tests/test_rowfe_model.py);
-// on the GPU: zkp_debug_row_selftest (test-hook build) against the oracle, and every MSM of the suite ends in this chain.
+// on the GPU: tools/microbench/row_probe.hip runs every function below on full register images at the edges of those classes and must write the
+// model's images byte for byte, idle lanes included, in this build and in the -DZKP_AB_ROW_BPERMUTE one (tests/test_gpu_row_quad_probe.py);
+// zkp_debug_row_selftest (test-hook build) against the oracle, and every MSM of the suite ends in this chain.
 //
 // Limb classes are fe25519.h's: row_mul / row_carry return "tight"; row_mul takes a x b with max(a) * max(b) * 9 + 2^46 < 2^64.
 #pragma once
