@@ -531,6 +531,8 @@ int zkp_ctx_set_profiling(zkp_ctx* ctx, int enabled);
  *   ZKP_TESTOPT_DUMMY_LAUNCHES = n empty kernels added to every zkp_fused_prove_dev call (what a launch costs a pipelined caller);
  *   ZKP_TESTOPT_GENERIC_CLASSIFIER = 1 sends the fused flows through the generic six-kernel term classifier instead of
  *   k_stmt_classify;
+ *   ZKP_TESTOPT_PIP_MERGE picks the form of the Pippenger bucket merge whatever the call's size: 1 = a quad of lanes per bucket, 2 = one lane per
+ *   bucket, 0 = by the call's bucket count again (same bytes either way);
  *   ZKP_TESTOPT_WAVE_CYCLES = 1 switches on a per-wavefront cycle recorder in the term kernel (s_memtime at entry and exit);
  * zkp_debug_wave_cycles copies out (and clears) up to cap records, [block][wavefront 0..3] = block class << 56 | cycles (class 1 =
  *   ladder, 2 = comb scan, 3 = grouped comb walk, 4 = fixed-base; 0 = no record): the timing side of the constant-time evidence.
@@ -540,7 +542,9 @@ int zkp_ctx_set_profiling(zkp_ctx* ctx, int enabled);
  *   against the term path), pip_c, pip_part, status_shared (batch verification's status words without memsets), lat_split, grouped, comb_min,
  *   ladder_interleave, riders, straus_lanes, straus_wins, tr_lanes, tr_steps, fuse_tt (tables + transcript in one launch), terms_split (the
  *   classified term path against one k_terms_r4 lane per term), ragged_classes, ragged_compiled, ragged_base and fused_plans (the _ragged calls:
- *   position classes, class programs compiled by this call, 1 if it built its position-free base plan, the size of the aligned plan cache).  Writes a
+ *   position classes, class programs compiled by this call, 1 if it built its position-free base plan, the size of the aligned plan cache), pip_merge
+ *   (the bucket merge: 0 = a quad per bucket, 1 = a lane per bucket), pip_buckets (batches x windows x buckets per window, what pip_merge goes by) and
+ *   no_carry (1 = the term kernel skipped the carry window: the fused prove flows, whose scalars are reduced mod l).  Writes a
  *   NUL-terminated string of at most cap - 1 characters and returns the untruncated length. */
 int zkp_debug_quad_selftest(zkp_ctx* ctx, uint32_t n, const uint8_t* pairs /*[n][64]*/, uint8_t* out /*[n][128]*/);
 int zkp_debug_row_selftest(zkp_ctx* ctx, uint32_t n, const uint8_t* pairs /*[n][64]*/, uint8_t* out /*[n][96]*/);
@@ -550,7 +554,7 @@ int zkp_debug_last_schedule(zkp_ctx* ctx, char* buf, size_t cap);
 /* zkp_debug_ragged_blocks: the class grouping the _ragged calls launch: idx [N] = proof indices sorted stably by class, blocks [cap][3] =
  * (class, first, count) per wavefront, classes in order of first appearance.  Returns the number of blocks. */
 int zkp_debug_ragged_blocks(const uint8_t* transcripts, uint32_t N, uint32_t* idx, uint32_t* blocks, uint32_t cap);
-enum { ZKP_TESTOPT_DUMMY_LAUNCHES = 1001, ZKP_TESTOPT_GENERIC_CLASSIFIER = 1002, ZKP_TESTOPT_WAVE_CYCLES = 1003 };
+enum { ZKP_TESTOPT_DUMMY_LAUNCHES = 1001, ZKP_TESTOPT_GENERIC_CLASSIFIER = 1002, ZKP_TESTOPT_WAVE_CYCLES = 1003, ZKP_TESTOPT_PIP_MERGE = 1004 };
 #endif
 
 #ifdef __cplusplus

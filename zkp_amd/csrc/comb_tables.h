@@ -304,7 +304,7 @@ __device__ __forceinline__ void comb_select(ge_cached& sel, const dev_ext* __res
 // partial[t] = scalars[t] * P through P's comb table.  CT: no branch or address depends on the scalar.
 template <bool CT, int TEETH>
 __device__ __forceinline__ void term_comb(uint32_t t, const uint8_t* __restrict__ scalars, const dev_ext* __restrict__ tbl,
-                                          dev_ext* __restrict__ partial, uint32_t* ecol) {
+                                          dev_ext* __restrict__ partial, uint32_t* ecol, bool no_carry = false) {
   using cfg = comb_cfg<TEETH>;
   uint32_t s[8], e[8], top;
   load_vec<2>(s, scalars + 32 * (size_t)t);
@@ -352,7 +352,8 @@ __device__ __forceinline__ void term_comb(uint32_t t, const uint8_t* __restrict_
         load_comb_entry(n0, next + 0);
         load_comb_entry(n1, next + 1);
         ge_cached_cneg(sel, neg);
-        ge_add_cached(acc, acc, sel);
+        if (w == cfg::WINDOWS - 1 && j == 0) ge_from_cached(acc, sel);     // the first entry is the accumulator
+        else ge_add_cached(acc, acc, sel);
       }
     }
   } else {
@@ -370,11 +371,12 @@ __device__ __forceinline__ void term_comb(uint32_t t, const uint8_t* __restrict_
         ge_cached sel;
         comb_select<false>(sel, tbl + 8 * j, mag);
         ge_cached_cneg(sel, neg);
-        ge_add_cached(acc, acc, sel);
+        if (w == cfg::WINDOWS - 1 && j == 0) ge_from_cached(acc, sel);
+        else ge_add_cached(acc, acc, sel);
       }
     }
   }
-  {
+  if (!no_carry) {                                               // (uniform: the caller's word about the whole call, not a digit)
     ge_cached sel, c;
     ge_cached_identity(sel);
     load_comb_entry(c, tbl + 8 * TEETH);
@@ -397,7 +399,7 @@ __device__ __forceinline__ void ge_p3_dpp_from(ge_p3& r, const ge_p3& a, int ctr
 }
 template <int TEETH>
 __device__ __forceinline__ void term_comb_split4(uint32_t t, uint32_t q, const uint8_t* __restrict__ scalars, const dev_ext* __restrict__ comb, uint32_t slot,
-                                                 dev_ext* __restrict__ partial, uint32_t* ecol) {
+                                                 dev_ext* __restrict__ partial, uint32_t* ecol, bool no_carry = false) {
   using cfg = comb_cfg<TEETH>;
   static_assert(cfg::WINDOWS == 4, "one lane of the quad per window");
   // (the term and slot numbers wait in the lane's LDS column for the last step instead of in registers: the additions below need all of them)
@@ -441,7 +443,8 @@ __device__ __forceinline__ void term_comb_split4(uint32_t t, uint32_t q, const u
       load_comb_entry(n0, next + 0);
       load_comb_entry(n1, next + 1);
       ge_cached_cneg(sel, neg);
-      ge_add_cached(acc, acc, sel);
+      if (j == 0) ge_from_cached(acc, sel);                       // the first entry is the accumulator
+      else ge_add_cached(acc, acc, sel);
     }
   }
   // the quad's Horner: every lane runs every step (DPP sources must be active lanes); a lane keeps a step's result only where the schedule above says so
@@ -464,7 +467,7 @@ __device__ __forceinline__ void term_comb_split4(uint32_t t, uint32_t q, const u
     ge_add_cached(d, acc, c);
     fe_pick(acc.X, d.X, q == 0u); fe_pick(acc.Y, d.Y, q == 0u); fe_pick(acc.Z, d.Z, q == 0u); fe_pick(acc.T, d.T, q == 0u);
   }
-  {
+  if (!no_carry) {
     ge_cached sel, c;
     ge_cached_identity(sel);
     load_comb_entry(c, comb + (size_t)stash[0] * cfg::ENTRIES + 8 * TEETH);      // carry out of bit 255: 2^256 * P
@@ -606,17 +609,20 @@ __device__ __forceinline__ void comb_group_block(uint32_t i0, uint32_t n_g, cons
       asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");      // this step's rows have landed, for every wavefront's part
       ge_cached sel;
       uint32_t neg = 0;
+      const bool first = pass == 0 && j == 0;                        // (uniform) the first entry of either chain is its accumulator
       if (live) {
         pick(alo, ahi, sel, neg);
         ge_cached_cneg(sel, neg);
-        ge_add_cached(acc, acc, sel);                                      // (the rows stay: the second look-up reads them too)
+        if (first) ge_from_cached(acc, sel);
+        else ge_add_cached(acc, acc, sel);                                 // (the rows stay: the second look-up reads them too)
         pick(blo, bhi, sel, neg);
       }
       lds_barrier();                                               // every lane holds its second entry: the rows may be replaced
       if (pass == 0 || j != 15) issue((uint32_t)((j + 1) & 15));   // next step's rows arrive during the second addition
       if (live) {
         ge_cached_cneg(sel, neg);
-        ge_add_cached(lo, lo, sel);
+        if (first) ge_from_cached(lo, sel);
+        else ge_add_cached(lo, lo, sel);
       }
     }
   }
@@ -665,7 +671,7 @@ static_assert(2 + (XBAR_HALF_TERMS - 2) / GROUP_MIN_USES <= 4 && XBAR_HALF_TERMS
 
 __device__ __forceinline__ void comb_group_xbar(uint32_t i0, uint32_t n_g, const uint32_t* __restrict__ list_g, const uint8_t* __restrict__ scalars,
                                                 const uint32_t* __restrict__ pidx, const uint32_t* __restrict__ slot_of,
-                                                const dev_ext* __restrict__ comb, dev_ext* __restrict__ partial, uint4* lds) {
+                                                const dev_ext* __restrict__ comb, dev_ext* __restrict__ partial, uint4* lds, bool no_carry = false) {
   using cfg = comb_cfg<16>;
   constexpr uint32_t NONE = 0xffffffffu;
   const uint32_t tid = threadIdx.x, lane = tid & 63u;
@@ -769,14 +775,17 @@ __device__ __forceinline__ void comb_group_xbar(uint32_t i0, uint32_t n_g, const
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // this step's pairs have landed in this wavefront's slots
       ge_cached sel;
       uint32_t neg = 0;
+      const bool first = pass == 0 && j == 0;                        // (uniform) the first entry of either chain is its accumulator: ge_from_cached
       pick(alo, ahi, sel, neg);
       ge_cached_cneg(sel, neg);
-      ge_add_cached(acc, acc, sel);
+      if (first) ge_from_cached(acc, sel);
+      else ge_add_cached(acc, acc, sel);
       pick(blo, bhi, sel, neg);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");             // every slot has been read: the next row may overwrite them
       if (pass == 0 || j != 15) issue((uint32_t)((j + 1) & 15));      // ... and arrives during the second addition
       ge_cached_cneg(sel, neg);
-      ge_add_cached(lo, lo, sel);
+      if (first) ge_from_cached(lo, sel);
+      else ge_add_cached(lo, lo, sel);
     }
   }
   ge_double4(acc);
@@ -786,14 +795,14 @@ __device__ __forceinline__ void comb_group_xbar(uint32_t i0, uint32_t n_g, const
     ge_to_cached(c, lo);
     ge_add_cached(acc, acc, c);
   }
-  if (live) {
+  if (live && !no_carry) {
     ge_cached sel, c;
     ge_cached_identity(sel);
     load_comb_entry(c, comb + (size_t)slot * cfg::ENTRIES + 8 * 16);     // carry out of bit 255: 2^256 * P
     ge_cached_cmov(sel, c, top);
     ge_add_cached(acc, acc, sel);
-    store_ext(partial + t, acc);
   }
+  if (live) store_ext(partial + t, acc);
 }
 
 // partial[t] = scalars[t] * P for a point that no other cold term of the call uses (a constraint's left-hand side in
@@ -840,7 +849,8 @@ __device__ __forceinline__ void ladder_select(ge_cached& sel, const uint4* __res
 
 template <bool CT>
 __device__ __forceinline__ void term_ladder16(uint32_t t, const uint8_t* __restrict__ scalars, const dev_affine* __restrict__ pt,
-                                              uint4* __restrict__ tbl /* this lane's slot 0 of its wavefront group */, dev_ext* __restrict__ partial, uint32_t* ecol) {
+                                              uint4* __restrict__ tbl /* this lane's slot 0 of its wavefront group */, dev_ext* __restrict__ partial, uint32_t* ecol,
+                                              bool no_carry = false) {
   uint32_t s[8], e[8], top;
   load_vec<2>(s, scalars + 32 * (size_t)t);
   sc_add_pattern(e, top, s, 0x88888888u);                       // signed radix-16 digits: nibble - 8 in [-8, 7]
@@ -867,11 +877,13 @@ __device__ __forceinline__ void term_ladder16(uint32_t t, const uint8_t* __restr
     ge_to_cached(c, m); ladder_store_entry(tbl, 6, c);
     ge_double<true>(m, m4);
     ge_to_cached(c, m); ladder_store_entry(tbl, 7, c);
-    ge_cached sel;                                              // carry out of bit 255: one more P at the top
-    ge_cached_identity(sel);
-    ge_cached_cmov(sel, c1, top);
     ge_identity(acc);
-    ge_add_cached(acc, acc, sel);
+    if (!no_carry) {
+      ge_cached sel;                                            // carry out of bit 255: one more P at the top
+      ge_cached_identity(sel);
+      ge_cached_cmov(sel, c1, top);
+      ge_from_cached(acc, sel);                                 // (identity + sel without the addition)
+    }
   }
 #pragma unroll 1
   for (int j = 7; j >= 0; --j) {

@@ -361,7 +361,8 @@ k_straus_each(uint32_t N, uint32_t K, uint32_t L, uint32_t ns, uint32_t ni, uint
       ge_cached q;
       load_straus_entry(q, table_of(i));
       ge_cached_cneg(q, flip);
-      ge_add_cached(acc, acc, q);
+      if (started) ge_add_cached(acc, acc, q);
+      else ge_from_cached(acc, q);                                     // the first entry is the accumulator
       started = true;
     }
   }
@@ -390,7 +391,8 @@ k_straus_each(uint32_t N, uint32_t K, uint32_t L, uint32_t ns, uint32_t ni, uint
         if (i + L < K) fetch(i + L, o + 1, k);
         if (mag) {
           ge_cached_cneg(q, neg);
-          ge_add_cached(acc, acc, q);
+          if (started) ge_add_cached(acc, acc, q);
+          else ge_from_cached(acc, q);
           started = true;
         }
       }
@@ -440,7 +442,8 @@ k_straus_each_win(uint32_t N, uint32_t K, uint32_t P, uint32_t ns, uint32_t ni, 
       ge_cached q;
       load_straus_entry(q, table_of(i));
       ge_cached_cneg(q, f & 1u);
-      ge_add_cached(acc, acc, q);
+      if (started) ge_add_cached(acc, acc, q);
+      else ge_from_cached(acc, q);                                     // the first entry is the accumulator
       started = true;
     }
   }
@@ -468,7 +471,8 @@ k_straus_each_win(uint32_t N, uint32_t K, uint32_t P, uint32_t ns, uint32_t ni, 
       if (i + 1 < K) fetch(i + 1, k);
       if (mag) {
         ge_cached_cneg(q, neg);
-        ge_add_cached(acc, acc, q);
+        if (started) ge_add_cached(acc, acc, q);
+        else ge_from_cached(acc, q);
         started = true;
       }
     }
@@ -1167,6 +1171,9 @@ int prove_core(zkp_ctx* c, const fused_plan& pl, const prove_inter& o, size_t ws
   // the blindings are canonical (k_wide_reduce), so the halving the batched encoder wants is three instructions per limb here
   // instead of a kernel with a reduction of its own
   tk.prehalved = nc && terms_batched_encode(c, N * T, N * nc, tk.throughput);
+  // every term operand below is a blinding reduced mod l (sc_from_wide), halved mod l or not, or comes out of k_halve_scalars (reduced as well): below
+  // 2^253, so the signed recoding of the walks cannot carry out of bit 255
+  tk.canonical = true;
   if (m && std::max(m, T) <= 256) {                     // (one launch; every 64-byte string reduced once)
     const uint32_t P = 256 / std::max(m, T);
     hipLaunchKernelGGL(k_blind_scalars, dim3((N + P - 1) / P), dim3(256), 0, c->stream, N, T, m, P, pl.d_tarr + nc + 1, w.u8(o.wide), w.u8(o.blind), w.u8(o.sc),

@@ -140,6 +140,58 @@ ZKP_HD void ge_msub(ge_p3& r, const ge_p3& p, const ge_niels& q) {
   fe_mul(r.T, e, h);
 }
 
+// r = q as an extended point, i.e. identity + q without the addition (1M by a constant + 2 carries instead of 7M / 8M): the first
+// entry of a chain of additions.  From (y+x, y-x, 2dxy):  X = 2x, Y = 2y, Z = 2, T = XY/Z = 2xy = xy2d / d; the cached form likewise
+// with Z = 2Z and T = T2d / d.  The identity entry (1, 1, 0) / (1, 1, 2, 0) gives (0, 2, 2, 0).  Same group element as ge_madd /
+// ge_add_cached onto ge_identity, in other coordinates: the encodings agree.  xy2d / T2d may be the uncarried negation of
+// ge_niels_cneg / ge_cached_cneg (a 2p-class operand times a constant).  The _neg forms give -q.
+ZKP_HD void ge_from_niels(ge_p3& r, const ge_niels& q) {
+  fe t, dinv;
+  fe_sub(t, q.ypx, q.ymx);
+  fe_carry(r.X, t);
+  fe_add(t, q.ypx, q.ymx);
+  fe_carry(r.Y, t);
+  fe_0(r.Z);
+  r.Z.v[0] = 2;
+  FE_TRACK(fe_set_ub_exact(r.Z));
+  fe_from_const(dinv, FE_D_INV);
+  fe_mul(r.T, q.xy2d, dinv);
+}
+ZKP_HD void ge_from_niels_neg(ge_p3& r, const ge_niels& q) {
+  fe t, dinv;
+  fe_sub(t, q.ymx, q.ypx);
+  fe_carry(r.X, t);
+  fe_add(t, q.ypx, q.ymx);
+  fe_carry(r.Y, t);
+  fe_0(r.Z);
+  r.Z.v[0] = 2;
+  FE_TRACK(fe_set_ub_exact(r.Z));
+  fe_from_const(dinv, FE_D_INV);
+  fe_neg(t, q.xy2d);
+  fe_mul(r.T, t, dinv);
+}
+ZKP_HD void ge_from_cached(ge_p3& r, const ge_cached& q) {
+  fe t, dinv;
+  fe_sub(t, q.YpX, q.YmX);
+  fe_carry(r.X, t);
+  fe_add(t, q.YpX, q.YmX);
+  fe_carry(r.Y, t);
+  r.Z = q.Z2;
+  fe_from_const(dinv, FE_D_INV);
+  fe_mul(r.T, q.T2d, dinv);
+}
+ZKP_HD void ge_from_cached_neg(ge_p3& r, const ge_cached& q) {
+  fe t, dinv;
+  fe_sub(t, q.YmX, q.YpX);
+  fe_carry(r.X, t);
+  fe_add(t, q.YpX, q.YmX);
+  fe_carry(r.Y, t);
+  r.Z = q.Z2;
+  fe_from_const(dinv, FE_D_INV);
+  fe_neg(t, q.T2d);
+  fe_mul(r.T, t, dinv);
+}
+
 // r = 2p (4S + 4M + 2 carries); only X, Y, Z of p are read.  WITH_T = false skips T (3M) when the
 // result feeds another doubling.
 template <bool WITH_T = true>

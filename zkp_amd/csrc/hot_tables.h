@@ -486,7 +486,8 @@ __device__ __forceinline__ void fixed_base_block(ge_p3& acc, uint32_t e[9], bool
       ge_niels q;
       fe_set(q.ypx, wd); fe_set(q.ymx, wd + 9); fe_set(q.xy2d, wd + 18);
       ge_niels_cneg(q, neg);
-      ge_madd(acc, acc, q);
+      if (w == 0) ge_from_niels(acc, q);                           // the first window's entry is the accumulator
+      else ge_madd(acc, acc, q);
     }
   }
 }
@@ -571,7 +572,8 @@ __device__ __forceinline__ void fixed_base_xbar(ge_p3& acc, uint32_t e[9], const
     ge_niels q;
     fe_set(q.ypx, wd); fe_set(q.ymx, wd + 9); fe_set(q.xy2d, wd + 18);
     ge_niels_cneg(q, neg);
-    ge_madd(acc, acc, q);
+    if (w == 0) ge_from_niels(acc, q);                                // the first window's entry is the accumulator (acc arrives as the identity)
+    else ge_madd(acc, acc, q);
   }
 }
 

@@ -175,7 +175,9 @@ k_terms_split(const uint8_t* __restrict__ scalars, const uint32_t* __restrict__ 
               const dev_ext* __restrict__ comb, const uint32_t* __restrict__ slot_of, const uint32_t* __restrict__ class_start,
               const uint32_t* __restrict__ blk_start, const uint32_t* __restrict__ list, const dev_niels* __restrict__ tables,
               const dev_affine* __restrict__ pts, dev_ext* __restrict__ ladder_rw, uint32_t max_ladder, dev_ext* __restrict__ partial,
-              uint32_t ladder_stride, const uint32_t* __restrict__ pair, uint32_t stmt_T) {
+              uint32_t ladder_stride, const uint32_t* __restrict__ pair, uint32_t stmt_T, uint32_t no_carry) {
+  // no_carry (constant-time calls): the caller vouches that every scalar is below 2^254 (the fused prove flows: reduced mod l), so the signed radix-16
+  // recoding s + 0x88...8 cannot carry out of bit 255 and the comb walks and the ladder leave their 65th addition -- of the identity -- out.
   // A block of fixed-base terms serves ONE table; its rows pass through LDS one window at a time, in 16 copies, so that every
   // lane reads the entry its digit names from banks of its own (hot_tables.h): no masked scan, no bank conflict, the same
   // LDS cycles for every scalar.
@@ -224,7 +226,7 @@ k_terms_split(const uint8_t* __restrict__ scalars, const uint32_t* __restrict__ 
             joint = true;
           }
         }
-        if (!joint) term_ladder16<CT>(t, scalars, pts + pi, tbl, partial, ecol);
+        if (!joint) term_ladder16<CT>(t, scalars, pts + pi, tbl, partial, ecol, CT && no_carry);
       }
     }
     ZKP_WAVE_T1(1);
@@ -238,7 +240,7 @@ k_terms_split(const uint8_t* __restrict__ scalars, const uint32_t* __restrict__ 
           const uint32_t pi = pidx[t];
           if (pi < n_points) {
             const uint32_t slot = slot_of[pi];
-            if (slot != 0xffffffffu) term_comb_split4<TEETH>(t, i & 3u, scalars, comb, slot, partial, ecol);
+            if (slot != 0xffffffffu) term_comb_split4<TEETH>(t, i & 3u, scalars, comb, slot, partial, ecol, CT && no_carry);
           }
         }
         ZKP_WAVE_T1(2);
@@ -250,14 +252,14 @@ k_terms_split(const uint8_t* __restrict__ scalars, const uint32_t* __restrict__ 
       const uint32_t pi = pidx[t];
       if (pi < n_points) {                                        // (out of range: flagged by k_reduce_encode)
         const uint32_t slot = slot_of[pi];
-        if (slot != 0xffffffffu) term_comb<CT, TEETH>(t, scalars, comb + (size_t)slot * comb_cfg<TEETH>::ENTRIES, partial, ecol);
+        if (slot != 0xffffffffu) term_comb<CT, TEETH>(t, scalars, comb + (size_t)slot * comb_cfg<TEETH>::ENTRIES, partial, ecol, CT && no_carry);
       }
     }
     ZKP_WAVE_T1(2);
   } else if (vb < ladder_blocks + comb_blocks + group_blocks) {
     if constexpr (CT && TEETH == 16) {                            // terms of points with many uses, listed point by point
       if constexpr (LOOKUP == LOOKUP_XBAR)
-        comb_group_xbar((vb - ladder_blocks - comb_blocks) * XBAR_BLOCK_TERMS, n_group, list + class_start[CLASS_GROUP], scalars, pidx, slot_of, comb, partial, hot_lds);
+        comb_group_xbar((vb - ladder_blocks - comb_blocks) * XBAR_BLOCK_TERMS, n_group, list + class_start[CLASS_GROUP], scalars, pidx, slot_of, comb, partial, hot_lds, no_carry != 0);
       else
         comb_group_block((vb - ladder_blocks - comb_blocks) * 256u, n_group, list + class_start[CLASS_GROUP], scalars, pidx, slot_of, comb, partial, hot_lds);
     }
@@ -320,11 +322,14 @@ k_reduce_encode(uint32_t n_msm, const uint32_t* __restrict__ off, const uint32_t
   ge_p3 acc;
   ge_identity(acc);
   uint32_t bad = 0;
+  if (b < e) load_ext(acc, partial + b);               // the first term is the accumulator
 #pragma unroll 1
   for (uint32_t t = b; t < e; ++t) {
-    ge_p3 q;
-    load_ext(q, partial + t);
-    ge_add_p3(acc, acc, q);
+    if (t != b) {
+      ge_p3 q;
+      load_ext(q, partial + t);
+      ge_add_p3(acc, acc, q);
+    }
     const uint32_t pi = pidx[t];
     bad |= pi < n_points ? (pts[pi].valid ^ 1u) : 1u;
   }
@@ -397,11 +402,14 @@ __device__ __forceinline__ uint32_t msm_sum(ge_p3& acc, uint32_t i, const uint32
   const uint32_t b = off[i], e = off[i + 1];
   ge_identity(acc);
   uint32_t bad = 0;
+  if (b < e) load_ext(acc, partial + b);               // the first term is the accumulator
 #pragma unroll 1
   for (uint32_t t = b; t < e; ++t) {
-    ge_p3 q;
-    load_ext(q, partial + t);
-    ge_add_p3(acc, acc, q);
+    if (t != b) {
+      ge_p3 q;
+      load_ext(q, partial + t);
+      ge_add_p3(acc, acc, q);
+    }
     const uint32_t pi = pidx[t];
     bad |= pi < n_points ? (pts[pi].valid ^ 1u) : 1u;
   }
@@ -839,21 +847,25 @@ k_pip_bucket_part(uint32_t n, uint32_t W1, uint32_t bins, uint32_t L, uint32_t v
   const uint32_t* lst = sorted + (size_t)w * n + start[g] + first;
   niels += (size_t)(w / W1) * n;                      // window id = batch * W1 + window: the sorted lists hold indices within the batch
   ge_p3 acc;
-  ge_identity(acc);
   // ping-pong software pipeline: the gather of the next entry is in flight while the current one is added, and the
-  // two buffers are distinct registers so that no copy (and therefore no early wait) sits between load and use
+  // two buffers are distinct registers so that no copy (and therefore no early wait) sits between load and use.
+  // A part is never empty (v < vs[bins]).  Its first entry IS the accumulator (ge_from_niels: one multiplication by a constant
+  // instead of a 7 M addition onto the identity -- with L = 16 every 15th addition of this kernel was that one).
   ge_niels qa, qb;
-  uint32_t ia = 0, ib = 0;
-  if (cnt) { ia = lst[0]; load_niels(qa, niels + (ia & 0x7fffffffu)); }
+  uint32_t ia = lst[0], ib = 0;
+  load_niels(qa, niels + (ia & 0x7fffffffu));
+  if (1 < cnt) { ib = lst[1]; load_niels(qb, niels + (ib & 0x7fffffffu)); }
+  ge_niels_cneg(qa, ia >> 31);
+  ge_from_niels(acc, qa);
 #pragma unroll 1
-  for (uint32_t k = 0; k < cnt; k += 2) {
-    if (k + 1 < cnt) { ib = lst[k + 1]; load_niels(qb, niels + (ib & 0x7fffffffu)); }
-    ge_niels_cneg(qa, ia >> 31);
-    ge_madd(acc, acc, qa);
+  for (uint32_t k = 1; k < cnt; k += 2) {
+    if (k + 1 < cnt) { ia = lst[k + 1]; load_niels(qa, niels + (ia & 0x7fffffffu)); }
+    ge_niels_cneg(qb, ib >> 31);
+    ge_madd(acc, acc, qb);
     if (k + 1 < cnt) {
-      if (k + 2 < cnt) { ia = lst[k + 2]; load_niels(qa, niels + (ia & 0x7fffffffu)); }
-      ge_niels_cneg(qb, ib >> 31);
-      ge_madd(acc, acc, qb);
+      if (k + 2 < cnt) { ib = lst[k + 2]; load_niels(qb, niels + (ib & 0x7fffffffu)); }
+      ge_niels_cneg(qa, ia >> 31);
+      ge_madd(acc, acc, qa);
     }
   }
   store_ext(parts + (size_t)w * vmax + v, acc);
@@ -863,16 +875,22 @@ k_pip_bucket_part(uint32_t n, uint32_t W1, uint32_t bins, uint32_t L, uint32_t v
 // window have sqrt(cnt) parts each -- a batch of 32,768 CMZ proofs has 64 such buckets of 75 parts side by side).  The few buckets
 // with more than kMergeSeqParts parts -- the huge ones, see part_len -- are then summed by the whole block, one after the other:
 // quad i adds up parts i, i + 64, ..., and a tree over the 64 quads (through LDS) finishes.
+//
+// LANE = true is the throughput form of the same sums: ONE lane per bucket with the plain unified addition.  A quad is the form for chains
+// nothing runs beside; a call whose buckets outnumber the chip's lanes several times over (many batches per call) has nothing to gain
+// from a shorter chain, and four quad lanes spend about twice the instructions of one lane per addition (quad.h).  The huge buckets keep
+// the block-wide sum below (a 256-lane block then covers 256 buckets instead of 64).  Same sums, hence the same bytes.
 constexpr uint32_t kMergeSeqParts = 128;
+template <bool LANE>
 __global__ void __launch_bounds__(256, 2)
 k_pip_bucket_merge(uint32_t bins, uint32_t total, uint32_t vmax, const uint32_t* __restrict__ vstart,
                    const dev_ext* __restrict__ parts, dev_ext* __restrict__ buckets) {
-  __shared__ uint32_t big[64];
+  __shared__ uint32_t big[LANE ? 256 : 64];
   __shared__ uint32_t n_big;
   __shared__ uint32_t red[64][4][9];
   const uint32_t gt = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t g = gt >> 2, qi = threadIdx.x >> 2;
-  const int q = (int)(gt & 3u);
+  const uint32_t g = LANE ? gt : gt >> 2, qi = threadIdx.x >> 2;
+  const int q = (int)(threadIdx.x & 3u);
   if (threadIdx.x == 0) n_big = 0;
   __syncthreads();
   if (g < total) {
@@ -881,7 +899,24 @@ k_pip_bucket_merge(uint32_t bins, uint32_t total, uint32_t vmax, const uint32_t*
     const uint32_t v0 = vs[b], v1 = vs[b + 1];
     const dev_ext* p = parts + (size_t)w * vmax;
     if (v1 - v0 > kMergeSeqParts) {
-      if (q == 0) big[atomicAdd(&n_big, 1u)] = g;
+      if (LANE || q == 0) big[atomicAdd(&n_big, 1u)] = g;
+    } else if constexpr (LANE) {
+      ge_p3 acc;
+      if (v1 == v0) {
+        ge_identity(acc);
+      } else {
+        load_ext(acc, p + v0);                                         // (the first part is the accumulator)
+        ge_p3 nx = acc;
+        if (v0 + 1 < v1) load_ext(nx, p + v0 + 1);
+#pragma unroll 1
+        for (uint32_t v = v0 + 1; v < v1; ++v) {
+          ge_cached c;
+          ge_to_cached(c, nx);
+          if (v + 1 < v1) load_ext(nx, p + v + 1);                     // the next part travels during the addition
+          ge_add_cached(acc, acc, c);
+        }
+      }
+      store_ext(buckets + g, acc);
     } else {
       qpt acc;
       if (v1 == v0) {
@@ -1381,8 +1416,9 @@ struct zkp_ctx {
   // zkp_debug_last_schedule: the size-driven choices the last call made (cleared by prof_begin; -1 = the call did not make it)
   enum { SCH_BATCH_ENCODE, SCH_ENC_GROUPS, SCH_OPT_PIP, SCH_PIP_C, SCH_PIP_PART, SCH_STATUS_SHARED, SCH_LAT_SPLIT, SCH_GROUPED, SCH_COMB_MIN,
          SCH_LADDER_INTERLEAVE, SCH_RIDERS, SCH_STRAUS_LANES, SCH_STRAUS_WINS, SCH_TR_LANES, SCH_TR_STEPS, SCH_FUSE_TT, SCH_TERMS_SPLIT,
-         SCH_RAGGED_CLASSES, SCH_RAGGED_COMPILED, SCH_RAGGED_BASE, SCH_FUSED_PLANS, SCH_COUNT };
-  int64_t sched[SCH_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+         SCH_RAGGED_CLASSES, SCH_RAGGED_COMPILED, SCH_RAGGED_BASE, SCH_FUSED_PLANS, SCH_PIP_MERGE, SCH_PIP_BUCKETS, SCH_NO_CARRY, SCH_COUNT };
+  int64_t sched[SCH_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+  int debug_pip_merge = 0;           // ZKP_TESTOPT_PIP_MERGE: 0 = by the call's bucket count, 1 = a quad per bucket, 2 = a lane per bucket
 #endif
   static constexpr size_t kGroupedCombTerms = 400000;
   static constexpr size_t kSplitCombTerms = 8192;   // narrow constant-time calls on the latency schedule from this many terms on: grouped walk + quad-split scans (ZKP_OPT_COMB_SPLIT)
@@ -1542,6 +1578,7 @@ struct terms_cfg {
   msm_map map;                     // lane -> MSM assignment of the reduce / encode kernels (fused flows: constraints by length)
   bool prehalved = false;          // the caller already wrote s / 2 mod l where the batched encoder is used (terms_batched_encode)
   stmt_job stmt;                   // fused flows: the statement's term structure (one-launch classifier, k_stmt_classify)
+  bool canonical = false;          // constant-time calls: every scalar the term kernel reads is reduced mod l (the fused prove flows), so the walks skip the carry window
   bool rider_tables = false;       // stmt.pair: max_tables counts a table of multiples for every per-proof point whose terms all ride (stmt_pairs.h: stmt_rider)
 };
 inline bool stmt_classify_applies(const terms_cfg& k, uint32_t n_terms) {
@@ -1604,7 +1641,8 @@ inline bool terms_batched_encode(const zkp_ctx* c, uint32_t n_terms, uint32_t n_
 template <bool CT, int TEETH, int LOOKUP>
 void launch_terms_split(zkp_ctx* c, dim3 grid, bool ladder, const uint8_t* d_scalars, const uint32_t* d_pidx, uint32_t n_points, const dev_ext* comb,
                         const uint32_t* slot_of, const uint32_t* class_start, const uint32_t* blk_start, const uint32_t* list,
-                        const dev_affine* pts, dev_ext* ladder_rw, uint32_t max_ladder, dev_ext* part, uint32_t comb_split, const uint32_t* pair, uint32_t stmt_T) {
+                        const dev_affine* pts, dev_ext* ladder_rw, uint32_t max_ladder, dev_ext* part, uint32_t comb_split, const uint32_t* pair, uint32_t stmt_T,
+                        uint32_t no_carry) {
   // ladder blocks spread over the first half of the grid (ZKP_OPT_LADDER_INTERLEAVE), or all at the front
   uint32_t stride = 0;
   const uint32_t lb = (max_ladder + 255) / 256;
@@ -1624,16 +1662,16 @@ void launch_terms_split(zkp_ctx* c, dim3 grid, bool ladder, const uint8_t* d_sca
   if constexpr (CT && TEETH == 16 && LOOKUP == LOOKUP_XBAR) {
     if (comb_split && !ladder) {                                   // (the caller asks for it on narrow calls only: they have no ladder class)
       hipLaunchKernelGGL((k_terms_split<CT, TEETH, false, LOOKUP, true>), grid, dim3(256), 0, c->stream, d_scalars, d_pidx, n_points, comb, slot_of, class_start, blk_start, list,
-                         c->hot_tables, pts, ladder_rw, max_ladder, part, stride, pair, stmt_T);
+                         c->hot_tables, pts, ladder_rw, max_ladder, part, stride, pair, stmt_T, no_carry);
       return;
     }
   }
   if (ladder)
     hipLaunchKernelGGL((k_terms_split<CT, TEETH, true, LOOKUP>), grid, dim3(256), 0, c->stream, d_scalars, d_pidx, n_points, comb, slot_of, class_start, blk_start, list,
-                       c->hot_tables, pts, ladder_rw, max_ladder, part, stride, pair, stmt_T);
+                       c->hot_tables, pts, ladder_rw, max_ladder, part, stride, pair, stmt_T, no_carry);
   else
     hipLaunchKernelGGL((k_terms_split<CT, TEETH, false, LOOKUP>), grid, dim3(256), 0, c->stream, d_scalars, d_pidx, n_points, comb, slot_of, class_start, blk_start, list,
-                       c->hot_tables, pts, ladder_rw, max_ladder, part, stride, pair, stmt_T);
+                       c->hot_tables, pts, ladder_rw, max_ladder, part, stride, pair, stmt_T, no_carry);
 }
 
 // phase: everything (default), or only the part that does not look at the scalars (decode, classification, comb tables:
@@ -1764,8 +1802,10 @@ int msm_terms_path(zkp_ctx* c, uint32_t n_msm, const uint32_t* d_off, const uint
     }
     if (phase & PH_SCALARS) {
       // (vartime calls have nothing to hide: they never scan)
+      const uint32_t no_carry = (k.canonical && flags == ZKP_CT) ? 1u : 0u;
+      ZKP_SCHED(c, NO_CARRY, no_carry);
       const int lookup = (!HOT_LDS_ROWS || c->ct_lookup == LOOKUP_XBAR) ? LOOKUP_XBAR : (flags == ZKP_CT ? c->ct_lookup : LOOKUP_LDS);
-#define ZKP_LAUNCH_TERMS(CT_, TEETH_, LK_) launch_terms_split<CT_, TEETH_, LK_>(c, grid, k.max_ladder != 0, d_scalars, d_pidx, n_points, comb, slot_of, class_start, blk_start, list, pts, ladder, k.max_ladder, part, comb_split ? 1u : 0u, pair_on ? k.stmt.pair : (const uint32_t*)nullptr, k.stmt.T)
+#define ZKP_LAUNCH_TERMS(CT_, TEETH_, LK_) launch_terms_split<CT_, TEETH_, LK_>(c, grid, k.max_ladder != 0, d_scalars, d_pidx, n_points, comb, slot_of, class_start, blk_start, list, pts, ladder, k.max_ladder, part, comb_split ? 1u : 0u, pair_on ? k.stmt.pair : (const uint32_t*)nullptr, k.stmt.T, no_carry)
       if (lookup == LOOKUP_XBAR) {
         if (flags == ZKP_CT) { if (k.teeth == 16) ZKP_LAUNCH_TERMS(true, 16, LOOKUP_XBAR); else ZKP_LAUNCH_TERMS(true, 4, LOOKUP_XBAR); }
         else { if (k.teeth == 16) ZKP_LAUNCH_TERMS(false, 16, LOOKUP_XBAR); else ZKP_LAUNCH_TERMS(false, 4, LOOKUP_XBAR); }
@@ -1896,7 +1936,18 @@ int pip_run(zkp_ctx* c, uint32_t n, const uint8_t* d_scalars, const uint8_t* d_p
   hipLaunchKernelGGL(k_pip_vmap, grid1(nb, 256), dim3(256), 0, c->stream, cfg::B1, (uint32_t)nb, (uint32_t)vmax, vstart, vmap);
   hipLaunchKernelGGL(k_pip_bucket_part, dim3((unsigned)((vmax + 255) / 256), (unsigned)WK), dim3(256), 0, c->stream, n, (uint32_t)cfg::W1, cfg::B1, L, (uint32_t)vmax,
                      start, hist, vstart, vmap, sorted, niels, parts);
-  hipLaunchKernelGGL(k_pip_bucket_merge, grid1(nb * 4, 256), dim3(256), 0, c->stream, cfg::B1, (uint32_t)nb, (uint32_t)vmax, vstart, parts, buckets);
+  // the merge form by the call's BUCKET count (batches x windows x buckets per window), not by n: a lane per bucket once the buckets alone are eight
+  // wavefronts for every SIMD of the chip (256 CUs x 4 SIMDs x 64 lanes x 8 = 2^19); below that the quads' shorter chains win
+  constexpr size_t MERGE_LANE_MIN_BUCKETS = (size_t)1 << 19;
+#ifdef ZKP_BUILD_TEST_HOOKS
+  const bool lane_merge = c->debug_pip_merge ? c->debug_pip_merge == 2 : nb >= MERGE_LANE_MIN_BUCKETS;
+#else
+  const bool lane_merge = nb >= MERGE_LANE_MIN_BUCKETS;
+#endif
+  ZKP_SCHED(c, PIP_MERGE, lane_merge ? 1 : 0);
+  ZKP_SCHED(c, PIP_BUCKETS, nb);
+  if (lane_merge) hipLaunchKernelGGL(k_pip_bucket_merge<true>, grid1(nb, 256), dim3(256), 0, c->stream, cfg::B1, (uint32_t)nb, (uint32_t)vmax, vstart, parts, buckets);
+  else hipLaunchKernelGGL(k_pip_bucket_merge<false>, grid1(nb * 4, 256), dim3(256), 0, c->stream, cfg::B1, (uint32_t)nb, (uint32_t)vmax, vstart, parts, buckets);
   prof_mark(c, ZKP_K_BUCKET);
   // radix-8 tree over bucket indices 0 .. B-1 (bucket B is added in k_pip_combine)
   const dev_ext* Ain = nullptr;
@@ -2115,6 +2166,7 @@ int zkp_ctx_set_option(zkp_ctx* c, int option, uint64_t value) {
     case ZKP_OPT_DEV_OVERLAP: c->dev_overlap = value != 0 && value != ~0ull; c->dev_latency = value == 2; return ZKP_OK;
 #ifdef ZKP_BUILD_TEST_HOOKS
     case ZKP_TESTOPT_GENERIC_CLASSIFIER: c->stmt_classify = value == 0; return ZKP_OK;
+    case ZKP_TESTOPT_PIP_MERGE: c->debug_pip_merge = value <= 2 ? (int)value : 0; return ZKP_OK;
     case ZKP_TESTOPT_DUMMY_LAUNCHES: c->debug_dummy_launches = (int)std::min<uint64_t>(value, 1000); return ZKP_OK;
     case ZKP_TESTOPT_WAVE_CYCLES: {
       HIP_TRY(hipSetDevice(c->device));
@@ -2614,7 +2666,7 @@ int zkp_debug_last_schedule(zkp_ctx* c, char* buf, size_t cap) {
   if (!c || !buf || !cap) return fail(ZKP_ERR_ARG, "bad argument");
   static const char* const names[zkp_ctx::SCH_COUNT] = {"batch_encode", "enc_groups", "opt_pip", "pip_c", "pip_part", "status_shared", "lat_split", "grouped", "comb_min",
                                                         "ladder_interleave", "riders", "straus_lanes", "straus_wins", "tr_lanes", "tr_steps", "fuse_tt", "terms_split",
-                                                        "ragged_classes", "ragged_compiled", "ragged_base", "fused_plans"};
+                                                        "ragged_classes", "ragged_compiled", "ragged_base", "fused_plans", "pip_merge", "pip_buckets", "no_carry"};
   std::string s;
   for (int i = 0; i < zkp_ctx::SCH_COUNT; ++i)
     if (c->sched[i] >= 0) s += (s.empty() ? "" : " ") + std::string(names[i]) + "=" + std::to_string(c->sched[i]);
