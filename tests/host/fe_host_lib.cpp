@@ -108,8 +108,11 @@ int t_scalarmult(const uint8_t* s, const uint8_t* pe, uint8_t* out) {
   return ok;
 }
 // scalar arithmetic mod l (device header sc25519.h): op 0 mul, 1 add, 2 neg(a), 3 reduce(a), 4 mont(to_mont(a), b), 5 from_wide(lo=a, hi=b)
-void t_sc_op(int op, const uint8_t* a, const uint8_t* b, uint8_t* out) {
+// 8 .. 15: what tools/microbench/sc_probe.hip computes beyond those.  Returns the flag of the operation that has one (6 fold, 11 not canonical,
+// 12 - 14 the carry out `top`), else 0.
+int t_sc_op(int op, const uint8_t* a, const uint8_t* b, uint8_t* out) {
   sc x, y, r;
+  uint32_t flag = 0;
   memcpy(x.v, a, 32); memcpy(y.v, b, 32);
   switch (op) {
     case 0: sc_mul(r, x, y); break;
@@ -118,10 +121,20 @@ void t_sc_op(int op, const uint8_t* a, const uint8_t* b, uint8_t* out) {
     case 3: sc_reduce(r, x); break;
     case 4: { sc t; sc_to_mont(t, x); sc_mont(r, t, y); break; }
     case 5: sc_from_wide(r, x, y); break;      // a + b * 2^256
-    case 6: { r = x; const uint32_t f = sc_fold_sign(r.v); r.v[7] |= f << 31; break; }   // folded scalar, flag in bit 255
+    case 6: { r = x; const uint32_t f = sc_fold_sign(r.v); r.v[7] |= f << 31; flag = f; break; }   // folded scalar, flag in bit 255
     case 7: sc_halve(r, x); break;             // a / 2 mod l
+    case 8: sc_to_mont(r, x); break;           // a * 2^256 mod l
+    case 9: sc_mont(r, x, y); break;           // a * b * 2^-256 mod l   (b < l)
+    case 10: sc_halve_canonical(r, x); break;  // a / 2 mod l   (a < l)
+    case 11: r = x; flag = sc_not_canonical(x.v); break;
+    case 12: sc_add_pattern(r.v, flag, x.v, 0x88888888u); break;
+    case 13: sc_add_pattern(r.v, flag, x.v, 0xAAAAAAAAu); break;
+    case 14: sc_add_pattern(r.v, flag, x.v, 0x80808080u); break;
+    case 15: { sc c, t; memcpy(c.v, b + 32, 32); sc_mul(t, x, c); sc_add(r, t, y); break; }   // a * c + b, b = 64 bytes (b, c), both < l: k_responses
+    case 16: { r = x; flag = sc_fold_sign(r.v); break; }   // folded scalar as it is (bit 255 may belong to the value), flag returned
     default: sc_zero(r);
   }
   memcpy(out, r.v, 32);
+  return (int)flag;
 }
 }

@@ -36,14 +36,6 @@ k_neg_reduce(uint32_t n, const uint8_t* in, uint8_t* out) {       // in may equa
   store_vec<2>(out + 32 * (size_t)i, r.v);
 }
 
-// l <= the 256-bit little-endian value?  (Scalar::from_canonical_bytes / dalek's Deserialize accept only values < l.)
-__device__ __forceinline__ uint32_t sc_not_canonical(const uint32_t v[8]) {
-  uint64_t br = 0;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) br = (((uint64_t)v[i] - sc_l(i) - br) >> 63) & 1u;
-  return br ? 0u : 1u;                              // no borrow: v >= l
-}
-
 // The CSR multiscalar job of a batch of proofs of one statement: T terms per proof in nc MSMs.
 //   term t of proof j:  scalar = tsc[t] == ~0 ? special[j] : vals[j][tsc[t]];   point = table index of point id tpt[t]
 // (prover.rs:94-97 with vals = blindings; verifier.rs:97-106 with vals = responses, special = -c)

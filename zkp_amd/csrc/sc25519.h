@@ -2,7 +2,8 @@
 // multiplication (R = 2^256) built from the same full-rate v_mad_u64_u32 the field code uses.
 // Needed by the batch-verification coefficient build (reference src/toolbox/batch_verifier.rs:173-206:
 // `random_factor * minus_c[j]`, `random_factor * resp`, accumulation into the coefficient matrix).
-// Host + device header, tested on the CPU against Python integers (tests/test_host_field.py).
+// Host + device header, tested on the CPU against Python integers (tests/test_host_field.py, tests/test_host_scalar_edges.py) and on
+// the device against the same integers (tools/microbench/sc_probe.hip, tests/test_gpu_sc_probe.py).
 #pragma once
 #include <stdint.h>
 #include "fe25519.h"   // ZKP_HD
@@ -128,6 +129,27 @@ ZKP_HD void sc_reduce(sc& r, const sc& a) {
   sc t;
   sc_to_mont(t, a);          // a R mod l   (a may be >= l: sc_mont allows it in the first operand)
   sc_mont(r, t, one);        // a
+}
+
+// l <= the 256-bit little-endian value?  (Scalar::from_canonical_bytes / dalek's Deserialize accept only values < l.)
+ZKP_HD uint32_t sc_not_canonical(const uint32_t v[8]) {
+  uint64_t br = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) br = (((uint64_t)v[i] - sc_l(i) - br) >> 63) & 1u;
+  return br ? 0u : 1u;                              // no borrow: v >= l
+}
+
+// e = s + K where K has the bit pattern `pattern` in every word: signed-digit recoding without a
+// sequential carry (digit_i = e_i - 2^(c-1)).  top receives the carry out of bit 255.
+ZKP_HD void sc_add_pattern(uint32_t e[8], uint32_t& top, const uint32_t s[8], uint32_t pattern) {
+  uint64_t c = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    c += (uint64_t)s[i] + pattern;
+    e[i] = (uint32_t)c;
+    c >>= 32;
+  }
+  top = (uint32_t)c;
 }
 
 // Sign folding for multiscalar multiplication: s * P = (l - s) * (-P).  If (l-1)/2 < s <= l, replaces s by l - s and

@@ -43,19 +43,6 @@ using namespace zkp;
 // =============================================================================================
 // scalar recoding
 // =============================================================================================
-// e = s + K where K has the bit pattern `pattern` in every word: signed-digit recoding without a
-// sequential carry (digit_i = e_i - 2^(c-1)).  top receives the carry out of bit 255.
-__device__ __forceinline__ void sc_add_pattern(uint32_t e[8], uint32_t& top, const uint32_t s[8], uint32_t pattern) {
-  uint64_t c = 0;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    c += (uint64_t)s[i] + pattern;
-    e[i] = (uint32_t)c;
-    c >>= 32;
-  }
-  top = (uint32_t)c;
-}
-
 // w[j] for a run-time j without dynamic register indexing (which would go to scratch)
 __device__ __forceinline__ uint32_t sel8(const uint32_t w[8], int j) {
   uint32_t r = w[0];
@@ -64,11 +51,11 @@ __device__ __forceinline__ uint32_t sel8(const uint32_t w[8], int j) {
   return r;
 }
 
+#include "sc25519.h"     // sc_add_pattern: before the table headers that recode with it
 #include "hot_tables.h"
 #include "quad.h"
 #include "rowfe.h"
 #include "comb_tables.h"
-#include "sc25519.h"
 #include "transcript_kernels.h"
 #include "sha512.h"
 
