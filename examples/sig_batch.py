@@ -31,9 +31,8 @@ def main():
     messages = [rng.bytes(int(k)) for k in rng.integers(8, 600, size=n)]
     B = np.frombuffer(BASEPOINT, np.uint8).reshape(1, 32).copy()
 
-    # one key pair per signer: x < 2^252 < l, A = x B
-    x = np.frombuffer(os.urandom(32 * n), np.uint8).reshape(n, 32).copy()
-    x[:, 31] &= 0x0f
+    # one key pair per signer: x = Scalar::random (sig_and_vrf_example.rs:49), A = x B
+    x = T.scalar_random(eng, n)
     A, _ = eng.msm_many(np.arange(n + 1, dtype=np.uint32), x, np.zeros(n, np.uint32), B, ZKP_CT)
 
     # KeyPair::sign: the message goes into the transcript, then prove_batchable

@@ -40,9 +40,8 @@ def main():
     messages = [b"Test Message %d" % j for j in range(n)]
     B = np.frombuffer(BASEPOINT, np.uint8).reshape(1, 32).copy()
 
-    # one key pair per message (a batch of VRF evaluations for many users): x < 2^252 < l, A = x B
-    x = np.frombuffer(os.urandom(32 * n), np.uint8).reshape(n, 32).copy()
-    x[:, 31] &= 0x0f
+    # one key pair per message (a batch of VRF evaluations for many users): x = Scalar::random (sig_and_vrf_example.rs:49), A = x B
+    x = T.scalar_random(eng, n)
     iota = np.arange(n + 1, dtype=np.uint32)
     A, _ = eng.msm_many(iota, x, np.zeros(n, np.uint32), B, ZKP_CT)
 

@@ -494,6 +494,35 @@ int zkp_hash_from_bytes_sha512(zkp_ctx* ctx, uint64_t n, const uint8_t* msgs, co
 int zkp_hash_from_bytes_sha512_dev(zkp_ctx* ctx, uint64_t n, const uint8_t* d_msgs, uint64_t msgs_len, const uint64_t* d_offsets /*[n+1]*/,
                                    uint8_t* d_out /*[n][32]*/);
 
+/* (6) Scalars mod l, batched (curve25519_dalek::scalar::Scalar).  Every output is a canonical 32-byte little-endian scalar; an input
+ *     documented as "any 32 bytes" is read as Scalar::from_bytes_mod_order reads it.  One lane per output; no branch or address depends
+ *     on an operand.  n = 0 is a no-op; a NULL buffer with n > 0, or n > 2^31 - 1, is ZKP_ERR_ARG.  The plain forms take host pointers,
+ *     upload, run, download and synchronise; the _dev forms take device pointers (32- and 64-byte elements 16-byte aligned), enqueue on
+ *     the context's stream without synchronising and may be recorded between zkp_ctx_capture_begin / _end (zkp_sc_random_dev once the
+ *     same call has run outside the capture: it draws into the workspace).  Timed under ZKP_K_SCALARS.
+ *     zkp_sc_invert: out[i] = (in[i] mod l)^-1, 0 -> 0 (Scalar::invert); in = any 32 bytes; out may equal in.
+ *     zkp_sc_from_wide: n x Scalar::from_bytes_mod_order_wide.
+ *     zkp_sc_muladd: out[i] = a[i a_stride] b[i b_stride] + c[i c_stride] mod l.  A stride counts elements and is 1, or 0 for one scalar
+ *       shared by all outputs (anything else is ZKP_ERR_ARG); c == NULL means + 0.  Operands are any 32 bytes; out may equal an operand
+ *       of stride 1.
+ *     zkp_sc_random: n x Scalar::random: out[i] = from_bytes_mod_order_wide(zkp_chacha20_block(key, i, nonce)), drawn on the device.
+ *     zkp_sc_hash_from_bytes_sha512: n x Scalar::hash_from_bytes::<Sha512> over a CSR batch, with the arguments, offset checks, clamping
+ *       and rebasing of zkp_hash_from_bytes_sha512 / _dev above (d_msgs of any alignment, d_offsets 8-byte aligned).  One kernel: the
+ *       digest never reaches memory.  Branches depend on the message lengths only.  Timed under ZKP_K_TRANSCRIPT. */
+int zkp_sc_invert(zkp_ctx* ctx, uint64_t n, const uint8_t* in /*[n][32]*/, uint8_t* out /*[n][32]*/);
+int zkp_sc_invert_dev(zkp_ctx* ctx, uint64_t n, const uint8_t* d_in /*[n][32]*/, uint8_t* d_out /*[n][32]*/);
+int zkp_sc_from_wide(zkp_ctx* ctx, uint64_t n, const uint8_t* in /*[n][64]*/, uint8_t* out /*[n][32]*/);
+int zkp_sc_from_wide_dev(zkp_ctx* ctx, uint64_t n, const uint8_t* d_in /*[n][64]*/, uint8_t* d_out /*[n][32]*/);
+int zkp_sc_muladd(zkp_ctx* ctx, uint64_t n, const uint8_t* a, uint32_t a_stride, const uint8_t* b, uint32_t b_stride, const uint8_t* c, uint32_t c_stride,
+                  uint8_t* out /*[n][32]*/);
+int zkp_sc_muladd_dev(zkp_ctx* ctx, uint64_t n, const uint8_t* d_a, uint32_t a_stride, const uint8_t* d_b, uint32_t b_stride, const uint8_t* d_c,
+                      uint32_t c_stride, uint8_t* d_out /*[n][32]*/);
+int zkp_sc_random(zkp_ctx* ctx, uint64_t n, const uint8_t key[32], uint64_t nonce, uint8_t* out /*[n][32]*/);
+int zkp_sc_random_dev(zkp_ctx* ctx, uint64_t n, const uint8_t key[32], uint64_t nonce, uint8_t* d_out /*[n][32]*/);
+int zkp_sc_hash_from_bytes_sha512(zkp_ctx* ctx, uint64_t n, const uint8_t* msgs, const uint64_t* offsets /*[n+1]*/, uint8_t* out /*[n][32]*/);
+int zkp_sc_hash_from_bytes_sha512_dev(zkp_ctx* ctx, uint64_t n, const uint8_t* d_msgs, uint64_t msgs_len, const uint64_t* d_offsets /*[n+1]*/,
+                                      uint8_t* d_out /*[n][32]*/);
+
 /* Timing of the last *_dev / host call on this context, measured with HIP events on the stream the
  * kernels were launched on.  kernel_ms[] is indexed by ZKP_K_*; returns the number of entries. */
 enum {

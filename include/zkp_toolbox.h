@@ -275,6 +275,25 @@ int zkp_hash_to_group_batch(zkp_ctx* ctx, uint32_t N, uint8_t* transcripts /*[N]
 int zkp_hash_from_bytes_sha512_batch(zkp_ctx* ctx, uint64_t n, const uint8_t* msgs, const uint64_t* offsets /*[n+1]*/, int n_threads,
                                      uint8_t* out /*[n][32]*/);
 
+/* Scalars mod l, batched (zkp_mi355x.h (6)): every output a canonical scalar, inputs any 32 bytes.  Each call routes as
+ * zkp_hash_from_bytes_sha512_batch does: ctx == NULL or n <= zkp_toolbox_get_host_max_terms() on the host threads (the kernels' scalar
+ * header and SHA-512 compiled for the host), anything else on the device; same bytes on both routes.  n = 0 is a no-op; a NULL buffer (with
+ * n > 0), decreasing offsets or a stride other than 0 and 1 are ZKP_TB_BAD_STATEMENT.
+ *   zkp_scalar_invert_batch: out[i] = (in[i] mod l)^-1, 0 -> 0 (Scalar::invert, reference tests/zkp.rs:35); out may equal in.
+ *   zkp_scalar_from_wide_batch: n x Scalar::from_bytes_mod_order_wide.
+ *   zkp_scalar_muladd_batch: out[i] = a[i a_stride] b[i b_stride] + c[i c_stride] mod l; stride 0 = one scalar for all i; c == NULL: + 0;
+ *     out may equal an operand of stride 1.
+ *   zkp_scalar_hash_from_bytes_sha512_batch: n x Scalar::hash_from_bytes::<Sha512> over a CSR batch.
+ *   zkp_scalar_random_batch: n x Scalar::random (tests/sig_and_vrf_example.rs:49): out[i] = from_bytes_mod_order_wide(zkp_chacha20_block(key, i,
+ *     nonce)); key == NULL: 32 bytes of getrandom() (ZKP_TB_NO_ENTROPY if that fails).  On the device the stream is drawn there. */
+int zkp_scalar_invert_batch(zkp_ctx* ctx, uint64_t n, const uint8_t* in /*[n][32]*/, int n_threads, uint8_t* out /*[n][32]*/);
+int zkp_scalar_from_wide_batch(zkp_ctx* ctx, uint64_t n, const uint8_t* in /*[n][64]*/, int n_threads, uint8_t* out /*[n][32]*/);
+int zkp_scalar_muladd_batch(zkp_ctx* ctx, uint64_t n, const uint8_t* a, uint32_t a_stride, const uint8_t* b, uint32_t b_stride, const uint8_t* c,
+                            uint32_t c_stride, int n_threads, uint8_t* out /*[n][32]*/);
+int zkp_scalar_hash_from_bytes_sha512_batch(zkp_ctx* ctx, uint64_t n, const uint8_t* msgs, const uint64_t* offsets /*[n+1]*/, int n_threads,
+                                            uint8_t* out /*[n][32]*/);
+int zkp_scalar_random_batch(zkp_ctx* ctx, uint64_t n, const uint8_t* key /*[32] or NULL*/, uint64_t nonce, int n_threads, uint8_t* out /*[n][32]*/);
+
 /* The ChaCha20 block function (RFC 8439 section 2.3; state words 12-13 = counter, 14-15 = nonce) behind the default
  * entropy / weights of the calls above (`entropy == NULL`, `weights16 == NULL`): like the reference's `thread_rng()`, a
  * ChaCha stream keyed from the operating system.  Exposed for the known-answer test. */

@@ -206,6 +206,19 @@ extern "C" {
     // hash_from_bytes::<Sha512> over a CSR batch of messages (zkp.rs:34): SHA-512, then from_uniform_bytes
     pub fn zkp_hash_from_bytes_sha512(ctx: *mut zkp_ctx, n: u64, msgs: *const u8, offsets: *const u64, out: *mut u8) -> c_int;
     pub fn zkp_hash_from_bytes_sha512_dev(ctx: *mut zkp_ctx, n: u64, d_msgs: *const u8, msgs_len: u64, d_offsets: *const u64, d_out: *mut u8) -> c_int;
+    // scalars mod l, batched (Scalar::invert, from_bytes_mod_order_wide, a * b + c, Scalar::random, hash_from_bytes::<Sha512>)
+    pub fn zkp_sc_invert(ctx: *mut zkp_ctx, n: u64, input: *const u8, out: *mut u8) -> c_int;
+    pub fn zkp_sc_invert_dev(ctx: *mut zkp_ctx, n: u64, d_in: *const u8, d_out: *mut u8) -> c_int;
+    pub fn zkp_sc_from_wide(ctx: *mut zkp_ctx, n: u64, input: *const u8, out: *mut u8) -> c_int;
+    pub fn zkp_sc_from_wide_dev(ctx: *mut zkp_ctx, n: u64, d_in: *const u8, d_out: *mut u8) -> c_int;
+    pub fn zkp_sc_muladd(ctx: *mut zkp_ctx, n: u64, a: *const u8, a_stride: u32, b: *const u8, b_stride: u32, c: *const u8, c_stride: u32,
+                         out: *mut u8) -> c_int;
+    pub fn zkp_sc_muladd_dev(ctx: *mut zkp_ctx, n: u64, d_a: *const u8, a_stride: u32, d_b: *const u8, b_stride: u32, d_c: *const u8, c_stride: u32,
+                             d_out: *mut u8) -> c_int;
+    pub fn zkp_sc_random(ctx: *mut zkp_ctx, n: u64, key: *const u8, nonce: u64, out: *mut u8) -> c_int;
+    pub fn zkp_sc_random_dev(ctx: *mut zkp_ctx, n: u64, key: *const u8, nonce: u64, d_out: *mut u8) -> c_int;
+    pub fn zkp_sc_hash_from_bytes_sha512(ctx: *mut zkp_ctx, n: u64, msgs: *const u8, offsets: *const u64, out: *mut u8) -> c_int;
+    pub fn zkp_sc_hash_from_bytes_sha512_dev(ctx: *mut zkp_ctx, n: u64, d_msgs: *const u8, msgs_len: u64, d_offsets: *const u64, d_out: *mut u8) -> c_int;
     pub fn zkp_ctx_last_timing(ctx: *mut zkp_ctx, kernel_ms: *mut f32, total_ms: *mut f32) -> c_int;
     pub fn zkp_ctx_last_kernels(ctx: *mut zkp_ctx, kind: c_int, buf: *mut c_char, cap: usize) -> c_int;
     pub fn zkp_ctx_set_profiling(ctx: *mut zkp_ctx, enabled: c_int) -> c_int;
@@ -306,6 +319,13 @@ extern "C" {
     pub fn zkp_from_uniform_bytes_batch(ctx: *mut zkp_ctx, n: u64, input: *const u8, n_threads: c_int, out: *mut u8) -> c_int;
     pub fn zkp_hash_to_group_batch(ctx: *mut zkp_ctx, n: u32, transcripts: *mut u8, label: *const c_char, n_threads: c_int, out: *mut u8) -> c_int;
     pub fn zkp_hash_from_bytes_sha512_batch(ctx: *mut zkp_ctx, n: u64, msgs: *const u8, offsets: *const u64, n_threads: c_int, out: *mut u8) -> c_int;
+    // scalars mod l on the host backend (ctx NULL or n <= host_max_terms) or the device
+    pub fn zkp_scalar_invert_batch(ctx: *mut zkp_ctx, n: u64, input: *const u8, n_threads: c_int, out: *mut u8) -> c_int;
+    pub fn zkp_scalar_from_wide_batch(ctx: *mut zkp_ctx, n: u64, input: *const u8, n_threads: c_int, out: *mut u8) -> c_int;
+    pub fn zkp_scalar_muladd_batch(ctx: *mut zkp_ctx, n: u64, a: *const u8, a_stride: u32, b: *const u8, b_stride: u32, c: *const u8, c_stride: u32,
+                                   n_threads: c_int, out: *mut u8) -> c_int;
+    pub fn zkp_scalar_hash_from_bytes_sha512_batch(ctx: *mut zkp_ctx, n: u64, msgs: *const u8, offsets: *const u64, n_threads: c_int, out: *mut u8) -> c_int;
+    pub fn zkp_scalar_random_batch(ctx: *mut zkp_ctx, n: u64, key: *const u8, nonce: u64, n_threads: c_int, out: *mut u8) -> c_int;
     pub fn zkp_chacha20_block(key: *const u8, counter: u64, nonce: u64, out: *mut u8);
     // ---- proof wire format (proofs.rs:14-32 under bincode 1.x) ------------------------------------------------------------
     pub fn zkp_proof_compact_size(m: u32) -> usize;

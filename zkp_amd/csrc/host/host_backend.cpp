@@ -17,6 +17,7 @@
 //   decode_check  ristretto decode.
 //   from_uniform_bytes  RFC 9496 section 4.3.4 (ristretto_from_uniform_bytes of ge25519.h: selects only, constant time), then the encoder.
 //   hash_from_bytes_sha512  sha512_range of sha512.h (the kernel's SHA-512, byte loads on the host), then from_uniform_bytes.
+//   sc_*          the scalar kernels' bodies: sc25519.h (sc_invert, sc_from_wide, sc_mont) compiled for the host, element by element.
 #include "host_backend.hpp"
 
 #include <cstring>
@@ -25,6 +26,7 @@
 #define ZKP_HOST_FE51 1        // this translation unit (and no other of the library) gets the 5 x 51-bit field under the device's point formulas
 #include "../ge25519.h"
 #include "../sha512.h"
+#include "../sc25519.h"
 
 namespace zkp {
 namespace hostbk {
@@ -191,6 +193,63 @@ int hash_from_bytes_sha512(uint64_t n, const uint8_t* msgs, const uint64_t* offs
     encode(out + 32 * i, p);
   }
   return ZKP_OK;
+}
+
+// ---- scalars mod l: the bodies of k_sc_invert / k_sc_from_wide / k_sc_muladd / k_sc_hash_sha512 (element i0 + i of the call is i here) ----
+namespace {
+inline void sc_load(sc& r, const uint8_t* p) { std::memcpy(r.v, p, 32); }
+inline void sc_store(uint8_t* p, const sc& a) { std::memcpy(p, a.v, 32); }
+}  // namespace
+
+void sc_invert_n(uint64_t n, const uint8_t* in, uint8_t* out) {
+  for (uint64_t i = 0; i < n; ++i) {
+    sc a, r;
+    sc_load(a, in + 32 * i);
+    sc_invert(r, a);
+    sc_store(out + 32 * i, r);
+  }
+}
+
+void sc_from_wide_n(uint64_t n, const uint8_t* in, uint8_t* out) {
+  for (uint64_t i = 0; i < n; ++i) {
+    sc lo, hi, r;
+    sc_load(lo, in + 64 * i);
+    sc_load(hi, in + 64 * i + 32);
+    sc_from_wide(r, lo, hi);
+    sc_store(out + 32 * i, r);
+  }
+}
+
+void sc_muladd_n(uint64_t n, const uint8_t* a, uint32_t sa, const uint8_t* b, uint32_t sb, const uint8_t* c, uint32_t sc_, uint8_t* out) {
+  sc r1;
+  for (int k = 0; k < 8; ++k) r1.v[k] = sc_r1(k);
+  for (uint64_t i = 0; i < n; ++i) {
+    sc x, y, r;
+    sc_load(x, a + 32 * i * sa);
+    sc_load(y, b + 32 * i * sb);
+    sc_to_mont(y, y);
+    sc_mont(r, x, y);
+    if (c) {
+      sc z;
+      sc_load(z, c + 32 * i * sc_);
+      sc_mont(z, z, r1);
+      sc_add(r, r, z);
+    }
+    sc_store(out + 32 * i, r);
+  }
+}
+
+void sc_hash_sha512_n(uint64_t n, const uint8_t* msgs, const uint64_t* offsets, uint8_t* out) {
+  for (uint64_t i = 0; i < n; ++i) {
+    uint64_t H[8];
+    uint32_t w[16];
+    sha512_range(H, msgs, offsets[n], offsets[i], offsets[i + 1]);
+    sha512_digest_words(w, H);
+    sc lo, hi, r;
+    for (int k = 0; k < 8; ++k) { lo.v[k] = w[k]; hi.v[k] = w[8 + k]; }
+    sc_from_wide(r, lo, hi);
+    sc_store(out + 32 * i, r);
+  }
 }
 
 }  // namespace hostbk

@@ -15,5 +15,11 @@ int decode_check(uint64_t n, const uint8_t* points, uint8_t* status);
 int from_uniform_bytes(uint64_t n, const uint8_t* in /*[n][64]*/, uint8_t* out /*[n][32]*/);      // zkp_from_uniform_bytes (5)
 // zkp_hash_from_bytes_sha512 (5): message i = msgs[offsets[i], offsets[i + 1]) clamped to [0, offsets[n]); the caller has checked the offsets
 int hash_from_bytes_sha512(uint64_t n, const uint8_t* msgs, const uint64_t* offsets /*[n+1]*/, uint8_t* out /*[n][32]*/);
+// zkp_sc_* (6): the caller has checked pointers and strides; a slice of a call is a call of its own (strided operands advanced by the caller)
+void sc_invert_n(uint64_t n, const uint8_t* in /*[n][32]*/, uint8_t* out /*[n][32]*/);
+void sc_from_wide_n(uint64_t n, const uint8_t* in /*[n][64]*/, uint8_t* out /*[n][32]*/);
+void sc_muladd_n(uint64_t n, const uint8_t* a, uint32_t a_stride, const uint8_t* b, uint32_t b_stride, const uint8_t* c /*or NULL*/, uint32_t c_stride,
+                 uint8_t* out /*[n][32]*/);
+void sc_hash_sha512_n(uint64_t n, const uint8_t* msgs, const uint64_t* offsets /*[n+1]*/, uint8_t* out /*[n][32]*/);
 }  // namespace hostbk
 }  // namespace zkp

@@ -890,6 +890,72 @@ int zkp_hash_from_bytes_sha512_batch(zkp_ctx* ctx, uint64_t n, const uint8_t* ms
   return ZKP_TB_OK;
 }
 
+// ---- scalars mod l, batched (zkp_mi355x.h (6)): host threads through sc25519.h / sha512.h compiled for the host, or the device ------
+int zkp_scalar_invert_batch(zkp_ctx* ctx, uint64_t n, const uint8_t* in, int n_threads, uint8_t* out) {
+  if (n == 0) return ZKP_TB_OK;
+  if (!in || !out) return ZKP_TB_BAD_STATEMENT;
+  if (!on_host(ctx, n)) return zkp_sc_invert(ctx, n, in, out);
+  if (n > 0xffffffffull) return ZKP_TB_BAD_STATEMENT;
+  parallel_for((uint32_t)n, n_threads, [&](uint32_t lo, uint32_t hi) { zkp::hostbk::sc_invert_n(hi - lo, in + 32 * (size_t)lo, out + 32 * (size_t)lo); });
+  return ZKP_TB_OK;
+}
+
+int zkp_scalar_from_wide_batch(zkp_ctx* ctx, uint64_t n, const uint8_t* in, int n_threads, uint8_t* out) {
+  if (n == 0) return ZKP_TB_OK;
+  if (!in || !out) return ZKP_TB_BAD_STATEMENT;
+  if (!on_host(ctx, n)) return zkp_sc_from_wide(ctx, n, in, out);
+  if (n > 0xffffffffull) return ZKP_TB_BAD_STATEMENT;
+  parallel_for((uint32_t)n, n_threads, [&](uint32_t lo, uint32_t hi) { zkp::hostbk::sc_from_wide_n(hi - lo, in + 64 * (size_t)lo, out + 32 * (size_t)lo); });
+  return ZKP_TB_OK;
+}
+
+int zkp_scalar_muladd_batch(zkp_ctx* ctx, uint64_t n, const uint8_t* a, uint32_t a_stride, const uint8_t* b, uint32_t b_stride, const uint8_t* c, uint32_t c_stride,
+                            int n_threads, uint8_t* out) {
+  if (a_stride > 1 || b_stride > 1 || c_stride > 1) return ZKP_TB_BAD_STATEMENT;
+  if (n == 0) return ZKP_TB_OK;
+  if (!a || !b || !out) return ZKP_TB_BAD_STATEMENT;
+  if (!on_host(ctx, n)) return zkp_sc_muladd(ctx, n, a, a_stride, b, b_stride, c, c_stride, out);
+  if (n > 0xffffffffull) return ZKP_TB_BAD_STATEMENT;
+  parallel_for((uint32_t)n, n_threads, [&](uint32_t lo, uint32_t hi) {
+    zkp::hostbk::sc_muladd_n(hi - lo, a + 32 * (size_t)lo * a_stride, a_stride, b + 32 * (size_t)lo * b_stride, b_stride, c ? c + 32 * (size_t)lo * c_stride : nullptr,
+                             c_stride, out + 32 * (size_t)lo);
+  });
+  return ZKP_TB_OK;
+}
+
+// Scalar::hash_from_bytes::<Sha512> of n messages (CSR, checked here as zkp_hash_from_bytes_sha512_batch checks it)
+int zkp_scalar_hash_from_bytes_sha512_batch(zkp_ctx* ctx, uint64_t n, const uint8_t* msgs, const uint64_t* offsets, int n_threads, uint8_t* out) {
+  if (n == 0) return ZKP_TB_OK;
+  if (!msgs || !offsets || !out) return ZKP_TB_BAD_STATEMENT;
+  for (uint64_t i = 0; i < n; ++i)
+    if (offsets[i + 1] < offsets[i]) return ZKP_TB_BAD_STATEMENT;
+  if (!on_host(ctx, n)) return zkp_sc_hash_from_bytes_sha512(ctx, n, msgs, offsets, out);
+  if (n > 0xffffffffull) return ZKP_TB_BAD_STATEMENT;
+  parallel_for((uint32_t)n, n_threads, [&](uint32_t lo, uint32_t hi) { zkp::hostbk::sc_hash_sha512_n(hi - lo, msgs, offsets + lo, out + 32 * (size_t)lo); });
+  return ZKP_TB_OK;
+}
+
+// n x Scalar::random (64 bytes of a ChaCha20 stream through from_bytes_mod_order_wide): element i from block i of (key, nonce)
+int zkp_scalar_random_batch(zkp_ctx* ctx, uint64_t n, const uint8_t* key, uint64_t nonce, int n_threads, uint8_t* out) {
+  if (n == 0) return ZKP_TB_OK;
+  if (!out) return ZKP_TB_BAD_STATEMENT;
+  uint8_t own[32];
+  if (!key) {
+    if (!os_entropy(own, sizeof(own))) return ZKP_TB_NO_ENTROPY;
+    key = own;
+  }
+  if (!on_host(ctx, n)) return zkp_sc_random(ctx, n, key, nonce, out);
+  if (n > 0xffffffffull) return ZKP_TB_BAD_STATEMENT;
+  parallel_for((uint32_t)n, n_threads, [&](uint32_t lo, uint32_t hi) {
+    uint8_t wide[64];
+    for (uint64_t i = lo; i < hi; ++i) {
+      zkp_chacha20_block(key, i, nonce, wide);
+      zkp::hostbk::sc_from_wide_n(1, wide, out + 32 * (size_t)i);
+    }
+  });
+  return ZKP_TB_OK;
+}
+
 // tests/sig_and_vrf_example.rs:36-40 for N transcripts.  Aligned batches of fused_min_batch or more squeeze on the device and map there
 // (zkp_fused_hash_to_group); otherwise host Merlin on the host threads, then the map on the backend zkp_from_uniform_bytes_batch picks.
 int zkp_hash_to_group_batch(zkp_ctx* ctx, uint32_t N, uint8_t* ts, const char* label, int n_threads, uint8_t* out) {

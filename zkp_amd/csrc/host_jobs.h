@@ -536,6 +536,46 @@ int zkp_chacha20_fill_dev(zkp_ctx* c, const uint8_t key[32], uint64_t nonce, uin
   return chacha_fill(c, seed, first_block, d_out, bytes);
 }
 
+// n x Scalar::random: blocks 0 .. n - 1 of the stream into the workspace, k_sc_from_wide over them.  No random byte crosses the link.
+int zkp_sc_random_dev(zkp_ctx* c, uint64_t n, const uint8_t key[32], uint64_t nonce, uint8_t* d_out) {
+  if (!c) return fail(ZKP_ERR_ARG, "ctx is NULL");
+  if (n == 0) return ZKP_OK;
+  if (!key || !d_out) return fail(ZKP_ERR_ARG, "NULL pointer");
+  if (n > 0x7fffffffull) return fail(ZKP_ERR_ARG, "n too large");
+  if (!aligned16(d_out)) return fail(ZKP_ERR_ARG, "d_out must be 16-byte aligned");
+  HIP_TRY(hipSetDevice(c->device));
+  carve cv;
+  const size_t o_wide = cv.take((size_t)n * 64);
+  int rc = ensure_ws(c, cv.off);
+  if (rc) return rc;
+  uint8_t* d_wide = static_cast<uint8_t*>(c->ws) + o_wide;
+  uint8_t seed[40];
+  memcpy(seed, key, 32);
+  memcpy(seed + 32, &nonce, 8);
+  prof_begin(c);
+  rc = chacha_fill(c, seed, 0, d_wide, (size_t)n * 64);
+  if (rc) return rc;
+  return launch_sc_from_wide(c, n, d_wide, d_out);
+}
+int zkp_sc_random(zkp_ctx* c, uint64_t n, const uint8_t key[32], uint64_t nonce, uint8_t* out) {
+  if (!c) return fail(ZKP_ERR_ARG, "ctx is NULL");
+  if (n == 0) return ZKP_OK;
+  if (!key || !out) return fail(ZKP_ERR_ARG, "NULL pointer");
+  if (n > 0x7fffffffull) return fail(ZKP_ERR_ARG, "n too large");
+  HIP_TRY(hipSetDevice(c->device));
+  carve cv;
+  const size_t o_wide = cv.take((size_t)n * 64);
+  const size_t o_out = cv.take((size_t)n * 32);
+  int rc = ensure_ws(c, cv.off);          // (zkp_sc_random_dev below carves the same first block: no second growth)
+  if (rc) return rc;
+  uint8_t* d_out = static_cast<uint8_t*>(c->ws) + o_out;
+  rc = zkp_sc_random_dev(c, n, key, nonce, d_out);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return ZKP_OK;
+}
+
 // ---- jobs ---------------------------------------------------------------------------------------------------------------------
 int zkp_fused_prove_submit(zkp_ctx* c, const zkp_fused_statement* st, uint32_t N, uint32_t flags, const uint8_t* transcripts, const uint8_t* secrets,
                            const uint8_t* inst, uint32_t inst_stride, const uint8_t* common, const uint8_t* entropy, const uint8_t* rng_seed,

@@ -217,4 +217,58 @@ ZKP_HD void sc_from_wide(sc& r, const sc& lo, const sc& hi) {
   sc_add(r, a, b);
 }
 
+// y = y^(2^n) * t in Montgomery form: n squarings in a rolled loop (n is a constant at every call site), one product
+ZKP_HD void sc_sqmul(sc& y, int n, const sc& t) {
+#pragma unroll 1
+  for (int k = 0; k < n; ++k) sc_mont(y, y, y);
+  sc_mont(y, y, t);
+}
+// r = a^(l-2) mod l: the inverse, 0 for 0 (Scalar::invert).  a < l (any 256-bit a works: sc_to_mont reduces it).  The exponent
+// l - 2 = 2^252 + 0x14def9dea2f79cd65812631a5cf5d3eb is public: a fixed chain, a 4-bit sliding window over the odd powers a^3 .. a^15
+// held in named values.  289 Montgomery products: 1 into Montgomery form, 8 for a^2 and the seven odd powers, 252 squarings and 27
+// products of the walk, 1 out.  No branch, address or trip count depends on a.
+ZKP_HD void sc_invert(sc& r, const sc& a) {
+  sc y, a2, t3, t5, t7, t9, t11, t13, t15, one;
+  sc_to_mont(y, a);
+  sc_mont(a2, y, y);
+  sc_mont(t3, a2, y);
+  sc_mont(t5, a2, t3);
+  sc_mont(t7, a2, t5);
+  sc_mont(t9, a2, t7);
+  sc_mont(t11, a2, t9);
+  sc_mont(t13, a2, t11);
+  sc_mont(t15, a2, t13);
+  // bits 251 .. 0 of l - 2 after the leading one (y = a): 127 zeros, then the 125-bit tail window by window
+  sc_sqmul(y, 130, t5);
+  sc_sqmul(y, 6, t13);
+  sc_sqmul(y, 3, t7);
+  sc_sqmul(y, 5, t15);
+  sc_sqmul(y, 4, t9);
+  sc_sqmul(y, 4, t13);
+  sc_sqmul(y, 3, t7);
+  sc_sqmul(y, 4, t5);
+  sc_sqmul(y, 7, t11);
+  sc_sqmul(y, 4, t13);
+  sc_sqmul(y, 3, t7);
+  sc_sqmul(y, 5, t7);
+  sc_sqmul(y, 6, t13);
+  sc_sqmul(y, 3, t3);
+  sc_sqmul(y, 6, t11);
+  sc_sqmul(y, 10, t9);
+  sc_sqmul(y, 4, t3);
+  sc_sqmul(y, 5, t3);
+  sc_sqmul(y, 7, t13);
+  sc_sqmul(y, 6, t11);
+  sc_sqmul(y, 4, t9);
+  sc_sqmul(y, 3, t7);
+  sc_sqmul(y, 5, t11);
+  sc_sqmul(y, 3, t5);
+  sc_sqmul(y, 6, t15);
+  sc_sqmul(y, 3, t5);
+  sc_sqmul(y, 3, t3);
+  sc_zero(one);
+  one.v[0] = 1;
+  sc_mont(r, y, one);
+}
+
 }  // namespace zkp

@@ -1334,6 +1334,70 @@ k_sha512_csr(uint32_t n, const uint8_t* __restrict__ msgs, uint64_t msgs_len, co
   }
 }
 
+// Batched scalars mod l (zkp_mi355x.h (6)): one lane per output over a grid-stride loop, canonical 32-byte scalars out.  Inputs are any
+// 32 bytes, read as Scalar::from_bytes_mod_order reads them (sc_mont takes any 256-bit first operand).  No branch or address depends
+// on an operand.  `in` / an operand of stride 1 may be `out`: a lane loads its own element before it stores it.
+__global__ void __launch_bounds__(256)
+k_sc_invert(uint32_t n, const uint8_t* in, uint8_t* out) {
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    sc a, r;
+    load_vec<2>(a.v, in + 32 * (size_t)i);
+    sc_invert(r, a);
+    store_vec<2>(out + 32 * (size_t)i, r.v);
+  }
+}
+
+// Scalar::from_bytes_mod_order_wide over n 64-byte strings
+__global__ void __launch_bounds__(256)
+k_sc_from_wide(uint32_t n, const uint8_t* __restrict__ in, uint8_t* __restrict__ out) {
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    sc lo, hi, r;
+    load_vec<2>(lo.v, in + 64 * (size_t)i);
+    load_vec<2>(hi.v, in + 64 * (size_t)i + 32);
+    sc_from_wide(r, lo, hi);
+    store_vec<2>(out + 32 * (size_t)i, r.v);
+  }
+}
+
+// out[i] = a[i sa] * b[i sb] + c[i sc] mod l, strides 0 (one scalar for all lanes) or 1; c == NULL: + 0.  Three Montgomery products:
+// b R mod l, a b mod l, c mod l.
+__global__ void __launch_bounds__(256)
+k_sc_muladd(uint32_t n, const uint8_t* a, uint32_t sa, const uint8_t* b, uint32_t sb, const uint8_t* c, uint32_t sc_, uint8_t* out) {
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    sc x, y, r;
+    load_vec<2>(x.v, a + 32 * (size_t)i * sa);
+    load_vec<2>(y.v, b + 32 * (size_t)i * sb);
+    sc_to_mont(y, y);
+    sc_mont(r, x, y);
+    if (c) {
+      sc z, r1;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) r1.v[k] = sc_r1(k);
+      load_vec<2>(z.v, c + 32 * (size_t)i * sc_);
+      sc_mont(z, z, r1);
+      sc_add(r, r, z);
+    }
+    store_vec<2>(out + 32 * (size_t)i, r.v);
+  }
+}
+
+// Scalar::hash_from_bytes::<Sha512> over a CSR batch: k_sha512_csr's ranges and clamping, the digest reduced in registers.  Branches
+// depend on the message lengths only.
+__global__ void __launch_bounds__(256)
+k_sc_hash_sha512(uint32_t n, const uint8_t* __restrict__ msgs, uint64_t msgs_len, const uint64_t* __restrict__ offsets, uint8_t* __restrict__ out) {
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    uint64_t H[8];
+    sha512_range(H, msgs, msgs_len, offsets[i], offsets[i + 1]);
+    uint32_t w[16];
+    sha512_digest_words(w, H);
+    sc lo, hi, r;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { lo.v[k] = w[k]; hi.v[k] = w[8 + k]; }
+    sc_from_wide(r, lo, hi);
+    store_vec<2>(out + 32 * (size_t)i, r.v);
+  }
+}
+
 // =============================================================================================
 // host side: context, workspace, C ABI
 // =============================================================================================
@@ -2036,9 +2100,51 @@ int launch_sha512(zkp_ctx* c, uint64_t n, const uint8_t* d_msgs, uint64_t msgs_l
   return ZKP_OK;
 }
 
+// The scalar kernels of zkp_mi355x.h (6) over n outputs on the context's stream (device pointers), grid as launch_from_uniform.
+inline unsigned sc_blocks(uint64_t n) {
+  constexpr uint64_t kMaxBlocks = 2048;
+  return (unsigned)std::min<uint64_t>(kMaxBlocks, (n + 255) / 256);
+}
+int launch_sc_invert(zkp_ctx* c, uint64_t n, const uint8_t* d_in, uint8_t* d_out) {
+  hipLaunchKernelGGL(k_sc_invert, dim3(sc_blocks(n)), dim3(256), 0, c->stream, (uint32_t)n, d_in, d_out);
+  prof_mark(c, ZKP_K_SCALARS);
+  HIP_TRY(hipGetLastError());
+  return ZKP_OK;
+}
+int launch_sc_from_wide(zkp_ctx* c, uint64_t n, const uint8_t* d_in, uint8_t* d_out) {
+  hipLaunchKernelGGL(k_sc_from_wide, dim3(sc_blocks(n)), dim3(256), 0, c->stream, (uint32_t)n, d_in, d_out);
+  prof_mark(c, ZKP_K_SCALARS);
+  HIP_TRY(hipGetLastError());
+  return ZKP_OK;
+}
+int launch_sc_muladd(zkp_ctx* c, uint64_t n, const uint8_t* d_a, uint32_t sa, const uint8_t* d_b, uint32_t sb, const uint8_t* d_c, uint32_t sc_, uint8_t* d_out) {
+  hipLaunchKernelGGL(k_sc_muladd, dim3(sc_blocks(n)), dim3(256), 0, c->stream, (uint32_t)n, d_a, sa, d_b, sb, d_c, sc_, d_out);
+  prof_mark(c, ZKP_K_SCALARS);
+  HIP_TRY(hipGetLastError());
+  return ZKP_OK;
+}
+// (one kernel, SHA-512 and the reduction: filed under the SHA stage's kind, which is all but three Montgomery products of it)
+int launch_sc_hash_sha512(zkp_ctx* c, uint64_t n, const uint8_t* d_msgs, uint64_t msgs_len, const uint64_t* d_offsets, uint8_t* d_out) {
+  hipLaunchKernelGGL(k_sc_hash_sha512, dim3(sc_blocks(n)), dim3(256), 0, c->stream, (uint32_t)n, d_msgs, msgs_len, d_offsets, d_out);
+  prof_mark(c, ZKP_K_TRANSCRIPT);
+  HIP_TRY(hipGetLastError());
+  return ZKP_OK;
+}
+// the checks the four calls share; stride_ok: zkp_sc_muladd's strides
+int sc_call_check(zkp_ctx* c, uint64_t n, bool null_buffer, bool stride_ok = true) {
+  if (!c) return fail(ZKP_ERR_ARG, "ctx is NULL");
+  if (!stride_ok) return fail(ZKP_ERR_ARG, "strides must be 0 or 1");
+  if (n == 0) return ZKP_OK;
+  if (null_buffer) return fail(ZKP_ERR_ARG, "NULL pointer");
+  if (n > 0x7fffffffull) return fail(ZKP_ERR_ARG, "n too large");
+  return ZKP_OK;
+}
+
 // zkp_hash_from_bytes_sha512 and zkp_debug_sha512: checks the offsets on the host (non-decreasing), uploads msgs[offsets[0], offsets[n])
-// and the offsets rebased to 0, hashes, and (map) maps the digests in place of the workspace.  out: [n][32] encodings, or [n][64] digests.
-int hash_from_bytes_host(zkp_ctx* c, uint64_t n, const uint8_t* msgs, const uint64_t* offsets, uint8_t* out, bool map) {
+// and the offsets rebased to 0, hashes, and (HASH_MAP) maps the digests in place of the workspace.  out: [n][32] encodings, or [n][64] digests.
+// HASH_SCALAR (zkp_sc_hash_from_bytes_sha512): the same checks and upload, k_sc_hash_sha512 instead: out = [n][32] scalars.
+enum hash_mode { HASH_DIGEST, HASH_MAP, HASH_SCALAR };
+int hash_from_bytes_host(zkp_ctx* c, uint64_t n, const uint8_t* msgs, const uint64_t* offsets, uint8_t* out, hash_mode mode) {
   if (!c) return fail(ZKP_ERR_ARG, "ctx is NULL");
   if (n == 0) return ZKP_OK;
   if (!msgs || !offsets || !out) return fail(ZKP_ERR_ARG, "NULL pointer");
@@ -2052,7 +2158,7 @@ int hash_from_bytes_host(zkp_ctx* c, uint64_t n, const uint8_t* msgs, const uint
   carve cv;
   const size_t o_msgs = cv.take((size_t)total);
   const size_t o_off = cv.take((size_t)(n + 1) * 8);
-  const size_t o_wide = cv.take((size_t)n * 64);
+  const size_t o_wide = cv.take(mode == HASH_SCALAR ? 0 : (size_t)n * 64);
   const size_t o_out = cv.take((size_t)n * 32);
   int rc = ensure_ws(c, cv.off);
   if (rc) return rc;
@@ -2060,10 +2166,18 @@ int hash_from_bytes_host(zkp_ctx* c, uint64_t n, const uint8_t* msgs, const uint
   if (total) HIP_TRY(hipMemcpyAsync(base + o_msgs, msgs + base_off, (size_t)total, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(base + o_off, rebased.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, c->stream));
   prof_begin(c);
+  if (mode == HASH_SCALAR) {
+    rc = launch_sc_hash_sha512(c, n, reinterpret_cast<const uint8_t*>(base + o_msgs), total, reinterpret_cast<const uint64_t*>(base + o_off),
+                               reinterpret_cast<uint8_t*>(base + o_out));
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return ZKP_OK;
+  }
   uint8_t* d_wide = reinterpret_cast<uint8_t*>(base + o_wide);
   rc = launch_sha512(c, n, reinterpret_cast<const uint8_t*>(base + o_msgs), total, reinterpret_cast<const uint64_t*>(base + o_off), d_wide);
   if (rc) return rc;
-  if (map) {
+  if (mode == HASH_MAP) {
     rc = launch_from_uniform(c, n, d_wide, reinterpret_cast<uint8_t*>(base + o_out));
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
@@ -2624,7 +2738,7 @@ int zkp_from_uniform_bytes(zkp_ctx* c, uint64_t n, const uint8_t* in, uint8_t* o
 }
 
 int zkp_hash_from_bytes_sha512(zkp_ctx* c, uint64_t n, const uint8_t* msgs, const uint64_t* offsets, uint8_t* out) {
-  return hash_from_bytes_host(c, n, msgs, offsets, out, /*map=*/true);
+  return hash_from_bytes_host(c, n, msgs, offsets, out, HASH_MAP);
 }
 
 // The digests go to the workspace (which must not grow under capture: run the call once first), then k_from_uniform maps them to d_out.
@@ -2648,6 +2762,110 @@ int zkp_hash_from_bytes_sha512_dev(zkp_ctx* c, uint64_t n, const uint8_t* d_msgs
   return launch_from_uniform(c, n, d_wide, d_out);
 }
 
+// ---- (6) batched scalars mod l ---------------------------------------------------------------------------------------------------
+int zkp_sc_invert_dev(zkp_ctx* c, uint64_t n, const uint8_t* d_in, uint8_t* d_out) {
+  const int rc = sc_call_check(c, n, !d_in || !d_out);
+  if (rc || n == 0) return rc;
+  if (!aligned16(d_in) || !aligned16(d_out)) return fail(ZKP_ERR_ARG, "device buffers must be 16-byte aligned");
+  HIP_TRY(hipSetDevice(c->device));
+  prof_begin(c);
+  return launch_sc_invert(c, n, d_in, d_out);
+}
+int zkp_sc_invert(zkp_ctx* c, uint64_t n, const uint8_t* in, uint8_t* out) {
+  int rc = sc_call_check(c, n, !in || !out);
+  if (rc || n == 0) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  carve cv;
+  const size_t o_io = cv.take((size_t)n * 32);
+  rc = ensure_ws(c, cv.off);
+  if (rc) return rc;
+  uint8_t* d_io = static_cast<uint8_t*>(c->ws) + o_io;
+  HIP_TRY(hipMemcpyAsync(d_io, in, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
+  prof_begin(c);
+  rc = launch_sc_invert(c, n, d_io, d_io);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(out, d_io, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return ZKP_OK;
+}
+
+int zkp_sc_from_wide_dev(zkp_ctx* c, uint64_t n, const uint8_t* d_in, uint8_t* d_out) {
+  const int rc = sc_call_check(c, n, !d_in || !d_out);
+  if (rc || n == 0) return rc;
+  if (!aligned16(d_in) || !aligned16(d_out)) return fail(ZKP_ERR_ARG, "device buffers must be 16-byte aligned");
+  HIP_TRY(hipSetDevice(c->device));
+  prof_begin(c);
+  return launch_sc_from_wide(c, n, d_in, d_out);
+}
+int zkp_sc_from_wide(zkp_ctx* c, uint64_t n, const uint8_t* in, uint8_t* out) {
+  int rc = sc_call_check(c, n, !in || !out);
+  if (rc || n == 0) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  carve cv;
+  const size_t o_in = cv.take((size_t)n * 64);
+  const size_t o_out = cv.take((size_t)n * 32);
+  rc = ensure_ws(c, cv.off);
+  if (rc) return rc;
+  uint8_t* base = static_cast<uint8_t*>(c->ws);
+  HIP_TRY(hipMemcpyAsync(base + o_in, in, (size_t)n * 64, hipMemcpyHostToDevice, c->stream));
+  prof_begin(c);
+  rc = launch_sc_from_wide(c, n, base + o_in, base + o_out);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return ZKP_OK;
+}
+
+int zkp_sc_muladd_dev(zkp_ctx* c, uint64_t n, const uint8_t* d_a, uint32_t a_stride, const uint8_t* d_b, uint32_t b_stride, const uint8_t* d_c, uint32_t c_stride,
+                      uint8_t* d_out) {
+  const int rc = sc_call_check(c, n, !d_a || !d_b || !d_out, a_stride <= 1 && b_stride <= 1 && c_stride <= 1);
+  if (rc || n == 0) return rc;
+  if (!aligned16(d_a) || !aligned16(d_b) || !aligned16(d_c) || !aligned16(d_out)) return fail(ZKP_ERR_ARG, "device buffers must be 16-byte aligned");
+  HIP_TRY(hipSetDevice(c->device));
+  prof_begin(c);
+  return launch_sc_muladd(c, n, d_a, a_stride, d_b, b_stride, d_c, c_stride, d_out);
+}
+int zkp_sc_muladd(zkp_ctx* c, uint64_t n, const uint8_t* a, uint32_t a_stride, const uint8_t* b, uint32_t b_stride, const uint8_t* cc, uint32_t c_stride,
+                  uint8_t* out) {
+  int rc = sc_call_check(c, n, !a || !b || !out, a_stride <= 1 && b_stride <= 1 && c_stride <= 1);
+  if (rc || n == 0) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t na = a_stride ? (size_t)n : 1, nb = b_stride ? (size_t)n : 1, nc = !cc ? 0 : c_stride ? (size_t)n : 1;
+  carve cv;
+  const size_t o_a = cv.take(na * 32);
+  const size_t o_b = cv.take(nb * 32);
+  const size_t o_c = cv.take(nc * 32);
+  const size_t o_out = cv.take((size_t)n * 32);
+  rc = ensure_ws(c, cv.off);
+  if (rc) return rc;
+  uint8_t* base = static_cast<uint8_t*>(c->ws);
+  HIP_TRY(hipMemcpyAsync(base + o_a, a, na * 32, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(base + o_b, b, nb * 32, hipMemcpyHostToDevice, c->stream));
+  if (cc) HIP_TRY(hipMemcpyAsync(base + o_c, cc, nc * 32, hipMemcpyHostToDevice, c->stream));
+  prof_begin(c);
+  rc = launch_sc_muladd(c, n, base + o_a, a_stride, base + o_b, b_stride, cc ? base + o_c : nullptr, c_stride, base + o_out);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return ZKP_OK;
+}
+
+int zkp_sc_hash_from_bytes_sha512(zkp_ctx* c, uint64_t n, const uint8_t* msgs, const uint64_t* offsets, uint8_t* out) {
+  return hash_from_bytes_host(c, n, msgs, offsets, out, HASH_SCALAR);
+}
+// No workspace: the digest stays in registers.  The device offsets are not validated: the kernel clamps every range to [0, msgs_len).
+int zkp_sc_hash_from_bytes_sha512_dev(zkp_ctx* c, uint64_t n, const uint8_t* d_msgs, uint64_t msgs_len, const uint64_t* d_offsets, uint8_t* d_out) {
+  if (!c) return fail(ZKP_ERR_ARG, "ctx is NULL");
+  if (n == 0) return ZKP_OK;
+  if ((!d_msgs && msgs_len) || !d_offsets || !d_out) return fail(ZKP_ERR_ARG, "NULL device pointer");
+  if (n > 0x7fffffffull) return fail(ZKP_ERR_ARG, "n too large");
+  if ((reinterpret_cast<uintptr_t>(d_offsets) & 7) || !aligned16(d_out))
+    return fail(ZKP_ERR_ARG, "d_offsets must be 8-byte and d_out 16-byte aligned");
+  HIP_TRY(hipSetDevice(c->device));
+  prof_begin(c);
+  return launch_sc_hash_sha512(c, n, d_msgs, msgs_len, d_offsets, d_out);
+}
+
 #ifdef ZKP_BUILD_TEST_HOOKS
 int zkp_debug_last_schedule(zkp_ctx* c, char* buf, size_t cap) {
   if (!c || !buf || !cap) return fail(ZKP_ERR_ARG, "bad argument");
@@ -2664,7 +2882,7 @@ int zkp_debug_last_schedule(zkp_ctx* c, char* buf, size_t cap) {
 }
 
 int zkp_debug_sha512(zkp_ctx* c, uint64_t n, const uint8_t* msgs, const uint64_t* offsets, uint8_t* out) {
-  return hash_from_bytes_host(c, n, msgs, offsets, out, /*map=*/false);
+  return hash_from_bytes_host(c, n, msgs, offsets, out, HASH_DIGEST);
 }
 #endif  // ZKP_BUILD_TEST_HOOKS
 

@@ -116,6 +116,29 @@ def _csr_args(data, offsets) -> Tuple[np.ndarray, np.ndarray]:
     return data, offsets
 
 
+def scalar_operands(a, b, c=None):
+    """The operands of a * b + c as (n, (a, stride), (b, stride), (c, stride)): uint8 [n][32] has stride 1, shape (32,) or (1, 32) is one
+    scalar for every row (stride 0); all three shared gives n = 1; c = None stays None."""
+    ops = []
+    for x in (a, b, c):
+        if x is None:
+            ops.append(None)
+            continue
+        x = np.ascontiguousarray(x, dtype=np.uint8)
+        if x.shape == (32,):
+            x = x.reshape(1, 32)
+        if x.ndim != 2 or x.shape[1] != 32:
+            raise ValueError(f"expected uint8 array of shape [n][32] or (32,), got {x.shape}")
+        ops.append(x)
+    if ops[0] is None or ops[1] is None:
+        raise ValueError("a and b are required")
+    sizes = {len(x) for x in ops if x is not None and len(x) != 1}
+    if len(sizes) > 1:
+        raise ValueError(f"operands of different lengths: {sorted(sizes)}")
+    n = sizes.pop() if sizes else 1
+    return (n,) + tuple((x, 0 if x is None or (len(x) == 1 and n != 1) else 1) for x in ops)
+
+
 class Engine:
     """One context on one GPU (HIP device ordinal `device`)."""
 
@@ -207,6 +230,49 @@ class Engine:
         _check(self._lib.zkp_hash_from_bytes_sha512(self._h, n, _ptr(data), _ptr(offsets), _ptr(out)), "zkp_hash_from_bytes_sha512")
         return out
 
+    # ---- scalars mod l, batched (include/zkp_mi355x.h section 6): [n][32] canonical scalars out ----
+    def scalar_invert(self, s) -> np.ndarray:
+        """Scalar::invert of every row (any 32 bytes, read mod l; 0 -> 0)"""
+        s = _u8(s, 32)
+        out = np.zeros((len(s), 32), np.uint8)
+        _check(self._lib.zkp_sc_invert(self._h, len(s), _ptr(s), _ptr(out)), "zkp_sc_invert")
+        return out
+
+    def scalar_from_wide(self, wide) -> np.ndarray:
+        """Scalar::from_bytes_mod_order_wide of every 64-byte row"""
+        wide = _u8(wide, 64)
+        out = np.zeros((len(wide), 32), np.uint8)
+        _check(self._lib.zkp_sc_from_wide(self._h, len(wide), _ptr(wide), _ptr(out)), "zkp_sc_from_wide")
+        return out
+
+    def scalar_muladd(self, a, b, c=None) -> np.ndarray:
+        """a * b + c mod l row by row; an operand of shape (32,) or (1, 32) is shared by all rows (stride 0); c = None: + 0"""
+        n, (a, sa), (b, sb), (c, sc) = scalar_operands(a, b, c)
+        out = np.zeros((n, 32), np.uint8)
+        _check(self._lib.zkp_sc_muladd(self._h, n, _ptr(a), sa, _ptr(b), sb, _ptr(c), sc, _ptr(out)), "zkp_sc_muladd")
+        return out
+
+    def scalar_random(self, n: int, key: bytes, nonce: int = 0) -> np.ndarray:
+        """n x Scalar::random drawn on the GPU: row i = from_bytes_mod_order_wide(ChaCha20 block i of (key, nonce))"""
+        k = np.frombuffer(bytes(key), np.uint8).copy()
+        if k.size != 32:
+            raise ValueError("key must be 32 bytes")
+        out = np.zeros((n, 32), np.uint8)
+        _check(self._lib.zkp_sc_random(self._h, n, _ptr(k), nonce, _ptr(out)), "zkp_sc_random")
+        return out
+
+    def scalar_hash_from_bytes_sha512(self, messages) -> np.ndarray:
+        """Scalar::hash_from_bytes::<Sha512> of every message (a list of byte strings) on the GPU"""
+        return self.scalar_hash_from_bytes_sha512_csr(*messages_csr(messages))
+
+    def scalar_hash_from_bytes_sha512_csr(self, data, offsets) -> np.ndarray:
+        """the same for a CSR batch held in numpy buffers: message i = data[offsets[i]:offsets[i + 1]]"""
+        data, offsets = _csr_args(data, offsets)
+        n = len(offsets) - 1
+        out = np.zeros((n, 32), np.uint8)
+        _check(self._lib.zkp_sc_hash_from_bytes_sha512(self._h, n, _ptr(data), _ptr(offsets), _ptr(out)), "zkp_sc_hash_from_bytes_sha512")
+        return out
+
     def debug_sha512(self, data, offsets) -> np.ndarray:
         """the SHA-512 stage alone (test-hook build): CSR batch -> digests [n][64]"""
         self._need_hooks("zkp_debug_sha512")
@@ -279,6 +345,29 @@ class Engine:
         """zkp_hash_from_bytes_sha512_dev: message i = d_msgs[d_offsets[i], d_offsets[i + 1]) (u64 offsets, 8-byte aligned) -> d_out [n][32]
         (16-byte aligned), device pointers, queued on the context's stream"""
         _check(self._lib.zkp_hash_from_bytes_sha512_dev(self._h, n, d_msgs, msgs_len, d_offsets, d_out), "zkp_hash_from_bytes_sha512_dev")
+
+    def scalar_invert_dev(self, n, d_in, d_out) -> None:
+        """zkp_sc_invert_dev: d_in [n][32] -> d_out [n][32] (may be d_in), device pointers (16-byte aligned), queued on the context's stream"""
+        _check(self._lib.zkp_sc_invert_dev(self._h, n, d_in, d_out), "zkp_sc_invert_dev")
+
+    def scalar_from_wide_dev(self, n, d_in, d_out) -> None:
+        """zkp_sc_from_wide_dev: d_in [n][64] -> d_out [n][32]"""
+        _check(self._lib.zkp_sc_from_wide_dev(self._h, n, d_in, d_out), "zkp_sc_from_wide_dev")
+
+    def scalar_muladd_dev(self, n, d_a, a_stride, d_b, b_stride, d_c, c_stride, d_out) -> None:
+        """zkp_sc_muladd_dev: strides 0 or 1 in elements, d_c = None: + 0"""
+        _check(self._lib.zkp_sc_muladd_dev(self._h, n, d_a, a_stride, d_b, b_stride, d_c, c_stride, d_out), "zkp_sc_muladd_dev")
+
+    def scalar_random_dev(self, n, key: bytes, nonce, d_out) -> None:
+        """zkp_sc_random_dev: key = 32 host bytes; d_out [n][32]"""
+        k = np.frombuffer(bytes(key), np.uint8).copy()
+        if k.size != 32:
+            raise ValueError("key must be 32 bytes")
+        _check(self._lib.zkp_sc_random_dev(self._h, n, _ptr(k), nonce, d_out), "zkp_sc_random_dev")
+
+    def scalar_hash_from_bytes_sha512_dev(self, n, d_msgs, msgs_len, d_offsets, d_out) -> None:
+        """zkp_sc_hash_from_bytes_sha512_dev: arguments as hash_from_bytes_sha512_dev -> d_out [n][32] scalars"""
+        _check(self._lib.zkp_sc_hash_from_bytes_sha512_dev(self._h, n, d_msgs, msgs_len, d_offsets, d_out), "zkp_sc_hash_from_bytes_sha512_dev")
 
     # ---- fused statement flows on device-resident buffers (include/zkp_mi355x.h section 2c) -------------
     def fused_prove_dev(self, fst: "FusedStatement", n, strobe_pos, d_ts, d_secrets, d_table, d_entropy, d_chal, d_resp, d_coms, d_status) -> None:

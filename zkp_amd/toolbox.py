@@ -487,6 +487,61 @@ def hash_from_bytes_sha512_csr(eng, data, offsets, threads: int = 0) -> np.ndarr
     return out
 
 
+# ---- scalars mod l, batched (include/zkp_toolbox.h): canonical scalars [n][32] out; eng = None is the host backend ------------------------
+def scalar_invert(eng, s, threads: int = 0) -> np.ndarray:
+    """Scalar::invert (reference tests/zkp.rs:35) of every row of s [n][32] (any 32 bytes, read mod l; 0 -> 0)"""
+    from .engine import _u8
+    s = _u8(s, 32)
+    out = np.zeros((len(s), 32), np.uint8)
+    _raise(lib().zkp_scalar_invert_batch(None if eng is None else eng._h, len(s), _p(s), threads, _p(out)), "zkp_scalar_invert_batch")
+    return out
+
+
+def scalar_from_wide(eng, wide, threads: int = 0) -> np.ndarray:
+    """Scalar::from_bytes_mod_order_wide of every row of wide [n][64]"""
+    from .engine import _u8
+    wide = _u8(wide, 64)
+    out = np.zeros((len(wide), 32), np.uint8)
+    _raise(lib().zkp_scalar_from_wide_batch(None if eng is None else eng._h, len(wide), _p(wide), threads, _p(out)), "zkp_scalar_from_wide_batch")
+    return out
+
+
+def scalar_muladd(eng, a, b, c=None, threads: int = 0) -> np.ndarray:
+    """a * b + c mod l row by row (prover.rs:108 for a batch).  An operand of shape (32,) or (1, 32) is one scalar for every row; c = None: + 0."""
+    from .engine import scalar_operands
+    n, (a, sa), (b, sb), (c, sc) = scalar_operands(a, b, c)
+    out = np.zeros((n, 32), np.uint8)
+    _raise(lib().zkp_scalar_muladd_batch(None if eng is None else eng._h, n, _p(a), sa, _p(b), sb, _p(c), sc, threads, _p(out)), "zkp_scalar_muladd_batch")
+    return out
+
+
+def scalar_hash_from_bytes_sha512(eng, messages, threads: int = 0) -> np.ndarray:
+    """Scalar::hash_from_bytes::<Sha512> of every message (a list of byte strings)"""
+    from .engine import messages_csr
+    return scalar_hash_from_bytes_sha512_csr(eng, *messages_csr(messages), threads=threads)
+
+
+def scalar_hash_from_bytes_sha512_csr(eng, data, offsets, threads: int = 0) -> np.ndarray:
+    """the same for a CSR batch held in numpy buffers: message i = data[offsets[i]:offsets[i + 1]]"""
+    from .engine import _csr_args
+    data, offsets = _csr_args(data, offsets)
+    n = len(offsets) - 1
+    out = np.zeros((n, 32), np.uint8)
+    rc = lib().zkp_scalar_hash_from_bytes_sha512_batch(None if eng is None else eng._h, n, _p(data), _p(offsets), threads, _p(out))
+    _raise(rc, "zkp_scalar_hash_from_bytes_sha512_batch")
+    return out
+
+
+def scalar_random(eng, n: int, key: Optional[bytes] = None, nonce: int = 0, threads: int = 0) -> np.ndarray:
+    """n x Scalar::random (tests/sig_and_vrf_example.rs:49): row i = from_bytes_mod_order_wide(ChaCha20 block i of (key, nonce)); key = None
+    takes 32 bytes from the operating system.  With an Engine and n above get_host_max_terms() the stream is drawn on the GPU."""
+    k = None if key is None else np.frombuffer(bytes(key), np.uint8).copy()
+    if k is not None and k.size != 32:
+        raise ValueError("key must be 32 bytes")
+    out = np.zeros((n, 32), np.uint8)
+    _raise(lib().zkp_scalar_random_batch(None if eng is None else eng._h, n, _p(k), nonce, threads, _p(out)), "zkp_scalar_random_batch")
+    return out
+
 
 # ---- pipelines and device groups (include/zkp_toolbox.h, round 4) ------------------------------------------------------
 def pinned_empty(shape, dtype=np.uint8) -> np.ndarray:
