@@ -583,6 +583,14 @@ int zkp_debug_last_schedule(zkp_ctx* ctx, char* buf, size_t cap);
 /* zkp_debug_ragged_blocks: the class grouping the _ragged calls launch: idx [N] = proof indices sorted stably by class, blocks [cap][3] =
  * (class, first, count) per wavefront, classes in order of first appearance.  Returns the number of blocks. */
 int zkp_debug_ragged_blocks(const uint8_t* transcripts, uint32_t N, uint32_t* idx, uint32_t* blocks, uint32_t cap);
+/* zkp_debug_fill_workspace: leaves in the device workspace what earlier calls of any kind may have left there.  Grows the workspace to at least
+ * min_bytes the way every call does (a captured graph goes stale exactly as after a larger call), sets every 32-bit word of ALL of it to `word` on
+ * the context's stream and waits for both of the context's streams.  Plans, tables and options are untouched.  ZKP_ERR_ARG during a capture or
+ * with a job pending.  Results never depend on it: tests/test_gpu_workspace_residue.py runs every layout behind word = 0 (what a fresh allocation
+ * holds), 3 (both bits of the two-bit status words; a small counter) and 0xFFFFFFFF. */
+int zkp_debug_fill_workspace(zkp_ctx* ctx, size_t min_bytes, uint32_t word);
+/* zkp_debug_ws_bytes: the size of the device workspace as it stands (0 before the first call): grow-only, the largest call's need plus an eighth. */
+size_t zkp_debug_ws_bytes(zkp_ctx* ctx);
 enum { ZKP_TESTOPT_DUMMY_LAUNCHES = 1001, ZKP_TESTOPT_GENERIC_CLASSIFIER = 1002, ZKP_TESTOPT_WAVE_CYCLES = 1003, ZKP_TESTOPT_PIP_MERGE = 1004 };
 #endif
 

@@ -2937,6 +2937,25 @@ int zkp_debug_wave_cycles(zkp_ctx* c, uint64_t* out, uint32_t cap) {
   HIP_TRY(hipMemset(c->wave_cycles, 0, sizeof(uint64_t) * zkp_ctx::kWaveCyclesCap));
   return (int)n;
 }
+
+// What an hour of mixed traffic leaves in the workspace, in one call: every 32-bit word of it = `word`.  Grows through ensure_ws like any call
+// (so ws_generation moves the same way); touches no plan, table or option.
+int zkp_debug_fill_workspace(zkp_ctx* c, size_t min_bytes, uint32_t word) {
+  if (!c) return fail(ZKP_ERR_ARG, "ctx is NULL");
+  if (c->capturing) return fail(ZKP_ERR_ARG, "graph capture: zkp_debug_fill_workspace synchronises");
+  if (c->job.kind) return fail(ZKP_ERR_ARG, "a submitted job is pending on this context: zkp_ctx_job_wait first");
+  HIP_TRY(hipSetDevice(c->device));
+  const int rc = ensure_ws(c, min_bytes);
+  if (rc) return rc;
+  if (c->ws_bytes) HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->ws), (int)word, c->ws_bytes / 4, c->stream));
+  if (c->ws_bytes % 4)           // (ensure_ws adds an eighth: the size need not be whole words)
+    HIP_TRY(hipMemsetAsync(static_cast<char*>(c->ws) + (c->ws_bytes & ~(size_t)3), (int)(word & 0xff), c->ws_bytes % 4, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (c->side_stream) HIP_TRY(hipStreamSynchronize(c->side_stream));
+  return ZKP_OK;
+}
+// the bytes of the workspace as it stands (what the largest call so far asked for, plus ensure_ws's eighth)
+size_t zkp_debug_ws_bytes(zkp_ctx* c) { return c ? c->ws_bytes : 0; }
 #endif
 
 int zkp_encode_many(zkp_ctx* c, uint64_t n, const uint8_t* xyzt, uint8_t* out) {

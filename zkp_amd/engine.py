@@ -318,6 +318,17 @@ class Engine:
             _check(n, "zkp_debug_last_schedule")
         return {k: int(v) for k, v in (kv.split("=") for kv in buf.value.decode().split())}
 
+    def debug_fill_workspace(self, min_bytes: int, word: int) -> None:
+        """(test-hook build) grow the device workspace to at least min_bytes as any call would, set every 32-bit word of all of it to `word`
+        and wait for the context's streams: what earlier calls may have left behind, in one call (zkp_debug_fill_workspace)"""
+        self._need_hooks("zkp_debug_fill_workspace")
+        _check(self._lib.zkp_debug_fill_workspace(self._h, min_bytes, word & 0xffffffff), "zkp_debug_fill_workspace")
+
+    def debug_ws_bytes(self) -> int:
+        """(test-hook build) the size of the device workspace as it stands (zkp_debug_ws_bytes)"""
+        self._need_hooks("zkp_debug_ws_bytes")
+        return int(self._lib.zkp_debug_ws_bytes(self._h))
+
     def prepare_fixed_points(self, encodings) -> None:
         """Hint: these points (the statement's common / static points) will be referenced by many terms."""
         encodings = _u8(encodings, 32)
