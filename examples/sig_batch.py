@@ -5,7 +5,8 @@ product calls alone:
     define_proof! {sig_proof, "Sig", (x), (A), (B) : A = (x * B) }
 
 sign = Transcript::new(domain) ; append_message(b"msg", message) ; prove_batchable.  Messages of different lengths leave the transcripts
-at different STROBE positions (a ragged batch): the toolbox runs them on the device with one transcript program per position class.
+at different STROBE positions (a ragged batch): the appends run on the device, one lane per transcript, and the toolbox runs the proofs there with one transcript
+program per position class.
 Every signature is then verified one by one (verify_batchable_each) and as one batch (batch_verify), and the example's reject cases --
 wrong public key, wrong message, wrong domain separator -- fail.
 
@@ -36,18 +37,18 @@ def main():
     A, _ = eng.msm_many(np.arange(n + 1, dtype=np.uint32), x, np.zeros(n, np.uint32), B, ZKP_CT)
 
     # KeyPair::sign: the message goes into the transcript, then prove_batchable
-    ts = T.append_messages(DOMAIN, b"msg", messages)
+    ts = T.append_messages(DOMAIN, b"msg", messages, eng=eng)
     positions = len({bytes(r[200:203]) for r in ts})
     _, resp, coms = T.prove_batch(eng, st, ts, x.reshape(n, 1, 32), np.ascontiguousarray(A[None]), B)
     print("signed %d messages of 8..599 bytes (%d STROBE positions): %d-byte batchable signatures" % (n, positions, 32 + 32 * st.m))
 
     def verify_each(msgs, A_v, domain):
         """Signature::verify for every signature -> verdicts, 0 = accepted"""
-        return T.verify_batchable_each(eng, st, T.append_messages(domain, b"msg", msgs), np.ascontiguousarray(A_v[None]), B, coms, resp)
+        return T.verify_batchable_each(eng, st, T.append_messages(domain, b"msg", msgs, eng=eng), np.ascontiguousarray(A_v[None]), B, coms, resp)
 
     def verify_batch(msgs, A_v, domain):
         try:
-            T.batch_verify(eng, st, T.append_messages(domain, b"msg", msgs), np.ascontiguousarray(A_v[None]), B, coms, resp)
+            T.batch_verify(eng, st, T.append_messages(domain, b"msg", msgs, eng=eng), np.ascontiguousarray(A_v[None]), B, coms, resp)
             return True
         except T.VerificationFailure:
             return False

@@ -22,14 +22,9 @@ BASEPOINT = bytes.fromhex("e2f2ae0a6abc4e71a884a961c500515f58e30b6aa582dd8db6a65
 DOMAIN = b"My VRF Application"
 
 
-def function_transcripts(messages, domain=DOMAIN):
-    """Transcript::new(domain) + append_message_example(message) (sig_and_vrf_example.rs:33-35), one per message"""
-    ts = []
-    for m in messages:
-        t = T.Transcript(domain)
-        t.append_message(b"msg", m)
-        ts.append(t.state)
-    return np.stack(ts)
+def function_transcripts(eng, messages, domain=DOMAIN):
+    """Transcript::new(domain) + append_message_example(message) (sig_and_vrf_example.rs:33-35), one per message, appended on the device"""
+    return T.append_messages(domain, b"msg", messages, eng=eng)
 
 
 def main():
@@ -46,7 +41,7 @@ def main():
     A, _ = eng.msm_many(iota, x, np.zeros(n, np.uint32), B, ZKP_CT)
 
     # VRF evaluation: H = hash_to_group(function transcript), G = x H, proof on Transcript::new(domain)
-    H = T.hash_to_group(eng, function_transcripts(messages))
+    H = T.hash_to_group(eng, function_transcripts(eng, messages))
     G, _ = eng.msm_many(iota, x, np.arange(n, dtype=np.uint32), H, ZKP_CT)
     proof_ts = np.stack([T.Transcript(DOMAIN).state] * n)
     chal, resp, _ = T.prove_batch(eng, st, proof_ts, x.reshape(n, 1, 32), np.ascontiguousarray(np.stack([A, G, H])), B)
@@ -54,7 +49,7 @@ def main():
 
     def verify(msgs, A_v, G_v, domain):
         """VrfOutput::verify (sig_and_vrf_example.rs): the verifier hashes the message itself -> verdicts, 0 = accepted"""
-        H_v = T.hash_to_group(eng, function_transcripts(msgs))
+        H_v = T.hash_to_group(eng, function_transcripts(eng, msgs))
         ts = np.stack([T.Transcript(domain).state] * n)
         return T.verify_compact_batch(eng, st, ts, np.ascontiguousarray(np.stack([A_v, G_v, H_v])), B, chal, resp)
 

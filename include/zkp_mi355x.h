@@ -523,6 +523,42 @@ int zkp_sc_hash_from_bytes_sha512(zkp_ctx* ctx, uint64_t n, const uint8_t* msgs,
 int zkp_sc_hash_from_bytes_sha512_dev(zkp_ctx* ctx, uint64_t n, const uint8_t* d_msgs, uint64_t msgs_len, const uint64_t* d_offsets /*[n+1]*/,
                                       uint8_t* d_out /*[n][32]*/);
 
+/* (7) Merlin operations on N transcripts, batched: what every flow starts from (the reference's KeyPair::sign, Signature::verify and
+ *     KeyPair::vrf are `append_message(b"msg", message)` followed by a proof call, tests/sig_and_vrf_example.rs:86-160).  One lane runs one
+ *     transcript through STROBE-128 (zkp_amd/csrc/strobe_lane.h); the transcripts may stand at any mix of positions and the messages may
+ *     have any mix of lengths, so a batch runs at the pace of its longest message.  Branches and addresses depend on positions, the
+ *     label's length and the messages' lengths, never on message or state bytes.  Timed under ZKP_K_TRANSCRIPT.
+ *     Common rules: N = 0 is a no-op; a NULL buffer with N > 0, a NULL label, a label of more than 248 bytes or N > 2^31 - 1 is
+ *     ZKP_ERR_ARG, and a failed check changes nothing.  Transcripts are 208-byte blobs (ZKP_TRANSCRIPT_BYTES of zkp_toolbox.h).
+ *     zkp_transcripts_append_message: N x Transcript::append_message(label, message j) over a CSR batch, message j = msgs[offsets[j],
+ *       offsets[j + 1]) at any byte offset; msgs may be NULL when every message is empty.  shared_initial != 0: ts[0] is the one blob
+ *       every transcript starts from (Transcript::new(label) per proof) and all N blobs are written; shared_initial == 0: blob j is
+ *       advanced in place.  Host pointers: offsets must not decrease, every length must fit 32 bits (merlin asserts that) and every
+ *       position byte must be below 166, ZKP_ERR_ARG otherwise; uploads msgs[offsets[0], offsets[N]) with rebased offsets, synchronises.
+ *     zkp_transcripts_append_message_dev: device pointers (blobs 16-byte aligned, d_offsets 8-byte aligned, d_msgs of any alignment and
+ *       NULL when msgs_len = 0); enqueues on the context's stream without synchronising, uses no workspace, and may be recorded between
+ *       zkp_ctx_capture_begin / _end.  d_ts_out may equal d_ts_in when shared_initial == 0; the shared blob must lie outside d_ts_out.
+ *       It does not check d_offsets: every range is clamped to [0, msgs_len) and hi < lo is the empty message, and the clamped length is
+ *       what gets framed: a bad offset gives another transcript, never a read outside d_msgs.  A blob whose position byte is 166 or
+ *       more is corrupt and is copied through unchanged.
+ *     zkp_transcripts_challenge_bytes / _dev: N x Transcript::challenge_bytes(label, out[j], len), the blobs advanced in place; len = 0 is
+ *       allowed (the frame and the PRF's begin still advance the transcript; out may then be NULL).  The host-pointer form rejects a
+ *       position byte of 166 or more; the _dev form (recordable, no workspace, d_out of any alignment) leaves such a blob as it is and
+ *       writes zeros to its output.
+ *     zkp_strobe_pos_after_append: pure arithmetic, no GPU: the position word pos | pos_begin << 8 | cur_flags << 16 of a transcript
+ *       after one append_message with a label of label_len and a message of msg_len bytes, given its position word before.  A resident
+ *       caller whose messages have one length passes d_ts_out straight to zkp_fused_prove_dev / _batch_verify_dev with it, without
+ *       downloading a blob to learn strobe_pos.  (A position byte of 166 or more returns strobe_pos unchanged.) */
+int zkp_transcripts_append_message(zkp_ctx* ctx, uint32_t N, int shared_initial, uint8_t* ts /*[N][208]*/, const char* label,
+                                   const uint8_t* msgs, const uint64_t* offsets /*[N+1]*/);
+int zkp_transcripts_append_message_dev(zkp_ctx* ctx, uint32_t N, int shared_initial, const uint8_t* d_ts_in, uint8_t* d_ts_out,
+                                       const char* label, const uint8_t* d_msgs, uint64_t msgs_len, const uint64_t* d_offsets /*[N+1]*/);
+int zkp_transcripts_challenge_bytes(zkp_ctx* ctx, uint32_t N, uint8_t* ts /*[N][208]*/, const char* label, uint32_t len,
+                                    uint8_t* out /*[N][len]*/);
+int zkp_transcripts_challenge_bytes_dev(zkp_ctx* ctx, uint32_t N, uint8_t* d_ts /*[N][208]*/, const char* label, uint32_t len,
+                                        uint8_t* d_out /*[N][len]*/);
+uint32_t zkp_strobe_pos_after_append(uint32_t strobe_pos, uint64_t label_len, uint64_t msg_len);
+
 /* Timing of the last *_dev / host call on this context, measured with HIP events on the stream the
  * kernels were launched on.  kernel_ms[] is indexed by ZKP_K_*; returns the number of entries. */
 enum {
@@ -540,7 +576,7 @@ enum {
 int zkp_ctx_last_timing(zkp_ctx* ctx, float* kernel_ms /*[ZKP_K_COUNT]*/, float* total_ms);
 /* With profiling on: which VARIANT of a kind's kernel the last call launched, by the name rocprofv3 prints -- the kernels whose template
  * arguments depend on the call's size, flags or options (ZKP_K_TERMS: "k_terms_split<true, 16, true, false>", ZKP_K_TABLES:
- * "zkp::k_comb_tables_lane<16>" / "zkp::k_tables_transcript_pc<16>", ZKP_K_TRANSCRIPT: "zkp::k_transcript_run" / "...run1", ZKP_K_DECODE of the
+ * "zkp::k_comb_tables_lane<16>" / "zkp::k_tables_transcript_pc<16>", ZKP_K_TRANSCRIPT: "zkp::k_transcript_run" / "...run1", "zkp::k_strobe_append_csr" / "zkp::k_strobe_challenge" of section (7), ZKP_K_DECODE of the
  * large-MSM path: "k_pip_prepare<11>"); several names are joined with ';', kinds whose kernels never vary give "".  Writes a NUL-terminated
  * string of at most cap - 1 characters and returns the untruncated length.  Profiles and benchmarks label kernels from THIS, not from a
  * copy of the dispatch thresholds. */

@@ -49,6 +49,19 @@ int zkp_transcript_challenge_bytes(uint8_t t[ZKP_TRANSCRIPT_BYTES], const char* 
  * ZKP_TB_TOO_LONG rule above per message; decreasing offsets or NULL buffers are ZKP_TB_BAD_STATEMENT; nothing changes on an error. */
 int zkp_transcripts_append_message_batch(uint8_t* ts /*[N][208]*/, uint32_t N, int shared_initial, const char* label, const uint8_t* msgs,
                                          const uint64_t* offsets /*[N + 1]*/, int n_threads);
+/* The same with a context, and its counterpart for challenge_bytes (zkp_mi355x.h (7)).  Both route as the other batch calls do: ctx == NULL
+ * or N <= zkp_toolbox_get_host_max_terms() on the host threads (host Merlin), anything else on the device, one lane per transcript
+ * (a label of more than 248 bytes stays on the host; so does an append whose messages hold fewer than 128 bytes per transcript on
+ * average: the device call moves every blob over the bus, and measured, profiles/transcript_ops_bench.txt, it loses to the host threads
+ * on 32-byte messages at every N).  Same bytes on both routes; with ctx == NULL the append gives the bytes of
+ * zkp_transcripts_append_message_batch.  The transcripts may stand at any mix of positions.  Errors as above, and a position byte
+ * (byte 200 of a blob) of 166 or more is ZKP_TB_BAD_STATEMENT: it is no STROBE state.  Nothing changes on an error.
+ *   zkp_transcripts_challenge_bytes_batch: N x challenge_bytes(label, out[j], len), the blobs advanced in place; len = 0 is allowed (the
+ *   frame and the PRF's begin still advance the transcript; out may then be NULL). */
+int zkp_transcripts_append_message_batch_ctx(zkp_ctx* ctx, uint8_t* ts /*[N][208]*/, uint32_t N, int shared_initial, const char* label,
+                                             const uint8_t* msgs, const uint64_t* offsets /*[N + 1]*/, int n_threads);
+int zkp_transcripts_challenge_bytes_batch(zkp_ctx* ctx, uint8_t* ts /*[N][208]*/, uint32_t N, const char* label, uint32_t len, int n_threads,
+                                          uint8_t* out /*[N][len]*/);
 
 /* ---- scalars mod l (curve25519_dalek::scalar::Scalar) -------------------------------------------- */
 void zkp_scalar_from_wide(uint8_t out[32], const uint8_t in[64]);   /* from_bytes_mod_order_wide */

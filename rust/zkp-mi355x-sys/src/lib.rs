@@ -219,6 +219,14 @@ extern "C" {
     pub fn zkp_sc_random_dev(ctx: *mut zkp_ctx, n: u64, key: *const u8, nonce: u64, d_out: *mut u8) -> c_int;
     pub fn zkp_sc_hash_from_bytes_sha512(ctx: *mut zkp_ctx, n: u64, msgs: *const u8, offsets: *const u64, out: *mut u8) -> c_int;
     pub fn zkp_sc_hash_from_bytes_sha512_dev(ctx: *mut zkp_ctx, n: u64, d_msgs: *const u8, msgs_len: u64, d_offsets: *const u64, d_out: *mut u8) -> c_int;
+    // (7) Merlin operations on N transcripts at any mix of positions
+    pub fn zkp_transcripts_append_message(ctx: *mut zkp_ctx, n: u32, shared_initial: c_int, ts: *mut u8, label: *const c_char, msgs: *const u8,
+                                          offsets: *const u64) -> c_int;
+    pub fn zkp_transcripts_append_message_dev(ctx: *mut zkp_ctx, n: u32, shared_initial: c_int, d_ts_in: *const u8, d_ts_out: *mut u8, label: *const c_char,
+                                              d_msgs: *const u8, msgs_len: u64, d_offsets: *const u64) -> c_int;
+    pub fn zkp_transcripts_challenge_bytes(ctx: *mut zkp_ctx, n: u32, ts: *mut u8, label: *const c_char, len: u32, out: *mut u8) -> c_int;
+    pub fn zkp_transcripts_challenge_bytes_dev(ctx: *mut zkp_ctx, n: u32, d_ts: *mut u8, label: *const c_char, len: u32, d_out: *mut u8) -> c_int;
+    pub fn zkp_strobe_pos_after_append(strobe_pos: u32, label_len: u64, msg_len: u64) -> u32;
     pub fn zkp_ctx_last_timing(ctx: *mut zkp_ctx, kernel_ms: *mut f32, total_ms: *mut f32) -> c_int;
     pub fn zkp_ctx_last_kernels(ctx: *mut zkp_ctx, kind: c_int, buf: *mut c_char, cap: usize) -> c_int;
     pub fn zkp_ctx_set_profiling(ctx: *mut zkp_ctx, enabled: c_int) -> c_int;
@@ -229,6 +237,9 @@ extern "C" {
     pub fn zkp_transcript_challenge_bytes(t: *mut u8, label: *const c_char, out: *mut u8, len: usize) -> c_int;
     pub fn zkp_transcripts_append_message_batch(ts: *mut u8, n: u32, shared_initial: c_int, label: *const c_char, msgs: *const u8, offsets: *const u64,
                                                 n_threads: c_int) -> c_int;
+    pub fn zkp_transcripts_append_message_batch_ctx(ctx: *mut zkp_ctx, ts: *mut u8, n: u32, shared_initial: c_int, label: *const c_char, msgs: *const u8,
+                                                    offsets: *const u64, n_threads: c_int) -> c_int;
+    pub fn zkp_transcripts_challenge_bytes_batch(ctx: *mut zkp_ctx, ts: *mut u8, n: u32, label: *const c_char, len: u32, n_threads: c_int, out: *mut u8) -> c_int;
     pub fn zkp_scalar_from_wide(out: *mut u8, input: *const u8);
     pub fn zkp_scalar_muladd(out: *mut u8, a: *const u8, b: *const u8, c: *const u8);
     pub fn zkp_scalar_neg(out: *mut u8, a: *const u8);

@@ -256,12 +256,57 @@ int zkp_transcripts_append_message_batch(uint8_t* ts, uint32_t N, int shared_ini
   });
   return ZKP_TB_OK;
 }
+// (zkp_mi355x.h (7) takes labels of up to 248 bytes as a kernel argument; merlin's labels are short literals, a longer one stays on the host)
+static bool device_label(const char* label) { return std::strlen(label) <= 248; }
+static bool positions_ok(const uint8_t* ts, uint32_t n) {
+  for (uint32_t j = 0; j < n; ++j)
+    if (ts[TB * (size_t)j + 200] >= 166) return false;
+  return true;
+}
+// The same with a context: the checks of the call above plus the position bytes (a position of 166 or more is no STROBE state: host
+// Merlin would index past its state with it), then the host threads for ctx == NULL, N <= host_max_terms or messages of fewer than 128
+// bytes on average, the device otherwise (zkp_transcripts_append_message: one lane per transcript).  Same bytes on both routes.
+int zkp_transcripts_append_message_batch_ctx(zkp_ctx* ctx, uint8_t* ts, uint32_t N, int shared_initial, const char* label, const uint8_t* msgs,
+                                             const uint64_t* offsets, int n_threads) {
+  if (!label) return ZKP_TB_BAD_STATEMENT;
+  if (!fits_u32(std::strlen(label))) return ZKP_TB_TOO_LONG;
+  if (N == 0) return ZKP_TB_OK;
+  if (!ts || !offsets || (offsets[N] > offsets[0] && !msgs)) return ZKP_TB_BAD_STATEMENT;
+  for (uint32_t j = 0; j < N; ++j) {
+    if (offsets[j + 1] < offsets[j]) return ZKP_TB_BAD_STATEMENT;
+    if (!fits_u32(offsets[j + 1] - offsets[j])) return ZKP_TB_TOO_LONG;
+  }
+  if (!positions_ok(ts, shared_initial ? 1 : N)) return ZKP_TB_BAD_STATEMENT;
+  // The device call moves every 208-byte blob over the bus, which is what the host threads pay for a message that fits the block the
+  // transcript stands in; it wins once the permutations dominate (profiles/transcript_ops_bench.txt: 32-byte messages are faster on the
+  // host threads at every measured N, the 0..599-byte mix and 4,096-byte messages on the device): from 128 message bytes per transcript on.
+  const bool short_messages = offsets[N] - offsets[0] < 128 * (uint64_t)N;
+  if (on_host(ctx, N) || short_messages || !device_label(label))
+    return zkp_transcripts_append_message_batch(ts, N, shared_initial, label, msgs, offsets, n_threads);
+  return zkp_transcripts_append_message(ctx, N, shared_initial, ts, label, msgs, offsets);
+}
 int zkp_transcript_challenge_bytes(uint8_t* t, const char* label, uint8_t* out, size_t len) {
   if (!t || !label || (len && !out)) return ZKP_TB_BAD_STATEMENT;
   if (!fits_u32(len) || !fits_u32(std::strlen(label))) return ZKP_TB_TOO_LONG;
   Transcript x = Transcript::from_bytes(t);
   x.challenge_bytes(label, out, len);
   x.to_bytes(t);
+  return ZKP_TB_OK;
+}
+// N x challenge_bytes(label, out[j], len), routed as the append above; the transcripts advance in place
+int zkp_transcripts_challenge_bytes_batch(zkp_ctx* ctx, uint8_t* ts, uint32_t N, const char* label, uint32_t len, int n_threads, uint8_t* out) {
+  if (!label) return ZKP_TB_BAD_STATEMENT;
+  if (!fits_u32(std::strlen(label))) return ZKP_TB_TOO_LONG;
+  if (N == 0) return ZKP_TB_OK;
+  if (!ts || (len && !out) || !positions_ok(ts, N)) return ZKP_TB_BAD_STATEMENT;
+  if (!on_host(ctx, N) && device_label(label)) return zkp_transcripts_challenge_bytes(ctx, N, ts, label, len, out);
+  parallel_for(N, n_threads, [&](uint32_t lo, uint32_t hi) {
+    for (uint32_t j = lo; j < hi; ++j) {
+      Transcript x = Transcript::from_bytes(ts + TB * (size_t)j);
+      x.challenge_bytes(label, out + (size_t)len * j, len);
+      x.to_bytes(ts + TB * (size_t)j);
+    }
+  });
   return ZKP_TB_OK;
 }
 void zkp_scalar_from_wide(uint8_t out[32], const uint8_t in[64]) { Scalar::from_bytes_mod_order_wide(in).to_bytes(out); }

@@ -110,27 +110,20 @@ ZKP_HD uint64_t tr_chi(uint64_t a, uint64_t b, uint64_t c) {
   return (uint64_t)tr_chi32((uint32_t)(a >> 32), (uint32_t)(b >> 32), (uint32_t)(c >> 32)) << 32 | tr_chi32((uint32_t)a, (uint32_t)b, (uint32_t)c);
 }
 
-// The APPLY operation on a strided column (S[i * stride]): the block's constant table, then (permute) Keccak-f[1600]
-// with the 25 lanes held in registers for the 24 rounds.
-ZKP_HD void tr_apply_block(uint64_t* S, int stride, const uint64_t* tbl, bool permute) {
+// `rounds` rounds of Keccak-f[1600] (24 = the permutation, 0 = nothing) on 25 lanes the caller holds in registers, a<x><y> = A[x + 5y].
+ZKP_HD void tr_keccak_rounds(int rounds, uint64_t& a00, uint64_t& a10, uint64_t& a20, uint64_t& a30, uint64_t& a40,
+                             uint64_t& a01, uint64_t& a11, uint64_t& a21, uint64_t& a31, uint64_t& a41,
+                             uint64_t& a02, uint64_t& a12, uint64_t& a22, uint64_t& a32, uint64_t& a42,
+                             uint64_t& a03, uint64_t& a13, uint64_t& a23, uint64_t& a33, uint64_t& a43,
+                             uint64_t& a04, uint64_t& a14, uint64_t& a24, uint64_t& a34, uint64_t& a44) {
   const uint64_t RC[24] = {
       0x0000000000000001ULL, 0x0000000000008082ULL, 0x800000000000808aULL, 0x8000000080008000ULL, 0x000000000000808bULL,
       0x0000000080000001ULL, 0x8000000080008081ULL, 0x8000000000008009ULL, 0x000000000000008aULL, 0x0000000000000088ULL,
       0x0000000080008009ULL, 0x000000008000000aULL, 0x000000008000808bULL, 0x800000000000008bULL, 0x8000000000008089ULL,
       0x8000000000008003ULL, 0x8000000000008002ULL, 0x8000000000000080ULL, 0x000000000000800aULL, 0x800000008000000aULL,
       0x8000000080008081ULL, 0x8000000000008080ULL, 0x0000000080000001ULL, 0x8000000080008008ULL};
-  uint64_t a00 = S[0 * stride], a10 = S[1 * stride], a20 = S[2 * stride], a30 = S[3 * stride], a40 = S[4 * stride];
-  uint64_t a01 = S[5 * stride], a11 = S[6 * stride], a21 = S[7 * stride], a31 = S[8 * stride], a41 = S[9 * stride];
-  uint64_t a02 = S[10 * stride], a12 = S[11 * stride], a22 = S[12 * stride], a32 = S[13 * stride], a42 = S[14 * stride];
-  uint64_t a03 = S[15 * stride], a13 = S[16 * stride], a23 = S[17 * stride], a33 = S[18 * stride], a43 = S[19 * stride];
-  uint64_t a04 = S[20 * stride], a14 = S[21 * stride], a24 = S[22 * stride], a34 = S[23 * stride], a44 = S[24 * stride];
-#define TR_T(v, i) v = (v & tbl[i]) ^ tbl[21 + i]
-  TR_T(a00, 0); TR_T(a10, 1); TR_T(a20, 2); TR_T(a30, 3); TR_T(a40, 4); TR_T(a01, 5); TR_T(a11, 6);
-  TR_T(a21, 7); TR_T(a31, 8); TR_T(a41, 9); TR_T(a02, 10); TR_T(a12, 11); TR_T(a22, 12); TR_T(a32, 13);
-  TR_T(a42, 14); TR_T(a03, 15); TR_T(a13, 16); TR_T(a23, 17); TR_T(a33, 18); TR_T(a43, 19); TR_T(a04, 20);
-#undef TR_T
 #pragma unroll 1
-  for (int round = 0; round < (permute ? 24 : 0); ++round) {
+  for (int round = 0; round < rounds; ++round) {
     const uint64_t c0 = tr_xor5(a00, a01, a02, a03, a04), c1 = tr_xor5(a10, a11, a12, a13, a14), c2 = tr_xor5(a20, a21, a22, a23, a24),
                    c3 = tr_xor5(a30, a31, a32, a33, a34), c4 = tr_xor5(a40, a41, a42, a43, a44);
     const uint64_t d0 = c4 ^ tr_rotl(c1, 1), d1 = c0 ^ tr_rotl(c2, 1), d2 = c1 ^ tr_rotl(c3, 1), d3 = c2 ^ tr_rotl(c4, 1),
@@ -152,6 +145,37 @@ ZKP_HD void tr_apply_block(uint64_t* S, int stride, const uint64_t* tbl, bool pe
     a04 = tr_chi(b04, b14, b24); a14 = tr_chi(b14, b24, b34); a24 = tr_chi(b24, b34, b44); a34 = tr_chi(b34, b44, b04); a44 = tr_chi(b44, b04, b14);
     a00 ^= RC[round];
   }
+}
+
+// The APPLY operation on a strided column (S[i * stride]): the block's constant table, then (permute) Keccak-f[1600]
+// with the 25 lanes held in registers for the 24 rounds.
+ZKP_HD void tr_apply_block(uint64_t* S, int stride, const uint64_t* tbl, bool permute) {
+  uint64_t a00 = S[0 * stride], a10 = S[1 * stride], a20 = S[2 * stride], a30 = S[3 * stride], a40 = S[4 * stride];
+  uint64_t a01 = S[5 * stride], a11 = S[6 * stride], a21 = S[7 * stride], a31 = S[8 * stride], a41 = S[9 * stride];
+  uint64_t a02 = S[10 * stride], a12 = S[11 * stride], a22 = S[12 * stride], a32 = S[13 * stride], a42 = S[14 * stride];
+  uint64_t a03 = S[15 * stride], a13 = S[16 * stride], a23 = S[17 * stride], a33 = S[18 * stride], a43 = S[19 * stride];
+  uint64_t a04 = S[20 * stride], a14 = S[21 * stride], a24 = S[22 * stride], a34 = S[23 * stride], a44 = S[24 * stride];
+#define TR_T(v, i) v = (v & tbl[i]) ^ tbl[21 + i]
+  TR_T(a00, 0); TR_T(a10, 1); TR_T(a20, 2); TR_T(a30, 3); TR_T(a40, 4); TR_T(a01, 5); TR_T(a11, 6);
+  TR_T(a21, 7); TR_T(a31, 8); TR_T(a41, 9); TR_T(a02, 10); TR_T(a12, 11); TR_T(a22, 12); TR_T(a32, 13);
+  TR_T(a42, 14); TR_T(a03, 15); TR_T(a13, 16); TR_T(a23, 17); TR_T(a33, 18); TR_T(a43, 19); TR_T(a04, 20);
+#undef TR_T
+  tr_keccak_rounds(permute ? 24 : 0, a00, a10, a20, a30, a40, a01, a11, a21, a31, a41, a02, a12, a22, a32, a42, a03, a13, a23, a33, a43, a04, a14, a24, a34, a44);
+  S[0 * stride] = a00; S[1 * stride] = a10; S[2 * stride] = a20; S[3 * stride] = a30; S[4 * stride] = a40;
+  S[5 * stride] = a01; S[6 * stride] = a11; S[7 * stride] = a21; S[8 * stride] = a31; S[9 * stride] = a41;
+  S[10 * stride] = a02; S[11 * stride] = a12; S[12 * stride] = a22; S[13 * stride] = a32; S[14 * stride] = a42;
+  S[15 * stride] = a03; S[16 * stride] = a13; S[17 * stride] = a23; S[18 * stride] = a33; S[19 * stride] = a43;
+  S[20 * stride] = a04; S[21 * stride] = a14; S[22 * stride] = a24; S[23 * stride] = a34; S[24 * stride] = a44;
+}
+
+// The bare permutation on a strided column: what STROBE's run_f calls (strobe_lane.h).
+ZKP_HD void tr_keccak_f(uint64_t* S, int stride) {
+  uint64_t a00 = S[0 * stride], a10 = S[1 * stride], a20 = S[2 * stride], a30 = S[3 * stride], a40 = S[4 * stride];
+  uint64_t a01 = S[5 * stride], a11 = S[6 * stride], a21 = S[7 * stride], a31 = S[8 * stride], a41 = S[9 * stride];
+  uint64_t a02 = S[10 * stride], a12 = S[11 * stride], a22 = S[12 * stride], a32 = S[13 * stride], a42 = S[14 * stride];
+  uint64_t a03 = S[15 * stride], a13 = S[16 * stride], a23 = S[17 * stride], a33 = S[18 * stride], a43 = S[19 * stride];
+  uint64_t a04 = S[20 * stride], a14 = S[21 * stride], a24 = S[22 * stride], a34 = S[23 * stride], a44 = S[24 * stride];
+  tr_keccak_rounds(24, a00, a10, a20, a30, a40, a01, a11, a21, a31, a41, a02, a12, a22, a32, a42, a03, a13, a23, a33, a43, a04, a14, a24, a34, a44);
   S[0 * stride] = a00; S[1 * stride] = a10; S[2 * stride] = a20; S[3 * stride] = a30; S[4 * stride] = a40;
   S[5 * stride] = a01; S[6 * stride] = a11; S[7 * stride] = a21; S[8 * stride] = a31; S[9 * stride] = a41;
   S[10 * stride] = a02; S[11 * stride] = a12; S[12 * stride] = a22; S[13 * stride] = a32; S[14 * stride] = a42;

@@ -3,6 +3,7 @@
 // and by fused_flows.h.
 #pragma once
 #include "merlin_prog.h"
+#include "strobe_lane.h"
 #include "comb_tables.h"
 
 namespace zkp {
@@ -408,6 +409,66 @@ k_transcript_run1(const tr_op* __restrict__ prog, uint32_t n_ops, const uint64_t
   blob[25] = tail & 0xffffffu;
   if (bad || (tail >> 31)) failed[j] = bad;
   if ((tail >> 31) && j_raw == 0) failed[N] = 0;
+}
+
+// ---- Merlin operations on transcripts at ANY mix of positions, with no program: strobe_lane.h, one lane per transcript ------------------
+// The state is an LDS column per lane (25 words x 8 bytes x 64 lanes = 12.5 KB per workgroup of one wavefront, plus the label's 256 bytes),
+// because the position is a run-time value: it indexes LDS, never a register array, so the kernels use no scratch.  Grid-stride over the
+// transcripts.  strobe_merlin_op keeps the permutation at one place of its loop: a wavefront runs at the pace of its longest lane, as
+// k_sha512_csr does.  Branches and addresses depend on positions, the label's length and the messages' lengths only.
+constexpr int STROBE_BLOCK = 64;
+
+// the label's words from the kernel argument into LDS (constant indices on the argument: it stays in scalar registers)
+__device__ __forceinline__ void strobe_label_to_lds(uint64_t* lab, const strobe_label& label) {
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int i = 0; i < (int)STROBE_LABEL_WORDS; ++i) lab[i] = label.w[i];
+  }
+  __syncthreads();
+}
+
+// N x Transcript::append_message(label, message j) over a CSR batch: message j = msgs[offsets[j], offsets[j + 1]) clamped to
+// [0, msgs_len) (sha512_clamp: whatever the offsets hold, no read leaves the buffer; hi < lo is the empty message), framed with the
+// clamped length.  Transcript j starts from blob j of ts_in, or from blob 0 when shared_initial, and goes to blob j of ts_out; ts_out may
+// be ts_in when not shared.  A blob whose position byte is >= 166 is copied through unchanged.  Blobs 16-byte aligned.
+__global__ void __launch_bounds__(STROBE_BLOCK)
+k_strobe_append_csr(uint32_t N, uint32_t shared_initial, const uint8_t* ts_in, uint8_t* ts_out, const strobe_label label,
+                    const uint8_t* __restrict__ msgs, uint64_t msgs_len, const uint64_t* __restrict__ offsets) {
+  __shared__ uint64_t S[25 * STROBE_BLOCK];
+  __shared__ uint64_t lab[STROBE_LABEL_WORDS];
+  strobe_label_to_lds(lab, label);
+  for (uint32_t j = blockIdx.x * STROBE_BLOCK + threadIdx.x; j < N; j += gridDim.x * STROBE_BLOCK) {
+    strobe_lane L{S + threadIdx.x, STROBE_BLOCK, 0, 0, 0};
+    uint64_t tail = strobe_load(L, reinterpret_cast<const uint64_t*>(ts_in + 208 * (size_t)(shared_initial ? 0u : j)));
+    if (strobe_valid(L)) {
+      uint64_t lo = offsets[j];
+      const uint64_t len = sha512_clamp(lo, offsets[j + 1], msgs_len);
+      strobe_append_message(L, lab, label.len, strobe_msg{msgs + lo, len}, len);
+      tail = strobe_tail(L);
+    }
+    strobe_store(L, reinterpret_cast<uint64_t*>(ts_out + 208 * (size_t)j), tail);
+  }
+}
+
+// N x Transcript::challenge_bytes(label, out[j], len), the transcripts advanced in place.  A blob whose position byte is >= 166 stays
+// as it is and its output is zeros.  Blobs 16-byte aligned, out [N][len] of any alignment.
+__global__ void __launch_bounds__(STROBE_BLOCK)
+k_strobe_challenge(uint32_t N, uint8_t* __restrict__ ts, const strobe_label label, uint32_t len, uint8_t* __restrict__ out) {
+  __shared__ uint64_t S[25 * STROBE_BLOCK];
+  __shared__ uint64_t lab[STROBE_LABEL_WORDS];
+  strobe_label_to_lds(lab, label);
+  for (uint32_t j = blockIdx.x * STROBE_BLOCK + threadIdx.x; j < N; j += gridDim.x * STROBE_BLOCK) {
+    strobe_lane L{S + threadIdx.x, STROBE_BLOCK, 0, 0, 0};
+    uint64_t* blob = reinterpret_cast<uint64_t*>(ts + 208 * (size_t)j);
+    uint8_t* o = out + (size_t)len * j;
+    strobe_load(L, blob);
+    if (strobe_valid(L)) {
+      strobe_challenge_bytes(L, lab, label.len, strobe_out{o}, len);
+      strobe_store(L, blob, strobe_tail(L));
+    } else {
+      for (uint32_t i = 0; i < len; ++i) o[i] = 0;
+    }
+  }
 }
 
 }  // namespace zkp

@@ -2188,6 +2188,45 @@ int hash_from_bytes_host(zkp_ctx* c, uint64_t n, const uint8_t* msgs, const uint
   return ZKP_OK;
 }
 
+// ---- batched Merlin operations (zkp_mi355x.h (7)): k_strobe_append_csr / k_strobe_challenge, a wavefront per workgroup, grid-stride from
+// 2,048 workgroups (8 per CU of an MI355X) ----
+inline unsigned strobe_blocks(uint64_t n) {
+  constexpr uint64_t kMaxBlocks = 2048;
+  return (unsigned)std::min<uint64_t>(kMaxBlocks, (n + STROBE_BLOCK - 1) / STROBE_BLOCK);
+}
+int launch_strobe_append(zkp_ctx* c, uint32_t N, int shared_initial, const uint8_t* d_ts_in, uint8_t* d_ts_out, const strobe_label& label,
+                         const uint8_t* d_msgs, uint64_t msgs_len, const uint64_t* d_offsets) {
+  hipLaunchKernelGGL(k_strobe_append_csr, dim3(strobe_blocks(N)), dim3(STROBE_BLOCK), 0, c->stream, N, shared_initial ? 1u : 0u, d_ts_in, d_ts_out, label,
+                     d_msgs, msgs_len, d_offsets);
+  prof_note(c, ZKP_K_TRANSCRIPT, "zkp::k_strobe_append_csr");
+  prof_mark(c, ZKP_K_TRANSCRIPT);
+  HIP_TRY(hipGetLastError());
+  return ZKP_OK;
+}
+int launch_strobe_challenge(zkp_ctx* c, uint32_t N, uint8_t* d_ts, const strobe_label& label, uint32_t len, uint8_t* d_out) {
+  hipLaunchKernelGGL(k_strobe_challenge, dim3(strobe_blocks(N)), dim3(STROBE_BLOCK), 0, c->stream, N, d_ts, label, len, d_out);
+  prof_note(c, ZKP_K_TRANSCRIPT, "zkp::k_strobe_challenge");
+  prof_mark(c, ZKP_K_TRANSCRIPT);
+  HIP_TRY(hipGetLastError());
+  return ZKP_OK;
+}
+// what the four calls check first: the context, the label (packed into `label`), then N.  *done = nothing is left to do (N = 0)
+int strobe_call_check(zkp_ctx* c, uint32_t N, const char* label_text, strobe_label& label, bool* done) {
+  *done = false;
+  if (!c) return fail(ZKP_ERR_ARG, "ctx is NULL");
+  if (!label_text) return fail(ZKP_ERR_ARG, "label is NULL");
+  if (!strobe_label_pack(label, label_text, strlen(label_text))) return fail(ZKP_ERR_ARG, "label longer than 248 bytes");
+  if (N > 0x7fffffffu) return fail(ZKP_ERR_ARG, "N too large");
+  *done = N == 0;
+  return ZKP_OK;
+}
+// every position byte of n host blobs below 166
+bool strobe_positions_ok(const uint8_t* ts, uint32_t n) {
+  for (uint32_t j = 0; j < n; ++j)
+    if (ts[208 * (size_t)j + 200] >= STROBE_RATE) return false;
+  return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2864,6 +2903,100 @@ int zkp_sc_hash_from_bytes_sha512_dev(zkp_ctx* c, uint64_t n, const uint8_t* d_m
   HIP_TRY(hipSetDevice(c->device));
   prof_begin(c);
   return launch_sc_hash_sha512(c, n, d_msgs, msgs_len, d_offsets, d_out);
+}
+
+// ---- (7) batched Merlin operations on transcripts at any mix of positions ------------------------------------------------------------
+uint32_t zkp_strobe_pos_after_append(uint32_t strobe_pos, uint64_t label_len, uint64_t msg_len) {
+  return strobe_pos_after_append(strobe_pos, label_len, msg_len);
+}
+
+// No workspace: may be recorded without a warm-up call.  The device offsets are not validated: the kernel clamps every range to [0, msgs_len).
+int zkp_transcripts_append_message_dev(zkp_ctx* c, uint32_t N, int shared_initial, const uint8_t* d_ts_in, uint8_t* d_ts_out, const char* label,
+                                       const uint8_t* d_msgs, uint64_t msgs_len, const uint64_t* d_offsets) {
+  strobe_label lab;
+  bool done;
+  const int rc = strobe_call_check(c, N, label, lab, &done);
+  if (rc || done) return rc;
+  if (!d_ts_in || !d_ts_out || !d_offsets || (!d_msgs && msgs_len)) return fail(ZKP_ERR_ARG, "NULL device pointer");
+  if (!aligned16(d_ts_in) || !aligned16(d_ts_out) || (reinterpret_cast<uintptr_t>(d_offsets) & 7))
+    return fail(ZKP_ERR_ARG, "transcripts must be 16-byte and d_offsets 8-byte aligned");
+  if (shared_initial && d_ts_in + 208 > d_ts_out && d_ts_in < d_ts_out + 208 * (size_t)N)
+    return fail(ZKP_ERR_ARG, "the shared initial transcript must not lie inside d_ts_out");
+  HIP_TRY(hipSetDevice(c->device));
+  prof_begin(c);
+  return launch_strobe_append(c, N, shared_initial, d_ts_in, d_ts_out, lab, d_msgs, msgs_len, d_offsets);
+}
+
+int zkp_transcripts_append_message(zkp_ctx* c, uint32_t N, int shared_initial, uint8_t* ts, const char* label, const uint8_t* msgs,
+                                   const uint64_t* offsets) {
+  strobe_label lab;
+  bool done;
+  int rc = strobe_call_check(c, N, label, lab, &done);
+  if (rc || done) return rc;
+  if (!ts || !offsets || (offsets[N] > offsets[0] && !msgs)) return fail(ZKP_ERR_ARG, "NULL pointer");
+  for (uint32_t j = 0; j < N; ++j) {
+    if (offsets[j + 1] < offsets[j]) return fail(ZKP_ERR_ARG, "offsets must be non-decreasing");
+    if (offsets[j + 1] - offsets[j] > 0xffffffffull) return fail(ZKP_ERR_ARG, "a message is longer than 2^32 - 1 bytes");
+  }
+  if (!strobe_positions_ok(ts, shared_initial ? 1 : N)) return fail(ZKP_ERR_ARG, "a transcript's position byte is 166 or more");
+  const uint64_t base_off = offsets[0], total = offsets[N] - offsets[0];
+  std::vector<uint64_t> rebased((size_t)N + 1);
+  for (uint32_t j = 0; j <= N; ++j) rebased[j] = offsets[j] - base_off;
+  HIP_TRY(hipSetDevice(c->device));
+  carve cv;
+  const size_t o_init = cv.take(shared_initial ? 208 : 0);
+  const size_t o_ts = cv.take(208 * (size_t)N);
+  const size_t o_msgs = cv.take((size_t)total);
+  const size_t o_off = cv.take(((size_t)N + 1) * 8);
+  rc = ensure_ws(c, cv.off);
+  if (rc) return rc;
+  uint8_t* base = static_cast<uint8_t*>(c->ws);
+  HIP_TRY(hipMemcpyAsync(base + (shared_initial ? o_init : o_ts), ts, shared_initial ? 208 : 208 * (size_t)N, hipMemcpyHostToDevice, c->stream));
+  if (total) HIP_TRY(hipMemcpyAsync(base + o_msgs, msgs + base_off, (size_t)total, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(base + o_off, rebased.data(), ((size_t)N + 1) * 8, hipMemcpyHostToDevice, c->stream));
+  prof_begin(c);
+  rc = launch_strobe_append(c, N, shared_initial, base + (shared_initial ? o_init : o_ts), base + o_ts, lab, base + o_msgs, total,
+                            reinterpret_cast<const uint64_t*>(base + o_off));
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(ts, base + o_ts, 208 * (size_t)N, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return ZKP_OK;
+}
+
+int zkp_transcripts_challenge_bytes_dev(zkp_ctx* c, uint32_t N, uint8_t* d_ts, const char* label, uint32_t len, uint8_t* d_out) {
+  strobe_label lab;
+  bool done;
+  const int rc = strobe_call_check(c, N, label, lab, &done);
+  if (rc || done) return rc;
+  if (!d_ts || (len && !d_out)) return fail(ZKP_ERR_ARG, "NULL device pointer");
+  if (!aligned16(d_ts)) return fail(ZKP_ERR_ARG, "transcripts must be 16-byte aligned");
+  HIP_TRY(hipSetDevice(c->device));
+  prof_begin(c);
+  return launch_strobe_challenge(c, N, d_ts, lab, len, d_out);
+}
+
+int zkp_transcripts_challenge_bytes(zkp_ctx* c, uint32_t N, uint8_t* ts, const char* label, uint32_t len, uint8_t* out) {
+  strobe_label lab;
+  bool done;
+  int rc = strobe_call_check(c, N, label, lab, &done);
+  if (rc || done) return rc;
+  if (!ts || (len && !out)) return fail(ZKP_ERR_ARG, "NULL pointer");
+  if (!strobe_positions_ok(ts, N)) return fail(ZKP_ERR_ARG, "a transcript's position byte is 166 or more");
+  HIP_TRY(hipSetDevice(c->device));
+  carve cv;
+  const size_t o_ts = cv.take(208 * (size_t)N);
+  const size_t o_out = cv.take((size_t)N * len);
+  rc = ensure_ws(c, cv.off);
+  if (rc) return rc;
+  uint8_t* base = static_cast<uint8_t*>(c->ws);
+  HIP_TRY(hipMemcpyAsync(base + o_ts, ts, 208 * (size_t)N, hipMemcpyHostToDevice, c->stream));
+  prof_begin(c);
+  rc = launch_strobe_challenge(c, N, base + o_ts, lab, len, base + o_out);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(ts, base + o_ts, 208 * (size_t)N, hipMemcpyDeviceToHost, c->stream));
+  if (len) HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)N * len, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return ZKP_OK;
 }
 
 #ifdef ZKP_BUILD_TEST_HOOKS

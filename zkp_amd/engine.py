@@ -116,6 +116,19 @@ def _csr_args(data, offsets) -> Tuple[np.ndarray, np.ndarray]:
     return data, offsets
 
 
+def _blobs(transcripts, n: int) -> np.ndarray:
+    ts = transcripts
+    if not (isinstance(ts, np.ndarray) and ts.dtype == np.uint8 and ts.shape == (n, 208) and ts.flags["C_CONTIGUOUS"]):
+        raise ValueError("transcripts must be a C-contiguous uint8 array of shape [N][208] (they advance in place)")
+    return ts
+
+
+def strobe_pos_after_append(strobe_pos: int, label_len: int, msg_len: int) -> int:
+    """zkp_strobe_pos_after_append (no GPU): the position word pos | pos_begin << 8 | cur_flags << 16 of a transcript after one
+    append_message with a label of label_len and a message of msg_len bytes, from its position word before"""
+    return int(load_library().zkp_strobe_pos_after_append(strobe_pos, label_len, msg_len))
+
+
 def scalar_operands(a, b, c=None):
     """The operands of a * b + c as (n, (a, stride), (b, stride), (c, stride)): uint8 [n][32] has stride 1, shape (32,) or (1, 32) is one
     scalar for every row (stride 0); all three shared gives n = 1; c = None stays None."""
@@ -228,6 +241,26 @@ class Engine:
         n = len(offsets) - 1
         out = np.zeros((n, 32), np.uint8)
         _check(self._lib.zkp_hash_from_bytes_sha512(self._h, n, _ptr(data), _ptr(offsets), _ptr(out)), "zkp_hash_from_bytes_sha512")
+        return out
+
+    # ---- Merlin operations on transcripts, batched (include/zkp_mi355x.h section 7) ----
+    strobe_pos_after_append = staticmethod(strobe_pos_after_append)
+
+    def transcripts_append_message(self, transcripts, label: bytes, data, offsets, shared_initial: bool = False) -> np.ndarray:
+        """N x append_message(label, data[offsets[j]:offsets[j + 1]]) on the GPU.  transcripts: C-contiguous uint8 [N][208], advanced in
+        place (shared_initial: row 0 is what every transcript starts from, all N rows are written).  Returns transcripts."""
+        data, offsets = _csr_args(data, offsets)
+        n = len(offsets) - 1
+        ts = _blobs(transcripts, n)
+        _check(self._lib.zkp_transcripts_append_message(self._h, n, int(bool(shared_initial)), _ptr(ts), bytes(label), _ptr(data), _ptr(offsets)),
+               "zkp_transcripts_append_message")
+        return ts
+
+    def transcripts_challenge_bytes(self, transcripts, label: bytes, n_bytes: int) -> np.ndarray:
+        """N x challenge_bytes(label, n_bytes) on the GPU -> uint8 [N][n_bytes]; transcripts (C-contiguous uint8 [N][208]) advance in place"""
+        ts = _blobs(transcripts, len(transcripts))
+        out = np.zeros((len(ts), n_bytes), np.uint8)
+        _check(self._lib.zkp_transcripts_challenge_bytes(self._h, len(ts), _ptr(ts), bytes(label), n_bytes, _ptr(out)), "zkp_transcripts_challenge_bytes")
         return out
 
     # ---- scalars mod l, batched (include/zkp_mi355x.h section 6): [n][32] canonical scalars out ----
@@ -379,6 +412,16 @@ class Engine:
     def scalar_hash_from_bytes_sha512_dev(self, n, d_msgs, msgs_len, d_offsets, d_out) -> None:
         """zkp_sc_hash_from_bytes_sha512_dev: arguments as hash_from_bytes_sha512_dev -> d_out [n][32] scalars"""
         _check(self._lib.zkp_sc_hash_from_bytes_sha512_dev(self._h, n, d_msgs, msgs_len, d_offsets, d_out), "zkp_sc_hash_from_bytes_sha512_dev")
+
+    def transcripts_append_message_dev(self, n, shared_initial, d_ts_in, d_ts_out, label: bytes, d_msgs, msgs_len, d_offsets) -> None:
+        """zkp_transcripts_append_message_dev: blobs 16-byte aligned (d_ts_out may be d_ts_in when not shared), d_offsets u64 [n + 1] 8-byte
+        aligned, d_msgs of any alignment; every range is clamped to [0, msgs_len); queued on the context's stream"""
+        _check(self._lib.zkp_transcripts_append_message_dev(self._h, n, int(bool(shared_initial)), d_ts_in, d_ts_out, bytes(label), d_msgs, msgs_len, d_offsets),
+               "zkp_transcripts_append_message_dev")
+
+    def transcripts_challenge_bytes_dev(self, n, d_ts, label: bytes, n_bytes, d_out) -> None:
+        """zkp_transcripts_challenge_bytes_dev: d_ts [n][208] (16-byte aligned) advanced in place, d_out [n][n_bytes]"""
+        _check(self._lib.zkp_transcripts_challenge_bytes_dev(self._h, n, d_ts, bytes(label), n_bytes, d_out), "zkp_transcripts_challenge_bytes_dev")
 
     # ---- fused statement flows on device-resident buffers (include/zkp_mi355x.h section 2c) -------------
     def fused_prove_dev(self, fst: "FusedStatement", n, strobe_pos, d_ts, d_secrets, d_table, d_entropy, d_chal, d_resp, d_coms, d_status) -> None:

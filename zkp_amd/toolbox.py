@@ -440,14 +440,16 @@ def hash_to_group(eng, transcripts, label: bytes = b"output", threads: int = 0) 
     return out
 
 
-def append_messages(ts_or_label, label: bytes, messages, threads: int = 0) -> np.ndarray:
-    """merlin append_message(label, messages[j]) for every transcript j on the host threads.  ts_or_label: a [N][208] uint8 array (C-contiguous,
-    advanced in place) or a bytes label (N fresh Transcript(label) states).  Returns the [N][208] states."""
+def append_messages(ts_or_label, label: bytes, messages, threads: int = 0, eng=None) -> np.ndarray:
+    """merlin append_message(label, messages[j]) for every transcript j.  ts_or_label: a [N][208] uint8 array (C-contiguous, advanced in
+    place) or a bytes label (N fresh Transcript(label) states).  Returns the [N][208] states.  eng = None (or a HostEngine) appends on the
+    host threads; with an Engine, batches above get_host_max_terms() transcripts whose messages average 128 bytes or more append on the GPU,
+    one lane per transcript.  Same bytes either way."""
     from .engine import messages_csr
-    return append_messages_csr(ts_or_label, label, *messages_csr(messages), threads=threads)
+    return append_messages_csr(ts_or_label, label, *messages_csr(messages), threads=threads, eng=eng)
 
 
-def append_messages_csr(ts_or_label, label: bytes, data, offsets, threads: int = 0) -> np.ndarray:
+def append_messages_csr(ts_or_label, label: bytes, data, offsets, threads: int = 0, eng=None) -> np.ndarray:
     """append_messages over a CSR batch: message j = data[offsets[j]:offsets[j + 1]] (offsets: N + 1 entries, non-decreasing, uint64)"""
     from .engine import _csr_args
     data, offsets = _csr_args(data, offsets)
@@ -461,10 +463,29 @@ def append_messages_csr(ts_or_label, label: bytes, data, offsets, threads: int =
         ts = ts_or_label
         if not (isinstance(ts, np.ndarray) and ts.dtype == np.uint8 and ts.shape == (n, TRANSCRIPT_BYTES) and ts.flags["C_CONTIGUOUS"]):
             raise ValueError("transcripts must be a C-contiguous uint8 array of shape [N][%d] with N = len(offsets) - 1" % TRANSCRIPT_BYTES)
-    rc = lib().zkp_transcripts_append_message_batch(_p(ts), n, int(shared), bytes(label), _p(data), _p(offsets), threads)
+    h = None if eng is None else eng._h
+    if h is None:
+        rc, what = lib().zkp_transcripts_append_message_batch(_p(ts), n, int(shared), bytes(label), _p(data), _p(offsets), threads), "zkp_transcripts_append_message_batch"
+    else:
+        rc, what = lib().zkp_transcripts_append_message_batch_ctx(h, _p(ts), n, int(shared), bytes(label), _p(data), _p(offsets), threads), "zkp_transcripts_append_message_batch_ctx"
     if rc != 0:
-        raise ValueError("zkp_transcripts_append_message_batch: code %d (messages and labels are limited to 2^32 - 1 bytes, as in merlin)" % rc)
+        raise ValueError("%s: code %d (messages and labels are limited to 2^32 - 1 bytes, as in merlin)" % (what, rc))
     return ts
+
+
+def challenge_bytes(eng, transcripts, label: bytes, n: int, threads: int = 0) -> np.ndarray:
+    """merlin challenge_bytes(label, n bytes) of every transcript -> [N][n] uint8; transcripts: a C-contiguous [N][208] uint8 array, advanced
+    in place.  Routed as append_messages: eng = None (or a HostEngine) on the host threads, otherwise batches above get_host_max_terms()
+    transcripts on the GPU."""
+    ts = transcripts
+    if not (isinstance(ts, np.ndarray) and ts.dtype == np.uint8 and ts.ndim == 2 and ts.shape[1] == TRANSCRIPT_BYTES and ts.flags["C_CONTIGUOUS"]):
+        raise ValueError("transcripts must be a C-contiguous uint8 array of shape [N][%d]" % TRANSCRIPT_BYTES)
+    if not 0 <= n <= 0xffffffff:
+        raise ValueError("challenge_bytes: outputs are limited to 2^32 - 1 bytes, as in merlin")
+    out = np.zeros((len(ts), n), np.uint8)
+    rc = lib().zkp_transcripts_challenge_bytes_batch(None if eng is None else eng._h, _p(ts), len(ts), bytes(label), n, threads, _p(out))
+    _raise(rc, "zkp_transcripts_challenge_bytes_batch")
+    return out
 
 
 def hash_from_bytes_sha512(eng, messages, threads: int = 0) -> np.ndarray:
