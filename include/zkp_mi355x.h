@@ -598,6 +598,9 @@ int zkp_ctx_set_profiling(zkp_ctx* ctx, int enabled);
  *   k_stmt_classify;
  *   ZKP_TESTOPT_PIP_MERGE picks the form of the Pippenger bucket merge whatever the call's size: 1 = a quad of lanes per bucket, 2 = one lane per
  *   bucket, 0 = by the call's bucket count again (same bytes either way);
+ *   ZKP_TESTOPT_VOUCH_REDUCED = 1: constant-time zkp_msm_many calls vouch that every scalar is reduced mod l, as the fused prove flows do for
+ *   their blindings: the term kernel skips the carry window and walks sign-folded scalars (same bytes for reduced scalars; anything else is the
+ *   caller's error);
  *   ZKP_TESTOPT_WAVE_CYCLES = 1 switches on a per-wavefront cycle recorder in the term kernel (s_memtime at entry and exit);
  * zkp_debug_wave_cycles copies out (and clears) up to cap records, [block][wavefront 0..3] = block class << 56 | cycles (class 1 =
  *   ladder, 2 = comb scan, 3 = grouped comb walk, 4 = fixed-base; 0 = no record): the timing side of the constant-time evidence.
@@ -609,7 +612,8 @@ int zkp_ctx_set_profiling(zkp_ctx* ctx, int enabled);
  *   classified term path against one k_terms_r4 lane per term), ragged_classes, ragged_compiled, ragged_base and fused_plans (the _ragged calls:
  *   position classes, class programs compiled by this call, 1 if it built its position-free base plan, the size of the aligned plan cache), pip_merge
  *   (the bucket merge: 0 = a quad per bucket, 1 = a lane per bucket), pip_buckets (batches x windows x buckets per window, what pip_merge goes by) and
- *   no_carry (1 = the term kernel skipped the carry window: the fused prove flows, whose scalars are reduced mod l).  Writes a
+ *   no_carry (1 = the term kernel skipped the carry window: the fused prove flows, whose scalars are reduced mod l) and sign_fold (1 = its
+ *   fixed-base blocks walked min(s, l - s) in 36 windows and negated the result where l - s was walked).  Writes a
  *   NUL-terminated string of at most cap - 1 characters and returns the untruncated length. */
 int zkp_debug_quad_selftest(zkp_ctx* ctx, uint32_t n, const uint8_t* pairs /*[n][64]*/, uint8_t* out /*[n][128]*/);
 int zkp_debug_row_selftest(zkp_ctx* ctx, uint32_t n, const uint8_t* pairs /*[n][64]*/, uint8_t* out /*[n][96]*/);
@@ -627,7 +631,7 @@ int zkp_debug_ragged_blocks(const uint8_t* transcripts, uint32_t N, uint32_t* id
 int zkp_debug_fill_workspace(zkp_ctx* ctx, size_t min_bytes, uint32_t word);
 /* zkp_debug_ws_bytes: the size of the device workspace as it stands (0 before the first call): grow-only, the largest call's need plus an eighth. */
 size_t zkp_debug_ws_bytes(zkp_ctx* ctx);
-enum { ZKP_TESTOPT_DUMMY_LAUNCHES = 1001, ZKP_TESTOPT_GENERIC_CLASSIFIER = 1002, ZKP_TESTOPT_WAVE_CYCLES = 1003, ZKP_TESTOPT_PIP_MERGE = 1004 };
+enum { ZKP_TESTOPT_DUMMY_LAUNCHES = 1001, ZKP_TESTOPT_GENERIC_CLASSIFIER = 1002, ZKP_TESTOPT_WAVE_CYCLES = 1003, ZKP_TESTOPT_PIP_MERGE = 1004, ZKP_TESTOPT_VOUCH_REDUCED = 1005 };
 #endif
 
 #ifdef __cplusplus

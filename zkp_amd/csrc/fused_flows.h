@@ -126,8 +126,7 @@ k_responses(uint32_t N, uint32_t m, uint32_t P, const uint8_t* __restrict__ secr
   for (int i = 0; i < 8; ++i) c.v[i] = cs[tid / m][i];
   load_vec<2>(s.v, secrets + 32 * g);
   load_vec<2>(b.v, blind + 32 * g);
-  sc_mul(r, s, c);                      // s may be any 256-bit value (first operand), c and b are canonical
-  sc_add(r, r, b);
+  sc_muladd(r, s, c, b);                // one product, one reduction (s may be any 256-bit value)
   store_vec<2>(resp + 32 * g, r.v);
 }
 
@@ -141,8 +140,7 @@ k_responses_wide(uint32_t N, uint32_t m, const uint8_t* __restrict__ secrets, co
   load_vec<2>(s.v, secrets + 32 * g);
   load_vec<2>(c.v, chal + 32 * (g / m));
   load_vec<2>(b.v, blind + 32 * g);
-  sc_mul(r, s, c);
-  sc_add(r, r, b);
+  sc_muladd(r, s, c, b);
   store_vec<2>(resp + 32 * g, r.v);
 }
 

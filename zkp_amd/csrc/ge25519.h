@@ -240,6 +240,14 @@ ZKP_HD void ge_neg(ge_p3& r, const ge_p3& p) {
   fe_carry(r.T, t);
 }
 
+// r = flag ? -r : r, flag in {0,1}, both forms computed (the result of a sign-folded walk)
+ZKP_HD void ge_cneg(ge_p3& r, uint32_t flag) {
+  ge_p3 n;
+  ge_neg(n, r);
+  fe_cmov(r.X, n.X, flag);
+  fe_cmov(r.T, n.T, flag);
+}
+
 // conditional negation of cached / niels forms: swap (Y+X, Y-X), negate the T term.  flag in {0,1}.
 // The negated term is NOT carried (round 5): 2p - x has limbs <= 2^30, and the one place it goes is the product with the accumulator's tight T
 // (c = T * T2d / T * xy2d), whose columns stay below 2^64 with a 2p-class operand -- the interval tracker checks exactly these compositions

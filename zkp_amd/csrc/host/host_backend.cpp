@@ -221,20 +221,13 @@ void sc_from_wide_n(uint64_t n, const uint8_t* in, uint8_t* out) {
 }
 
 void sc_muladd_n(uint64_t n, const uint8_t* a, uint32_t sa, const uint8_t* b, uint32_t sb, const uint8_t* c, uint32_t sc_, uint8_t* out) {
-  sc r1;
-  for (int k = 0; k < 8; ++k) r1.v[k] = sc_r1(k);
   for (uint64_t i = 0; i < n; ++i) {
-    sc x, y, r;
+    sc x, y, z, r;
     sc_load(x, a + 32 * i * sa);
     sc_load(y, b + 32 * i * sb);
-    sc_to_mont(y, y);
-    sc_mont(r, x, y);
-    if (c) {
-      sc z;
-      sc_load(z, c + 32 * i * sc_);
-      sc_mont(z, z, r1);
-      sc_add(r, r, z);
-    }
+    sc_zero(z);
+    if (c) sc_load(z, c + 32 * i * sc_);
+    sc_muladd(r, x, y, z);
     sc_store(out + 32 * i, r);
   }
 }

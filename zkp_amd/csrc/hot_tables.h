@@ -44,36 +44,48 @@ constexpr int HOT_COPIES = 16;
 static_assert(HOT_W >= 6 && HOT_W <= 7 && HOT_W * HOT_WINDOWS >= 258, "fixed-base window shape");
 constexpr bool HOT_LDS_ROWS = HOT_ROW_CHUNKS <= 256;             // the replicated-LDS-row walk (fixed_base_block) stages one chunk per lane: W = 6 only
 
-// word i of the recoding constant sum_w 2^(W w + W - 1)
-constexpr uint32_t hot_pattern_word(int i) {
+// Sign-folded walk (constant-time calls whose caller vouches that every scalar is reduced mod l: k_terms_split's no_carry).  The walk takes
+// the smaller of s and l - s (sc_fold_sign: at most (l - 1) / 2 = 2^251 + (delta - 1) / 2 with delta = l - 2^252 < 2^125) and negates the result
+// when it was l - s.  HOT_FOLD_WINDOWS = 252 / W windows then cover the scalar: the last of them is read as it stands, without the offset, and is
+// at most 2^251 / 2^(W (HOT_FOLD_WINDOWS - 1)) = HOT_HALF -- when a scalar reaches 2^251 every bit between 124 and 250 is zero, so the offsets of
+// the windows below cannot carry into it, and below 2^251 the sum stays below 2^251 + 2^(252 - W).  Digit HOT_HALF has a table entry.
+constexpr int HOT_FOLD_WINDOWS = 252 / HOT_W;                    // 42, 36
+static_assert(HOT_FOLD_WINDOWS * HOT_W == 252 && HOT_FOLD_WINDOWS < HOT_WINDOWS, "the folded walk ends at bit 252");
+
+// word i of the recoding constant sum_w 2^(W w + W - 1) over the first n windows
+constexpr uint32_t hot_pattern_word(int i, int n = HOT_WINDOWS) {
   uint32_t v = 0;
-  for (int w = 0; w < HOT_WINDOWS; ++w) {
+  for (int w = 0; w < n; ++w) {
     const int bit = HOT_W * w + HOT_W - 1;
     if (bit / 32 == i) v |= 1u << (bit % 32);
   }
   return v;
 }
-// e = s + pattern over 288 bits
-__device__ __forceinline__ void hot_recode(uint32_t e[9], const uint32_t s[8]) {
+// e = s + pattern over 288 bits.  fold (uniform): s is a folded scalar, the last window of its walk and what lies above carry no offset
+__device__ __forceinline__ void hot_recode(uint32_t e[9], const uint32_t s[8], bool fold = false) {
   constexpr uint32_t P[9] = {hot_pattern_word(0), hot_pattern_word(1), hot_pattern_word(2), hot_pattern_word(3), hot_pattern_word(4),
                              hot_pattern_word(5), hot_pattern_word(6), hot_pattern_word(7), hot_pattern_word(8)};
+  constexpr uint32_t F[9] = {hot_pattern_word(0, HOT_FOLD_WINDOWS - 1), hot_pattern_word(1, HOT_FOLD_WINDOWS - 1), hot_pattern_word(2, HOT_FOLD_WINDOWS - 1),
+                             hot_pattern_word(3, HOT_FOLD_WINDOWS - 1), hot_pattern_word(4, HOT_FOLD_WINDOWS - 1), hot_pattern_word(5, HOT_FOLD_WINDOWS - 1),
+                             hot_pattern_word(6, HOT_FOLD_WINDOWS - 1), hot_pattern_word(7, HOT_FOLD_WINDOWS - 1), hot_pattern_word(8, HOT_FOLD_WINDOWS - 1)};
   uint64_t c = 0;
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
-    c += (uint64_t)s[i] + P[i];
+    c += (uint64_t)s[i] + (fold ? F[i] : P[i]);
     e[i] = (uint32_t)c;
     c >>= 32;
   }
-  e[8] = (uint32_t)c + P[8];
+  e[8] = (uint32_t)c + (fold ? F[8] : P[8]);
 }
-// takes the lowest window off e: magnitude 0 .. HOT_HALF and sign of the digit
-__device__ __forceinline__ void hot_next_digit(uint32_t e[9], uint32_t& mag, uint32_t& neg) {
+// takes the lowest window off e: magnitude 0 .. HOT_HALF and sign of the digit.  raw (uniform): the window is the digit itself (the last window of a
+// folded walk)
+__device__ __forceinline__ void hot_next_digit(uint32_t e[9], uint32_t& mag, uint32_t& neg, bool raw = false) {
   const uint32_t d = e[0] & ((1u << HOT_W) - 1u);
 #pragma unroll
   for (int i = 0; i < 8; ++i) e[i] = __builtin_amdgcn_alignbit(e[i + 1], e[i], HOT_W);
   e[8] >>= HOT_W;
-  neg = (uint32_t)(d < (uint32_t)HOT_HALF);
-  mag = neg ? (uint32_t)HOT_HALF - d : d - (uint32_t)HOT_HALF;
+  neg = raw ? 0u : (uint32_t)(d < (uint32_t)HOT_HALF);
+  mag = raw ? d : neg ? (uint32_t)HOT_HALF - d : d - (uint32_t)HOT_HALF;
 }
 
 // ---- table construction ---------------------------------------------------------------------------------------------
@@ -514,7 +526,8 @@ __device__ __forceinline__ void fixed_base_block(ge_p3& acc, uint32_t e[9], bool
 // (a crossbar source must be an active lane); lanes without a term walk the scalar 0 and store nothing.
 __device__ __forceinline__ uint32_t xbar_fetch(int src_lane_x4, uint32_t v) { return (uint32_t)__builtin_amdgcn_ds_bpermute(src_lane_x4, (int)v); }
 
-__device__ __forceinline__ void fixed_base_xbar(ge_p3& acc, uint32_t e[9], const uint4* __restrict__ rows) {
+// fold (uniform): e is the recoding of a folded scalar (hot_recode): HOT_FOLD_WINDOWS windows, the last one read as it stands.
+__device__ __forceinline__ void fixed_base_xbar(ge_p3& acc, uint32_t e[9], const uint4* __restrict__ rows, bool fold = false) {
   const uint32_t lane = threadIdx.x & 63u;
   constexpr int SETS = HOT_HALF / 32;                                // 1 (W = 6) or 2 (W = 7)
   static_assert(HOT_HALF == 32 * SETS && SETS >= 1 && SETS <= 2, "the crossbar walk holds sets of 32 entries");
@@ -526,10 +539,11 @@ __device__ __forceinline__ void fixed_base_xbar(ge_p3& acc, uint32_t e[9], const
   for (int s = 0; s < SETS; ++s)
 #pragma unroll
     for (int q = 0; q < 4; ++q) r[s][q] = my[(size_t)s * 32 * 7 + (q < 3 ? (uint32_t)q : last)];
+  const int windows = fold ? HOT_FOLD_WINDOWS : HOT_WINDOWS;
 #pragma unroll 1
-  for (int w = 0; w < HOT_WINDOWS; ++w) {
+  for (int w = 0; w < windows; ++w) {
     uint32_t mag, neg;
-    hot_next_digit(e, mag, neg);
+    hot_next_digit(e, mag, neg, fold && w == HOT_FOLD_WINDOWS - 1);
     const uint32_t nz = (uint32_t)(mag != 0u);
     const uint32_t m1 = mag - nz;                                     // magnitude - 1 (0 for a zero digit)
     const int src = (int)((m1 & 31u) << 2);                          // lane (magnitude - 1) mod 32, x 4: always in the lower half
@@ -557,7 +571,7 @@ __device__ __forceinline__ void fixed_base_xbar(ge_p3& acc, uint32_t e[9], const
         for (int i = 0; i < 27; ++i) wd[i] = hi ? t[i] : wd[i];
       }
     }
-    if (w + 1 < HOT_WINDOWS) {                                        // the next row travels during the addition
+    if (w + 1 < windows) {                                            // the next row travels during the addition
       const uint4* nx = my + (size_t)(w + 1) * HOT_ROW_CHUNKS;
 #pragma unroll
       for (int s = 0; s < SETS; ++s)

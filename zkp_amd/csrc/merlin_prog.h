@@ -97,6 +97,18 @@ ZKP_HD uint64_t tr_xor5(uint64_t a, uint64_t b, uint64_t c, uint64_t d, uint64_t
          tr_xor5_32((uint32_t)a, (uint32_t)b, (uint32_t)c, (uint32_t)d, (uint32_t)e);
 }
 
+// a ^ b ^ c: one v_bitop3_b32 (truth table 0x96) per half
+ZKP_HD uint32_t tr_xor3_32(uint32_t a, uint32_t b, uint32_t c) {
+#ifdef __HIP_DEVICE_COMPILE__
+  return (uint32_t)__builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
+#else
+  return a ^ b ^ c;
+#endif
+}
+ZKP_HD uint64_t tr_xor3(uint64_t a, uint64_t b, uint64_t c) {
+  return (uint64_t)tr_xor3_32((uint32_t)(a >> 32), (uint32_t)(b >> 32), (uint32_t)(c >> 32)) << 32 | tr_xor3_32((uint32_t)a, (uint32_t)b, (uint32_t)c);
+}
+
 // a ^ (~b & c)  (chi): one v_bitop3_b32 (truth table 0xD2 = 0xF0 ^ (~0xCC & 0xAA)) per half; left to itself the compiler
 // builds the 64-bit form from v_bfi_b32 + v_xor_b32
 ZKP_HD uint32_t tr_chi32(uint32_t a, uint32_t b, uint32_t c) {
@@ -126,13 +138,13 @@ ZKP_HD void tr_keccak_rounds(int rounds, uint64_t& a00, uint64_t& a10, uint64_t&
   for (int round = 0; round < rounds; ++round) {
     const uint64_t c0 = tr_xor5(a00, a01, a02, a03, a04), c1 = tr_xor5(a10, a11, a12, a13, a14), c2 = tr_xor5(a20, a21, a22, a23, a24),
                    c3 = tr_xor5(a30, a31, a32, a33, a34), c4 = tr_xor5(a40, a41, a42, a43, a44);
-    const uint64_t d0 = c4 ^ tr_rotl(c1, 1), d1 = c0 ^ tr_rotl(c2, 1), d2 = c1 ^ tr_rotl(c3, 1), d3 = c2 ^ tr_rotl(c4, 1),
-                   d4 = c3 ^ tr_rotl(c0, 1);
-    a00 ^= d0; a01 ^= d0; a02 ^= d0; a03 ^= d0; a04 ^= d0;
-    a10 ^= d1; a11 ^= d1; a12 ^= d1; a13 ^= d1; a14 ^= d1;
-    a20 ^= d2; a21 ^= d2; a22 ^= d2; a23 ^= d2; a24 ^= d2;
-    a30 ^= d3; a31 ^= d3; a32 ^= d3; a33 ^= d3; a34 ^= d3;
-    a40 ^= d4; a41 ^= d4; a42 ^= d4; a43 ^= d4; a44 ^= d4;
+    // theta without D: A ^= C[x-1] ^ rotl(C[x+1], 1) as one xor3 per lane (50 v_bitop3_b32 a round instead of 10 + 50 v_xor_b32)
+    const uint64_t r0 = tr_rotl(c1, 1), r1 = tr_rotl(c2, 1), r2 = tr_rotl(c3, 1), r3 = tr_rotl(c4, 1), r4 = tr_rotl(c0, 1);
+    a00 = tr_xor3(a00, c4, r0); a01 = tr_xor3(a01, c4, r0); a02 = tr_xor3(a02, c4, r0); a03 = tr_xor3(a03, c4, r0); a04 = tr_xor3(a04, c4, r0);
+    a10 = tr_xor3(a10, c0, r1); a11 = tr_xor3(a11, c0, r1); a12 = tr_xor3(a12, c0, r1); a13 = tr_xor3(a13, c0, r1); a14 = tr_xor3(a14, c0, r1);
+    a20 = tr_xor3(a20, c1, r2); a21 = tr_xor3(a21, c1, r2); a22 = tr_xor3(a22, c1, r2); a23 = tr_xor3(a23, c1, r2); a24 = tr_xor3(a24, c1, r2);
+    a30 = tr_xor3(a30, c2, r3); a31 = tr_xor3(a31, c2, r3); a32 = tr_xor3(a32, c2, r3); a33 = tr_xor3(a33, c2, r3); a34 = tr_xor3(a34, c2, r3);
+    a40 = tr_xor3(a40, c3, r4); a41 = tr_xor3(a41, c3, r4); a42 = tr_xor3(a42, c3, r4); a43 = tr_xor3(a43, c3, r4); a44 = tr_xor3(a44, c3, r4);
     const uint64_t b00 = a00,               b13 = tr_rotl(a01, 36), b21 = tr_rotl(a02, 3),  b34 = tr_rotl(a03, 41), b42 = tr_rotl(a04, 18);
     const uint64_t b02 = tr_rotl(a10, 1),   b10 = tr_rotl(a11, 44), b23 = tr_rotl(a12, 10), b31 = tr_rotl(a13, 45), b44 = tr_rotl(a14, 2);
     const uint64_t b04 = tr_rotl(a20, 62),  b12 = tr_rotl(a21, 6),  b20 = tr_rotl(a22, 43), b33 = tr_rotl(a23, 15), b41 = tr_rotl(a24, 61);

@@ -1,5 +1,7 @@
-// Scalars modulo l = 2^252 + 27742317777372353535851937790883648493 on the GPU: eight 32-bit limbs, Montgomery
-// multiplication (R = 2^256) built from the same full-rate v_mad_u64_u32 the field code uses.
+// Scalars modulo l = 2^252 + 27742317777372353535851937790883648493 on the GPU: eight 32-bit limbs, products from the same full-rate
+// v_mad_u64_u32 the field code uses.  A product, a * b + c and a 64-byte string are reduced in ONE pass with l = 2^252 + delta
+// (2^252 == -delta, delta < 2^125: sc_reduce_wide); the chain of the inversion stays in Montgomery form (R = 2^256, sc_mont), whose
+// reduction uses only the four non-zero low limbs of l and a shift for limb 7.
 // Needed by the batch-verification coefficient build (reference src/toolbox/batch_verifier.rs:173-206:
 // `random_factor * minus_c[j]`, `random_factor * resp`, accumulation into the coefficient matrix).
 // Host + device header, tested on the CPU against Python integers (tests/test_host_field.py, tests/test_host_scalar_edges.py) and on
@@ -72,7 +74,147 @@ ZKP_HD void sc_neg(sc& r, const sc& a) {
     br = (t >> 63) & 1u;
   }
 }
-// Montgomery product a * b * 2^-256 mod l.  b < l; a any 256-bit value.  Result < l.
+// ---- one-pass reduction --------------------------------------------------------------------------------------------------------
+// delta = l - 2^252 (125 bits) = the four low limbs of l
+ZKP_HD uint32_t sc_delta(int i) { return sc_l(i); }
+// 2^252 - 66 delta   (the bias of sc_reduce_tail)
+ZKP_HD uint32_t sc_bias(int i) {
+  return i == 0 ? 0x089f5ce6u : i == 1 ? 0x4b427334u : i == 2 ? 0xfc2990bdu : i == 3 ? 0x9e839499u : i == 4 ? 0xfffffffau : i == 7 ? 0x0fffffffu : 0xffffffffu;
+}
+// 32 l (nine limbs)
+ZKP_HD uint32_t sc_32l(int i) {
+  return i == 0 ? 0x9eba7da0u : i == 1 ? 0x024c634bu : i == 2 ? 0x5ef39acbu : i == 3 ? 0x9bdf3bd4u : i == 4 ? 0x00000002u : i == 8 ? 0x00000002u : 0u;
+}
+
+// out[NA + NB] = a * b (+ add[0 .. NB) when add != nullptr): operand scanning, one v_mad_u64_u32 per product with the carry and the
+// running limb in its 64-bit addend ((2^32 - 1)^2 + 2 (2^32 - 1) = 2^64 - 1: it never overflows)
+template <int NA, int NB>
+ZKP_HD void sc_mul_words(uint32_t* out, const uint32_t* a, const uint32_t* b, const uint32_t* add = nullptr) {
+#pragma unroll
+  for (int i = 0; i < NA; ++i) {
+    uint64_t c = 0;
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+      c += (uint64_t)a[i] * b[j] + (i ? out[i + j] : add ? add[j] : 0u);
+      out[i + j] = (uint32_t)c;
+      c >>= 32;
+    }
+    out[i + NB] = (uint32_t)c;
+  }
+}
+// out[NA + 4] = delta * a
+template <int NA>
+ZKP_HD void sc_mul_delta(uint32_t* out, const uint32_t* a) {
+  uint32_t d[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) d[i] = sc_delta(i);
+  sc_mul_words<4, NA>(out, d, a);
+}
+// x = lo + 2^252 hi: lo[8] < 2^252, hi[NH] = the NH limbs above bit 252 (x has at least NH + 8 limbs, or exactly NH + 7 when TOP: then
+// its missing limb counts as zero)
+template <int NH, bool TOP>
+ZKP_HD void sc_split252(uint32_t* lo, uint32_t* hi, const uint32_t* x) {
+#pragma unroll
+  for (int i = 0; i < 7; ++i) lo[i] = x[i];
+  lo[7] = x[7] & 0x0fffffffu;
+#pragma unroll
+  for (int k = 0; k < NH; ++k) hi[k] = (TOP && k == NH - 1) ? x[7 + k] >> 28 : (x[7 + k] >> 28) | (x[8 + k] << 4);
+}
+// The last step of every reduction: v[9] = any value below 67 * 2^252 -> its canonical representative.  With q = v >> 252 (<= 66) and
+// 2^252 == -delta:  v == (v mod 2^252) - q delta =: t, -66 delta <= t < 2^252.  The sum w = (v mod 2^252) + (66 - q) delta + (2^252 - 66 delta)
+// = t + 2^252 is positive and below 2^253: bit 252 of w says whether t is negative (then the result is t + l = w + delta, which is
+// below l) or not (then it is t = w - 2^252, which is below 2^252 < l).  No conditional subtraction of l is left to do.
+ZKP_HD void sc_reduce_tail(sc& r, const uint32_t* v) {
+  const uint32_t n = 66u - ((v[8] << 4) | (v[7] >> 28));
+  uint32_t w[8];
+  uint64_t c = 0, m = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    if (i < 4) m += (uint64_t)n * sc_delta(i);
+    c += (uint64_t)(i == 7 ? v[7] & 0x0fffffffu : v[i]) + sc_bias(i) + (uint32_t)m;
+    w[i] = (uint32_t)c;
+    c >>= 32;
+    m >>= 32;
+  }
+  const uint32_t neg = 0u - (uint32_t)((w[7] >> 28) == 0);       // t < 0
+  c = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    c += (uint64_t)w[i] + (i < 4 ? sc_delta(i) & neg : 0u);
+    r.v[i] = (uint32_t)c;
+    c >>= 32;
+  }
+  r.v[7] -= ~neg & 0x10000000u;
+}
+// x[16] (any 512-bit value) -> canonical scalar.  Two folds of what lies above bit 252:
+//   x = L + 2^252 H == L - delta H,  delta H = L2 + 2^252 H2 == L2 - delta H2  =>  x == L + delta H2 + (l - L2)
+// H < 2^260 (9 limbs), delta H < 2^385 (13 limbs), H2 < 2^133 (5 limbs), delta H2 < 2^258 (9 limbs): the sum is below 2^258 + 2^253 + delta.
+ZKP_HD void sc_reduce_wide(sc& r, const uint32_t* x) {
+  uint32_t L[8], H[9], y[13], L2[8], H2[5], z[9], v[9];
+  sc_split252<9, true>(L, H, x);
+  sc_mul_delta<9>(y, H);
+  sc_split252<5, false>(L2, H2, y);
+  sc_mul_delta<5>(z, H2);
+  uint64_t c = 0, br = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const uint64_t t = (uint64_t)sc_l(i) - L2[i] - br;           // l - L2 > 0: no borrow out of limb 7
+    br = (t >> 63) & 1u;
+    c += (uint64_t)L[i] + z[i] + (uint32_t)t;
+    v[i] = (uint32_t)c;
+    c >>= 32;
+  }
+  v[8] = (uint32_t)c + z[8];
+  sc_reduce_tail(r, v);
+}
+// x[12] (any 384-bit value) -> canonical scalar.  One fold: H < 2^132 (5 limbs), delta H < 2^257 (9 limbs), x == L + (32 l - delta H),
+// below 2^252 + 2^257 + 32 delta.
+ZKP_HD void sc_reduce_384(sc& r, const uint32_t* x) {
+  uint32_t L[8], H[5], y[9], v[9];
+  sc_split252<5, true>(L, H, x);
+  sc_mul_delta<5>(y, H);
+  uint64_t c = 0, br = 0;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) {
+    const uint64_t t = (uint64_t)sc_32l(i) - y[i] - br;          // 32 l > 2^257 > delta H: no borrow out of limb 8
+    br = (t >> 63) & 1u;
+    c += (uint64_t)(i < 8 ? L[i] : 0u) + (uint32_t)t;
+    v[i] = (uint32_t)c;
+    c >>= 32;
+  }
+  sc_reduce_tail(r, v);
+}
+
+// r = a * b + c mod l: one product, one reduction.  a, b, c: ANY 256-bit values (a b + c < 2^512).  r may be an operand.
+ZKP_HD void sc_muladd(sc& r, const sc& a, const sc& b, const sc& c) {
+  uint32_t x[16];
+  sc_mul_words<8, 8>(x, a.v, b.v, c.v);
+  sc_reduce_wide(r, x);
+}
+// r = a * b mod l   (a, b: any 256-bit values)
+ZKP_HD void sc_mul(sc& r, const sc& a, const sc& b) {
+  uint32_t x[16];
+  sc_mul_words<8, 8>(x, a.v, b.v);
+  sc_reduce_wide(r, x);
+}
+// r = a * w mod l for a 128-bit w (the batch verifier's weights: Scalar::from(u128)) and any 256-bit a
+ZKP_HD void sc_mul_u128(sc& r, const sc& a, const uint32_t w[4]) {
+  uint32_t x[12];
+  sc_mul_words<4, 8>(x, w, a.v);
+  sc_reduce_384(r, x);
+}
+// any 256-bit value -> canonical representative
+ZKP_HD void sc_reduce(sc& r, const sc& a) {
+  uint32_t v[9];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) v[i] = a.v[i];
+  v[8] = 0;
+  sc_reduce_tail(r, v);
+}
+
+// ---- Montgomery form (the inversion chain) ---------------------------------------------------------------------------------------
+// Montgomery product a * b * 2^-256 mod l.  b < l; a any 256-bit value.  Result < l.  Each row adds m l with l's limbs 4 .. 6 = 0
+// (only the carry passes through) and limb 7 = 2^28 (a shift): four products by l instead of eight.
 ZKP_HD void sc_mont(sc& r, const sc& a, const sc& b) {
   uint32_t t[10];
 #pragma unroll
@@ -93,11 +235,20 @@ ZKP_HD void sc_mont(sc& r, const sc& a, const sc& b) {
     c = (uint64_t)m * sc_l(0) + t[0];
     c >>= 32;
 #pragma unroll
-    for (int j = 1; j < 8; ++j) {
+    for (int j = 1; j < 4; ++j) {
       c += (uint64_t)m * sc_l(j) + t[j];
       t[j - 1] = (uint32_t)c;
       c >>= 32;
     }
+#pragma unroll
+    for (int j = 4; j < 7; ++j) {
+      c += t[j];
+      t[j - 1] = (uint32_t)c;
+      c >>= 32;
+    }
+    c += ((uint64_t)m << 28) + t[7];
+    t[6] = (uint32_t)c;
+    c >>= 32;
     c += t[8];
     t[7] = (uint32_t)c;
     t[8] = t[9] + (uint32_t)(c >> 32);
@@ -106,29 +257,12 @@ ZKP_HD void sc_mont(sc& r, const sc& a, const sc& b) {
   for (int i = 0; i < 8; ++i) r.v[i] = t[i];
   sc_cond_sub_l(r);                           // < 2 l before
 }
-// r = a * b mod l   (two Montgomery products)
-ZKP_HD void sc_mul(sc& r, const sc& a, const sc& b) {
-  sc t, rr;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) rr.v[i] = sc_rr(i);
-  sc_mont(t, a, b);
-  sc_mont(r, t, rr);
-}
 // to Montgomery form: a * R mod l  (so that sc_mont(to_mont(a), b) = a * b)
 ZKP_HD void sc_to_mont(sc& r, const sc& a) {
   sc rr;
 #pragma unroll
   for (int i = 0; i < 8; ++i) rr.v[i] = sc_rr(i);
   sc_mont(r, a, rr);
-}
-// any 256-bit value -> canonical representative
-ZKP_HD void sc_reduce(sc& r, const sc& a) {
-  sc one;
-  sc_zero(one);
-  one.v[0] = 1;
-  sc t;
-  sc_to_mont(t, a);          // a R mod l   (a may be >= l: sc_mont allows it in the first operand)
-  sc_mont(r, t, one);        // a
 }
 
 // l <= the 256-bit little-endian value?  (Scalar::from_canonical_bytes / dalek's Deserialize accept only values < l.)
@@ -209,12 +343,10 @@ ZKP_HD void sc_halve_canonical(sc& r, const sc& t) {
 
 // 512-bit little-endian value (lo + hi * 2^256) -> canonical scalar: Scalar::from_bytes_mod_order_wide
 ZKP_HD void sc_from_wide(sc& r, const sc& lo, const sc& hi) {
-  sc r1, rr, a, b;
+  uint32_t x[16];
 #pragma unroll
-  for (int i = 0; i < 8; ++i) { r1.v[i] = sc_r1(i); rr.v[i] = sc_rr(i); }
-  sc_mont(a, lo, r1);        // lo * R / R = lo mod l
-  sc_mont(b, hi, rr);        // hi * R^2 / R = hi * 2^256 mod l
-  sc_add(r, a, b);
+  for (int i = 0; i < 8; ++i) { x[i] = lo.v[i]; x[8 + i] = hi.v[i]; }
+  sc_reduce_wide(r, x);
 }
 
 // y = y^(2^n) * t in Montgomery form: n squarings in a rolled loop (n is a constant at every call site), one product

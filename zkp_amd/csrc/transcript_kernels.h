@@ -39,11 +39,11 @@ __device__ __forceinline__ void keccak_f1600_split(uint32_t a[25], uint32_t h) {
 #pragma unroll
     for (int x = 0; x < 5; ++x) c[x] = tr_xor5_32(a[x], a[x + 5], a[x + 10], a[x + 15], a[x + 20]);
 #pragma unroll
-    for (int x = 0; x < 5; ++x) {                       // theta: D[x] = C[x-1] ^ rotl(C[x+1], 1)
-      const uint32_t cn = c[(x + 1) % 5];
-      const uint32_t d = c[(x + 4) % 5] ^ rotl_half(cn, pair_swap(cn), 1);
+    for (int x = 0; x < 5; ++x) {                       // theta: A[x][y] ^= C[x-1] ^ rotl(C[x+1], 1), one xor3 per word and no D
+      const uint32_t cn = c[(x + 1) % 5], cp = c[(x + 4) % 5];
+      const uint32_t r = rotl_half(cn, pair_swap(cn), 1);
 #pragma unroll
-      for (int y = 0; y < 5; ++y) a[x + 5 * y] ^= d;
+      for (int y = 0; y < 5; ++y) a[x + 5 * y] = tr_xor3_32(a[x + 5 * y], cp, r);
     }
 #pragma unroll
     for (int y = 0; y < 5; ++y)                         // rho + pi: B[y][2x+3y] = rotl(A[x][y], r[x][y])

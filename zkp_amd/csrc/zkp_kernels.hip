@@ -163,8 +163,10 @@ k_terms_split(const uint8_t* __restrict__ scalars, const uint32_t* __restrict__ 
               const uint32_t* __restrict__ blk_start, const uint32_t* __restrict__ list, const dev_niels* __restrict__ tables,
               const dev_affine* __restrict__ pts, dev_ext* __restrict__ ladder_rw, uint32_t max_ladder, dev_ext* __restrict__ partial,
               uint32_t ladder_stride, const uint32_t* __restrict__ pair, uint32_t stmt_T, uint32_t no_carry) {
-  // no_carry (constant-time calls): the caller vouches that every scalar is below 2^254 (the fused prove flows: reduced mod l), so the signed radix-16
-  // recoding s + 0x88...8 cannot carry out of bit 255 and the comb walks and the ladder leave their 65th addition -- of the identity -- out.
+  // no_carry (constant-time calls): the caller vouches that every scalar is reduced mod l (at most l; the fused prove flows' blindings and the halves
+  // of them; a larger vouched scalar gives a wrong point).  Then the signed radix-16 recoding s + 0x88...8 cannot carry out of bit 255, and the comb
+  // walks and the ladder leave their 65th addition -- of the identity -- out; the fixed-base blocks walk the sign-folded scalar in 36 windows
+  // instead of 37 (hot_tables.h).
   // A block of fixed-base terms serves ONE table; its rows pass through LDS one window at a time, in 16 copies, so that every
   // lane reads the entry its digit names from banks of its own (hot_tables.h): no masked scan, no bank conflict, the same
   // LDS cycles for every scalar.
@@ -268,8 +270,12 @@ k_terms_split(const uint8_t* __restrict__ scalars, const uint32_t* __restrict__ 
 #pragma unroll
       for (int q = 0; q < 8; ++q) s[q] = 0;
       if (live) load_vec<2>(s, scalars + 32 * (size_t)t);
-      hot_recode(e, s);                                            // (lanes without a term walk the scalar 0: they are crossbar sources)
-      fixed_base_xbar(acc, e, src);
+      const bool fold = CT && no_carry;                            // (uniform) reduced scalars: walk min(s, l - s) in one window less, negate after
+      uint32_t flip = 0;
+      if (fold) flip = sc_fold_sign(s);
+      hot_recode(e, s, fold);                                      // (lanes without a term walk the scalar 0: they are crossbar sources)
+      fixed_base_xbar(acc, e, src, fold);
+      if (fold) ge_cneg(acc, flip);
     } else {
       if (live) {
         load_vec<2>(s, scalars + 32 * (size_t)t);
@@ -1182,13 +1188,12 @@ __device__ __forceinline__ void coeff_of_point(sc& acc, uint32_t p, uint32_t j, 
   sc_zero(acc);
   for (uint32_t e = inc_off[p]; e < inc_off[p + 1]; ++e) {
     const uint32_t k = inc_k[e], svar = inc_sc[e];
-    sc r, rm, x, t;
-    sc_zero(r);
-    load_vec<1>(r.v, weights16 + 16 * ((size_t)k * wk + (size_t)j * wj));   // Scalar::from(u128)
-    sc_to_mont(rm, r);
+    sc x, t;
+    uint32_t r[4];
+    load_vec<1>(r, weights16 + 16 * ((size_t)k * wk + (size_t)j * wj));     // Scalar::from(u128)
     const uint8_t* src = svar == 0xffffffffu ? minus_c + 32 * (size_t)j : responses + 32 * ((size_t)j * m + svar);
     load_vec<2>(x.v, src);
-    sc_mont(t, x, rm);                                             // x * r mod l (x may be any 256-bit value)
+    sc_mul_u128(t, x, r);                                          // x * r mod l: a 256 x 128-bit product, one fold (x may be any 256-bit value)
     sc_add(acc, acc, t);
   }
 }
@@ -1335,7 +1340,7 @@ k_sha512_csr(uint32_t n, const uint8_t* __restrict__ msgs, uint64_t msgs_len, co
 }
 
 // Batched scalars mod l (zkp_mi355x.h (6)): one lane per output over a grid-stride loop, canonical 32-byte scalars out.  Inputs are any
-// 32 bytes, read as Scalar::from_bytes_mod_order reads them (sc_mont takes any 256-bit first operand).  No branch or address depends
+// 32 bytes, read as Scalar::from_bytes_mod_order reads them (sc_muladd and sc_to_mont take any 256-bit operand).  No branch or address depends
 // on an operand.  `in` / an operand of stride 1 may be `out`: a lane loads its own element before it stores it.
 __global__ void __launch_bounds__(256)
 k_sc_invert(uint32_t n, const uint8_t* in, uint8_t* out) {
@@ -1359,24 +1364,17 @@ k_sc_from_wide(uint32_t n, const uint8_t* __restrict__ in, uint8_t* __restrict__
   }
 }
 
-// out[i] = a[i sa] * b[i sb] + c[i sc] mod l, strides 0 (one scalar for all lanes) or 1; c == NULL: + 0.  Three Montgomery products:
-// b R mod l, a b mod l, c mod l.
+// out[i] = a[i sa] * b[i sb] + c[i sc] mod l, strides 0 (one scalar for all lanes) or 1; c == NULL: + 0.  One 512-bit product with c
+// added into it, one reduction.
 __global__ void __launch_bounds__(256)
 k_sc_muladd(uint32_t n, const uint8_t* a, uint32_t sa, const uint8_t* b, uint32_t sb, const uint8_t* c, uint32_t sc_, uint8_t* out) {
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    sc x, y, r;
+    sc x, y, z, r;
     load_vec<2>(x.v, a + 32 * (size_t)i * sa);
     load_vec<2>(y.v, b + 32 * (size_t)i * sb);
-    sc_to_mont(y, y);
-    sc_mont(r, x, y);
-    if (c) {
-      sc z, r1;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) r1.v[k] = sc_r1(k);
-      load_vec<2>(z.v, c + 32 * (size_t)i * sc_);
-      sc_mont(z, z, r1);
-      sc_add(r, r, z);
-    }
+    sc_zero(z);
+    if (c) load_vec<2>(z.v, c + 32 * (size_t)i * sc_);
+    sc_muladd(r, x, y, z);
     store_vec<2>(out + 32 * (size_t)i, r.v);
   }
 }
@@ -1467,9 +1465,10 @@ struct zkp_ctx {
   // zkp_debug_last_schedule: the size-driven choices the last call made (cleared by prof_begin; -1 = the call did not make it)
   enum { SCH_BATCH_ENCODE, SCH_ENC_GROUPS, SCH_OPT_PIP, SCH_PIP_C, SCH_PIP_PART, SCH_STATUS_SHARED, SCH_LAT_SPLIT, SCH_GROUPED, SCH_COMB_MIN,
          SCH_LADDER_INTERLEAVE, SCH_RIDERS, SCH_STRAUS_LANES, SCH_STRAUS_WINS, SCH_TR_LANES, SCH_TR_STEPS, SCH_FUSE_TT, SCH_TERMS_SPLIT,
-         SCH_RAGGED_CLASSES, SCH_RAGGED_COMPILED, SCH_RAGGED_BASE, SCH_FUSED_PLANS, SCH_PIP_MERGE, SCH_PIP_BUCKETS, SCH_NO_CARRY, SCH_COUNT };
-  int64_t sched[SCH_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+         SCH_RAGGED_CLASSES, SCH_RAGGED_COMPILED, SCH_RAGGED_BASE, SCH_FUSED_PLANS, SCH_PIP_MERGE, SCH_PIP_BUCKETS, SCH_NO_CARRY, SCH_SIGN_FOLD, SCH_COUNT };
+  int64_t sched[SCH_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
   int debug_pip_merge = 0;           // ZKP_TESTOPT_PIP_MERGE: 0 = by the call's bucket count, 1 = a quad per bucket, 2 = a lane per bucket
+  bool debug_vouch_reduced = false;  // ZKP_TESTOPT_VOUCH_REDUCED: constant-time zkp_msm_many calls vouch that their scalars are reduced mod l (terms_cfg::canonical)
 #endif
   static constexpr size_t kGroupedCombTerms = 400000;
   static constexpr size_t kSplitCombTerms = 8192;   // narrow constant-time calls on the latency schedule from this many terms on: grouped walk + quad-split scans (ZKP_OPT_COMB_SPLIT)
@@ -1856,6 +1855,7 @@ int msm_terms_path(zkp_ctx* c, uint32_t n_msm, const uint32_t* d_off, const uint
       const uint32_t no_carry = (k.canonical && flags == ZKP_CT) ? 1u : 0u;
       ZKP_SCHED(c, NO_CARRY, no_carry);
       const int lookup = (!HOT_LDS_ROWS || c->ct_lookup == LOOKUP_XBAR) ? LOOKUP_XBAR : (flags == ZKP_CT ? c->ct_lookup : LOOKUP_LDS);
+      ZKP_SCHED(c, SIGN_FOLD, (no_carry && lookup == LOOKUP_XBAR) ? 1 : 0);      // (only the crossbar walk of the fixed-base blocks folds)
 #define ZKP_LAUNCH_TERMS(CT_, TEETH_, LK_) launch_terms_split<CT_, TEETH_, LK_>(c, grid, k.max_ladder != 0, d_scalars, d_pidx, n_points, comb, slot_of, class_start, blk_start, list, pts, ladder, k.max_ladder, part, comb_split ? 1u : 0u, pair_on ? k.stmt.pair : (const uint32_t*)nullptr, k.stmt.T, no_carry)
       if (lookup == LOOKUP_XBAR) {
         if (flags == ZKP_CT) { if (k.teeth == 16) ZKP_LAUNCH_TERMS(true, 16, LOOKUP_XBAR); else ZKP_LAUNCH_TERMS(true, 4, LOOKUP_XBAR); }
@@ -2307,6 +2307,7 @@ int zkp_ctx_set_option(zkp_ctx* c, int option, uint64_t value) {
 #ifdef ZKP_BUILD_TEST_HOOKS
     case ZKP_TESTOPT_GENERIC_CLASSIFIER: c->stmt_classify = value == 0; return ZKP_OK;
     case ZKP_TESTOPT_PIP_MERGE: c->debug_pip_merge = value <= 2 ? (int)value : 0; return ZKP_OK;
+    case ZKP_TESTOPT_VOUCH_REDUCED: c->debug_vouch_reduced = value != 0; return ZKP_OK;
     case ZKP_TESTOPT_DUMMY_LAUNCHES: c->debug_dummy_launches = (int)std::min<uint64_t>(value, 1000); return ZKP_OK;
     case ZKP_TESTOPT_WAVE_CYCLES: {
       HIP_TRY(hipSetDevice(c->device));
@@ -2598,7 +2599,10 @@ int zkp_msm_many(zkp_ctx* c, uint32_t n_msm, const uint32_t* off, const uint8_t*
   for (uint32_t t = 0; t < n_terms; ++t)
     if (pidx[t] >= n_points) return fail(ZKP_ERR_ARG, "pidx out of range");
   HIP_TRY(hipSetDevice(c->device));
-  const terms_cfg k = n_terms >= 1024 ? host_terms_cfg(c, n_terms, pidx, points, n_points, flags == ZKP_CT ? c->ct_comb_min(false, n_terms) : 2u) : terms_cfg();
+  terms_cfg k = n_terms >= 1024 ? host_terms_cfg(c, n_terms, pidx, points, n_points, flags == ZKP_CT ? c->ct_comb_min(false, n_terms) : 2u) : terms_cfg();
+#ifdef ZKP_BUILD_TEST_HOOKS
+  if (c->debug_vouch_reduced && flags == ZKP_CT) k.canonical = true;
+#endif
   carve cv;
   const size_t o_off = cv.take((size_t)(n_msm + 1) * 4);
   const size_t o_sc = cv.take((size_t)n_terms * 32);
@@ -3004,7 +3008,7 @@ int zkp_debug_last_schedule(zkp_ctx* c, char* buf, size_t cap) {
   if (!c || !buf || !cap) return fail(ZKP_ERR_ARG, "bad argument");
   static const char* const names[zkp_ctx::SCH_COUNT] = {"batch_encode", "enc_groups", "opt_pip", "pip_c", "pip_part", "status_shared", "lat_split", "grouped", "comb_min",
                                                         "ladder_interleave", "riders", "straus_lanes", "straus_wins", "tr_lanes", "tr_steps", "fuse_tt", "terms_split",
-                                                        "ragged_classes", "ragged_compiled", "ragged_base", "fused_plans", "pip_merge", "pip_buckets", "no_carry"};
+                                                        "ragged_classes", "ragged_compiled", "ragged_base", "fused_plans", "pip_merge", "pip_buckets", "no_carry", "sign_fold"};
   std::string s;
   for (int i = 0; i < zkp_ctx::SCH_COUNT; ++i)
     if (c->sched[i] >= 0) s += (s.empty() ? "" : " ") + std::string(names[i]) + "=" + std::to_string(c->sched[i]);

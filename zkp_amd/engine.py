@@ -16,7 +16,7 @@ from . import cabi
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libzkp_mi355x.so")
 TESTHOOKS_LIB_PATH = os.path.join(_HERE, "libzkp_mi355x_testhooks.so")     # -DZKP_BUILD_TEST_HOOKS build (tests / A-B tools)
-ZKP_TESTOPT_DUMMY_LAUNCHES, ZKP_TESTOPT_GENERIC_CLASSIFIER, ZKP_TESTOPT_WAVE_CYCLES, ZKP_TESTOPT_PIP_MERGE = 1001, 1002, 1003, 1004
+ZKP_TESTOPT_DUMMY_LAUNCHES, ZKP_TESTOPT_GENERIC_CLASSIFIER, ZKP_TESTOPT_WAVE_CYCLES, ZKP_TESTOPT_PIP_MERGE, ZKP_TESTOPT_VOUCH_REDUCED = 1001, 1002, 1003, 1004, 1005
 ZKP_OPT_CT_LOOKUP, ZKP_OPT_EACH_STRAUS, ZKP_OPT_LADDER_INTERLEAVE = 9, 10, 11
 ZKP_OPT_CT_MASKED_SCANS = ZKP_OPT_CT_LOOKUP           # the round-3 name (value 1 = masked scans)
 ZKP_CT_LOOKUP_XBAR, ZKP_CT_LOOKUP_SCAN, ZKP_CT_LOOKUP_LDS = 0, 1, 2
