@@ -576,7 +576,7 @@ enum {
 int zkp_ctx_last_timing(zkp_ctx* ctx, float* kernel_ms /*[ZKP_K_COUNT]*/, float* total_ms);
 /* With profiling on: which VARIANT of a kind's kernel the last call launched, by the name rocprofv3 prints -- the kernels whose template
  * arguments depend on the call's size, flags or options (ZKP_K_TERMS: "k_terms_split<true, 16, true, false>", ZKP_K_TABLES:
- * "zkp::k_comb_tables_lane<16>" / "zkp::k_tables_transcript_pc<16>", ZKP_K_TRANSCRIPT: "zkp::k_transcript_run" / "...run1", "zkp::k_strobe_append_csr" / "zkp::k_strobe_challenge" of section (7), ZKP_K_DECODE of the
+ * "zkp::k_comb_tables_lane<16>" / "zkp::k_comb_tables_lane_nc<16>" (a call that vouches for reduced scalars: no carry tooth) / "zkp::k_tables_transcript_pc<16>", ZKP_K_TRANSCRIPT: "zkp::k_transcript_run" / "...run1", "zkp::k_strobe_append_csr" / "zkp::k_strobe_challenge" of section (7), ZKP_K_DECODE of the
  * large-MSM path: "k_pip_prepare<11>"); several names are joined with ';', kinds whose kernels never vary give "".  Writes a NUL-terminated
  * string of at most cap - 1 characters and returns the untruncated length.  Profiles and benchmarks label kernels from THIS, not from a
  * copy of the dispatch thresholds. */
@@ -613,7 +613,8 @@ int zkp_ctx_set_profiling(zkp_ctx* ctx, int enabled);
  *   position classes, class programs compiled by this call, 1 if it built its position-free base plan, the size of the aligned plan cache), pip_merge
  *   (the bucket merge: 0 = a quad per bucket, 1 = a lane per bucket), pip_buckets (batches x windows x buckets per window, what pip_merge goes by) and
  *   no_carry (1 = the term kernel skipped the carry window: the fused prove flows, whose scalars are reduced mod l) and sign_fold (1 = its
- *   fixed-base blocks walked min(s, l - s) in 36 windows and negated the result where l - s was walked).  Writes a
+ *   fixed-base blocks walked min(s, l - s) in 36 windows and negated the result where l - s was walked, and so did the grouped comb walk in its
+ *   radix-16 digits; the comb scans and the constant-time ladder fold whenever no_carry is 1).  Writes a
  *   NUL-terminated string of at most cap - 1 characters and returns the untruncated length. */
 int zkp_debug_quad_selftest(zkp_ctx* ctx, uint32_t n, const uint8_t* pairs /*[n][64]*/, uint8_t* out /*[n][128]*/);
 int zkp_debug_row_selftest(zkp_ctx* ctx, uint32_t n, const uint8_t* pairs /*[n][64]*/, uint8_t* out /*[n][96]*/);

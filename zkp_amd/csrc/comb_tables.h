@@ -10,7 +10,7 @@
 //     TEETH = 4  (64 doublings per term, 33-entry table, 4.75 KB)   for points with a few uses,
 //     TEETH = 16 (16 doublings per term, 129-entry table, 18.6 KB)  from about 6 uses per point on (CMZ's P: 1564 -> 1168).
 // The first window's four doublings act on the identity and are skipped (12 doublings per term at TEETH = 16).
-// (The grouped walk through LDS, comb_group_block below, runs two accumulators instead: 16 doublings + 1 addition per term, each staged row serving two additions.)
+// (The grouped walks through LDS, comb_group_block and comb_group_xbar below, run two accumulators instead: 12 doublings + 3 merging additions per term, each staged row serving two additions.)
 // Each row of the TEETH = 16 table is read by exactly one window of a term, so the constant-time scans stream the table
 // once per term instead of cycling 4 rows 16 times through a cache they do not fit (round 1: 556 MB of fabric traffic
 // per launch for 9.6 MB of algorithmic bytes).
@@ -89,7 +89,9 @@ k_comb_slots(uint32_t n_points, const uint32_t* __restrict__ uses, uint32_t comb
 template <int TEETH>
 __global__ void __launch_bounds__(256, 2)
 k_comb_tables(const uint32_t* __restrict__ n_slots, uint32_t max_tables, const uint32_t* __restrict__ slot_pt,
-              const dev_affine* __restrict__ pts, dev_ext* __restrict__ comb) {
+              const dev_affine* __restrict__ pts, dev_ext* __restrict__ comb, uint32_t no_carry) {
+  // no_carry (uniform; the call's word, k_terms_split): no walk of this call reads the carry entry 8 TEETH = 2^256 * P, so the builders stop after the
+  // eight multiples of the last tooth -- BITS - 3 doublings, a conversion and a store less per table; the entry keeps whatever the workspace held.
   using cfg = comb_cfg<TEETH>;
   const uint32_t gt = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t slot = gt >> 2;
@@ -127,6 +129,7 @@ k_comb_tables(const uint32_t* __restrict__ n_slots, uint32_t max_tables, const u
     q_to_cached(c, m, q); q_store_cached(tbl + 8 * j + 6, c, q);
     q_double(base, m4, q);                                                 // 8
     q_to_cached(c, base, q); q_store_cached(tbl + 8 * j + 7, c, q);
+    if (no_carry && j == TEETH - 1) return;
 #pragma unroll 1
     for (int d = 0; d < cfg::BITS - 3; ++d) q_double(base, base, q);       // 8 * 2^(BITS-3) = 2^BITS
   }
@@ -164,7 +167,13 @@ __device__ __forceinline__ void store_entries_staged(uint32_t (*stage)[64], cons
   }
   __builtin_amdgcn_wave_barrier();
 }
-template <int TEETH>
+// NO_CARRY (the call vouches for reduced scalars: k_comb_tables) is a template parameter here, not a kernel argument.  With the run-time form
+// `if (no_carry && j == TEETH - 1) return;` AMD clang 22.0.0git (ROCm 7.2.0, -O3, gfx950) emitted a kernel whose first Y + X reads limb 8 of Y from a
+// register that the instruction before it has overwritten (tools/microbench/lane_builder_miscompile.hip keeps that form and says how to look); every
+// table of the throughput schedule was wrong.  As a template parameter the builder of unvouched calls is the instruction stream it was, and the
+// NO_CARRY one was read at that place.  The quad and producer / consumer builders keep the argument: other code (DPP quads; a hand-over
+// through LDS), and every schedule that runs them, vouched and unvouched, is in the GPU suite -- the wrong lane builder failed 29 of its tests.
+template <int TEETH, bool NO_CARRY>
 __device__ __forceinline__ void comb_table_lane(uint32_t slot, const uint32_t* __restrict__ n_slots, uint32_t max_tables, const uint32_t* __restrict__ slot_pt,
                                                 const dev_affine* __restrict__ pts, dev_ext* __restrict__ comb) {
   using cfg = comb_cfg<TEETH>;
@@ -194,6 +203,7 @@ __device__ __forceinline__ void comb_table_lane(uint32_t slot, const uint32_t* _
     ge_to_cached(c, m); store_comb_entry(tbl + 8 * j + 6, c);
     ge_double<true>(base, m4);                                             // 8
     ge_to_cached(c, base); store_comb_entry(tbl + 8 * j + 7, c);
+    if (NO_CARRY && j == TEETH - 1) return;                                // nothing reads the carry entry: k_comb_tables
 #pragma unroll 1
     for (int d = 0; d < cfg::BITS - 4; ++d) ge_double<false>(base, base);
     ge_double<true>(base, base);                                           // 8 * 2^(BITS-3) = 2^BITS
@@ -206,7 +216,13 @@ template <int TEETH>
 __global__ void __launch_bounds__(256, 2)
 k_comb_tables_lane(const uint32_t* __restrict__ n_slots, uint32_t max_tables, const uint32_t* __restrict__ slot_pt,
                    const dev_affine* __restrict__ pts, dev_ext* __restrict__ comb) {
-  comb_table_lane<TEETH>(blockIdx.x * blockDim.x + threadIdx.x, n_slots, max_tables, slot_pt, pts, comb);
+  comb_table_lane<TEETH, false>(blockIdx.x * blockDim.x + threadIdx.x, n_slots, max_tables, slot_pt, pts, comb);
+}
+template <int TEETH>
+__global__ void __launch_bounds__(256, 2)
+k_comb_tables_lane_nc(const uint32_t* __restrict__ n_slots, uint32_t max_tables, const uint32_t* __restrict__ slot_pt,
+                      const dev_affine* __restrict__ pts, dev_ext* __restrict__ comb) {
+  comb_table_lane<TEETH, true>(blockIdx.x * blockDim.x + threadIdx.x, n_slots, max_tables, slot_pt, pts, comb);
 }
 
 
@@ -218,7 +234,7 @@ k_comb_tables_lane(const uint32_t* __restrict__ n_slots, uint32_t max_tables, co
 // passes once it has read buffer (j - 2) & 1).  `hand` = LDS [2][36][64] words.
 template <int TEETH>
 __device__ __forceinline__ void comb_table_pc(uint32_t slot0, const uint32_t* __restrict__ n_slots, uint32_t max_tables, const uint32_t* __restrict__ slot_pt,
-                                              const dev_affine* __restrict__ pts, dev_ext* __restrict__ comb, uint32_t* hand) {
+                                              const dev_affine* __restrict__ pts, dev_ext* __restrict__ comb, uint32_t* hand, uint32_t no_carry) {
   using cfg = comb_cfg<TEETH>;
   const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
   const uint32_t ns = min(*n_slots, max_tables);
@@ -235,6 +251,7 @@ __device__ __forceinline__ void comb_table_pc(uint32_t slot0, const uint32_t* __
 #pragma unroll
       for (int i = 0; i < 9; ++i) { h[64 * i] = base.X.v[i]; h[64 * (9 + i)] = base.Y.v[i]; h[64 * (18 + i)] = base.Z.v[i]; h[64 * (27 + i)] = base.T.v[i]; }
       __syncthreads();                                                       // tooth j's base is there (and the consumer is done with tooth j - 1)
+      if (no_carry && j == TEETH - 1) return;                                // (uniform; after the last barrier) nothing reads the carry entry: k_comb_tables
 #pragma unroll 1
       for (int d = 0; d < cfg::BITS - 1; ++d) ge_double<false>(base, base);
       ge_double<true>(base, base);                                           // 2^BITS x base
@@ -302,13 +319,19 @@ __device__ __forceinline__ void comb_select(ge_cached& sel, const dev_ext* __res
 }
 
 // partial[t] = scalars[t] * P through P's comb table.  CT: no branch or address depends on the scalar.
+// no_carry (uniform; the call vouches for reduced scalars): the constant-time walk FOLDS as well -- it takes min(s, l - s) in the recoding of
+// sc_fold_recode16 -- nibble 63 (the last tooth's top window) does not exist and loses its addition, nibble 62 is read as it stands -- and the sum is
+// negated where l - s was walked.  One word for both: a folded walk has no carry tail to add after the negation.
 template <bool CT, int TEETH>
 __device__ __forceinline__ void term_comb(uint32_t t, const uint8_t* __restrict__ scalars, const dev_ext* __restrict__ tbl,
                                           dev_ext* __restrict__ partial, uint32_t* ecol, bool no_carry = false) {
   using cfg = comb_cfg<TEETH>;
-  uint32_t s[8], e[8], top;
+  static_assert(cfg::WINDOWS >= 2, "nibbles 62 and 63 are two windows of the last tooth");
+  const bool fold = CT && no_carry;
+  uint32_t s[8], e[8], top = 0, flip = 0;
   load_vec<2>(s, scalars + 32 * (size_t)t);
-  sc_add_pattern(e, top, s, 0x88888888u);                       // signed radix-16 digits: nibble - 8 in [-8, 7]
+  if (CT && fold) flip = sc_fold_recode16(e, s);
+  else sc_add_pattern(e, top, s, 0x88888888u);                  // signed radix-16 digits: nibble - 8 in [-8, 7]
   // the recoded scalar goes to this lane's LDS column (word j at ecol[256 j]): the walk picks nibbles in table order, i.e. by
   // a run-time word index (the compiler would do the same with a promoted private array, in LDS of its own on top of the
   // fixed-base rows')
@@ -333,8 +356,9 @@ __device__ __forceinline__ void term_comb(uint32_t t, const uint8_t* __restrict_
       for (int j = 0; j < TEETH; ++j) {
         const int nidx = j * cfg::WINDOWS + w;                  // nibble number of tooth j, window w
         const uint32_t nib = (ecol[256 * (nidx >> 3)] >> (4 * (nidx & 7))) & 15u;
-        const uint32_t neg = (uint32_t)(nib < 8u);
-        const uint32_t mag = neg ? 8u - nib : nib - 8u;         // 0..8
+        const bool raw = fold && nidx == (int)SC_FOLD16_TOP_NIBBLE;       // (uniform) the folded walk's top digit carries no offset
+        const uint32_t neg = raw ? 0u : (uint32_t)(nib < 8u);
+        const uint32_t mag = raw ? nib : (neg ? 8u - nib : nib - 8u);     // 0..8
         const dev_ext* row = tbl + 8 * j;
         ge_cached sel;
         ge_cached_identity(sel);
@@ -351,11 +375,13 @@ __device__ __forceinline__ void term_comb(uint32_t t, const uint8_t* __restrict_
         const dev_ext* next = (j + 1 < TEETH) ? row + 8 : tbl;  // (after the last row of the last window: a harmless re-read of row 0)
         load_comb_entry(n0, next + 0);
         load_comb_entry(n1, next + 1);
+        if (fold && nidx == (int)SC_FOLD16_TOP_NIBBLE + 1) continue;       // (uniform) a folded scalar has no nibble 63
         ge_cached_cneg(sel, neg);
         if (w == cfg::WINDOWS - 1 && j == 0) ge_from_cached(acc, sel);     // the first entry is the accumulator
         else ge_add_cached(acc, acc, sel);
       }
     }
+    if (fold) ge_cneg(acc, flip);
   } else {
 #pragma unroll 1
     for (int w = cfg::WINDOWS - 1; w >= 0; --w) {
@@ -494,7 +520,7 @@ static_assert(GROUP_MIN_USES >= 8, "a column of 16 consecutive grouped terms mus
 
 __device__ __forceinline__ void comb_group_block(uint32_t i0, uint32_t n_g, const uint32_t* __restrict__ list_g, const uint8_t* __restrict__ scalars,
                                                  const uint32_t* __restrict__ pidx, const uint32_t* __restrict__ slot_of,
-                                                 const dev_ext* __restrict__ comb, dev_ext* __restrict__ partial, uint4* lds) {
+                                                 const dev_ext* __restrict__ comb, dev_ext* __restrict__ partial, uint4* lds, bool no_carry = false) {
   using cfg = comb_cfg<16>;
   constexpr uint32_t NONE = 0xffffffffu;
   const uint32_t tid = threadIdx.x, col = tid & 15u, k = tid >> 4;
@@ -576,6 +602,8 @@ __device__ __forceinline__ void comb_group_block(uint32_t i0, uint32_t n_g, cons
   // through LDS twice instead of four times -- half the LDS-DMA loads, half the barriers, 42 % less HBM fetch in the term kernel (1,433 -> 834 MiB per launch of
   // 20,480 CMZ proofs) -- for 16 doublings + 1 addition per term instead of 12 doublings:
   //   pass 0: acc += T_j[d(j,3)], lo += T_j[d(j,1)] over the teeth j;  acc, lo <- 16 acc, 16 lo;  pass 1: acc += T_j[d(j,2)], lo += T_j[d(j,0)];  result = 256 acc + lo.
+  // Since then the windows are paired in Horner order, (3,2) then (1,0), as in comb_group_xbar: acc = 16 (16 S3 + S2) between the passes, a fresh lo in
+  // pass 1, 16 acc + lo at the end -- 12 doublings and three merges.  (This walk does not fold the sign: it is not the default look-up.)
   // Window-major with one accumulator (rounds 2 - 4) issued 15 LDS-DMA loads and two barriers per addition: 21 % of a wavefront's walk was spent issuing them
   // (profiles/r04_ab_experiments.txt, block t).  The kernel needs 229 VGPRs this way (249 before: the compiler keeps fewer temporaries alive across the shorter
   // loop body), +2 % on the term kernel at K = 50, +1 - 3 % on the step.  Four accumulators (every row staged once) would need ~72 more registers.
@@ -601,15 +629,21 @@ __device__ __forceinline__ void comb_group_block(uint32_t i0, uint32_t n_g, cons
   };
 #pragma unroll 1
   for (int pass = 0; pass < 2; ++pass) {
-    if (live && pass) { ge_double4(acc); ge_double4(lo); }
-    uint32_t alo = pass ? dlo[2] : dlo[3], ahi = pass ? dhi[2] : dhi[3];     // the 16 nibbles of the hi accumulator's window
-    uint32_t blo = pass ? dlo[0] : dlo[1], bhi = pass ? dhi[0] : dhi[1];     // ... and of the lo accumulator's
+    if (live && pass) {                                              // acc = 16 (16 S3 + S2)
+      ge_double4(acc);
+      ge_cached c;
+      ge_to_cached(c, lo);
+      ge_add_cached(acc, acc, c);
+      ge_double4(acc);
+    }
+    uint32_t alo = pass ? dlo[1] : dlo[3], ahi = pass ? dhi[1] : dhi[3];     // the 16 nibbles of the window `acc` takes
+    uint32_t blo = pass ? dlo[0] : dlo[2], bhi = pass ? dhi[0] : dhi[2];     // ... and of the one `lo` takes
 #pragma unroll 1
     for (int j = 0; j < 16; ++j) {
       asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");      // this step's rows have landed, for every wavefront's part
       ge_cached sel;
       uint32_t neg = 0;
-      const bool first = pass == 0 && j == 0;                        // (uniform) the first entry of either chain is its accumulator
+      const bool first = pass == 0 && j == 0;                        // (uniform) the first entry of a chain is its accumulator
       if (live) {
         pick(alo, ahi, sel, neg);
         ge_cached_cneg(sel, neg);
@@ -621,26 +655,25 @@ __device__ __forceinline__ void comb_group_block(uint32_t i0, uint32_t n_g, cons
       if (pass == 0 || j != 15) issue((uint32_t)((j + 1) & 15));   // next step's rows arrive during the second addition
       if (live) {
         ge_cached_cneg(sel, neg);
-        if (first) ge_from_cached(lo, sel);
+        if (j == 0) ge_from_cached(lo, sel);                       // (either pass: S2's chain, then S0's)
         else ge_add_cached(lo, lo, sel);
       }
     }
   }
   if (live) {
-    ge_double4(acc);
-    ge_double4(acc);                                               // 256 hi
+    ge_double4(acc);                                               // 16 (256 S3 + 16 S2 + S1) + S0
     ge_cached c;
     ge_to_cached(c, lo);
     ge_add_cached(acc, acc, c);
   }
-  if (live) {
+  if (live && !no_carry) {
     ge_cached sel, c;
     ge_cached_identity(sel);
     load_comb_entry(c, comb + (size_t)slot * cfg::ENTRIES + 8 * 16);     // carry out of bit 255: 2^256 * P
     ge_cached_cmov(sel, c, top);
     ge_add_cached(acc, acc, sel);
-    store_ext(partial + t, acc);
   }
+  if (live) store_ext(partial + t, acc);
 }
 
 // ---- grouped comb terms, look-up on the lane crossbar (round 5): constant time BY CONSTRUCTION ------------------------------------------
@@ -673,6 +706,7 @@ __device__ __forceinline__ void comb_group_xbar(uint32_t i0, uint32_t n_g, const
                                                 const uint32_t* __restrict__ pidx, const uint32_t* __restrict__ slot_of,
                                                 const dev_ext* __restrict__ comb, dev_ext* __restrict__ partial, uint4* lds, bool no_carry = false) {
   using cfg = comb_cfg<16>;
+  const bool fold = no_carry;                                      // (uniform) a call that vouches for reduced scalars: no carry tail AND the sign fold
   constexpr uint32_t NONE = 0xffffffffu;
   const uint32_t tid = threadIdx.x, lane = tid & 63u;
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
@@ -720,13 +754,16 @@ __device__ __forceinline__ void comb_group_xbar(uint32_t i0, uint32_t n_g, const
     }
   };
   // the scalar: signed radix-16 digits nibble - 8; D[w] = the 16 nibbles window w of the 16 teeth, tooth 0 lowest
-  uint32_t dlo[cfg::WINDOWS], dhi[cfg::WINDOWS], top = 0;
+  // fold (uniform; the call vouches for reduced scalars): the digits of min(s, l - s) in the recoding of sc_fold_recode16 -- tooth 15 has no window 3
+  // (nibble 63) and its window 2 (nibble 62) is read as it stands; the sum is negated at the end where l - s was walked
+  uint32_t dlo[cfg::WINDOWS], dhi[cfg::WINDOWS], top = 0, flip = 0;
   {
     uint32_t sc[8], e[8];
 #pragma unroll
     for (int q = 0; q < 8; ++q) sc[q] = 0;
     if (live) load_vec<2>(sc, scalars + 32 * (size_t)t);
-    sc_add_pattern(e, top, sc, 0x88888888u);
+    if (fold) flip = sc_fold_recode16(e, sc);
+    else sc_add_pattern(e, top, sc, 0x88888888u);
 #pragma unroll
     for (int w = 0; w < cfg::WINDOWS; ++w) {
       uint32_t lo = 0, hi = 0;
@@ -738,18 +775,20 @@ __device__ __forceinline__ void comb_group_xbar(uint32_t i0, uint32_t n_g, const
       dlo[w] = lo; dhi[w] = hi;
     }
   }
-  // two accumulators as in comb_group_block: `acc` collects windows 3 and 2, `lo` windows 1 and 0; a staged row serves two additions
+  // Two accumulators, two passes over the rows, a staged row serving two additions (comb_group_block), paired in HORNER order: pass 0 gives acc = S3 and
+  // lo = S2 (S_w = the sum over the teeth of window w's entries), then acc = 16 (16 acc + lo); pass 1 adds S1 to acc and collects S0 in a fresh lo; the
+  // result is 16 acc + lo.  12 doublings per term and three merges, where the pairing (3,1), (2,0) with 256 acc + lo at the end took 16.
   ge_p3 acc, lo;
   ge_identity(acc);
   ge_identity(lo);
   issue(0);
   const uint32_t run8 = (run & (XBAR_RUNS - 1u)) * 8u;
-  auto pick = [&](uint32_t& c0, uint32_t& c1, ge_cached& sel, uint32_t& neg) {      // EVERY lane runs this: a crossbar source must be an active lane
+  auto pick = [&](uint32_t& c0, uint32_t& c1, ge_cached& sel, uint32_t& neg, bool raw) {      // EVERY lane runs this: a crossbar source must be an active lane
     const uint32_t nib = c0 & 15u;
     c0 = __builtin_amdgcn_alignbit(c1, c0, 4);
     c1 >>= 4;
-    neg = (uint32_t)(nib < 8u);
-    const uint32_t mag = neg ? 8u - nib : nib - 8u;              // 0..8
+    neg = raw ? 0u : (uint32_t)(nib < 8u);                       // raw (uniform): the digit as it stands, the top one of a folded scalar
+    const uint32_t mag = raw ? nib : (neg ? 8u - nib : nib - 8u);      // 0..8
     const uint32_t nz = (uint32_t)(mag != 0u);
     const int src = (int)((run8 + mag - nz) << 2);               // lane 8 run + mag - 1 (entry 1 for a zero digit: masked below)
     uint32_t wd[36];
@@ -767,34 +806,42 @@ __device__ __forceinline__ void comb_group_xbar(uint32_t i0, uint32_t n_g, const
   };
 #pragma unroll 1
   for (int pass = 0; pass < 2; ++pass) {
-    if (pass) { ge_double4(acc); ge_double4(lo); }
-    uint32_t alo = pass ? dlo[2] : dlo[3], ahi = pass ? dhi[2] : dhi[3];     // the 16 nibbles of the hi accumulator's window
-    uint32_t blo = pass ? dlo[0] : dlo[1], bhi = pass ? dhi[0] : dhi[1];     // ... and of the lo accumulator's
+    if (pass) {                                                      // acc = 16 (16 S3 + S2)
+      ge_double4(acc);
+      ge_cached c;
+      ge_to_cached(c, lo);
+      ge_add_cached(acc, acc, c);
+      ge_double4(acc);
+    }
+    uint32_t alo = pass ? dlo[1] : dlo[3], ahi = pass ? dhi[1] : dhi[3];     // the 16 nibbles of the window `acc` takes
+    uint32_t blo = pass ? dlo[0] : dlo[2], bhi = pass ? dhi[0] : dhi[2];     // ... and of the one `lo` takes
 #pragma unroll 1
     for (int j = 0; j < 16; ++j) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // this step's pairs have landed in this wavefront's slots
       ge_cached sel;
       uint32_t neg = 0;
-      const bool first = pass == 0 && j == 0;                        // (uniform) the first entry of either chain is its accumulator: ge_from_cached
-      pick(alo, ahi, sel, neg);
-      ge_cached_cneg(sel, neg);
-      if (first) ge_from_cached(acc, sel);
-      else ge_add_cached(acc, acc, sel);
-      pick(blo, bhi, sel, neg);
+      const bool top_tooth = fold && pass == 0 && j == 15;           // (uniform) nibbles 63 and 62 of a folded scalar: no addition / the digit as it stands
+      if (!top_tooth) {
+        pick(alo, ahi, sel, neg, false);
+        ge_cached_cneg(sel, neg);
+        if (pass == 0 && j == 0) ge_from_cached(acc, sel);           // (uniform) the first entry of a chain is its accumulator
+        else ge_add_cached(acc, acc, sel);
+      }
+      pick(blo, bhi, sel, neg, top_tooth);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");             // every slot has been read: the next row may overwrite them
       if (pass == 0 || j != 15) issue((uint32_t)((j + 1) & 15));      // ... and arrives during the second addition
       ge_cached_cneg(sel, neg);
-      if (first) ge_from_cached(lo, sel);
+      if (j == 0) ge_from_cached(lo, sel);                           // (either pass: S2's chain, then S0's)
       else ge_add_cached(lo, lo, sel);
     }
   }
-  ge_double4(acc);
-  ge_double4(acc);                                                 // 256 hi
+  ge_double4(acc);                                                 // 16 (256 S3 + 16 S2 + S1) + S0
   {
     ge_cached c;
     ge_to_cached(c, lo);
     ge_add_cached(acc, acc, c);
   }
+  if (fold) ge_cneg(acc, flip);
   if (live && !no_carry) {
     ge_cached sel, c;
     ge_cached_identity(sel);
@@ -851,9 +898,14 @@ template <bool CT>
 __device__ __forceinline__ void term_ladder16(uint32_t t, const uint8_t* __restrict__ scalars, const dev_affine* __restrict__ pt,
                                               uint4* __restrict__ tbl /* this lane's slot 0 of its wavefront group */, dev_ext* __restrict__ partial, uint32_t* ecol,
                                               bool no_carry = false) {
-  uint32_t s[8], e[8], top;
+  // no_carry (uniform; the call vouches for reduced scalars): the constant-time ladder FOLDS as well: min(s, l - s) in the recoding of sc_fold_recode16.  The walk
+  // STARTS at nibble 62, whose digit 0 .. 8 is read as it stands and whose entry is the accumulator: 62 x (4 doublings + addition) follow instead of 64
+  // on an accumulator that starts as the identity.  The sum is negated where l - s was walked.
+  const bool folded = CT && no_carry;
+  uint32_t s[8], e[8], top = 0, flip = 0;
   load_vec<2>(s, scalars + 32 * (size_t)t);
-  sc_add_pattern(e, top, s, 0x88888888u);                       // signed radix-16 digits: nibble - 8 in [-8, 7]
+  if (folded) flip = sc_fold_recode16(e, s);
+  else sc_add_pattern(e, top, s, 0x88888888u);                  // signed radix-16 digits: nibble - 8 in [-8, 7]
 #pragma unroll
   for (int j = 0; j < 8; ++j) ecol[256 * j] = e[j];             // this lane's LDS column (see term_comb)
   ge_p3 acc;
@@ -885,11 +937,18 @@ __device__ __forceinline__ void term_ladder16(uint32_t t, const uint8_t* __restr
       ge_from_cached(acc, sel);                                 // (identity + sel without the addition)
     }
   }
+  if (folded) {
+    ge_cached sel;
+    ladder_select<CT>(sel, tbl, ecol[256 * 7] >> 24);           // nibble 62 as it stands (nibble 63 is empty): 0 .. 8
+    ge_from_cached(acc, sel);
+  }
 #pragma unroll 1
   for (int j = 7; j >= 0; --j) {
     uint32_t cur = ecol[256 * j];
+    int k = 0;
+    if (folded && j == 7) { cur <<= 8; k = 2; }                 // (uniform) the walk goes on at nibble 61
 #pragma unroll 1
-    for (int k = 0; k < 8; ++k) {
+    for (; k < 8; ++k) {
       ge_double4(acc);
       const uint32_t nib = cur >> 28;
       cur <<= 4;
@@ -901,6 +960,7 @@ __device__ __forceinline__ void term_ladder16(uint32_t t, const uint8_t* __restr
       ge_add_cached(acc, acc, sel);
     }
   }
+  if (folded) ge_cneg(acc, flip);
   store_ext(partial + t, acc);
 }
 

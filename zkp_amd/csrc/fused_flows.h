@@ -1123,6 +1123,9 @@ int prove_core(zkp_ctx* c, const fused_plan& pl, const prove_inter& o, size_t ws
   if (o.end + terms_path_ws(n_points, N * T, N * nc, tk) > ws_bound)
     return fail(ZKP_ERR_ARG, "internal: prove_core's term path does not fit the workspace its caller sized");
   tk.throughput = throughput;
+  // every term operand of this flow is a blinding reduced mod l (sc_from_wide), halved mod l or not, or comes out of k_halve_scalars (reduced as well): below
+  // 2^253, so the signed recoding of the walks cannot carry out of bit 255.  Said before the point phase: its table builders leave the carry tooth out.
+  tk.canonical = true;
   if (pl.d_order) { tk.map.N = N; tk.map.nc = nc; tk.map.order = pl.d_order; }
   tk.stmt.toff = pl.d_tarr; tk.stmt.tpt = pl.d_tarr + nc + 1 + T; tk.stmt.N = N; tk.stmt.T = T; tk.stmt.nc = nc; tk.stmt.ns = pl.s.ns; tk.stmt.np = pl.s.np;
   tk.stmt.off = w.u32(o.off); tk.stmt.pidx = w.u32(o.pidx); tk.stmt.on = c->stmt_classify;
@@ -1161,9 +1164,6 @@ int prove_core(zkp_ctx* c, const fused_plan& pl, const prove_inter& o, size_t ws
   // the blindings are canonical (k_wide_reduce), so the halving the batched encoder wants is three instructions per limb here
   // instead of a kernel with a reduction of its own
   tk.prehalved = nc && terms_batched_encode(c, N * T, N * nc, tk.throughput);
-  // every term operand below is a blinding reduced mod l (sc_from_wide), halved mod l or not, or comes out of k_halve_scalars (reduced as well): below
-  // 2^253, so the signed recoding of the walks cannot carry out of bit 255
-  tk.canonical = true;
   if (m && std::max(m, T) <= 256) {                     // (one launch; every 64-byte string reduced once)
     const uint32_t P = 256 / std::max(m, T);
     hipLaunchKernelGGL(k_blind_scalars, dim3((N + P - 1) / P), dim3(256), 0, c->stream, N, T, m, P, pl.d_tarr + nc + 1, w.u8(o.wide), w.u8(o.blind), w.u8(o.sc),

@@ -307,6 +307,29 @@ ZKP_HD uint32_t sc_fold_sign(uint32_t s[8]) {
   return fold ? 1u : 0u;
 }
 
+// The sign fold for the signed radix-16 walks (comb_tables.h: term_comb, comb_group_xbar, term_ladder16) of a scalar the caller vouches is reduced
+// (at most l).  f = min(s, l - s) <= (l - 1) / 2 = 2^251 + (delta - 1) / 2 with delta = l - 2^252 < 2^125; e = f + K62 with K62 = sum_{i < 62} 8 * 16^i
+// puts the offset on nibbles 0 .. 61 only:
+//     nibble i < 62 of e:  the signed digit nibble - 8 in [-8, 7], as in the unfolded recoding
+//     e >> 248:            the digit of nibble 62 as it stands, 0 .. 8 (every row has an entry 8); nibble 63 does not exist.
+// K62 < 0.534 * 2^248.  For f >= 2^251 the bits 125 .. 250 of f are zero, so the offsets cannot carry into bit 248 and the top digit is 8; below
+// 2^251 the sum stays under 8.534 * 2^248.  Returns 1 where l - s was taken: the caller negates the sum of the walk (ge_cneg).
+constexpr uint32_t SC_FOLD16_TOP_NIBBLE = 62;
+ZKP_HD uint32_t sc_fold_recode16(uint32_t e[8], const uint32_t s[8]) {
+  uint32_t f[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) f[i] = s[i];
+  const uint32_t flip = sc_fold_sign(f);
+  uint64_t c = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    c += (uint64_t)f[i] + (i < 7 ? 0x88888888u : 0x00888888u);
+    e[i] = (uint32_t)c;
+    c >>= 32;
+  }
+  return flip;
+}
+
 // r = a / 2 mod l for any 256-bit a (reduced first): (a + (a odd ? l : 0)) >> 1
 ZKP_HD void sc_halve(sc& r, const sc& a) {
   sc t;

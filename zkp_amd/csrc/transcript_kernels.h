@@ -347,7 +347,7 @@ __global__ void __launch_bounds__(2 * TR_BLOCK, 2)
 k_tables_transcript_pc(uint32_t tr_blocks, const tr_op* __restrict__ prog, uint32_t n_ops, const uint64_t* __restrict__ tables, uint32_t N, const tr_bufs bufs,
                        uint8_t* __restrict__ ts, uint32_t* __restrict__ saved, uint32_t* __restrict__ failed, uint32_t tail,
                        const uint32_t* __restrict__ n_slots, uint32_t max_tables, const uint32_t* __restrict__ slot_pt,
-                       const dev_affine* __restrict__ pts, dev_ext* __restrict__ comb) {
+                       const dev_affine* __restrict__ pts, dev_ext* __restrict__ comb, uint32_t no_carry) {
   __shared__ uint32_t S[2 * 36 * 64];                      // two transcript states (2 x 25 x 64 words), or the producer's double-buffered hand-over
   static_assert(2 * 36 * 64 >= 2 * 25 * TR_BLOCK, "LDS of k_tables_transcript_pc");
   const uint32_t wave = threadIdx.x >> 6, trb = (tr_blocks + 1) / 2;
@@ -355,7 +355,7 @@ k_tables_transcript_pc(uint32_t tr_blocks, const tr_op* __restrict__ prog, uint3
     const uint32_t bid = 2 * blockIdx.x + wave;
     if (bid < tr_blocks) transcript_pair_block(bid, S + wave * 25 * TR_BLOCK, prog, n_ops, tables, N, bufs, ts, saved, failed, tail);
   } else {
-    comb_table_pc<TEETH>((blockIdx.x - trb) * 64u, n_slots, max_tables, slot_pt, pts, comb, S);
+    comb_table_pc<TEETH>((blockIdx.x - trb) * 64u, n_slots, max_tables, slot_pt, pts, comb, S, no_carry);
   }
 }
 
@@ -364,14 +364,14 @@ template <int TEETH>
 __global__ void __launch_bounds__(2 * TR_BLOCK, 2)
 k_tables_chain_pc(uint32_t tr_blocks, const tr_steps_dev p, const uint32_t* __restrict__ img32, uint32_t N, const tr_bufs bufs, uint8_t* __restrict__ ts,
                   uint32_t* __restrict__ saved, const uint32_t* __restrict__ n_slots, uint32_t max_tables, const uint32_t* __restrict__ slot_pt,
-                  const dev_affine* __restrict__ pts, dev_ext* __restrict__ comb) {
+                  const dev_affine* __restrict__ pts, dev_ext* __restrict__ comb, uint32_t no_carry) {
   __shared__ uint32_t S[2 * 36 * 64];
   const uint32_t wave = threadIdx.x >> 6, trb = (tr_blocks + 1) / 2;
   if (blockIdx.x < trb) {
     const uint32_t bid = 2 * blockIdx.x + wave;
     if (bid < tr_blocks) transcript_chain_block(bid, S + wave * 25 * TR_BLOCK, p, img32, N, bufs, ts, saved);
   } else {
-    comb_table_pc<TEETH>((blockIdx.x - trb) * 64u, n_slots, max_tables, slot_pt, pts, comb, S);
+    comb_table_pc<TEETH>((blockIdx.x - trb) * 64u, n_slots, max_tables, slot_pt, pts, comb, S, no_carry);
   }
 }
 

@@ -250,7 +250,7 @@ k_terms_split(const uint8_t* __restrict__ scalars, const uint32_t* __restrict__ 
       if constexpr (LOOKUP == LOOKUP_XBAR)
         comb_group_xbar((vb - ladder_blocks - comb_blocks) * XBAR_BLOCK_TERMS, n_group, list + class_start[CLASS_GROUP], scalars, pidx, slot_of, comb, partial, hot_lds, no_carry != 0);
       else
-        comb_group_block((vb - ladder_blocks - comb_blocks) * 256u, n_group, list + class_start[CLASS_GROUP], scalars, pidx, slot_of, comb, partial, hot_lds);
+        comb_group_block((vb - ladder_blocks - comb_blocks) * 256u, n_group, list + class_start[CLASS_GROUP], scalars, pidx, slot_of, comb, partial, hot_lds, no_carry != 0);
     }
     ZKP_WAVE_T1(3);
   } else {
@@ -1775,6 +1775,10 @@ int msm_terms_path(zkp_ctx* c, uint32_t n_msm, const uint32_t* d_off, const uint
     ZKP_SCHED(c, GROUPED, group_on);
     ZKP_SCHED(c, COMB_MIN, comb_min);
     // (a caller that pairs terms sized its bounds for the pairs: it only does so where the statement classifier runs)
+    // no_carry: the caller vouches that every scalar of this constant-time call is reduced mod l.  BOTH phases of a call take it from the same word of
+    // the same configuration: the point phase then builds no carry tooth (comb_tables.h), and the scalar phase reads none.  (vartime calls have nothing to
+    // hide: they never scan, and they never vouch)
+    const uint32_t no_carry = (k.canonical && flags == ZKP_CT) ? 1u : 0u;
     const bool pair_on = k.stmt.pair && flags == ZKP_VARTIME && stmt_classify_applies(k, n_terms);
     if (k.stmt.pair && !pair_on) return fail(ZKP_ERR_ARG, "paired terms outside the statement classifier");
     // (a point whose terms all ride has no use the decoder would see: such jobs decode every point, as the verifiers do anyway -- verifier.rs:87-92)
@@ -1822,23 +1826,26 @@ int msm_terms_path(zkp_ctx* c, uint32_t n_msm, const uint32_t* d_off, const uint
             const uint32_t rows = t.sd.n_img * 3u + ((t.sd.n_chk || (t.sd.tail >> 31)) ? 1u : 0u);
             if (rows) hipLaunchKernelGGL(k_transcript_assemble, dim3((t.N + TA_BLOCK - 1) / TA_BLOCK, rows), dim3(TA_BLOCK), 0, c->stream, t.sd, t.N, t.bufs, t.img, t.failed);
             hipLaunchKernelGGL(k_tables_chain_pc<16>, dim3((tr_blocks + 1) / 2 + (k.max_tables + 63) / 64), dim3(2 * TR_BLOCK), 0, c->stream, tr_blocks, t.sd,
-                               reinterpret_cast<const uint32_t*>(t.img), t.N, t.bufs, t.ts, t.saved, n_slots, k.max_tables, slot_pt, pts, comb);
+                               reinterpret_cast<const uint32_t*>(t.img), t.N, t.bufs, t.ts, t.saved, n_slots, k.max_tables, slot_pt, pts, comb, no_carry);
           } else
             hipLaunchKernelGGL(k_tables_transcript_pc<16>, dim3((tr_blocks + 1) / 2 + (k.max_tables + 63) / 64), dim3(2 * TR_BLOCK), 0, c->stream, tr_blocks, t.ops, t.n_ops,
-                               t.tables, t.N, t.bufs, t.ts, t.saved, t.failed, t.tail, n_slots, k.max_tables, slot_pt, pts, comb);
+                               t.tables, t.N, t.bufs, t.ts, t.saved, t.failed, t.tail, n_slots, k.max_tables, slot_pt, pts, comb, no_carry);
           c->pending_tr.active = false;
           prof_note(c, ZKP_K_TABLES, t.steps ? "zkp::k_tables_chain_pc<16>" : "zkp::k_tables_transcript_pc<16>");
+        } else if (no_carry) {
+          if (k.teeth == 16) hipLaunchKernelGGL(k_comb_tables_lane_nc<16>, grid1(k.max_tables, 256), dim3(256), 0, c->stream, n_slots, k.max_tables, slot_pt, pts, comb);
+          else hipLaunchKernelGGL(k_comb_tables_lane_nc<4>, grid1(k.max_tables, 256), dim3(256), 0, c->stream, n_slots, k.max_tables, slot_pt, pts, comb);
         } else if (k.teeth == 16) hipLaunchKernelGGL(k_comb_tables_lane<16>, grid1(k.max_tables, 256), dim3(256), 0, c->stream, n_slots, k.max_tables, slot_pt, pts, comb);
         else hipLaunchKernelGGL(k_comb_tables_lane<4>, grid1(k.max_tables, 256), dim3(256), 0, c->stream, n_slots, k.max_tables, slot_pt, pts, comb);
       } else {
-        if (k.teeth == 16) hipLaunchKernelGGL(k_comb_tables<16>, grid1((size_t)k.max_tables * 4, 256), dim3(256), 0, c->stream, n_slots, k.max_tables, slot_pt, pts, comb);
-        else hipLaunchKernelGGL(k_comb_tables<4>, grid1((size_t)k.max_tables * 4, 256), dim3(256), 0, c->stream, n_slots, k.max_tables, slot_pt, pts, comb);
+        if (k.teeth == 16) hipLaunchKernelGGL(k_comb_tables<16>, grid1((size_t)k.max_tables * 4, 256), dim3(256), 0, c->stream, n_slots, k.max_tables, slot_pt, pts, comb, no_carry);
+        else hipLaunchKernelGGL(k_comb_tables<4>, grid1((size_t)k.max_tables * 4, 256), dim3(256), 0, c->stream, n_slots, k.max_tables, slot_pt, pts, comb, no_carry);
       }
     }
     if ((phase & PH_POINTS) && k.max_tables && rider_ok)
       hipLaunchKernelGGL(k_rider_tables, grid1(k.max_tables, 256), dim3(256), 0, c->stream, n_slots, k.max_tables, slot_pt, pts, comb);
     if ((phase & PH_POINTS) && k.max_tables && c->kernel_names[ZKP_K_TABLES].find("k_tables_transcript") == std::string::npos && c->kernel_names[ZKP_K_TABLES].find("k_tables_chain") == std::string::npos)
-      prof_note(c, ZKP_K_TABLES, std::string((c->tables_lane < 0 ? k.throughput : c->tables_lane != 0) ? "zkp::k_comb_tables_lane<" : "zkp::k_comb_tables<") + (k.teeth == 16 ? "16>" : "4>"));
+      prof_note(c, ZKP_K_TABLES, std::string((c->tables_lane < 0 ? k.throughput : c->tables_lane != 0) ? (no_carry ? "zkp::k_comb_tables_lane_nc<" : "zkp::k_comb_tables_lane<") : "zkp::k_comb_tables<") + (k.teeth == 16 ? "16>" : "4>"));
     if (phase & PH_POINTS) prof_mark(c, ZKP_K_TABLES);        // path A: comb-table construction
     // every class starts a new block (grouped blocks take 248 terms); with comb_split the scan class has four lanes per term
     const dim3 grid((unsigned)((n_terms + XBAR_BLOCK_TERMS - 1) / XBAR_BLOCK_TERMS + 4 + HOT_SLOTS + (comb_split ? 3 * ((n_terms + 255) / 256) + 1 : 0)));
@@ -1851,11 +1858,12 @@ int msm_terms_path(zkp_ctx* c, uint32_t n_msm, const uint32_t* d_off, const uint
       }
     }
     if (phase & PH_SCALARS) {
-      // (vartime calls have nothing to hide: they never scan)
-      const uint32_t no_carry = (k.canonical && flags == ZKP_CT) ? 1u : 0u;
       ZKP_SCHED(c, NO_CARRY, no_carry);
       const int lookup = (!HOT_LDS_ROWS || c->ct_lookup == LOOKUP_XBAR) ? LOOKUP_XBAR : (flags == ZKP_CT ? c->ct_lookup : LOOKUP_LDS);
-      ZKP_SCHED(c, SIGN_FOLD, (no_carry && lookup == LOOKUP_XBAR) ? 1 : 0);      // (only the crossbar walk of the fixed-base blocks folds)
+      // sign_fold speaks for the FIXED-BASE blocks (only their crossbar walk folds) and for the grouped crossbar walk.  The comb scans and the ladder of a
+      // constant-time call fold whenever it vouches, under every look-up; with the crossbar look-up -- the only one of the shipped 7-bit build -- the word is 1
+      // exactly when every walk of the call folds.
+      ZKP_SCHED(c, SIGN_FOLD, (no_carry && lookup == LOOKUP_XBAR) ? 1 : 0);
 #define ZKP_LAUNCH_TERMS(CT_, TEETH_, LK_) launch_terms_split<CT_, TEETH_, LK_>(c, grid, k.max_ladder != 0, d_scalars, d_pidx, n_points, comb, slot_of, class_start, blk_start, list, pts, ladder, k.max_ladder, part, comb_split ? 1u : 0u, pair_on ? k.stmt.pair : (const uint32_t*)nullptr, k.stmt.T, no_carry)
       if (lookup == LOOKUP_XBAR) {
         if (flags == ZKP_CT) { if (k.teeth == 16) ZKP_LAUNCH_TERMS(true, 16, LOOKUP_XBAR); else ZKP_LAUNCH_TERMS(true, 4, LOOKUP_XBAR); }
