@@ -559,6 +559,40 @@ int zkp_transcripts_challenge_bytes_dev(zkp_ctx* ctx, uint32_t N, uint8_t* d_ts 
                                         uint8_t* d_out /*[N][len]*/);
 uint32_t zkp_strobe_pos_after_append(uint32_t strobe_pos, uint64_t label_len, uint64_t msg_len);
 
+/* (8) Scalar * basepoint and Scalar * point, batched: `&sk * &RISTRETTO_BASEPOINT_TABLE` (PublicKey::from(&SecretKey), reference
+ *     tests/sig_and_vrf_example.rs:58) and `&H * &x` (:112; the instance points of tests/zkp.rs and benches/dleq.rs) for n operands, each
+ *     with the `compress()` that follows.  One launch per call: decode, walk and encode in one lane, no CSR index arrays.  Scalars are any
+ *     32 bytes, reduced or not (the kernels reduce them mod l).  n = 0 is a no-op; a NULL buffer with n > 0, a stride other than 0 and 1, bad
+ *     flags, n > 2^31 - 1 or a NULL context is ZKP_ERR_ARG with nothing written.  The zero scalar and the identity point give 32 zero bytes
+ *     (status 0).  The plain forms take host pointers, upload, run, download and synchronise; the _dev forms take device pointers (16-byte
+ *     aligned; d_status of any alignment), enqueue on the context's stream without synchronising and may be recorded between
+ *     zkp_ctx_capture_begin / _end once the same call has run outside the capture.  Timed under ZKP_K_TERMS; zkp_ctx_last_kernels names
+ *     "k_mul_base", "k_mul_pairs<true>" (ZKP_CT) or "k_mul_pairs<false>".
+ *     zkp_mul_base: out[i] = encode((scalars[i] mod l) * B), B = the ristretto255 basepoint.  Always constant time, never fails: a walk of
+ *       36 mixed additions over a fixed-base table of B that belongs to the context -- NOT one of the 64 slots of
+ *       zkp_ctx_prepare_fixed_points: the call evicts nothing and changes no other call's schedule -- with the lane-crossbar look-up
+ *       (ZKP_OPT_CT_LOOKUP 0).  The table (269 KB) is built at the first call, which therefore must not be inside a capture (ZKP_ERR_ARG).
+ *     zkp_mul_points: out[i] = encode((scalars[i s_stride] mod l) * decode(points[i p_stride])); a stride counts elements and is 1, or 0
+ *       for one operand shared by all outputs (as zkp_sc_muladd).  flags = ZKP_CT: a signed radix-16 ladder over the point's own eight
+ *       multiples, every entry read for every digit and the wanted one kept with selects -- no branch, address or bank depends on a scalar,
+ *       and a point that does not decode is walked as the identity, so the schedule does not depend on validity either; ZKP_VARTIME: the
+ *       entry a digit names is loaded, zero digits load nothing.  status[i] = 1 and out[i] = 32 zero bytes where the point does not decode
+ *       (decompress() == None), else 0.  out may equal points when p_stride = 1.
+ *     Sizes (profiles/point_mul_bench.txt, one MI355X, stream time against zkp_msm_many on the job callers used to build; measured at 4,096,
+ *       65,536, 262,144 and 2^20 outputs, nothing in between): zkp_mul_base is faster than zkp_msm_many after
+ *       zkp_ctx_prepare_fixed_points([B]) at 4,096 and 65,536 (x 1.3, x 1.4), ties it at 262,144 and is NOT faster at 2^20 (x 0.84: an
+ *       inverse square root per output where the term path encodes with one field inversion per 65,536); with B unregistered it is x 5 - 9
+ *       faster at every size.  zkp_mul_points is faster at 4,096, 65,536 (x 1.1) and 262,144 (x 1.04, constant time) and equal at 2^20.
+ *       The calls run these kernels at every size all the same -- the synchronous call is shorter at every measured size, no index arrays
+ *       being uploaded -- and a caller bound by kernel time at 2^20 can keep zkp_msm_many_dev.  A zkp_mul_points call of more than
+ *       262,144 outputs is launched in pieces that share the 302 MB of ladder tables. */
+int zkp_mul_base(zkp_ctx* ctx, uint64_t n, const uint8_t* scalars /*[n][32]*/, uint8_t* out /*[n][32]*/);
+int zkp_mul_base_dev(zkp_ctx* ctx, uint64_t n, const uint8_t* d_scalars /*[n][32]*/, uint8_t* d_out /*[n][32]*/);
+int zkp_mul_points(zkp_ctx* ctx, uint64_t n, const uint8_t* scalars, uint32_t s_stride, const uint8_t* points, uint32_t p_stride, int flags,
+                   uint8_t* out /*[n][32]*/, uint8_t* status /*[n]*/);
+int zkp_mul_points_dev(zkp_ctx* ctx, uint64_t n, const uint8_t* d_scalars, uint32_t s_stride, const uint8_t* d_points, uint32_t p_stride, int flags,
+                       uint8_t* d_out /*[n][32]*/, uint8_t* d_status /*[n]*/);
+
 /* Timing of the last *_dev / host call on this context, measured with HIP events on the stream the
  * kernels were launched on.  kernel_ms[] is indexed by ZKP_K_*; returns the number of entries. */
 enum {

@@ -307,6 +307,25 @@ int zkp_scalar_hash_from_bytes_sha512_batch(zkp_ctx* ctx, uint64_t n, const uint
                                             uint8_t* out /*[n][32]*/);
 int zkp_scalar_random_batch(zkp_ctx* ctx, uint64_t n, const uint8_t* key /*[32] or NULL*/, uint64_t nonce, int n_threads, uint8_t* out /*[n][32]*/);
 
+/* Scalar * basepoint, Scalar * point and multiscalar products, batched (zkp_mi355x.h (8), (1)): key generation `&sk * &RISTRETTO_BASEPOINT_TABLE`
+ * (tests/sig_and_vrf_example.rs:58), `&H * &x` (:112) and RistrettoPoint::[vartime_]multiscalar_mul, each with the `compress()` that follows.
+ * Routing is that of the scalar calls above: ctx == NULL or n <= zkp_toolbox_get_host_max_terms() on the host threads (the kernels' point
+ * formulas compiled for the host: a signed radix-16 walk per output), anything else on the device; same bytes on both routes.  For
+ * zkp_multiscalar_mul_batch n is the number of terms, off[n_msm].  n = 0 is a no-op; a NULL buffer (with n > 0), n > 2^31 - 1, a stride other
+ * than 0 and 1, flags other than ZKP_CT / ZKP_VARTIME, decreasing offsets, off[0] != 0 or a point index out of range are ZKP_TB_BAD_STATEMENT
+ * with nothing written.  Scalars are any 32 bytes.
+ *   zkp_basepoint_mul_batch: out[i] = encode(scalars[i] * B); always constant time.
+ *   zkp_point_mul_batch: out[i] = encode(scalars[i s_stride] * decode(points[i p_stride])); stride 0 = one operand for all i; status[i] = 1 and
+ *     out[i] = 32 zero bytes where the point does not decode; out may equal points when p_stride = 1.  ZKP_CT keeps masked look-ups and skips
+ *     no digit on either route.
+ *   zkp_multiscalar_mul_batch: zkp_msm_many (arguments and results as there) behind the routing above. */
+int zkp_basepoint_mul_batch(zkp_ctx* ctx, uint64_t n, const uint8_t* scalars /*[n][32]*/, int n_threads, uint8_t* out /*[n][32]*/);
+int zkp_point_mul_batch(zkp_ctx* ctx, uint64_t n, const uint8_t* scalars, uint32_t s_stride, const uint8_t* points, uint32_t p_stride, int flags,
+                        int n_threads, uint8_t* out /*[n][32]*/, uint8_t* status /*[n]*/);
+int zkp_multiscalar_mul_batch(zkp_ctx* ctx, uint32_t n_msm, const uint32_t* off /*[n_msm+1]*/, const uint8_t* scalars /*[T][32]*/,
+                              const uint32_t* pidx /*[T]*/, const uint8_t* points /*[n_points][32]*/, uint32_t n_points, int flags, int n_threads,
+                              uint8_t* out /*[n_msm][32]*/, uint8_t* status /*[n_msm]*/);
+
 /* The ChaCha20 block function (RFC 8439 section 2.3; state words 12-13 = counter, 14-15 = nonce) behind the default
  * entropy / weights of the calls above (`entropy == NULL`, `weights16 == NULL`): like the reference's `thread_rng()`, a
  * ChaCha stream keyed from the operating system.  Exposed for the known-answer test. */

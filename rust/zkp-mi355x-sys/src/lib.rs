@@ -219,6 +219,13 @@ extern "C" {
     pub fn zkp_sc_random_dev(ctx: *mut zkp_ctx, n: u64, key: *const u8, nonce: u64, d_out: *mut u8) -> c_int;
     pub fn zkp_sc_hash_from_bytes_sha512(ctx: *mut zkp_ctx, n: u64, msgs: *const u8, offsets: *const u64, out: *mut u8) -> c_int;
     pub fn zkp_sc_hash_from_bytes_sha512_dev(ctx: *mut zkp_ctx, n: u64, d_msgs: *const u8, msgs_len: u64, d_offsets: *const u64, d_out: *mut u8) -> c_int;
+    // (8) Scalar * basepoint (`&sk * &RISTRETTO_BASEPOINT_TABLE`) and Scalar * point (`&H * &x`), batched, each with its compress()
+    pub fn zkp_mul_base(ctx: *mut zkp_ctx, n: u64, scalars: *const u8, out: *mut u8) -> c_int;
+    pub fn zkp_mul_base_dev(ctx: *mut zkp_ctx, n: u64, d_scalars: *const u8, d_out: *mut u8) -> c_int;
+    pub fn zkp_mul_points(ctx: *mut zkp_ctx, n: u64, scalars: *const u8, s_stride: u32, points: *const u8, p_stride: u32, flags: c_int, out: *mut u8,
+                          status: *mut u8) -> c_int;
+    pub fn zkp_mul_points_dev(ctx: *mut zkp_ctx, n: u64, d_scalars: *const u8, s_stride: u32, d_points: *const u8, p_stride: u32, flags: c_int,
+                              d_out: *mut u8, d_status: *mut u8) -> c_int;
     // (7) Merlin operations on N transcripts at any mix of positions
     pub fn zkp_transcripts_append_message(ctx: *mut zkp_ctx, n: u32, shared_initial: c_int, ts: *mut u8, label: *const c_char, msgs: *const u8,
                                           offsets: *const u64) -> c_int;
@@ -337,6 +344,12 @@ extern "C" {
                                    n_threads: c_int, out: *mut u8) -> c_int;
     pub fn zkp_scalar_hash_from_bytes_sha512_batch(ctx: *mut zkp_ctx, n: u64, msgs: *const u8, offsets: *const u64, n_threads: c_int, out: *mut u8) -> c_int;
     pub fn zkp_scalar_random_batch(ctx: *mut zkp_ctx, n: u64, key: *const u8, nonce: u64, n_threads: c_int, out: *mut u8) -> c_int;
+    // Scalar * basepoint, Scalar * point and multiscalar products behind the same routing
+    pub fn zkp_basepoint_mul_batch(ctx: *mut zkp_ctx, n: u64, scalars: *const u8, n_threads: c_int, out: *mut u8) -> c_int;
+    pub fn zkp_point_mul_batch(ctx: *mut zkp_ctx, n: u64, scalars: *const u8, s_stride: u32, points: *const u8, p_stride: u32, flags: c_int,
+                               n_threads: c_int, out: *mut u8, status: *mut u8) -> c_int;
+    pub fn zkp_multiscalar_mul_batch(ctx: *mut zkp_ctx, n_msm: u32, off: *const u32, scalars: *const u8, pidx: *const u32, points: *const u8,
+                                     n_points: u32, flags: c_int, n_threads: c_int, out: *mut u8, status: *mut u8) -> c_int;
     pub fn zkp_chacha20_block(key: *const u8, counter: u64, nonce: u64, out: *mut u8);
     // ---- proof wire format (proofs.rs:14-32 under bincode 1.x) ------------------------------------------------------------
     pub fn zkp_proof_compact_size(m: u32) -> usize;

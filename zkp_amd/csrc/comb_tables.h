@@ -894,6 +894,8 @@ __device__ __forceinline__ void ladder_select(ge_cached& sel, const uint4* __res
   }
 }
 
+// (point_mul.h: ladder16_point is this walk's folded form on a point held in registers -- the table build, the start at nibble 62 and the digit loop
+//  are the same text: a change to one belongs in the other.)
 template <bool CT>
 __device__ __forceinline__ void term_ladder16(uint32_t t, const uint8_t* __restrict__ scalars, const dev_affine* __restrict__ pt,
                                               uint4* __restrict__ tbl /* this lane's slot 0 of its wavefront group */, dev_ext* __restrict__ partial, uint32_t* ecol,

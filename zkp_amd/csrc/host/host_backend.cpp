@@ -17,6 +17,8 @@
 //   decode_check  ristretto decode.
 //   from_uniform_bytes  RFC 9496 section 4.3.4 (ristretto_from_uniform_bytes of ge25519.h: selects only, constant time), then the encoder.
 //   hash_from_bytes_sha512  sha512_range of sha512.h (the kernel's SHA-512, byte loads on the host), then from_uniform_bytes.
+//   mul_base_n / mul_points_n  zkp_mul_base / zkp_mul_points (8): the Straus walk above with one operand -- signed radix-16 digits over the
+//                 table {1..8} P, 256 doublings + 65 additions; ZKP_CT keeps the masked look-ups and skips no digit (mul_base_n always).
 //   sc_*          the scalar kernels' bodies: sc25519.h (sc_invert, sc_from_wide, sc_mont) compiled for the host, element by element.
 #include "host_backend.hpp"
 
@@ -242,6 +244,46 @@ void sc_hash_sha512_n(uint64_t n, const uint8_t* msgs, const uint64_t* offsets, 
     for (int k = 0; k < 8; ++k) { lo.v[k] = w[k]; hi.v[k] = w[8 + k]; }
     sc_from_wide(r, lo, hi);
     sc_store(out + 32 * i, r);
+  }
+}
+
+// ---- Scalar * basepoint, Scalar * point (zkp_mi355x.h (8)): one Straus walk per output over the point's table {1..8} P ----
+namespace {
+const uint8_t kBasepoint[32] = {0xe2, 0xf2, 0xae, 0x0a, 0x6a, 0xbc, 0x4e, 0x71, 0xa8, 0x84, 0xa9, 0x61, 0xc5, 0x00, 0x51, 0x5f,
+                                0x58, 0xe3, 0x0b, 0x6a, 0xa5, 0x82, 0xdd, 0x8d, 0xb6, 0xa6, 0x59, 0x45, 0xe0, 0x8d, 0x2d, 0x76};
+template <bool CT>
+inline void mul_one(uint8_t* out, const uint8_t* scalar, const Table& t) {
+  int8_t dig[1][65];
+  recode16(dig[0], scalar);
+  const Table* tp[1] = {&t};
+  ge_p3 acc;
+  straus<CT>(acc, 1, dig, tp);
+  encode(out, acc);
+}
+}  // namespace
+
+void mul_base_n(uint64_t n, const uint8_t* scalars, uint8_t* out) {
+  if (n == 0) return;
+  ge_p3 b;
+  decode(b, kBasepoint);
+  Table t;
+  build_table(t, b);
+  for (uint64_t i = 0; i < n; ++i) mul_one<true>(out + 32 * i, scalars + 32 * i, t);
+}
+
+void mul_points_n(uint64_t n, const uint8_t* scalars, uint32_t ss, const uint8_t* points, uint32_t ps, int flags, uint8_t* out, uint8_t* status) {
+  Table t;
+  uint32_t good = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    if (i == 0 || ps) {                                              // (a shared point is decoded and tabulated once)
+      ge_p3 p;
+      good = decode(p, points + 32 * i * ps);                        // before out[i] is written: out may be points
+      if (good) build_table(t, p);
+    }
+    status[i] = good ? 0 : 1;
+    if (!good) { std::memset(out + 32 * i, 0, 32); continue; }
+    if (flags == ZKP_CT) mul_one<true>(out + 32 * i, scalars + 32 * i * ss, t);
+    else mul_one<false>(out + 32 * i, scalars + 32 * i * ss, t);
   }
 }
 

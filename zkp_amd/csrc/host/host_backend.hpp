@@ -21,5 +21,10 @@ void sc_from_wide_n(uint64_t n, const uint8_t* in /*[n][64]*/, uint8_t* out /*[n
 void sc_muladd_n(uint64_t n, const uint8_t* a, uint32_t a_stride, const uint8_t* b, uint32_t b_stride, const uint8_t* c /*or NULL*/, uint32_t c_stride,
                  uint8_t* out /*[n][32]*/);
 void sc_hash_sha512_n(uint64_t n, const uint8_t* msgs, const uint64_t* offsets /*[n+1]*/, uint8_t* out /*[n][32]*/);
+// zkp_mul_base / zkp_mul_points (8): the caller has checked pointers, strides and flags; a slice of a call is a call of its own (strided
+// operands advanced by the caller).  mul_base_n is always constant time; mul_points_n with ZKP_CT keeps masked look-ups and skips no digit.
+void mul_base_n(uint64_t n, const uint8_t* scalars /*[n][32]*/, uint8_t* out /*[n][32]*/);
+void mul_points_n(uint64_t n, const uint8_t* scalars, uint32_t s_stride, const uint8_t* points, uint32_t p_stride, int flags, uint8_t* out /*[n][32]*/,
+                  uint8_t* status /*[n]*/);
 }  // namespace hostbk
 }  // namespace zkp

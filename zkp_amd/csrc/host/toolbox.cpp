@@ -980,6 +980,57 @@ int zkp_scalar_hash_from_bytes_sha512_batch(zkp_ctx* ctx, uint64_t n, const uint
   return ZKP_TB_OK;
 }
 
+// ---- Scalar * basepoint, Scalar * point, multiscalar products (zkp_mi355x.h (8), (1)): routed as the scalar calls above ----------------
+int zkp_basepoint_mul_batch(zkp_ctx* ctx, uint64_t n, const uint8_t* scalars, int n_threads, uint8_t* out) {
+  if (n == 0) return ZKP_TB_OK;
+  if (!scalars || !out || n > 0x7fffffffull) return ZKP_TB_BAD_STATEMENT;
+  if (!on_host(ctx, n)) return zkp_mul_base(ctx, n, scalars, out);
+  parallel_for((uint32_t)n, n_threads, [&](uint32_t lo, uint32_t hi) { zkp::hostbk::mul_base_n(hi - lo, scalars + 32 * (size_t)lo, out + 32 * (size_t)lo); });
+  return ZKP_TB_OK;
+}
+
+int zkp_point_mul_batch(zkp_ctx* ctx, uint64_t n, const uint8_t* scalars, uint32_t s_stride, const uint8_t* points, uint32_t p_stride, int flags, int n_threads,
+                        uint8_t* out, uint8_t* status) {
+  if (s_stride > 1 || p_stride > 1 || (flags != ZKP_CT && flags != ZKP_VARTIME)) return ZKP_TB_BAD_STATEMENT;
+  if (n == 0) return ZKP_TB_OK;
+  if (!scalars || !points || !out || !status || n > 0x7fffffffull) return ZKP_TB_BAD_STATEMENT;
+  if (!on_host(ctx, n)) return zkp_mul_points(ctx, n, scalars, s_stride, points, p_stride, flags, out, status);
+  parallel_for((uint32_t)n, n_threads, [&](uint32_t lo, uint32_t hi) {
+    zkp::hostbk::mul_points_n(hi - lo, scalars + 32 * (size_t)lo * s_stride, s_stride, points + 32 * (size_t)lo * p_stride, p_stride, flags, out + 32 * (size_t)lo,
+                              status + lo);
+  });
+  return ZKP_TB_OK;
+}
+
+// zkp_msm_many / hostbk::msm_many behind the routing (n = the number of terms) and nothing more.  The device route leaves the CSR checks to
+// zkp_msm_many, which makes them before it writes anything (its ZKP_ERR_ARG is ZKP_TB_BAD_STATEMENT here); the host route makes them here,
+// then cuts the MSMs into one contiguous range per thread: a range is a CSR job of its own once its offsets are rebased.
+int zkp_multiscalar_mul_batch(zkp_ctx* ctx, uint32_t n_msm, const uint32_t* off, const uint8_t* scalars, const uint32_t* pidx, const uint8_t* points,
+                              uint32_t n_points, int flags, int n_threads, uint8_t* out, uint8_t* status) {
+  if (flags != ZKP_CT && flags != ZKP_VARTIME) return ZKP_TB_BAD_STATEMENT;
+  if (n_msm == 0) return ZKP_TB_OK;
+  if (!off || !out || !status || off[0] != 0) return ZKP_TB_BAD_STATEMENT;
+  if (!on_host(ctx, off[n_msm])) {
+    const int rc = zkp_msm_many(ctx, n_msm, off, scalars, pidx, points, n_points, flags, out, status);
+    return rc == ZKP_ERR_ARG ? ZKP_TB_BAD_STATEMENT : rc;
+  }
+  for (uint32_t i = 0; i < n_msm; ++i)
+    if (off[i + 1] < off[i]) return ZKP_TB_BAD_STATEMENT;
+  const uint32_t n_terms = off[n_msm];
+  if (n_terms && (!scalars || !pidx || !points || n_points == 0)) return ZKP_TB_BAD_STATEMENT;
+  for (uint32_t t = 0; t < n_terms; ++t)
+    if (pidx[t] >= n_points) return ZKP_TB_BAD_STATEMENT;
+  std::atomic<int> rc{ZKP_OK};
+  parallel_for(n_msm, n_threads, [&](uint32_t lo, uint32_t hi) {
+    std::vector<uint32_t> o(hi - lo + 1);
+    for (uint32_t i = lo; i <= hi; ++i) o[i - lo] = off[i] - off[lo];
+    const int r = zkp::hostbk::msm_many(hi - lo, o.data(), scalars ? scalars + 32 * (size_t)off[lo] : nullptr, pidx ? pidx + off[lo] : nullptr, points, n_points, flags,
+                                        out + 32 * (size_t)lo, status + lo);
+    if (r) rc = r;
+  });
+  return rc.load() ? ZKP_TB_BAD_STATEMENT : ZKP_TB_OK;
+}
+
 // n x Scalar::random (64 bytes of a ChaCha20 stream through from_bytes_mod_order_wide): element i from block i of (key, nonce)
 int zkp_scalar_random_batch(zkp_ctx* ctx, uint64_t n, const uint8_t* key, uint64_t nonce, int n_threads, uint8_t* out) {
   if (n == 0) return ZKP_TB_OK;

@@ -56,6 +56,7 @@ __device__ __forceinline__ uint32_t sel8(const uint32_t w[8], int j) {
 #include "quad.h"
 #include "rowfe.h"
 #include "comb_tables.h"
+#include "point_mul.h"
 #include "transcript_kernels.h"
 #include "sha512.h"
 
@@ -1396,6 +1397,64 @@ k_sc_hash_sha512(uint32_t n, const uint8_t* __restrict__ msgs, uint64_t msgs_len
   }
 }
 
+// Scalar * basepoint and scalar * point, one launch each (zkp_mi355x.h (8)): decode, walk and encode in the lane; nothing but the ladder's
+// multiples touches memory between the operands and the encodings.
+//
+// k_mul_base: out[i] = encode(scalars[i] * B) over the context's own fixed-base table of B (hot_tables.h format, one slot).  The walk is the
+// crossbar look-up (fixed_base_xbar): every lane of a wavefront that holds an output takes part, lanes at or beyond n walk the scalar 0 and store
+// nothing; a wavefront wholly beyond n leaves.  The caller does not vouch for reduced scalars, so the kernel reduces them itself (sc_reduce: one
+// Barrett tail on a 256-bit value, ~60 instructions) and walks the sign-folded scalar in HOT_FOLD_WINDOWS windows, as the vouched fixed-base blocks of
+// k_terms_split do: the fold (~40 instructions and a conditional negation) drops one of HOT_WINDOWS look-ups and mixed additions -- 54 crossbar moves and
+// 7 field products, ~1,000 instructions -- so by instruction count the folded walk wins over the unfolded one by about 2 %.
+__global__ void __launch_bounds__(256, 2)
+k_mul_base(uint32_t n, const uint8_t* scalars, const uint4* __restrict__ table, uint8_t* out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if ((i & ~63u) >= n) return;                                   // (uniform in the wavefront)
+  uint32_t s[8], e[9];
+#pragma unroll
+  for (int q = 0; q < 8; ++q) s[q] = 0;
+  if (i < n) load_vec<2>(s, scalars + 32 * (size_t)i);
+  sc red;
+#pragma unroll
+  for (int q = 0; q < 8; ++q) red.v[q] = s[q];
+  sc_reduce(red, red);
+  const uint32_t flip = sc_fold_sign(red.v);
+  hot_recode(e, red.v, true);
+  ge_p3 acc;
+  ge_identity(acc);
+  fixed_base_xbar(acc, e, table, true);
+  ge_cneg(acc, flip);
+  uint32_t w[8];
+  ristretto_encode(w, acc);
+  if (i < n) store_vec<2>(out + 32 * (size_t)i, w);
+}
+
+// k_mul_pairs: out[i] = encode(scalars[i ss] * decode(points[i ps])), strides 0 or 1; status[i] = 1 and zeros out where the point does not decode
+// (the lane then walks the identity: the schedule of a constant-time call does not depend on validity).  One output per lane and no loop around
+// the body: inside a grid-stride loop the compiler keeps the loop's invariants in registers through the walk and spills 86 VGPRs (202 without).
+// The table of eight multiples is slot (lane number) of ladder_rw; a call of more than MUL_PAIRS_MAX_LANES outputs is launched in pieces that
+// follow each other on the stream and share that workspace.  out may be points: a lane loads its point before it stores its output.
+constexpr uint32_t MUL_PAIRS_MAX_LANES = 1024 * 256;
+template <bool CT>
+__global__ void __launch_bounds__(256, 2)
+k_mul_pairs(uint32_t n, const uint8_t* scalars, uint32_t ss, const uint8_t* points, uint32_t ps, uint4* ladder_rw, uint8_t* out, uint8_t* status) {
+  __shared__ uint32_t ecols[8 * 256];
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint4* tbl = ladder_rw + (size_t)(i >> 6) * LADDER_GROUP_UINT4 + (i & 63u);
+  uint32_t s[8], w[8];
+  load_vec<2>(s, scalars + 32 * (size_t)i * ss);
+  load_vec<2>(w, points + 32 * (size_t)i * ps);
+  ge_p3 P, acc;
+  const uint32_t ok = ristretto_decode(P, w);                    // (the identity where it fails)
+  ladder16_point<CT>(acc, s, P, tbl, ecols + threadIdx.x);
+  ristretto_encode(w, acc);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) w[k] = ok ? w[k] : 0u;
+  store_vec<2>(out + 32 * (size_t)i, w);
+  status[i] = (uint8_t)(ok ^ 1u);
+}
+
 // =============================================================================================
 // host side: context, workspace, C ABI
 // =============================================================================================
@@ -1513,6 +1572,9 @@ struct zkp_ctx {
   uint64_t hot_used[HOT_SLOTS] = {};
   uint64_t hot_tick = 0;
   uint32_t hot_nreg = 0;
+  // zkp_mul_base (section 8): the basepoint's table in one slot's format, an allocation of the context's own OUTSIDE hot_tables -- it takes no
+  // LRU slot, k_hot_match never sees it; built at the first call (ensure_base_table)
+  dev_niels* base_table = nullptr;
   // fused flows (fused_flows.h): compiled transcript programs and operand templates per (flow, statement, N, position)
   std::map<std::string, void*> fused_plans;
   // ragged calls (ragged_transcripts.h): uploaded class programs per (flow, statement, N, position) and position-free base plans per
@@ -2235,6 +2297,80 @@ bool strobe_positions_ok(const uint8_t* ts, uint32_t n) {
   return true;
 }
 
+// ---- zkp_mi355x.h (8): the launchers of k_mul_base / k_mul_pairs and the context's basepoint table ----
+// RFC 9496 section 4.1: the canonical encoding of the ristretto255 generator
+const uint8_t kBasepointEncoding[32] = {0xe2, 0xf2, 0xae, 0x0a, 0x6a, 0xbc, 0x4e, 0x71, 0xa8, 0x84, 0xa9, 0x61, 0xc5, 0x00, 0x51, 0x5f,
+                                        0x58, 0xe3, 0x0b, 0x6a, 0xa5, 0x82, 0xdd, 0x8d, 0xb6, 0xa6, 0x59, 0x45, 0xe0, 0x8d, 0x2d, 0x76};
+
+// The context's table of B for k_mul_base: k_decode_affine, k_hot_bases and k_hot_rows over ONE point into an allocation of its own, with slot
+// number 0 of that allocation.  Built once, at the first zkp_mul_base[_dev]; synchronises, so not under capture.  The registry of
+// zkp_ctx_prepare_fixed_points (hot_key / hot_used / hot_reg_*) is not touched.
+int ensure_base_table(zkp_ctx* c) {
+  if (c->base_table) return ZKP_OK;
+  if (c->capturing) return fail(ZKP_ERR_ARG, "graph capture: the basepoint table is not built yet -- run zkp_mul_base once outside the capture");
+  if (c->job.kind) return fail(ZKP_ERR_ARG, "a submitted job is pending on this context: zkp_ctx_job_wait first");
+  carve cv;
+  const size_t o_enc = cv.take(32), o_aff = cv.take(sizeof(dev_affine)), o_slot = cv.take(4), o_bases = cv.take(sizeof(dev_ext) * HOT_WINDOWS);
+  const size_t o_mult = cv.take(sizeof(dev_ext) * (size_t)HOT_WINDOWS * HOT_HALF);
+  char* tmp = nullptr;
+  dev_niels* table = nullptr;
+  HIP_TRY(hipMalloc(&tmp, cv.off));
+  hipError_t err = hipMalloc(&table, sizeof(dev_niels) * HOT_SLOT_NIELS);
+  if (err == hipSuccess) err = hipMemcpyAsync(tmp + o_enc, kBasepointEncoding, 32, hipMemcpyHostToDevice, c->stream);
+  if (err == hipSuccess) err = hipMemsetAsync(tmp + o_slot, 0, 4, c->stream);
+  if (err == hipSuccess) {
+    dev_affine* d_aff = reinterpret_cast<dev_affine*>(tmp + o_aff);
+    dev_ext* d_bases = reinterpret_cast<dev_ext*>(tmp + o_bases);
+    hipLaunchKernelGGL(k_decode_affine, dim3(1), dim3(256), 0, c->stream, 1u, reinterpret_cast<const uint8_t*>(tmp + o_enc), d_aff, (const uint32_t*)nullptr);
+    hipLaunchKernelGGL(k_hot_bases, dim3(1), dim3(64), 0, c->stream, 1u, d_aff, d_bases);
+    hipLaunchKernelGGL(k_hot_rows, grid1(HOT_WINDOWS, 64), dim3(64), 0, c->stream, 1u, reinterpret_cast<const uint32_t*>(tmp + o_slot), d_bases,
+                       reinterpret_cast<dev_ext*>(tmp + o_mult), table);
+    err = hipGetLastError();
+  }
+  const hipError_t sync_err = hipStreamSynchronize(c->stream);
+  (void)hipFree(tmp);
+  if (err != hipSuccess || sync_err != hipSuccess) {
+    if (table) (void)hipFree(table);
+    HIP_TRY(err);
+    HIP_TRY(sync_err);
+  }
+  c->base_table = table;
+  return ZKP_OK;
+}
+
+int launch_mul_base(zkp_ctx* c, uint64_t n, const uint8_t* d_scalars, uint8_t* d_out) {
+  hipLaunchKernelGGL(k_mul_base, grid1((size_t)n, 256), dim3(256), 0, c->stream, (uint32_t)n, d_scalars, reinterpret_cast<const uint4*>(c->base_table), d_out);
+  prof_note(c, ZKP_K_TERMS, "k_mul_base");
+  prof_mark(c, ZKP_K_TERMS);
+  HIP_TRY(hipGetLastError());
+  return ZKP_OK;
+}
+
+// k_mul_pairs: one table of eight multiples per lane of a launch; calls above MUL_PAIRS_MAX_LANES outputs are launched in pieces over the same tables
+inline size_t mul_pairs_ws(uint64_t n) { return (size_t)((std::min<uint64_t>(n, MUL_PAIRS_MAX_LANES) + 63) / 64) * LADDER_GROUP_UINT4 * sizeof(uint4); }
+int launch_mul_pairs(zkp_ctx* c, uint64_t n, const uint8_t* d_scalars, uint32_t ss, const uint8_t* d_points, uint32_t ps, int flags, uint4* d_ladder,
+                     uint8_t* d_out, uint8_t* d_status) {
+  for (uint64_t i0 = 0; i0 < n; i0 += MUL_PAIRS_MAX_LANES) {
+    const uint32_t m = (uint32_t)std::min<uint64_t>(n - i0, MUL_PAIRS_MAX_LANES);
+    const uint8_t* sc = d_scalars + 32 * (size_t)i0 * ss;
+    const uint8_t* pt = d_points + 32 * (size_t)i0 * ps;
+    if (flags == ZKP_CT)
+      hipLaunchKernelGGL(k_mul_pairs<true>, grid1(m, 256), dim3(256), 0, c->stream, m, sc, ss, pt, ps, d_ladder, d_out + 32 * (size_t)i0, d_status + i0);
+    else
+      hipLaunchKernelGGL(k_mul_pairs<false>, grid1(m, 256), dim3(256), 0, c->stream, m, sc, ss, pt, ps, d_ladder, d_out + 32 * (size_t)i0, d_status + i0);
+  }
+  prof_note(c, ZKP_K_TERMS, flags == ZKP_CT ? "k_mul_pairs<true>" : "k_mul_pairs<false>");
+  prof_mark(c, ZKP_K_TERMS);
+  HIP_TRY(hipGetLastError());
+  return ZKP_OK;
+}
+int mul_points_check(zkp_ctx* c, uint64_t n, uint32_t ss, uint32_t ps, int flags, bool null_buffer) {
+  const int rc = sc_call_check(c, n, null_buffer, ss <= 1 && ps <= 1);
+  if (rc) return rc;
+  if (flags != ZKP_CT && flags != ZKP_VARTIME) return fail(ZKP_ERR_ARG, "flags must be ZKP_CT or ZKP_VARTIME");
+  return ZKP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2285,6 +2421,7 @@ void zkp_ctx_destroy(zkp_ctx* c) {
   if (c->job.pin) hipHostFree(c->job.pin);
   if (c->ws) hipFree(c->ws);
   if (c->hot_tables) hipFree(c->hot_tables);
+  if (c->base_table) hipFree(c->base_table);
   if (c->hot_reg_words) hipFree(c->hot_reg_words);
   if (c->hot_reg_slot) hipFree(c->hot_reg_slot);
   if (c->hot_scratch) hipFree(c->hot_scratch);
@@ -2915,6 +3052,75 @@ int zkp_sc_hash_from_bytes_sha512_dev(zkp_ctx* c, uint64_t n, const uint8_t* d_m
   HIP_TRY(hipSetDevice(c->device));
   prof_begin(c);
   return launch_sc_hash_sha512(c, n, d_msgs, msgs_len, d_offsets, d_out);
+}
+
+// ---- (8) batched Scalar * basepoint and Scalar * point ----------------------------------------------------------------------------------
+int zkp_mul_base_dev(zkp_ctx* c, uint64_t n, const uint8_t* d_scalars, uint8_t* d_out) {
+  int rc = sc_call_check(c, n, !d_scalars || !d_out);
+  if (rc || n == 0) return rc;
+  if (!aligned16(d_scalars) || !aligned16(d_out)) return fail(ZKP_ERR_ARG, "device buffers must be 16-byte aligned");
+  HIP_TRY(hipSetDevice(c->device));
+  rc = ensure_base_table(c);
+  if (rc) return rc;
+  prof_begin(c);
+  return launch_mul_base(c, n, d_scalars, d_out);
+}
+int zkp_mul_base(zkp_ctx* c, uint64_t n, const uint8_t* scalars, uint8_t* out) {
+  int rc = sc_call_check(c, n, !scalars || !out);
+  if (rc || n == 0) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  carve cv;
+  const size_t o_sc = cv.take((size_t)n * 32);
+  const size_t o_out = cv.take((size_t)n * 32);
+  rc = ensure_ws(c, cv.off);
+  if (rc) return rc;
+  rc = ensure_base_table(c);
+  if (rc) return rc;
+  uint8_t* base = static_cast<uint8_t*>(c->ws);
+  HIP_TRY(hipMemcpyAsync(base + o_sc, scalars, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
+  prof_begin(c);
+  rc = launch_mul_base(c, n, base + o_sc, base + o_out);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return ZKP_OK;
+}
+
+int zkp_mul_points_dev(zkp_ctx* c, uint64_t n, const uint8_t* d_scalars, uint32_t s_stride, const uint8_t* d_points, uint32_t p_stride, int flags,
+                       uint8_t* d_out, uint8_t* d_status) {
+  int rc = mul_points_check(c, n, s_stride, p_stride, flags, !d_scalars || !d_points || !d_out || !d_status);
+  if (rc || n == 0) return rc;
+  if (!aligned16(d_scalars) || !aligned16(d_points) || !aligned16(d_out)) return fail(ZKP_ERR_ARG, "device buffers must be 16-byte aligned");
+  HIP_TRY(hipSetDevice(c->device));
+  rc = ensure_ws(c, mul_pairs_ws(n));
+  if (rc) return rc;
+  prof_begin(c);
+  return launch_mul_pairs(c, n, d_scalars, s_stride, d_points, p_stride, flags, static_cast<uint4*>(c->ws), d_out, d_status);
+}
+int zkp_mul_points(zkp_ctx* c, uint64_t n, const uint8_t* scalars, uint32_t s_stride, const uint8_t* points, uint32_t p_stride, int flags, uint8_t* out,
+                   uint8_t* status) {
+  int rc = mul_points_check(c, n, s_stride, p_stride, flags, !scalars || !points || !out || !status);
+  if (rc || n == 0) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t ns = s_stride ? (size_t)n : 1, np = p_stride ? (size_t)n : 1;
+  carve cv;
+  const size_t o_sc = cv.take(ns * 32);
+  const size_t o_pt = cv.take(np * 32);
+  const size_t o_out = cv.take((size_t)n * 32);
+  const size_t o_st = cv.take((size_t)n);
+  const size_t o_ladder = cv.take(mul_pairs_ws(n));
+  rc = ensure_ws(c, cv.off);
+  if (rc) return rc;
+  uint8_t* base = static_cast<uint8_t*>(c->ws);
+  HIP_TRY(hipMemcpyAsync(base + o_sc, scalars, ns * 32, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(base + o_pt, points, np * 32, hipMemcpyHostToDevice, c->stream));
+  prof_begin(c);
+  rc = launch_mul_pairs(c, n, base + o_sc, s_stride, base + o_pt, p_stride, flags, reinterpret_cast<uint4*>(base + o_ladder), base + o_out, base + o_st);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(status, base + o_st, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return ZKP_OK;
 }
 
 // ---- (7) batched Merlin operations on transcripts at any mix of positions ------------------------------------------------------------

@@ -152,6 +152,13 @@ def scalar_operands(a, b, c=None):
     return (n,) + tuple((x, 0 if x is None or (len(x) == 1 and n != 1) else 1) for x in ops)
 
 
+def mul_operands(scalars, points):
+    """The operands of scalars * points as (n, (scalars, stride), (points, stride)): uint8 [n][32] has stride 1, shape (32,) or (1, 32) is one
+    operand for every row (stride 0); both shared gives n = 1"""
+    n, (s, ss), (p, ps), _ = scalar_operands(scalars, points)
+    return n, (s, ss), (p, ps)
+
+
 class Engine:
     """One context on one GPU (HIP device ordinal `device`)."""
 
@@ -306,6 +313,23 @@ class Engine:
         _check(self._lib.zkp_sc_hash_from_bytes_sha512(self._h, n, _ptr(data), _ptr(offsets), _ptr(out)), "zkp_sc_hash_from_bytes_sha512")
         return out
 
+    # ---- Scalar * basepoint, Scalar * point, batched (include/zkp_mi355x.h section 8): encodings [n][32] out ----
+    def mul_base(self, scalars) -> np.ndarray:
+        """scalars[i] * B for every row (any 32 bytes, read mod l), constant time -> encodings [n][32]"""
+        s = _u8(scalars, 32)
+        out = np.zeros((len(s), 32), np.uint8)
+        _check(self._lib.zkp_mul_base(self._h, len(s), _ptr(s), _ptr(out)), "zkp_mul_base")
+        return out
+
+    def mul_points(self, scalars, points, flags: int = ZKP_CT) -> Tuple[np.ndarray, np.ndarray]:
+        """scalars[i] * decode(points[i]) row by row -> (encodings [n][32], status [n]: 1 and a zero row where the point does not decode); an
+        operand of shape (32,) or (1, 32) is shared by all rows (stride 0)"""
+        n, (s, ss), (p, ps) = mul_operands(scalars, points)
+        out = np.zeros((n, 32), np.uint8)
+        status = np.zeros(n, np.uint8)
+        _check(self._lib.zkp_mul_points(self._h, n, _ptr(s), ss, _ptr(p), ps, flags, _ptr(out), _ptr(status)), "zkp_mul_points")
+        return out, status
+
     def debug_sha512(self, data, offsets) -> np.ndarray:
         """the SHA-512 stage alone (test-hook build): CSR batch -> digests [n][64]"""
         self._need_hooks("zkp_debug_sha512")
@@ -412,6 +436,14 @@ class Engine:
     def scalar_hash_from_bytes_sha512_dev(self, n, d_msgs, msgs_len, d_offsets, d_out) -> None:
         """zkp_sc_hash_from_bytes_sha512_dev: arguments as hash_from_bytes_sha512_dev -> d_out [n][32] scalars"""
         _check(self._lib.zkp_sc_hash_from_bytes_sha512_dev(self._h, n, d_msgs, msgs_len, d_offsets, d_out), "zkp_sc_hash_from_bytes_sha512_dev")
+
+    def mul_base_dev(self, n, d_scalars, d_out) -> None:
+        """zkp_mul_base_dev: d_scalars [n][32] -> d_out [n][32], device pointers (16-byte aligned), queued on the context's stream"""
+        _check(self._lib.zkp_mul_base_dev(self._h, n, d_scalars, d_out), "zkp_mul_base_dev")
+
+    def mul_points_dev(self, n, d_scalars, s_stride, d_points, p_stride, flags, d_out, d_status) -> None:
+        """zkp_mul_points_dev: strides 0 or 1 in elements; d_out [n][32] (may be d_points when p_stride = 1), d_status [n] bytes"""
+        _check(self._lib.zkp_mul_points_dev(self._h, n, d_scalars, s_stride, d_points, p_stride, flags, d_out, d_status), "zkp_mul_points_dev")
 
     def transcripts_append_message_dev(self, n, shared_initial, d_ts_in, d_ts_out, label: bytes, d_msgs, msgs_len, d_offsets) -> None:
         """zkp_transcripts_append_message_dev: blobs 16-byte aligned (d_ts_out may be d_ts_in when not shared), d_offsets u64 [n + 1] 8-byte

@@ -564,6 +564,49 @@ def scalar_random(eng, n: int, key: Optional[bytes] = None, nonce: int = 0, thre
     return out
 
 
+# ---- Scalar * basepoint, Scalar * point, multiscalar products (include/zkp_toolbox.h): encodings [n][32] out; eng = None is the host backend ----
+def basepoint_mul(eng, scalars, threads: int = 0) -> np.ndarray:
+    """scalars[i] * B for every row of scalars [n][32] (any 32 bytes, read mod l): `&sk * &RISTRETTO_BASEPOINT_TABLE` and compress()
+    (PublicKey::from(&SecretKey), reference tests/sig_and_vrf_example.rs:58) for a batch; constant time"""
+    from .engine import _u8
+    s = _u8(scalars, 32)
+    out = np.zeros((len(s), 32), np.uint8)
+    _raise(lib().zkp_basepoint_mul_batch(None if eng is None else eng._h, len(s), _p(s), threads, _p(out)), "zkp_basepoint_mul_batch")
+    return out
+
+
+def point_mul(eng, scalars, points, flags: int = 1, threads: int = 0):
+    """scalars[i] * decode(points[i]) row by row (`&H * &x`, tests/sig_and_vrf_example.rs:112) -> (encodings [n][32], status [n]); status 1 and a
+    zero row where the point does not decode.  An operand of shape (32,) or (1, 32) is shared by every row.  flags = ZKP_CT (default) or
+    ZKP_VARTIME."""
+    from .engine import mul_operands
+    n, (s, ss), (p, ps) = mul_operands(scalars, points)
+    out = np.zeros((n, 32), np.uint8)
+    status = np.zeros(n, np.uint8)
+    _raise(lib().zkp_point_mul_batch(None if eng is None else eng._h, n, _p(s), ss, _p(p), ps, flags, threads, _p(out), _p(status)), "zkp_point_mul_batch")
+    return out, status
+
+
+def multiscalar_mul(eng, off, scalars, pidx, points, flags: int = 0, threads: int = 0):
+    """Engine.msm_many behind the toolbox's routing (eng = None, or at most get_host_max_terms() terms: the host backend):
+    out[i] = encode(sum over t in [off[i], off[i + 1]) of scalars[t] * decode(points[pidx[t]])) -> (out [n_msm][32], status [n_msm])"""
+    from .engine import _u8
+    off = np.ascontiguousarray(off, dtype=np.uint32).reshape(-1)
+    pidx = np.ascontiguousarray(pidx, dtype=np.uint32).reshape(-1)
+    if len(off) < 1:
+        raise ValueError("off must hold n_msm + 1 entries")
+    n_msm, n_terms = len(off) - 1, int(off[-1])
+    scalars = _u8(scalars, 32) if n_terms else np.zeros((0, 32), np.uint8)
+    points = _u8(points, 32)
+    if len(scalars) != n_terms or len(pidx) != n_terms:
+        raise ValueError("scalars / pidx length must equal off[-1]")
+    out = np.zeros((n_msm, 32), np.uint8)
+    status = np.zeros(n_msm, np.uint8)
+    _raise(lib().zkp_multiscalar_mul_batch(None if eng is None else eng._h, n_msm, _p(off), _p(scalars), _p(pidx), _p(points), len(points), flags, threads,
+                                           _p(out), _p(status)), "zkp_multiscalar_mul_batch")
+    return out, status
+
+
 # ---- pipelines and device groups (include/zkp_toolbox.h, round 4) ------------------------------------------------------
 def pinned_empty(shape, dtype=np.uint8) -> np.ndarray:
     """A numpy array in pinned host memory (zkp_host_alloc): jobs copy from / to it without staging.  The memory is freed when
