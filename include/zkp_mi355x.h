@@ -593,6 +593,55 @@ int zkp_mul_points(zkp_ctx* ctx, uint64_t n, const uint8_t* scalars, uint32_t s_
 int zkp_mul_points_dev(zkp_ctx* ctx, uint64_t n, const uint8_t* d_scalars, uint32_t s_stride, const uint8_t* d_points, uint32_t p_stride, int flags,
                        uint8_t* d_out /*[n][32]*/, uint8_t* d_status /*[n]*/);
 
+/* (9) RistrettoPoint + RistrettoPoint, -, negation and iter().sum(), batched, each with the `compress()` that follows: how the instance points of
+ *     real statements are formed (C2 - M of an ElGamal proof, N - r Y of an unblinding, a sum of public keys or of ciphertext components) without a
+ *     253-bit walk per term, which is what a zkp_msm_many job with scalars 1 and l - 1 spends.  Neither call takes ZKP_CT / ZKP_VARTIME: there is no
+ *     secret operand, and the code is free of branches on point values anyway (signs are selects, the addition formulas are the complete ones:
+ *     a[i] == b[i], a[i] == -b[i] and identity operands are no special case).  Plain forms take host pointers, upload, run, download and synchronise;
+ *     _dev forms take device pointers (points and out 16-byte aligned, the others naturally), enqueue on the context's stream and may be recorded
+ *     between zkp_ctx_capture_begin / _end once the same call has run outside the capture.  A NULL context, a NULL buffer that the call would read or
+ *     write, a stride other than 0 and 1 or an op other than the two is ZKP_ERR_ARG with nothing written.
+ *     zkp_add_points: out[i] = encode(decode(a[i a_stride]) + decode(b[i b_stride])) (ZKP_PT_ADD) or the difference (ZKP_PT_SUB); a stride counts
+ *       elements and is 1, or 0 for one operand shared by all outputs.  status[i] = 1 and out[i] = 32 zero bytes where either operand does not
+ *       decode, else 0.  out may be a or b where that operand has stride 1 (a lane loads both rows before it stores).  Negation is ZKP_PT_SUB with
+ *       a = 32 zero bytes at stride 0; doubling is a == b.  One launch ("k_add_pairs" under ZKP_K_REDUCE), one output per lane, no workspace.
+ *     zkp_sum_points: out[i] = encode(sum over t in [off[i], off[i + 1]) of +- decode(points[pidx[t]])), off[0] = 0 and non-decreasing.
+ *       pidx == NULL: term t is point t, and n_points must equal the number of terms.  neg == NULL: every term is added; else neg[t] != 0
+ *       subtracts term t.  An empty range gives 32 zero bytes and status 0.  status[i] = 1 and out[i] = zeros where a point that sum i references
+ *       does not decode; a bad point no term references flags nothing, and a flagged sum leaves its neighbours alone.  An index >= n_points is
+ *       ZKP_ERR_ARG on the host-pointer form (as are decreasing offsets and off[0] != 0) and flags its sum on the _dev form, which does not read
+ *       its arrays on the host; n_terms there is the length of pidx / neg and MUST equal d_off[n_sums], as in zkp_msm_many_dev: the launches are
+ *       sized from it, and with any other value (or offsets that decrease) the outputs are unspecified -- every access stays inside the
+ *       buffers all the same.  Every point is decoded once
+ *       (ZKP_K_DECODE); the sums are then folded in levels over the term axis (ZKP_K_REDUCE): a lane folds zkp_sum_points_group() consecutive
+ *       items, writes the sums that begin and end between its first and last run, and hands exactly two partial sums to the next level (its
+ *       first and its last run; a lane with one run hands on that run and the identity), which is therefore 1/16 as wide; the level that is left with one group finishes, and one kernel encodes (ZKP_K_COMBINE).  The launches depend on n_terms and
+ *       n_sums alone -- any mix of segment lengths, 2^20 sums of two terms or one sum of 2^20, runs the same plan.  No atomics, no lane waits
+ *       for another, every output has one writer.  zkp_ctx_last_kernels(ZKP_K_REDUCE) names one entry per level launched: "k_sum_fold<true>"
+ *       (the terms), then "k_sum_fold<false>@2", "@3", ... (the level number is appended to the kernel's name).
+ *     zkp_sum_points_group: the items one lane folds per level (32); pure arithmetic, no context.
+ *     Sizes (profiles/point_sum_bench.txt, one MI355X, stream time, min / median / max over the rounds, against zkp_msm_many on the same job with
+ *       scalars 1, variable time, alternated in one process): pairs 0.170 / 0.170 / 0.173 ms at 4,096 outputs against 0.728 / 0.731 / 0.735,
+ *       0.178 / 0.185 / 0.199 against 1.382 / 1.414 / 1.530 at 65,536, 2.64 / 2.72 / 2.86 against 21.8 / 21.9 / 22.7 at 2^20; sums of two terms
+ *       0.435 / 0.447 / 0.457 against 0.729 / 0.731 / 0.734 at 4,096, 0.600 / 0.614 / 0.638 against 1.440 / 1.456 / 1.463 at 65,536, 3.33 / 3.38 / 3.42
+ *       against 21.5 / 21.9 / 21.9 at 2^20; 64 sums of 1,024 terms 0.470 / 0.478 / 0.498 against 4.10 / 4.11 / 4.12, 1,024 such sums 1.41 / 1.43 / 1.44
+ *       against 14.3; one sum of 65,536 terms 0.480 / 0.489 / 0.499 against 194 / 251 / 252, one of 2^20 terms 1.44 / 1.46 / 1.46 against 3,686 /
+ *       3,806 / 3,977.  Faster beyond the spread at every measured shape.  For pairs zkp_add_points is the call to use: zkp_sum_points on 4,096
+ *       pairs takes 0.45 ms (three dependent fold launches) where zkp_add_points takes 0.17 ms. */
+#define ZKP_PT_ADD 0
+#define ZKP_PT_SUB 1
+int zkp_add_points(zkp_ctx* ctx, uint64_t n, const uint8_t* a, uint32_t a_stride, const uint8_t* b, uint32_t b_stride, int op,
+                   uint8_t* out /*[n][32]*/, uint8_t* status /*[n]*/);
+int zkp_add_points_dev(zkp_ctx* ctx, uint64_t n, const uint8_t* d_a, uint32_t a_stride, const uint8_t* d_b, uint32_t b_stride, int op,
+                       uint8_t* d_out /*[n][32]*/, uint8_t* d_status /*[n]*/);
+int zkp_sum_points(zkp_ctx* ctx, uint32_t n_sums, const uint32_t* off /*[n_sums+1]*/, const uint32_t* pidx /*[T] or NULL*/,
+                   const uint8_t* neg /*[T] or NULL*/, const uint8_t* points /*[n_points][32]*/, uint32_t n_points,
+                   uint8_t* out /*[n_sums][32]*/, uint8_t* status /*[n_sums]*/);
+int zkp_sum_points_dev(zkp_ctx* ctx, uint32_t n_sums, const uint32_t* d_off /*[n_sums+1]*/, const uint32_t* d_pidx /*[n_terms] or NULL*/,
+                       const uint8_t* d_neg /*[n_terms] or NULL*/, const uint8_t* d_points /*[n_points][32]*/, uint32_t n_points, uint32_t n_terms,
+                       uint8_t* d_out /*[n_sums][32]*/, uint8_t* d_status /*[n_sums]*/);
+uint32_t zkp_sum_points_group(void);
+
 /* Timing of the last *_dev / host call on this context, measured with HIP events on the stream the
  * kernels were launched on.  kernel_ms[] is indexed by ZKP_K_*; returns the number of entries. */
 enum {

@@ -326,6 +326,23 @@ int zkp_multiscalar_mul_batch(zkp_ctx* ctx, uint32_t n_msm, const uint32_t* off 
                               const uint32_t* pidx /*[T]*/, const uint8_t* points /*[n_points][32]*/, uint32_t n_points, int flags, int n_threads,
                               uint8_t* out /*[n_msm][32]*/, uint8_t* status /*[n_msm]*/);
 
+/* RistrettoPoint sums, batched (zkp_mi355x.h (9)): `P + Q`, `P - Q`, `-P` (ZKP_PT_SUB from the identity, 32 zero bytes at stride 0) and
+ * `iter().sum()`, each with the `compress()` that follows.  Routing is that of the calls above: ctx == NULL or n <= zkp_toolbox_get_host_max_terms()
+ * (for zkp_point_sum_batch n is the number of terms, off[n_sums]) on the host threads, anything else on the device; same bytes on both routes.
+ * n = 0 is a no-op.  A NULL buffer with n > 0, a stride other than 0 and 1, an op other than ZKP_PT_ADD / ZKP_PT_SUB, decreasing offsets,
+ * off[0] != 0, a point index out of range or pidx == NULL with n_points != off[n_sums] are ZKP_TB_BAD_STATEMENT with nothing written.
+ *   zkp_point_add_batch: out[i] = encode(decode(a[i a_stride]) +- decode(b[i b_stride])); status[i] = 1 and out[i] = 32 zero bytes where an operand
+ *     does not decode; out may be a or b where that operand has stride 1.
+ *   zkp_point_sum_batch: out[i] = encode(sum over t in [off[i], off[i + 1]) of +- decode(points[pidx[t]])); pidx == NULL: term t is point t;
+ *     neg == NULL: every term is added, else neg[t] != 0 subtracts term t; an empty range is 32 zero bytes with status 0; status[i] = 1 and zeros
+ *     where a point sum i references does not decode.  On the host the sums are spread over the threads by their terms, and a sum longer than a
+ *     thread's share is split into per-thread partial sums that are added at the end. */
+int zkp_point_add_batch(zkp_ctx* ctx, uint64_t n, const uint8_t* a, uint32_t a_stride, const uint8_t* b, uint32_t b_stride, int op, int n_threads,
+                        uint8_t* out /*[n][32]*/, uint8_t* status /*[n]*/);
+int zkp_point_sum_batch(zkp_ctx* ctx, uint32_t n_sums, const uint32_t* off /*[n_sums+1]*/, const uint32_t* pidx /*[T] or NULL*/,
+                        const uint8_t* neg /*[T] or NULL*/, const uint8_t* points /*[n_points][32]*/, uint32_t n_points, int n_threads,
+                        uint8_t* out /*[n_sums][32]*/, uint8_t* status /*[n_sums]*/);
+
 /* The ChaCha20 block function (RFC 8439 section 2.3; state words 12-13 = counter, 14-15 = nonce) behind the default
  * entropy / weights of the calls above (`entropy == NULL`, `weights16 == NULL`): like the reference's `thread_rng()`, a
  * ChaCha stream keyed from the operating system.  Exposed for the known-answer test. */

@@ -36,6 +36,8 @@ pub const ZKP_ERR_NO_DEVICE: c_int = -3;
 pub const ZKP_ERR_OOM: c_int = -4;
 pub const ZKP_VARTIME: c_int = 0; // RistrettoPoint::vartime_multiscalar_mul (verifier.rs:97)
 pub const ZKP_CT: c_int = 1; //      RistrettoPoint::multiscalar_mul (prover.rs:94)
+pub const ZKP_PT_ADD: c_int = 0; //  zkp_add_points: a + b
+pub const ZKP_PT_SUB: c_int = 1; //  zkp_add_points: a - b
 pub const ZKP_OPT_BATCH_ENCODE_MIN: c_int = 1;
 pub const ZKP_OPT_COMB_TEETH: c_int = 2;
 pub const ZKP_OPT_CT_SINGLE_USE_TABLES: c_int = 3;
@@ -226,6 +228,16 @@ extern "C" {
                           status: *mut u8) -> c_int;
     pub fn zkp_mul_points_dev(ctx: *mut zkp_ctx, n: u64, d_scalars: *const u8, s_stride: u32, d_points: *const u8, p_stride: u32, flags: c_int,
                               d_out: *mut u8, d_status: *mut u8) -> c_int;
+    // (9) RistrettoPoint sums: pairs (op = ZKP_PT_ADD / ZKP_PT_SUB) and CSR segments, each with its compress()
+    pub fn zkp_add_points(ctx: *mut zkp_ctx, n: u64, a: *const u8, a_stride: u32, b: *const u8, b_stride: u32, op: c_int, out: *mut u8,
+                          status: *mut u8) -> c_int;
+    pub fn zkp_add_points_dev(ctx: *mut zkp_ctx, n: u64, d_a: *const u8, a_stride: u32, d_b: *const u8, b_stride: u32, op: c_int, d_out: *mut u8,
+                              d_status: *mut u8) -> c_int;
+    pub fn zkp_sum_points(ctx: *mut zkp_ctx, n_sums: u32, off: *const u32, pidx: *const u32, neg: *const u8, points: *const u8, n_points: u32,
+                          out: *mut u8, status: *mut u8) -> c_int;
+    pub fn zkp_sum_points_dev(ctx: *mut zkp_ctx, n_sums: u32, d_off: *const u32, d_pidx: *const u32, d_neg: *const u8, d_points: *const u8,
+                              n_points: u32, n_terms: u32, d_out: *mut u8, d_status: *mut u8) -> c_int;
+    pub fn zkp_sum_points_group() -> u32;
     // (7) Merlin operations on N transcripts at any mix of positions
     pub fn zkp_transcripts_append_message(ctx: *mut zkp_ctx, n: u32, shared_initial: c_int, ts: *mut u8, label: *const c_char, msgs: *const u8,
                                           offsets: *const u64) -> c_int;
@@ -350,6 +362,11 @@ extern "C" {
                                n_threads: c_int, out: *mut u8, status: *mut u8) -> c_int;
     pub fn zkp_multiscalar_mul_batch(ctx: *mut zkp_ctx, n_msm: u32, off: *const u32, scalars: *const u8, pidx: *const u32, points: *const u8,
                                      n_points: u32, flags: c_int, n_threads: c_int, out: *mut u8, status: *mut u8) -> c_int;
+    // RistrettoPoint sums behind the same routing
+    pub fn zkp_point_add_batch(ctx: *mut zkp_ctx, n: u64, a: *const u8, a_stride: u32, b: *const u8, b_stride: u32, op: c_int, n_threads: c_int,
+                               out: *mut u8, status: *mut u8) -> c_int;
+    pub fn zkp_point_sum_batch(ctx: *mut zkp_ctx, n_sums: u32, off: *const u32, pidx: *const u32, neg: *const u8, points: *const u8, n_points: u32,
+                               n_threads: c_int, out: *mut u8, status: *mut u8) -> c_int;
     pub fn zkp_chacha20_block(key: *const u8, counter: u64, nonce: u64, out: *mut u8);
     // ---- proof wire format (proofs.rs:14-32 under bincode 1.x) ------------------------------------------------------------
     pub fn zkp_proof_compact_size(m: u32) -> usize;

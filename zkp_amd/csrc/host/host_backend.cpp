@@ -19,6 +19,8 @@
 //   hash_from_bytes_sha512  sha512_range of sha512.h (the kernel's SHA-512, byte loads on the host), then from_uniform_bytes.
 //   mul_base_n / mul_points_n  zkp_mul_base / zkp_mul_points (8): the Straus walk above with one operand -- signed radix-16 digits over the
 //                 table {1..8} P, 256 doublings + 65 additions; ZKP_CT keeps the masked look-ups and skips no digit (mul_base_n always).
+//   add_points_n / sum_points_n  zkp_add_points / zkp_sum_points (9): decode, the complete addition of ge25519.h (a sign is a conditional negation of
+//                 the cached operand), encode.  A sum is one serial chain here; the toolbox cuts long ones (sum_points_partial / _finish).
 //   sc_*          the scalar kernels' bodies: sc25519.h (sc_invert, sc_from_wide, sc_mont) compiled for the host, element by element.
 #include "host_backend.hpp"
 
@@ -285,6 +287,90 @@ void mul_points_n(uint64_t n, const uint8_t* scalars, uint32_t ss, const uint8_t
     if (flags == ZKP_CT) mul_one<true>(out + 32 * i, scalars + 32 * i * ss, t);
     else mul_one<false>(out + 32 * i, scalars + 32 * i * ss, t);
   }
+}
+
+// ---- RistrettoPoint sums (zkp_mi355x.h (9)) ----
+void add_points_n(uint64_t n, const uint8_t* a, uint32_t as, const uint8_t* b, uint32_t bs, int op, uint8_t* out, uint8_t* status) {
+  ge_p3 pa, pb;
+  ge_cached qb;
+  uint32_t ok_a = 0, ok_b = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    if (i == 0 || as) ok_a = decode(pa, a + 32 * i * as);            // both before out[i] is written: out may be a or b
+    if (i == 0 || bs) {
+      ok_b = decode(pb, b + 32 * i * bs);
+      ge_to_cached(qb, pb);
+      ge_cached_cneg(qb, (uint32_t)(op == ZKP_PT_SUB));
+    }
+    status[i] = (ok_a & ok_b) ? 0 : 1;
+    if (!(ok_a & ok_b)) { std::memset(out + 32 * i, 0, 32); continue; }
+    ge_p3 r;
+    ge_add_cached(r, pa, qb);
+    encode(out + 32 * i, r);
+  }
+}
+
+namespace {
+// acc += +- decode(points[pidx[t]]) for t in [lo, hi); returns 1 if a point did not decode (such a point adds the identity)
+inline uint32_t sum_terms(ge_p3& acc, uint32_t lo, uint32_t hi, const uint32_t* pidx, const uint8_t* neg, const uint8_t* points) {
+  uint32_t bad = 0;
+  for (uint32_t t = lo; t < hi; ++t) {
+    ge_p3 p;
+    ge_cached q;
+    bad |= decode(p, points + 32 * (size_t)(pidx ? pidx[t] : t)) ^ 1u;
+    ge_to_cached(q, p);
+    ge_cached_cneg(q, (uint32_t)(neg && neg[t]));
+    ge_add_cached(acc, acc, q);
+  }
+  return bad;
+}
+}  // namespace
+
+void sum_points_n(uint32_t n_sums, const uint32_t* off, const uint32_t* pidx, const uint8_t* neg, const uint8_t* points, uint8_t* out, uint8_t* status,
+                  uint32_t skip_longer_than) {
+  for (uint32_t i = 0; i < n_sums; ++i) {
+    if (off[i + 1] - off[i] > skip_longer_than) continue;
+    ge_p3 acc;
+    ge_identity(acc);
+    const uint32_t bad = sum_terms(acc, off[i], off[i + 1], pidx, neg, points);
+    status[i] = (uint8_t)bad;
+    if (bad) std::memset(out + 32 * (size_t)i, 0, 32);
+    else encode(out + 32 * (size_t)i, acc);
+  }
+}
+
+void sum_points_partial(uint32_t t_lo, uint32_t t_hi, const uint32_t* pidx, const uint8_t* neg, const uint8_t* points, uint8_t partial[SUM_PARTIAL_BYTES]) {
+  ge_p3 acc;
+  ge_identity(acc);
+  partial[128] = (uint8_t)sum_terms(acc, t_lo, t_hi, pidx, neg, points);
+  const fe* co[4] = {&acc.X, &acc.Y, &acc.Z, &acc.T};
+  for (int k = 0; k < 4; ++k) {
+    uint32_t w[8];
+    fe_towords(w, *co[k]);
+    std::memcpy(partial + 32 * k, w, 32);
+  }
+}
+
+void sum_points_finish(uint32_t n, const uint8_t* partials, uint8_t out[32], uint8_t* status) {
+  ge_p3 acc;
+  ge_identity(acc);
+  uint32_t bad = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint8_t* p = partials + SUM_PARTIAL_BYTES * (size_t)i;
+    ge_p3 q;
+    fe* co[4] = {&q.X, &q.Y, &q.Z, &q.T};
+    for (int k = 0; k < 4; ++k) {
+      uint32_t w[8];
+      std::memcpy(w, p + 32 * k, 32);
+      fe_fromwords(*co[k], w);
+    }
+    bad |= p[128];
+    ge_cached c;
+    ge_to_cached(c, q);
+    ge_add_cached(acc, acc, c);
+  }
+  *status = (uint8_t)(bad != 0);
+  if (bad) std::memset(out, 0, 32);
+  else encode(out, acc);
 }
 
 }  // namespace hostbk

@@ -26,5 +26,17 @@ void sc_hash_sha512_n(uint64_t n, const uint8_t* msgs, const uint64_t* offsets /
 void mul_base_n(uint64_t n, const uint8_t* scalars /*[n][32]*/, uint8_t* out /*[n][32]*/);
 void mul_points_n(uint64_t n, const uint8_t* scalars, uint32_t s_stride, const uint8_t* points, uint32_t p_stride, int flags, uint8_t* out /*[n][32]*/,
                   uint8_t* status /*[n]*/);
+// zkp_add_points / zkp_sum_points (9): the caller has checked pointers, strides, op, offsets and indices; a slice of a call is a call of its own.
+// sum_points_n: off holds ABSOLUTE term numbers (off[0] need not be 0, so a range of sums is off + lo, out + 32 lo, status + lo with pidx / neg /
+// points unchanged); sums of more than skip_longer_than terms are left alone (neither out nor status written): the caller splits those with
+// sum_points_partial -- the sum of the terms [t_lo, t_hi) as four canonical field elements X, Y, Z, T and a bad flag -- and sum_points_finish,
+// which adds n partial sums and encodes.
+constexpr size_t SUM_PARTIAL_BYTES = 129;
+void add_points_n(uint64_t n, const uint8_t* a, uint32_t a_stride, const uint8_t* b, uint32_t b_stride, int op, uint8_t* out /*[n][32]*/,
+                  uint8_t* status /*[n]*/);
+void sum_points_n(uint32_t n_sums, const uint32_t* off /*[n_sums+1]*/, const uint32_t* pidx /*or NULL*/, const uint8_t* neg /*or NULL*/,
+                  const uint8_t* points, uint8_t* out /*[n_sums][32]*/, uint8_t* status /*[n_sums]*/, uint32_t skip_longer_than = 0xffffffffu);
+void sum_points_partial(uint32_t t_lo, uint32_t t_hi, const uint32_t* pidx, const uint8_t* neg, const uint8_t* points, uint8_t partial[SUM_PARTIAL_BYTES]);
+void sum_points_finish(uint32_t n, const uint8_t* partials /*[n][SUM_PARTIAL_BYTES]*/, uint8_t out[32], uint8_t* status);
 }  // namespace hostbk
 }  // namespace zkp

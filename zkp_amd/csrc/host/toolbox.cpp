@@ -1031,6 +1031,66 @@ int zkp_multiscalar_mul_batch(zkp_ctx* ctx, uint32_t n_msm, const uint32_t* off,
   return rc.load() ? ZKP_TB_BAD_STATEMENT : ZKP_TB_OK;
 }
 
+// ---- RistrettoPoint sums (zkp_mi355x.h (9)): pairs and CSR segments behind the same routing ------------------------------------------------
+int zkp_point_add_batch(zkp_ctx* ctx, uint64_t n, const uint8_t* a, uint32_t a_stride, const uint8_t* b, uint32_t b_stride, int op, int n_threads,
+                        uint8_t* out, uint8_t* status) {
+  if (a_stride > 1 || b_stride > 1 || (op != ZKP_PT_ADD && op != ZKP_PT_SUB)) return ZKP_TB_BAD_STATEMENT;
+  if (n == 0) return ZKP_TB_OK;
+  if (!a || !b || !out || !status || n > 0x7fffffffull) return ZKP_TB_BAD_STATEMENT;
+  if (!on_host(ctx, n)) return zkp_add_points(ctx, n, a, a_stride, b, b_stride, op, out, status);
+  parallel_for((uint32_t)n, n_threads, [&](uint32_t lo, uint32_t hi) {
+    zkp::hostbk::add_points_n(hi - lo, a + 32 * (size_t)lo * a_stride, a_stride, b + 32 * (size_t)lo * b_stride, b_stride, op, out + 32 * (size_t)lo, status + lo);
+  });
+  return ZKP_TB_OK;
+}
+
+// The host route cuts the work by TERMS.  With t threads and T terms a thread's share is ceil(T / t): a sum longer than that (and than 64 terms,
+// below which a cut costs more than it saves) is split over all threads into partial sums that one thread then adds; the other sums go to the
+// threads in contiguous ranges of about equal numbers of terms.
+int zkp_point_sum_batch(zkp_ctx* ctx, uint32_t n_sums, const uint32_t* off, const uint32_t* pidx, const uint8_t* neg, const uint8_t* points, uint32_t n_points,
+                        int n_threads, uint8_t* out, uint8_t* status) {
+  if (n_sums == 0) return ZKP_TB_OK;
+  if (!off || !out || !status || off[0] != 0) return ZKP_TB_BAD_STATEMENT;
+  for (uint32_t i = 0; i < n_sums; ++i)
+    if (off[i + 1] < off[i]) return ZKP_TB_BAD_STATEMENT;
+  const uint32_t n_terms = off[n_sums];
+  if (n_terms && (!points || n_points == 0)) return ZKP_TB_BAD_STATEMENT;
+  if (!pidx && n_points != n_terms) return ZKP_TB_BAD_STATEMENT;
+  if (pidx)
+    for (uint32_t t = 0; t < n_terms; ++t)
+      if (pidx[t] >= n_points) return ZKP_TB_BAD_STATEMENT;
+  if (!on_host(ctx, n_terms)) {
+    const int rc = zkp_sum_points(ctx, n_sums, off, pidx, neg, points, n_points, out, status);
+    return rc == ZKP_ERR_ARG ? ZKP_TB_BAD_STATEMENT : rc;
+  }
+  unsigned t = n_threads > 0 ? (unsigned)n_threads : std::thread::hardware_concurrency();
+  t = std::max(1u, std::min(t, 128u));
+  const uint32_t share = (uint32_t)(((uint64_t)n_terms + t - 1) / t);
+  const uint32_t long_len = t > 1 ? std::max(share, 64u) : 0xffffffffu;
+  std::vector<uint8_t> partials;
+  for (uint32_t s = 0; s < n_sums && t > 1; ++s) {
+    const uint32_t len = off[s + 1] - off[s];
+    if (len <= long_len) continue;
+    const uint32_t piece = (len + t - 1) / t, n_pieces = (len + piece - 1) / piece;
+    partials.resize(zkp::hostbk::SUM_PARTIAL_BYTES * (size_t)n_pieces);
+    Pool::instance().run(n_pieces, [&](unsigned k) {
+      const uint32_t lo = off[s] + k * piece, hi = std::min(off[s + 1], lo + piece);
+      zkp::hostbk::sum_points_partial(lo, hi, pidx, neg, points, partials.data() + zkp::hostbk::SUM_PARTIAL_BYTES * (size_t)k);
+    });
+    zkp::hostbk::sum_points_finish(n_pieces, partials.data(), out + 32 * (size_t)s, status + s);
+  }
+  const unsigned ranges = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(t, n_sums), ((uint64_t)n_terms + 63) / 64));
+  std::vector<uint32_t> cut(ranges + 1, n_sums);
+  cut[0] = 0;
+  for (unsigned k = 1; k < ranges; ++k)          // the first sum that starts at or after term k T / ranges
+    cut[k] = std::max(cut[k - 1], (uint32_t)(std::lower_bound(off, off + n_sums, (uint32_t)((uint64_t)k * n_terms / ranges)) - off));
+  Pool::instance().run(ranges, [&](unsigned k) {
+    const uint32_t lo = cut[k], hi = cut[k + 1];
+    if (lo < hi) zkp::hostbk::sum_points_n(hi - lo, off + lo, pidx, neg, points, out + 32 * (size_t)lo, status + lo, long_len);
+  });
+  return ZKP_TB_OK;
+}
+
 // n x Scalar::random (64 bytes of a ChaCha20 stream through from_bytes_mod_order_wide): element i from block i of (key, nonce)
 int zkp_scalar_random_batch(zkp_ctx* ctx, uint64_t n, const uint8_t* key, uint64_t nonce, int n_threads, uint8_t* out) {
   if (n == 0) return ZKP_TB_OK;

@@ -57,6 +57,7 @@ __device__ __forceinline__ uint32_t sel8(const uint32_t w[8], int j) {
 #include "rowfe.h"
 #include "comb_tables.h"
 #include "point_mul.h"
+#include "point_sum.h"
 #include "transcript_kernels.h"
 #include "sha512.h"
 
@@ -1455,6 +1456,104 @@ k_mul_pairs(uint32_t n, const uint8_t* scalars, uint32_t ss, const uint8_t* poin
   status[i] = (uint8_t)(ok ^ 1u);
 }
 
+// Sums of points (zkp_mi355x.h (9); point_sum.h has the scheme).
+//
+// k_add_pairs: out[i] = encode(decode(a[i as]) + decode(b[i bs])) or the difference (sub = 1), strides 0 or 1; status[i] = 1 and zeros out where an
+// operand does not decode.  One output per lane, no loop around the body, no workspace.  out may be a or b: a lane loads both rows before it stores.
+__global__ void __launch_bounds__(256, 2)
+k_add_pairs(uint32_t n, const uint8_t* a, uint32_t as, const uint8_t* b, uint32_t bs, uint32_t sub, uint8_t* out, uint8_t* status) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t wa[8], wb[8];
+  load_vec<2>(wa, a + 32 * (size_t)i * as);
+  load_vec<2>(wb, b + 32 * (size_t)i * bs);
+  ge_p3 r;
+  const uint32_t ok = ristretto_add_pair(r, wa, wb, sub);
+  ristretto_encode(wa, r);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) wa[k] = ok ? wa[k] : 0u;
+  store_vec<2>(out + 32 * (size_t)i, wa);
+  status[i] = (uint8_t)(ok ^ 1u);
+}
+
+// k_sum_fold: one level of the segmented fold.  Lane g walks items [g SUM_GROUP, (g + 1) SUM_GROUP) of n_items.  TERMS (level 1): item j is term j --
+// the decoded point pidx[j] (j itself without pidx) with the sign neg[j], added in its niels form; its segment comes from one binary search in off for
+// the lane's first term and a walk along off from there.  An index at or beyond n_points flags the sum and reads point 0.  Otherwise item j is
+// in[j], what the level below handed on.  Runs between the group's first and last go to fin[segment]; the first and the last run go to out[2g] and
+// out[2g + 1], or to fin as well when `last` says that this launch is a single group.  Every index that reaches memory is below its array's length
+// whatever off and pidx hold (segment_of_term, the bound on the walk along off, the clamp of the point index).
+template <bool TERMS>
+__global__ void __launch_bounds__(256, 2)
+k_sum_fold(uint32_t n_items, uint32_t last, const uint32_t* __restrict__ off, uint32_t n_sums, const uint32_t* __restrict__ pidx,
+           const uint8_t* __restrict__ neg, uint32_t n_points, const dev_affine* __restrict__ pts, const sum_item* __restrict__ in,
+           sum_item* __restrict__ out, sum_item* __restrict__ fin) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t b64 = (uint64_t)g * SUM_GROUP;
+  if (b64 >= n_items) return;
+  const uint32_t b = (uint32_t)b64, e = b64 + SUM_GROUP < n_items ? b + SUM_GROUP : n_items;
+  ge_p3 acc;
+  ge_identity(acc);
+  uint32_t cur = 0, end = 0, bad = 0, runs = 0;
+  if (TERMS) {
+    cur = segment_of_term(off, n_sums, b);
+    end = off[cur + 1];
+  }
+#pragma unroll 1
+  for (uint32_t j = b; j < e; ++j) {
+    uint32_t s = cur, ibad;
+    ge_p3 q;
+    ge_niels qn;
+    if (TERMS) {
+      while (j >= end && s + 1 < n_sums) { ++s; end = off[s + 1]; }
+      const uint32_t pi = pidx ? pidx[j] : j;
+      const uint32_t oob = (uint32_t)(pi >= n_points);
+      const uint32_t valid = load_affine(q, pts + (oob ? 0u : pi));
+      ibad = oob | (valid ^ 1u);
+      ge_affine_to_niels(qn, q);
+      ge_niels_cneg(qn, neg ? (uint32_t)(neg[j] != 0) : 0u);
+    } else {
+      load_item(q, s, ibad, in + j);
+    }
+    if (j != b && s != cur) {                                     // the run of `cur` ends here
+      store_item(runs == 0 && !last ? out + 2 * (size_t)g : fin + cur, acc, cur, bad);
+      ++runs;
+      ge_identity(acc);
+      bad = 0;
+    }
+    cur = s;
+    bad |= ibad;
+    if (TERMS) ge_madd(acc, acc, qn);
+    else ge_add_p3(acc, acc, q);
+  }
+  store_item(last ? fin + cur : out + 2 * (size_t)g + (runs != 0), acc, cur, bad);
+  if (!last && runs == 0) {                                       // one run: the second item is the identity under the same segment
+    ge_identity(acc);
+    store_item(out + 2 * (size_t)g + 1, acc, cur, 0u);
+  }
+}
+
+// k_sum_encode: out[s] = the encoding of fin[s], zeros and status 1 where the sum met a point that does not decode; an empty segment has no slot
+// and is the identity (32 zero bytes, status 0).
+__global__ void __launch_bounds__(256, 2)
+k_sum_encode(uint32_t n_sums, const uint32_t* __restrict__ off, const sum_item* __restrict__ fin, uint8_t* __restrict__ out, uint8_t* __restrict__ status) {
+  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= n_sums) return;
+  uint32_t w[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) w[k] = 0;
+  uint32_t bad = 0;
+  if (off[s + 1] > off[s]) {
+    ge_p3 p;
+    uint32_t seg;
+    load_item(p, seg, bad, fin + s);
+    ristretto_encode(w, p);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) w[k] = bad ? 0u : w[k];
+  }
+  store_vec<2>(out + 32 * (size_t)s, w);
+  status[s] = (uint8_t)(bad != 0);
+}
+
 // =============================================================================================
 // host side: context, workspace, C ABI
 // =============================================================================================
@@ -2371,6 +2470,69 @@ int mul_points_check(zkp_ctx* c, uint64_t n, uint32_t ss, uint32_t ps, int flags
   return ZKP_OK;
 }
 
+// ---- zkp_mi355x.h (9): the launchers of k_add_pairs and of the segmented fold (point_sum.h) ----
+int add_points_check(zkp_ctx* c, uint64_t n, uint32_t as, uint32_t bs, int op, bool null_buffer) {
+  const int rc = sc_call_check(c, n, null_buffer, as <= 1 && bs <= 1);
+  if (rc) return rc;
+  if (op != ZKP_PT_ADD && op != ZKP_PT_SUB) return fail(ZKP_ERR_ARG, "op must be ZKP_PT_ADD or ZKP_PT_SUB");
+  return ZKP_OK;
+}
+int launch_add_pairs(zkp_ctx* c, uint64_t n, const uint8_t* d_a, uint32_t as, const uint8_t* d_b, uint32_t bs, int op, uint8_t* d_out, uint8_t* d_status) {
+  hipLaunchKernelGGL(k_add_pairs, grid1((size_t)n, 256), dim3(256), 0, c->stream, (uint32_t)n, d_a, as, d_b, bs, (uint32_t)(op == ZKP_PT_SUB), d_out, d_status);
+  prof_note(c, ZKP_K_REDUCE, "k_add_pairs");
+  prof_mark(c, ZKP_K_REDUCE);
+  HIP_TRY(hipGetLastError());
+  return ZKP_OK;
+}
+
+// The plan of a segmented sum is a function of the number of terms alone: n_1 = T, n_{k+1} = 2 ceil(n_k / SUM_GROUP) while n_k > SUM_GROUP, and the level
+// that is left with at most SUM_GROUP items is one lane.  Levels hand their items on through two buffers in turn (level 1 writes A, level 2 reads A and
+// writes B, ...): A holds n_2 items, B n_3, and every later level needs less than the buffer it is given.
+inline uint32_t sum_next_items(uint32_t n) { return 2u * (uint32_t)(((uint64_t)n + SUM_GROUP - 1) / SUM_GROUP); }
+struct sum_ws { size_t aff = 0, fin = 0, a = 0, b = 0, total = 0; };
+sum_ws sum_points_ws(uint32_t n_points, uint32_t n_terms, uint32_t n_sums, size_t reserved = 0) {
+  carve cv;
+  cv.off = reserved;
+  sum_ws w;
+  const uint32_t na = n_terms > SUM_GROUP ? sum_next_items(n_terms) : 0, nb = na > SUM_GROUP ? sum_next_items(na) : 0;
+  w.aff = cv.take(sizeof(dev_affine) * (size_t)n_points);
+  w.fin = cv.take(sizeof(sum_item) * (size_t)n_sums);
+  w.a = cv.take(sizeof(sum_item) * (size_t)na);
+  w.b = cv.take(sizeof(sum_item) * (size_t)nb);
+  w.total = cv.off;
+  return w;
+}
+int launch_sum_points(zkp_ctx* c, uint32_t n_sums, const uint32_t* d_off, const uint32_t* d_pidx, const uint8_t* d_neg, const uint8_t* d_points, uint32_t n_points,
+                      uint32_t n_terms, char* ws, const sum_ws& w, uint8_t* d_out, uint8_t* d_status) {
+  sum_item* fin = reinterpret_cast<sum_item*>(ws + w.fin);
+  if (n_terms) {
+    dev_affine* pts = reinterpret_cast<dev_affine*>(ws + w.aff);
+    hipLaunchKernelGGL(k_decode_affine, grid1(n_points, 256), dim3(256), 0, c->stream, n_points, d_points, pts, (const uint32_t*)nullptr);
+    prof_mark(c, ZKP_K_DECODE);
+    sum_item* bufs[2] = {reinterpret_cast<sum_item*>(ws + w.a), reinterpret_cast<sum_item*>(ws + w.b)};
+    const sum_item* in = nullptr;
+    uint32_t n = n_terms;
+    for (uint32_t level = 1;; ++level) {
+      const uint32_t last = n <= SUM_GROUP;
+      sum_item* out = bufs[(level - 1) & 1];
+      const dim3 grid = grid1(((size_t)n + SUM_GROUP - 1) / SUM_GROUP, SUM_FOLD_BLOCK);
+      if (level == 1)
+        hipLaunchKernelGGL(k_sum_fold<true>, grid, dim3(SUM_FOLD_BLOCK), 0, c->stream, n, last, d_off, n_sums, d_pidx, d_neg, n_points, pts, in, out, fin);
+      else
+        hipLaunchKernelGGL(k_sum_fold<false>, grid, dim3(SUM_FOLD_BLOCK), 0, c->stream, n, last, d_off, n_sums, d_pidx, d_neg, n_points, pts, in, out, fin);
+      prof_note(c, ZKP_K_REDUCE, level == 1 ? std::string("k_sum_fold<true>") : "k_sum_fold<false>@" + std::to_string(level));
+      if (last) break;
+      n = sum_next_items(n);
+      in = out;
+    }
+    prof_mark(c, ZKP_K_REDUCE);
+  }
+  hipLaunchKernelGGL(k_sum_encode, grid1(n_sums, 256), dim3(256), 0, c->stream, n_sums, d_off, fin, d_out, d_status);
+  prof_mark(c, ZKP_K_COMBINE);
+  HIP_TRY(hipGetLastError());
+  return ZKP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3119,6 +3281,101 @@ int zkp_mul_points(zkp_ctx* c, uint64_t n, const uint8_t* scalars, uint32_t s_st
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipMemcpyAsync(status, base + o_st, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return ZKP_OK;
+}
+
+// ---- (9) batched RistrettoPoint sums: pairs and CSR segments -------------------------------------------------------------------------------
+uint32_t zkp_sum_points_group(void) { return SUM_GROUP; }
+
+int zkp_add_points_dev(zkp_ctx* c, uint64_t n, const uint8_t* d_a, uint32_t a_stride, const uint8_t* d_b, uint32_t b_stride, int op, uint8_t* d_out,
+                       uint8_t* d_status) {
+  const int rc = add_points_check(c, n, a_stride, b_stride, op, !d_a || !d_b || !d_out || !d_status);
+  if (rc || n == 0) return rc;
+  if (!aligned16(d_a) || !aligned16(d_b) || !aligned16(d_out)) return fail(ZKP_ERR_ARG, "device buffers must be 16-byte aligned");
+  HIP_TRY(hipSetDevice(c->device));
+  prof_begin(c);
+  return launch_add_pairs(c, n, d_a, a_stride, d_b, b_stride, op, d_out, d_status);
+}
+int zkp_add_points(zkp_ctx* c, uint64_t n, const uint8_t* a, uint32_t a_stride, const uint8_t* b, uint32_t b_stride, int op, uint8_t* out, uint8_t* status) {
+  int rc = add_points_check(c, n, a_stride, b_stride, op, !a || !b || !out || !status);
+  if (rc || n == 0) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t na = a_stride ? (size_t)n : 1, nb = b_stride ? (size_t)n : 1;
+  carve cv;
+  const size_t o_a = cv.take(na * 32);
+  const size_t o_b = cv.take(nb * 32);
+  const size_t o_out = cv.take((size_t)n * 32);
+  const size_t o_st = cv.take((size_t)n);
+  rc = ensure_ws(c, cv.off);
+  if (rc) return rc;
+  uint8_t* base = static_cast<uint8_t*>(c->ws);
+  HIP_TRY(hipMemcpyAsync(base + o_a, a, na * 32, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(base + o_b, b, nb * 32, hipMemcpyHostToDevice, c->stream));
+  prof_begin(c);
+  rc = launch_add_pairs(c, n, base + o_a, a_stride, base + o_b, b_stride, op, base + o_out, base + o_st);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(status, base + o_st, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return ZKP_OK;
+}
+
+int zkp_sum_points_dev(zkp_ctx* c, uint32_t n_sums, const uint32_t* d_off, const uint32_t* d_pidx, const uint8_t* d_neg, const uint8_t* d_points,
+                       uint32_t n_points, uint32_t n_terms, uint8_t* d_out, uint8_t* d_status) {
+  if (!c) return fail(ZKP_ERR_ARG, "ctx is NULL");
+  if (n_sums == 0) return ZKP_OK;
+  if (!d_off || !d_out || !d_status) return fail(ZKP_ERR_ARG, "NULL device pointer");
+  if (n_terms && (!d_points || n_points == 0)) return fail(ZKP_ERR_ARG, "terms without points");
+  if (!d_pidx && n_points != n_terms) return fail(ZKP_ERR_ARG, "without pidx, n_points must equal the number of terms");
+  if (!aligned16(d_points) || !aligned16(d_out)) return fail(ZKP_ERR_ARG, "device buffers must be 16-byte aligned");
+  HIP_TRY(hipSetDevice(c->device));
+  const sum_ws w = sum_points_ws(n_points, n_terms, n_sums);
+  const int rc = ensure_ws(c, w.total);
+  if (rc) return rc;
+  prof_begin(c);
+  return launch_sum_points(c, n_sums, d_off, d_pidx, d_neg, d_points, n_points, n_terms, static_cast<char*>(c->ws), w, d_out, d_status);
+}
+int zkp_sum_points(zkp_ctx* c, uint32_t n_sums, const uint32_t* off, const uint32_t* pidx, const uint8_t* neg, const uint8_t* points, uint32_t n_points,
+                   uint8_t* out, uint8_t* status) {
+  if (!c) return fail(ZKP_ERR_ARG, "ctx is NULL");
+  if (n_sums == 0) return ZKP_OK;
+  if (!off || !out || !status) return fail(ZKP_ERR_ARG, "NULL pointer");
+  if (off[0] != 0) return fail(ZKP_ERR_ARG, "off[0] must be 0");
+  for (uint32_t i = 0; i < n_sums; ++i)
+    if (off[i + 1] < off[i]) return fail(ZKP_ERR_ARG, "off must be non-decreasing");
+  const uint32_t n_terms = off[n_sums];
+  if (n_terms && (!points || n_points == 0)) return fail(ZKP_ERR_ARG, "terms without points");
+  if (!pidx && n_points != n_terms) return fail(ZKP_ERR_ARG, "without pidx, n_points must equal the number of terms");
+  if (pidx)
+    for (uint32_t t = 0; t < n_terms; ++t)
+      if (pidx[t] >= n_points) return fail(ZKP_ERR_ARG, "pidx out of range");
+  HIP_TRY(hipSetDevice(c->device));
+  const bool with_pts = n_terms != 0;
+  carve cv;
+  const size_t o_off = cv.take((size_t)(n_sums + 1) * 4);
+  const size_t o_pidx = cv.take(pidx ? (size_t)n_terms * 4 : 0);
+  const size_t o_neg = cv.take(neg ? (size_t)n_terms : 0);
+  const size_t o_pts = cv.take(with_pts ? (size_t)n_points * 32 : 0);
+  const size_t o_out = cv.take((size_t)n_sums * 32);
+  const size_t o_st = cv.take((size_t)n_sums);
+  const sum_ws w = sum_points_ws(with_pts ? n_points : 0, n_terms, n_sums, cv.off);
+  int rc = ensure_ws(c, w.total);
+  if (rc) return rc;
+  char* base = static_cast<char*>(c->ws);
+  HIP_TRY(hipMemcpyAsync(base + o_off, off, (size_t)(n_sums + 1) * 4, hipMemcpyHostToDevice, c->stream));
+  if (n_terms) {
+    if (pidx) HIP_TRY(hipMemcpyAsync(base + o_pidx, pidx, (size_t)n_terms * 4, hipMemcpyHostToDevice, c->stream));
+    if (neg) HIP_TRY(hipMemcpyAsync(base + o_neg, neg, (size_t)n_terms, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(base + o_pts, points, (size_t)n_points * 32, hipMemcpyHostToDevice, c->stream));
+  }
+  prof_begin(c);
+  rc = launch_sum_points(c, n_sums, reinterpret_cast<uint32_t*>(base + o_off), pidx ? reinterpret_cast<uint32_t*>(base + o_pidx) : nullptr,
+                         neg ? reinterpret_cast<uint8_t*>(base + o_neg) : nullptr, reinterpret_cast<uint8_t*>(base + o_pts), n_points, n_terms, base, w,
+                         reinterpret_cast<uint8_t*>(base + o_out), reinterpret_cast<uint8_t*>(base + o_st));
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)n_sums * 32, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(status, base + o_st, (size_t)n_sums, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return ZKP_OK;
 }

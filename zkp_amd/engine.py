@@ -24,6 +24,7 @@ ZKP_OPT_WS_LIMIT_BYTES, ZKP_OPT_JOB_DEFER_D2H, ZKP_OPT_SYNC_SCHEDULE, ZKP_OPT_TR
 
 ZKP_VARTIME = 0
 ZKP_CT = 1
+ZKP_PT_ADD, ZKP_PT_SUB = 0, 1               # zkp_add_points' op
 ZKP_OPT_BATCH_ENCODE_MIN = 1
 (ZKP_OPT_COMB_TEETH, ZKP_OPT_CT_SINGLE_USE_TABLES, ZKP_OPT_TRANSCRIPT_LANES, ZKP_OPT_DEV_OVERLAP, ZKP_OPT_GROUPED_COMB, ZKP_OPT_TABLES_LANE,
  ZKP_OPT_FUSE_TABLES_TRANSCRIPT) = 2, 3, 4, 5, 6, 7, 8
@@ -157,6 +158,25 @@ def mul_operands(scalars, points):
     operand for every row (stride 0); both shared gives n = 1"""
     n, (s, ss), (p, ps), _ = scalar_operands(scalars, points)
     return n, (s, ss), (p, ps)
+
+
+def sum_operands(off, points, pidx, neg):
+    """The arrays of a segmented sum as the C ABI takes them: off uint32 [n_sums + 1], pidx uint32 [T] or None, neg uint8 [T] (0 / 1) or None,
+    points uint8 [n_points][32]; lengths that disagree with off[-1] raise"""
+    off = np.ascontiguousarray(off, dtype=np.uint32).reshape(-1)
+    if len(off) < 1:
+        raise ValueError("off must hold n_sums + 1 entries")
+    n_terms = int(off[-1])
+    points = _u8(points, 32)
+    if pidx is not None:
+        pidx = np.ascontiguousarray(pidx, dtype=np.uint32).reshape(-1)
+        if len(pidx) != n_terms:
+            raise ValueError("pidx length must equal off[-1]")
+    if neg is not None:
+        neg = np.ascontiguousarray(np.asarray(neg) != 0, dtype=np.uint8).reshape(-1)
+        if len(neg) != n_terms:
+            raise ValueError("neg length must equal off[-1]")
+    return off, pidx, neg, points
 
 
 class Engine:
@@ -330,6 +350,27 @@ class Engine:
         _check(self._lib.zkp_mul_points(self._h, n, _ptr(s), ss, _ptr(p), ps, flags, _ptr(out), _ptr(status)), "zkp_mul_points")
         return out, status
 
+    # ---- RistrettoPoint sums, batched (include/zkp_mi355x.h section 9): encodings out, status 1 and a zero row where an operand does not decode ----
+    def add_points(self, a, b, op: int = ZKP_PT_ADD) -> Tuple[np.ndarray, np.ndarray]:
+        """decode(a[i]) + decode(b[i]) (ZKP_PT_ADD) or - (ZKP_PT_SUB) row by row -> (encodings [n][32], status [n]); an operand of shape (32,) or
+        (1, 32) is shared by all rows (stride 0)"""
+        n, (a, sa), (b, sb) = mul_operands(a, b)
+        out = np.zeros((n, 32), np.uint8)
+        status = np.zeros(n, np.uint8)
+        _check(self._lib.zkp_add_points(self._h, n, _ptr(a), sa, _ptr(b), sb, op, _ptr(out), _ptr(status)), "zkp_add_points")
+        return out, status
+
+    def sum_points(self, off, points, pidx=None, neg=None) -> Tuple[np.ndarray, np.ndarray]:
+        """out[i] = encode(sum over t in [off[i], off[i + 1]) of +- decode(points[pidx[t]])) -> (out [n_sums][32], status [n_sums]); pidx = None:
+        term t is point t; neg = None: every term is added, else neg[t] != 0 subtracts term t"""
+        off, pidx, neg, points = sum_operands(off, points, pidx, neg)
+        n_sums = len(off) - 1
+        out = np.zeros((n_sums, 32), np.uint8)
+        status = np.zeros(n_sums, np.uint8)
+        _check(self._lib.zkp_sum_points(self._h, n_sums, _ptr(off), None if pidx is None else _ptr(pidx), None if neg is None else _ptr(neg), _ptr(points),
+                                        len(points), _ptr(out), _ptr(status)), "zkp_sum_points")
+        return out, status
+
     def debug_sha512(self, data, offsets) -> np.ndarray:
         """the SHA-512 stage alone (test-hook build): CSR batch -> digests [n][64]"""
         self._need_hooks("zkp_debug_sha512")
@@ -444,6 +485,15 @@ class Engine:
     def mul_points_dev(self, n, d_scalars, s_stride, d_points, p_stride, flags, d_out, d_status) -> None:
         """zkp_mul_points_dev: strides 0 or 1 in elements; d_out [n][32] (may be d_points when p_stride = 1), d_status [n] bytes"""
         _check(self._lib.zkp_mul_points_dev(self._h, n, d_scalars, s_stride, d_points, p_stride, flags, d_out, d_status), "zkp_mul_points_dev")
+
+    def add_points_dev(self, n, d_a, a_stride, d_b, b_stride, op, d_out, d_status) -> None:
+        """zkp_add_points_dev: strides 0 or 1 in elements; d_out [n][32] (may be an operand of stride 1), d_status [n] bytes"""
+        _check(self._lib.zkp_add_points_dev(self._h, n, d_a, a_stride, d_b, b_stride, op, d_out, d_status), "zkp_add_points_dev")
+
+    def sum_points_dev(self, n_sums, d_off, d_pidx, d_neg, d_points, n_points, n_terms, d_out, d_status) -> None:
+        """zkp_sum_points_dev: d_off u32 [n_sums + 1], d_pidx u32 [n_terms] or None, d_neg u8 [n_terms] or None, d_points [n_points][32] ->
+        d_out [n_sums][32], d_status [n_sums]; nothing is read on the host, the launches depend on n_terms and n_sums alone"""
+        _check(self._lib.zkp_sum_points_dev(self._h, n_sums, d_off, d_pidx, d_neg, d_points, n_points, n_terms, d_out, d_status), "zkp_sum_points_dev")
 
     def transcripts_append_message_dev(self, n, shared_initial, d_ts_in, d_ts_out, label: bytes, d_msgs, msgs_len, d_offsets) -> None:
         """zkp_transcripts_append_message_dev: blobs 16-byte aligned (d_ts_out may be d_ts_in when not shared), d_offsets u64 [n + 1] 8-byte

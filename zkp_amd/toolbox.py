@@ -607,6 +607,46 @@ def multiscalar_mul(eng, off, scalars, pidx, points, flags: int = 0, threads: in
     return out, status
 
 
+# ---- RistrettoPoint sums (include/zkp_toolbox.h): `P + Q`, `P - Q`, `-P`, `iter().sum()`, each with its compress(); eng = None is the host backend ----
+def _point_pairs(eng, a, b, op: int, threads: int):
+    from .engine import mul_operands
+    n, (a, sa), (b, sb) = mul_operands(a, b)
+    out = np.zeros((n, 32), np.uint8)
+    status = np.zeros(n, np.uint8)
+    _raise(lib().zkp_point_add_batch(None if eng is None else eng._h, n, _p(a), sa, _p(b), sb, op, threads, _p(out), _p(status)), "zkp_point_add_batch")
+    return out, status
+
+
+def point_add(eng, a, b, threads: int = 0):
+    """decode(a[i]) + decode(b[i]) row by row -> (encodings [n][32], status [n]); status 1 and a zero row where an operand does not decode.  An
+    operand of shape (32,) or (1, 32) is shared by every row."""
+    return _point_pairs(eng, a, b, 0, threads)
+
+
+def point_sub(eng, a, b, threads: int = 0):
+    """decode(a[i]) - decode(b[i]) row by row; operands and results as point_add"""
+    return _point_pairs(eng, a, b, 1, threads)
+
+
+def point_neg(eng, a, threads: int = 0):
+    """-decode(a[i]) for every row of a [n][32] (or one row of shape (32,)): the identity minus a"""
+    return _point_pairs(eng, np.zeros(32, np.uint8), a, 1, threads)
+
+
+def point_sum(eng, off, points, pidx=None, neg=None, threads: int = 0):
+    """out[i] = encode(sum over t in [off[i], off[i + 1]) of +- decode(points[pidx[t]])) -> (out [n_sums][32], status [n_sums]): `iter().sum()` for a
+    batch of ranges.  pidx = None: term t is point t.  neg = None: every term is added; else neg[t] != 0 subtracts term t.  An empty range is the
+    identity (zero bytes, status 0); status 1 and a zero row where a referenced point does not decode."""
+    from .engine import sum_operands
+    off, pidx, neg, points = sum_operands(off, points, pidx, neg)
+    n_sums = len(off) - 1
+    out = np.zeros((n_sums, 32), np.uint8)
+    status = np.zeros(n_sums, np.uint8)
+    _raise(lib().zkp_point_sum_batch(None if eng is None else eng._h, n_sums, _p(off), _p(pidx), _p(neg), _p(points), len(points), threads, _p(out),
+                                     _p(status)), "zkp_point_sum_batch")
+    return out, status
+
+
 # ---- pipelines and device groups (include/zkp_toolbox.h, round 4) ------------------------------------------------------
 def pinned_empty(shape, dtype=np.uint8) -> np.ndarray:
     """A numpy array in pinned host memory (zkp_host_alloc): jobs copy from / to it without staging.  The memory is freed when
