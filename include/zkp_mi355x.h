@@ -642,6 +642,64 @@ int zkp_sum_points_dev(zkp_ctx* ctx, uint32_t n_sums, const uint32_t* d_off /*[n
                        uint8_t* d_out /*[n_sums][32]*/, uint8_t* d_status /*[n_sums]*/);
 uint32_t zkp_sum_points_group(void);
 
+/* (10) Bounded discrete logarithms to the basepoint, batched: recover m from encode(m B), m < 2^bits -- the last step of exponential ElGamal
+ *     (C2 - x C1 = m B), of a homomorphic tally or histogram and of an opened Pedersen value.  Baby-step / giant-step over canonical encodings:
+ *     the context holds the encodings of i B, i < 2^baby_bits, and a point is searched by subtracting 2^baby_bits B per giant step.  Every
+ *     candidate is walked as a HALF (the call first multiplies each point by (l + 1) / 2), so that its bytes come from the encoder of doubled
+ *     points, whose one plain inversion is shared by a whole workgroup of candidates (Montgomery's trick as a product tree; zkp_dlog_group()
+ *     candidates per inversion) instead of an inverse square root per candidate.
+ *     VARIABLE TIME BY NATURE, unlike the constant-time calls of section 8: the duration of a call depends on the logarithms (small ones are
+ *     found by the first launch, and a launch leaves early for finished points).  The logarithm of a SECRET must not be taken where timing is
+ *     observable.  The call takes no ZKP_CT / ZKP_VARTIME flag.
+ *     zkp_dlog_base: out[i] = the k in [0, 2^bits) with encode(k B) == points[i] and status[i] = ZKP_DLOG_FOUND; status[i] = ZKP_DLOG_INVALID and
+ *       out[i] = 0 where the encoding does not decode; status[i] = ZKP_DLOG_NOT_FOUND and out[i] = 0 where no such k is in range.  k is unique
+ *       when it exists (2^bits < l).  The identity (32 zero bytes) has logarithm 0.  bits is 1 .. 48: the cost of a point that is not found
+ *       is 2^(bits - baby_bits) giant steps, and the cap keeps a mistyped bits from holding a shared GPU for hours (48 bits over a 2^22 table is
+ *       2^26 steps per point); a call whose plan needs more than 65,536 step launches (n 2^(bits - baby_bits) above 2^41 or so) is refused as well:
+ *       prepare a larger table or split the call.  n = 0 is a no-op; a NULL context, a NULL buffer with n > 0, n > 2^31 - 1 or bits outside
+ *       1 .. 48 is ZKP_ERR_ARG with nothing written.  The plain form takes host pointers, uploads, runs, downloads and synchronises; the _dev
+ *       form takes device pointers (d_points 16-byte, d_out 8-byte aligned), enqueues on the context's stream and may be recorded between
+ *       zkp_ctx_capture_begin / _end once one call of the same size or one zkp_ctx_prepare_dlog has run outside the capture (the table and the
+ *       workspace must exist).  A call on a context without a table builds the default size (2^16 rows) first.
+ *     zkp_ctx_prepare_dlog: builds the context's baby-step table for baby_bits in 4 .. 22 (else ZKP_ERR_ARG): 32 bytes per row and 16 bytes of
+ *       probe slots per row (an open-addressing table of 2^(baby_bits + 1) slots keyed by 32 bits of the encoding; a slot holds 32 more bits and
+ *       the index; a match is confirmed against the 32 bytes of the row, and a refuted match does not end the probe).  The rows are computed on
+ *       the device ("k_dlog_rows": a lane walks 16 consecutive i from (i0 / 2) B by adding (1/2) B, a workgroup encodes the doubles of one step of its
+ *       lanes with one inversion), downloaded, and the slots are filled on the host and uploaded: no device atomics.  The table belongs to the
+ *       context like the table of B behind zkp_mul_base: it takes none of the 64 slots of zkp_ctx_prepare_fixed_points and evicts nothing.
+ *       Synchronous; ZKP_ERR_ARG inside a capture.  Preparing again with another size replaces the table (graphs captured over the old one are
+ *       refused by zkp_graph_launch, as after a workspace growth); the same size again is a no-op.
+ *     zkp_dlog_baby_bits: what the context holds; 0 = none yet (or a NULL context).
+ *     zkp_dlog_group / zkp_dlog_chunk / zkp_dlog_slice_chunks(n): the plan, pure arithmetic: candidates per shared inversion (256), giant steps per
+ *       work item (32), and the chunks per point one launch of a call of n points covers (max(1, 2^20 / n)).  A work item is (point, chunk), so
+ *       one point with a large range fills the chip as well as 2^20 points with small ones; the launches follow each other on the stream in
+ *       ascending order of k without host synchronisation.
+ *     Timed under ZKP_K_DECODE ("k_dlog_prepare": decode and the halving, a variable-time radix-16 ladder) and ZKP_K_TERMS ("k_dlog_steps").
+ *     Sizes (profiles/dlog_bench.txt, one MI355X, stream time, min / median / max over five rounds, table of 2^16 rows): a call whose range the
+ *       table covers is the halving ladder and one step -- 0.77 / 0.81 / 0.95 ms for one point at 16 bits, 0.79 / 0.79 / 0.79 for 4,096, 0.87 / 0.89 /
+ *       0.92 for 65,536; with giant steps a launch is never shorter than about 1.7 ms (a step of a workgroup is 16 barriers and one inversion, ~55 us):
+ *       24 bits 2.42 / 2.49 / 2.60 ms for one point, 2.55 / 2.56 / 2.57 for 4,096, 9.60 / 9.65 / 9.70 for 65,536 uniform logarithms (9.60 / 9.62 / 9.67
+ *       all small); 32 bits 2.56 / 2.64 / 2.77 ms for one point, 97.3 / 97.3 / 97.6 for 4,096 uniform (18.2 / 18.2 / 18.3 all small: later launches
+ *       leave early, the first one does not), 2,162 for 65,536 uniform -- about 1.4 x 10^9 candidates per second; with 2^20 rows 4,096 points at
+ *       32 bits take 9.72 / 9.74 / 9.75 ms: size the table to the range.  40 bits over 2^22 rows: 2.65 / 2.73 / 2.79 ms for one point, 379 / 380 /
+ *       381 for 4,096.  Prepare: 1.1 ms (2^12 rows), 1.5 (2^16), 26 (2^20), 125 (2^22).  Against the route callers had (k B for every k in range and a
+ *       row search; 4,096 points, synchronous call): 0.84 against 6.38 ms at 16 bits, 1.70 against 156 at 20, 2.62 against 3,965 at 24; beyond that
+ *       its table does not fit.
+ *       NOT faster than the host backend for small calls (synchronous call against zkp_basepoint_dlog_batch on 16 host threads): one point at
+ *       16 / 24 / 26 bits takes 0.042 / 0.26 / 0.77 ms on the host against 0.88 / 2.60 / 2.61 ms here, 16 points at 16 bits 0.11 against 0.94, 113
+ *       points 0.46 against 0.81; 227 points at 16 bits are the break-even (0.87 against 0.82).  zkp_toolbox.h routes calls up to that size to the
+ *       host and says how.  4,096 points are x 18 (16 bits) and x 107 (24 bits) faster here. */
+#define ZKP_DLOG_FOUND 0
+#define ZKP_DLOG_INVALID 1
+#define ZKP_DLOG_NOT_FOUND 2
+int zkp_ctx_prepare_dlog(zkp_ctx* ctx, uint32_t baby_bits);
+uint32_t zkp_dlog_baby_bits(zkp_ctx* ctx);
+int zkp_dlog_base(zkp_ctx* ctx, uint64_t n, const uint8_t* points /*[n][32]*/, uint32_t bits, uint64_t* out /*[n]*/, uint8_t* status /*[n]*/);
+int zkp_dlog_base_dev(zkp_ctx* ctx, uint64_t n, const uint8_t* d_points /*[n][32]*/, uint32_t bits, uint64_t* d_out /*[n]*/, uint8_t* d_status /*[n]*/);
+uint32_t zkp_dlog_group(void);
+uint32_t zkp_dlog_chunk(void);
+uint32_t zkp_dlog_slice_chunks(uint64_t n);
+
 /* Timing of the last *_dev / host call on this context, measured with HIP events on the stream the
  * kernels were launched on.  kernel_ms[] is indexed by ZKP_K_*; returns the number of entries. */
 enum {

@@ -343,6 +343,27 @@ int zkp_point_sum_batch(zkp_ctx* ctx, uint32_t n_sums, const uint32_t* off /*[n_
                         const uint8_t* neg /*[T] or NULL*/, const uint8_t* points /*[n_points][32]*/, uint32_t n_points, int n_threads,
                         uint8_t* out /*[n_sums][32]*/, uint8_t* status /*[n_sums]*/);
 
+/* Bounded discrete logarithms to the basepoint, batched (zkp_mi355x.h (10)): out[i] = the k in [0, 2^bits) with encode(k B) == points[i] and
+ * status[i] = ZKP_DLOG_FOUND; ZKP_DLOG_INVALID and 0 where the encoding does not decode; ZKP_DLOG_NOT_FOUND and 0 where no k is in range.  bits is
+ * 1 .. 48.  VARIABLE TIME: the duration depends on the logarithms.  n = 0 is a no-op; a NULL buffer with n > 0 or bits out of range is
+ * ZKP_TB_BAD_STATEMENT with nothing written.  Routing: ctx == NULL, or a call whose host work n (2^(bits - host baby_bits) + 128) -- giant steps of
+ * the host table, a point counting 128 for its decode and halving -- is at most zkp_toolbox_get_dlog_host_max_steps() PER THREAD (n_threads, or the
+ * machine's when 0, counted up to 16), runs on the host threads.  The default is 2,048, from profiles/dlog_bench.txt: no device call goes under
+ * 0.81 ms (2.5 ms once it has giant steps); one thread takes 0.51 ms for 14 points at 16 bits (work 2,016) and 0.49 ms for one point at 22 bits;
+ * sixteen threads take 0.11 ms for 16 points at 16 bits, 0.87 ms for 227 (work 32,688: the break-even, the device takes 0.82) and 0.77 ms for one
+ * point at 26 bits (device 2.6).  Larger calls go to the device: 228 points at 16 bits, one point at 27 bits, and with n_threads = 1 already 15
+ * points or one point at 23 bits.  The host runs the same algorithm from the same headers (dlog.h, ge25519.h): every point is halved once, and a
+ * point's giant-step axis split over the threads when there are fewer points than threads; anything else is zkp_dlog_base on ctx, with the
+ * table the context holds (zkp_ctx_prepare_dlog; 2^16 rows by default).  Same results on both routes.  The host's baby-step table
+ * (2^baby_bits rows of 32 bytes and as many 16-byte probe entries; default 2^12) is built at the first call that needs it and kept per size
+ * for the process behind a mutex; zkp_toolbox_set_dlog_baby_bits picks the size later calls use (4 .. 22, else ZKP_TB_BAD_STATEMENT). */
+int zkp_basepoint_dlog_batch(zkp_ctx* ctx, uint64_t n, const uint8_t* points /*[n][32]*/, uint32_t bits, uint64_t* out /*[n]*/, uint8_t* status /*[n]*/,
+                             int n_threads);
+int zkp_toolbox_set_dlog_baby_bits(uint32_t baby_bits);
+uint32_t zkp_toolbox_get_dlog_baby_bits(void);
+void zkp_toolbox_set_dlog_host_max_steps(uint32_t steps);
+uint32_t zkp_toolbox_get_dlog_host_max_steps(void);
+
 /* The ChaCha20 block function (RFC 8439 section 2.3; state words 12-13 = counter, 14-15 = nonce) behind the default
  * entropy / weights of the calls above (`entropy == NULL`, `weights16 == NULL`): like the reference's `thread_rng()`, a
  * ChaCha stream keyed from the operating system.  Exposed for the known-answer test. */

@@ -38,6 +38,9 @@ pub const ZKP_VARTIME: c_int = 0; // RistrettoPoint::vartime_multiscalar_mul (ve
 pub const ZKP_CT: c_int = 1; //      RistrettoPoint::multiscalar_mul (prover.rs:94)
 pub const ZKP_PT_ADD: c_int = 0; //  zkp_add_points: a + b
 pub const ZKP_PT_SUB: c_int = 1; //  zkp_add_points: a - b
+pub const ZKP_DLOG_FOUND: u8 = 0; //      zkp_dlog_base status: out[i] B == points[i]
+pub const ZKP_DLOG_INVALID: u8 = 1; //    the encoding does not decode
+pub const ZKP_DLOG_NOT_FOUND: u8 = 2; //  no logarithm below 2^bits
 pub const ZKP_OPT_BATCH_ENCODE_MIN: c_int = 1;
 pub const ZKP_OPT_COMB_TEETH: c_int = 2;
 pub const ZKP_OPT_CT_SINGLE_USE_TABLES: c_int = 3;
@@ -238,6 +241,14 @@ extern "C" {
     pub fn zkp_sum_points_dev(ctx: *mut zkp_ctx, n_sums: u32, d_off: *const u32, d_pidx: *const u32, d_neg: *const u8, d_points: *const u8,
                               n_points: u32, n_terms: u32, d_out: *mut u8, d_status: *mut u8) -> c_int;
     pub fn zkp_sum_points_group() -> u32;
+    // (10) bounded discrete logarithms to the basepoint (variable time by nature): the context's baby-step table and the search
+    pub fn zkp_ctx_prepare_dlog(ctx: *mut zkp_ctx, baby_bits: u32) -> c_int;
+    pub fn zkp_dlog_baby_bits(ctx: *mut zkp_ctx) -> u32;
+    pub fn zkp_dlog_base(ctx: *mut zkp_ctx, n: u64, points: *const u8, bits: u32, out: *mut u64, status: *mut u8) -> c_int;
+    pub fn zkp_dlog_base_dev(ctx: *mut zkp_ctx, n: u64, d_points: *const u8, bits: u32, d_out: *mut u64, d_status: *mut u8) -> c_int;
+    pub fn zkp_dlog_group() -> u32;
+    pub fn zkp_dlog_chunk() -> u32;
+    pub fn zkp_dlog_slice_chunks(n: u64) -> u32;
     // (7) Merlin operations on N transcripts at any mix of positions
     pub fn zkp_transcripts_append_message(ctx: *mut zkp_ctx, n: u32, shared_initial: c_int, ts: *mut u8, label: *const c_char, msgs: *const u8,
                                           offsets: *const u64) -> c_int;
@@ -367,6 +378,12 @@ extern "C" {
                                out: *mut u8, status: *mut u8) -> c_int;
     pub fn zkp_point_sum_batch(ctx: *mut zkp_ctx, n_sums: u32, off: *const u32, pidx: *const u32, neg: *const u8, points: *const u8, n_points: u32,
                                n_threads: c_int, out: *mut u8, status: *mut u8) -> c_int;
+    // bounded discrete logarithms to the basepoint behind the same routing; the host table's size and the routing threshold
+    pub fn zkp_basepoint_dlog_batch(ctx: *mut zkp_ctx, n: u64, points: *const u8, bits: u32, out: *mut u64, status: *mut u8, n_threads: c_int) -> c_int;
+    pub fn zkp_toolbox_set_dlog_baby_bits(baby_bits: u32) -> c_int;
+    pub fn zkp_toolbox_get_dlog_baby_bits() -> u32;
+    pub fn zkp_toolbox_set_dlog_host_max_steps(steps: u32);
+    pub fn zkp_toolbox_get_dlog_host_max_steps() -> u32;
     pub fn zkp_chacha20_block(key: *const u8, counter: u64, nonce: u64, out: *mut u8);
     // ---- proof wire format (proofs.rs:14-32 under bincode 1.x) ------------------------------------------------------------
     pub fn zkp_proof_compact_size(m: u32) -> usize;

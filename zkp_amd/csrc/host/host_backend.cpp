@@ -21,16 +21,24 @@
 //                 table {1..8} P, 256 doublings + 65 additions; ZKP_CT keeps the masked look-ups and skips no digit (mul_base_n always).
 //   add_points_n / sum_points_n  zkp_add_points / zkp_sum_points (9): decode, the complete addition of ge25519.h (a sign is a conditional negation of
 //                 the cached operand), encode.  A sum is one serial chain here; the toolbox cuts long ones (sum_points_partial / _finish).
+//   dlog_halve / dlog_base_range / dlog_base_n  zkp_dlog_base (10): baby-step / giant-step of dlog.h -- the point halved once, candidates walked by subtracting
+//                 (m / 2) B, encode(2 H) of DLOG_GROUP consecutive candidates from one inversion (the serial form of Montgomery's trick), the probe of
+//                 dlog.h.  The baby table is built here the same way and kept per baby_bits for the process behind a mutex.
 //   sc_*          the scalar kernels' bodies: sc25519.h (sc_invert, sc_from_wide, sc_mont) compiled for the host, element by element.
 #include "host_backend.hpp"
 
+#include <algorithm>
 #include <cstring>
+#include <map>
+#include <memory>
+#include <mutex>
 #include <vector>
 
 #define ZKP_HOST_FE51 1        // this translation unit (and no other of the library) gets the 5 x 51-bit field under the device's point formulas
 #include "../ge25519.h"
 #include "../sha512.h"
 #include "../sc25519.h"
+#include "../dlog.h"
 
 namespace zkp {
 namespace hostbk {
@@ -371,6 +379,181 @@ void sum_points_finish(uint32_t n, const uint8_t* partials, uint8_t out[32], uin
   *status = (uint8_t)(bad != 0);
   if (bad) std::memset(out, 0, 32);
   else encode(out, acc);
+}
+
+// ---- bounded discrete logarithms to the basepoint (zkp_mi355x.h (10); dlog.h has the scheme) ----
+namespace {
+inline void mul_p3(ge_p3& r, const uint8_t scalar[32], const ge_p3& p) {
+  Table t;
+  build_table(t, p);
+  int8_t dig[1][65];
+  recode16(dig[0], scalar);
+  const Table* tp[1] = {&t};
+  straus<false>(r, 1, dig, tp);
+}
+inline void small_scalar(uint8_t s[32], uint64_t v) {
+  std::memset(s, 0, 32);
+  std::memcpy(s, &v, 8);
+}
+inline void half_scalar(uint8_t s[32]) {             // (l + 1) / 2 = 1 / 2 mod l
+  uint32_t w[8];
+  for (int i = 0; i < 8; ++i) w[i] = sc_half(i);
+  w[0] += 1u;
+  std::memcpy(s, w, 32);
+}
+
+// w[i] = encode(2 cand[i]) for i < g from ONE inversion.  x = 0 (the double is the identity) is replaced by 1 with a select and the bytes by the
+// identity's encoding: the product of the group never vanishes.
+struct DoubleEncoder {
+  std::vector<ristretto_dc_state> st;
+  std::vector<fe> x, pre;
+  std::vector<uint32_t> zero;
+  void run(uint32_t (*w)[8], const ge_p3* cand, size_t g) {
+    st.resize(g); x.resize(g); pre.resize(g); zero.resize(g);
+    fe one;
+    fe_1(one);
+    for (size_t i = 0; i < g; ++i) {
+      ristretto_dc_prepare(st[i], x[i], cand[i]);
+      zero[i] = fe_iszero(x[i]);
+      fe_cmov(x[i], one, zero[i]);
+      if (i == 0) pre[0] = x[0];
+      else fe_mul(pre[i], pre[i - 1], x[i]);
+    }
+    fe inv;
+    fe_invert(inv, pre[g - 1]);
+    for (size_t i = g; i-- > 0;) {
+      fe mine;
+      if (i) { fe_mul(mine, inv, pre[i - 1]); fe_mul(inv, inv, x[i]); }
+      else mine = inv;
+      ristretto_dc_finish(w[i], st[i], mine);
+      for (int k = 0; k < 8; ++k) w[i][k] = zero[i] ? 0u : w[i][k];
+    }
+  }
+};
+
+struct DlogTable {
+  uint32_t baby_bits = 0;
+  std::vector<uint32_t> rows;
+  std::vector<dlog_slot> slots;
+  ge_p3 base;
+  ge_cached step;                                    // (m / 2) B
+};
+
+void build_dlog_table(DlogTable& t, uint32_t baby_bits) {
+  const uint32_t m = 1u << baby_bits;
+  t.baby_bits = baby_bits;
+  decode(t.base, kBasepoint);
+  uint8_t s[32];
+  ge_p3 hb, sp;
+  half_scalar(s);
+  mul_p3(hb, s, t.base);
+  ge_cached half_b;
+  ge_to_cached(half_b, hb);
+  small_scalar(s, m / 2);
+  mul_p3(sp, s, t.base);
+  ge_to_cached(t.step, sp);
+  t.rows.resize((size_t)m * 8);
+  DoubleEncoder enc;
+  std::vector<ge_p3> cand(DLOG_GROUP);
+  ge_p3 P;
+  ge_identity(P);
+  for (uint32_t i0 = 0; i0 < m; i0 += DLOG_GROUP) {
+    const size_t g = std::min<uint32_t>(DLOG_GROUP, m - i0);
+    for (size_t i = 0; i < g; ++i) {
+      cand[i] = P;
+      ge_add_cached(P, P, half_b);
+    }
+    enc.run(reinterpret_cast<uint32_t(*)[8]>(t.rows.data() + 8 * (size_t)i0), cand.data(), g);
+  }
+  t.slots.assign(dlog_slot_count(baby_bits), dlog_slot{0u, 0u});
+  dlog_fill_slots(t.slots.data(), t.rows.data(), baby_bits);
+}
+
+std::shared_ptr<const DlogTable> dlog_table(uint32_t baby_bits) {
+  static std::mutex mu;
+  static std::map<uint32_t, std::shared_ptr<const DlogTable>> tables;
+  std::lock_guard<std::mutex> lk(mu);
+  auto it = tables.find(baby_bits);
+  if (it != tables.end()) return it->second;
+  auto t = std::make_shared<DlogTable>();
+  build_dlog_table(*t, baby_bits);
+  tables[baby_bits] = t;
+  return t;
+}
+}  // namespace
+
+void dlog_prepare_table(uint32_t baby_bits) { (void)dlog_table(baby_bits); }
+
+int dlog_halve(const uint8_t point[32], uint8_t half[DLOG_HALF_BYTES]) {
+  ge_p3 Q, P;
+  if (!decode(Q, point)) {
+    std::memset(half, 0, DLOG_HALF_BYTES);
+    return ZKP_DLOG_INVALID;
+  }
+  uint8_t s[32];
+  half_scalar(s);
+  mul_p3(P, s, Q);                                   // Q / 2: every candidate of the search is a half, its bytes come from the encoder of doubles
+  const fe* co[4] = {&P.X, &P.Y, &P.Z, &P.T};
+  for (int k = 0; k < 4; ++k) {
+    uint32_t w[8];
+    fe_towords(w, *co[k]);
+    std::memcpy(half + 32 * k, w, 32);
+  }
+  return ZKP_DLOG_NOT_FOUND;
+}
+
+int dlog_base_range(const uint8_t half[DLOG_HALF_BYTES], uint32_t bits, uint32_t baby_bits, uint64_t j_lo, uint64_t j_hi, uint64_t* k) {
+  *k = 0;
+  ge_p3 P;
+  {
+    fe* co[4] = {&P.X, &P.Y, &P.Z, &P.T};
+    for (int c = 0; c < 4; ++c) {
+      uint32_t w[8];
+      std::memcpy(w, half + 32 * c, 32);
+      fe_fromwords(*co[c], w);
+    }
+  }
+  const std::shared_ptr<const DlogTable> tab = dlog_table(baby_bits);
+  const DlogTable& t = *tab;
+  uint8_t s[32];
+  if (j_lo) {
+    ge_p3 A;
+    ge_cached ca;
+    small_scalar(s, j_lo << (baby_bits - 1u));
+    mul_p3(A, s, t.base);
+    ge_to_cached(ca, A);
+    ge_sub_cached(P, P, ca);
+  }
+  DoubleEncoder enc;
+  std::vector<ge_p3> cand(DLOG_GROUP);
+  std::vector<uint32_t> w((size_t)DLOG_GROUP * 8);
+  for (uint64_t j0 = j_lo; j0 < j_hi; j0 += DLOG_GROUP) {
+    const size_t g = (size_t)std::min<uint64_t>(DLOG_GROUP, j_hi - j0);
+    for (size_t i = 0; i < g; ++i) {
+      cand[i] = P;
+      ge_sub_cached(P, P, t.step);
+    }
+    enc.run(reinterpret_cast<uint32_t(*)[8]>(w.data()), cand.data(), g);
+    for (size_t i = 0; i < g; ++i) {
+      const uint32_t b = dlog_probe(w.data() + 8 * i, t.slots.data(), t.rows.data(), baby_bits);
+      const uint64_t v = ((j0 + i) << baby_bits) + b;
+      if (b != DLOG_NONE && dlog_in_range(v, bits)) {
+        *k = v;
+        return ZKP_DLOG_FOUND;
+      }
+    }
+  }
+  return ZKP_DLOG_NOT_FOUND;
+}
+
+void dlog_base_n(uint64_t n, const uint8_t* points, uint32_t bits, uint32_t baby_bits, uint64_t* out, uint8_t* status) {
+  const uint64_t J = dlog_giant_steps(bits, baby_bits);
+  for (uint64_t i = 0; i < n; ++i) {
+    uint8_t half[DLOG_HALF_BYTES];
+    out[i] = 0;
+    status[i] = (uint8_t)dlog_halve(points + 32 * i, half);
+    if (status[i] != ZKP_DLOG_INVALID) status[i] = (uint8_t)dlog_base_range(half, bits, baby_bits, 0, J, out + i);
+  }
 }
 
 }  // namespace hostbk

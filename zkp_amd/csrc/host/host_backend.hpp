@@ -38,5 +38,16 @@ void sum_points_n(uint32_t n_sums, const uint32_t* off /*[n_sums+1]*/, const uin
                   const uint8_t* points, uint8_t* out /*[n_sums][32]*/, uint8_t* status /*[n_sums]*/, uint32_t skip_longer_than = 0xffffffffu);
 void sum_points_partial(uint32_t t_lo, uint32_t t_hi, const uint32_t* pidx, const uint8_t* neg, const uint8_t* points, uint8_t partial[SUM_PARTIAL_BYTES]);
 void sum_points_finish(uint32_t n, const uint8_t* partials /*[n][SUM_PARTIAL_BYTES]*/, uint8_t out[32], uint8_t* status);
+// zkp_dlog_base (10): the caller has checked pointers, bits (1 .. 48) and baby_bits (4 .. 22).  dlog_halve decodes a point and multiplies it by
+// (l + 1) / 2, once per point: half = four canonical field elements X, Y, Z, T; returns ZKP_DLOG_INVALID (half zeroed) where the encoding does not
+// decode, ZKP_DLOG_NOT_FOUND (nothing searched yet) otherwise.  dlog_base_range searches the giant steps [j_lo, j_hi) of a halved point
+// (k = j 2^baby_bits + i) and returns ZKP_DLOG_FOUND with *k, or ZKP_DLOG_NOT_FOUND in that range (*k = 0): ranges of one point are independent,
+// which is how the toolbox spreads a few points with large ranges over its threads.  dlog_base_n does both for the whole range of each of n points.
+// The baby table of a size is built at its first use (or by dlog_prepare_table) and kept for the process behind a mutex.
+constexpr size_t DLOG_HALF_BYTES = 128;
+void dlog_prepare_table(uint32_t baby_bits);
+int dlog_halve(const uint8_t point[32], uint8_t half[DLOG_HALF_BYTES]);
+int dlog_base_range(const uint8_t half[DLOG_HALF_BYTES], uint32_t bits, uint32_t baby_bits, uint64_t j_lo, uint64_t j_hi, uint64_t* k);
+void dlog_base_n(uint64_t n, const uint8_t* points /*[n][32]*/, uint32_t bits, uint32_t baby_bits, uint64_t* out /*[n]*/, uint8_t* status /*[n]*/);
 }  // namespace hostbk
 }  // namespace zkp

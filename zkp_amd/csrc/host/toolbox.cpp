@@ -35,6 +35,11 @@ static std::atomic<uint32_t> g_fused_min_batch{32};
 // calls whose group arithmetic is at most this many (scalar, point) terms run on the host cores (host_backend.cpp) instead of paying the
 // ~1 ms launch chain of the GPU; a NULL context always does (no GPU needed at all)
 static std::atomic<uint32_t> g_host_max_terms{16};
+// zkp_basepoint_dlog_batch: the host table's size, and the host work per thread (n (2^(bits - baby_bits) + 128) giant steps over min(threads, 16)) up
+// to which a call with a context stays on the host threads.  Measured (profiles/dlog_bench.txt): no device call goes under 0.81 ms; 2,016 steps
+// take 0.51 ms on one core, 32,688 steps 0.87 ms on sixteen -- the break-even.
+static std::atomic<uint32_t> g_dlog_host_baby_bits{12};
+static std::atomic<uint32_t> g_dlog_host_max_steps{2048};
 
 namespace {
 inline bool on_host(const zkp_ctx* ctx, uint64_t terms) { return !ctx || terms <= g_host_max_terms.load(); }
@@ -1088,6 +1093,68 @@ int zkp_point_sum_batch(zkp_ctx* ctx, uint32_t n_sums, const uint32_t* off, cons
     const uint32_t lo = cut[k], hi = cut[k + 1];
     if (lo < hi) zkp::hostbk::sum_points_n(hi - lo, off + lo, pidx, neg, points, out + 32 * (size_t)lo, status + lo, long_len);
   });
+  return ZKP_TB_OK;
+}
+
+// ---- bounded discrete logarithms to the basepoint (zkp_mi355x.h (10)) behind the same routing ------------------------------------------------
+int zkp_toolbox_set_dlog_baby_bits(uint32_t baby_bits) {
+  if (baby_bits < 4 || baby_bits > 22) return ZKP_TB_BAD_STATEMENT;
+  g_dlog_host_baby_bits = baby_bits;
+  return ZKP_TB_OK;
+}
+uint32_t zkp_toolbox_get_dlog_baby_bits(void) { return g_dlog_host_baby_bits.load(); }
+void zkp_toolbox_set_dlog_host_max_steps(uint32_t steps) { g_dlog_host_max_steps = steps; }
+uint32_t zkp_toolbox_get_dlog_host_max_steps(void) { return g_dlog_host_max_steps.load(); }
+
+// The host route halves every point once (spread over the threads by points), then cuts the search into (point, range of giant steps) items: with
+// fewer points than threads a point's giant-step axis is split into ranges of whole inversion groups, which are searched independently (at most
+// one of them finds the point's unique k).
+// Routing: the host work of a call is n (J + 128) giant steps -- J = 2^(bits - host baby_bits) for a point that is not found, and 128 for its decode and
+// halving, a 253-bit ladder.  A call with a context stays on the host while that work is at most host_max_steps PER THREAD, the threads counted up to 16
+// (what was measured: profiles/dlog_bench.txt).
+int zkp_basepoint_dlog_batch(zkp_ctx* ctx, uint64_t n, const uint8_t* points, uint32_t bits, uint64_t* out, uint8_t* status, int n_threads) {
+  if (bits < 1 || bits > 48) return ZKP_TB_BAD_STATEMENT;
+  if (n == 0) return ZKP_TB_OK;
+  if (!points || !out || !status || n > 0x7fffffffull) return ZKP_TB_BAD_STATEMENT;
+  const uint32_t bb = g_dlog_host_baby_bits.load();
+  const uint64_t J = bits <= bb ? 1ull : 1ull << (bits - bb);
+  unsigned t = n_threads > 0 ? (unsigned)n_threads : std::thread::hardware_concurrency();
+  t = std::max(1u, std::min(t, 128u));
+  if (ctx && n * (J + 128) > (uint64_t)g_dlog_host_max_steps.load() * std::min(t, 16u)) {
+    const int rc = zkp_dlog_base(ctx, n, points, bits, out, status);
+    return rc == ZKP_ERR_ARG ? ZKP_TB_BAD_STATEMENT : rc;
+  }
+  zkp::hostbk::dlog_prepare_table(bb);               // (built once, before the threads ask for it)
+  constexpr size_t HB = zkp::hostbk::DLOG_HALF_BYTES;
+  std::vector<uint8_t> halves(HB * (size_t)n), bad(n);
+  const unsigned tp = (unsigned)std::min<uint64_t>(t, n);
+  auto halve = [&](unsigned k) {
+    for (uint64_t p = k; p < n; p += tp) bad[p] = zkp::hostbk::dlog_halve(points + 32 * (size_t)p, halves.data() + HB * (size_t)p) == ZKP_DLOG_INVALID;
+  };
+  if (tp <= 1) halve(0);
+  else Pool::instance().run(tp, halve);
+  const uint64_t groups = (J + zkp_dlog_group() - 1) / zkp_dlog_group();
+  const uint64_t segs = std::max<uint64_t>(1, std::min<uint64_t>(groups, t / n));
+  const uint64_t seg_len = ((groups + segs - 1) / segs) * zkp_dlog_group();
+  const uint64_t items = n * segs;
+  std::vector<uint64_t> ks(items);
+  std::vector<uint8_t> sts(items);
+  const unsigned ts = (unsigned)std::min<uint64_t>(t, items);
+  auto work = [&](unsigned k) {
+    for (uint64_t it = k; it < items; it += ts) {
+      const uint64_t p = it / segs, lo = (it % segs) * seg_len, hi = std::min<uint64_t>(J, lo + seg_len);
+      sts[it] = (uint8_t)ZKP_DLOG_NOT_FOUND;
+      if (!bad[p] && lo < hi) sts[it] = (uint8_t)zkp::hostbk::dlog_base_range(halves.data() + HB * (size_t)p, bits, bb, lo, hi, &ks[it]);
+    }
+  };
+  if (ts <= 1) work(0);
+  else Pool::instance().run(ts, work);
+  for (uint64_t p = 0; p < n; ++p) {
+    out[p] = 0;
+    status[p] = bad[p] ? (uint8_t)ZKP_DLOG_INVALID : (uint8_t)ZKP_DLOG_NOT_FOUND;
+    for (uint64_t s2 = 0; s2 < segs; ++s2)
+      if (sts[p * segs + s2] == ZKP_DLOG_FOUND) { out[p] = ks[p * segs + s2]; status[p] = ZKP_DLOG_FOUND; }
+  }
   return ZKP_TB_OK;
 }
 

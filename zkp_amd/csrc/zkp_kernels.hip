@@ -58,6 +58,7 @@ __device__ __forceinline__ uint32_t sel8(const uint32_t w[8], int j) {
 #include "comb_tables.h"
 #include "point_mul.h"
 #include "point_sum.h"
+#include "dlog.h"
 #include "transcript_kernels.h"
 #include "sha512.h"
 
@@ -1554,6 +1555,183 @@ k_sum_encode(uint32_t n_sums, const uint32_t* __restrict__ off, const sum_item* 
   status[s] = (uint8_t)(bad != 0);
 }
 
+// Bounded discrete logarithms to the basepoint (zkp_mi355x.h (10); dlog.h has the scheme).
+//
+// dlog_group_encode: w = encode(2 P) for the candidate of every lane of a DLOG_GROUP-lane workgroup from ONE field inversion: the product tree of the
+// batched encoder over the lanes' x = e g f h, the root inverted by the first wavefront (one limb per lane, rowfe.h), the tree walked down.  Every
+// lane of the workgroup must call it (barriers).  x = 0 -- the doubled candidate is the identity -- is replaced by 1 with a select and the lane's
+// bytes by the identity's encoding, so that the group's product never vanishes.
+static_assert(DLOG_GROUP == ENC_BLOCK, "a dlog group is one product tree");
+__device__ __forceinline__ void dlog_group_encode(uint32_t w[8], const ge_p3& P, enc_tree& tree, int tid) {
+  ristretto_dc_state s;
+  fe x, one;
+  ristretto_dc_prepare(s, x, P);
+  const uint32_t zero = fe_iszero(x);
+  fe_1(one);
+  fe_cmov(x, one, zero);
+  tree_put(tree, ENC_BLOCK + tid, x);
+  __syncthreads();
+  tree_up(tree, tid);
+  if (tid < 64) {
+    rowctx rc;
+    row_init(rc);
+    const uint32_t z = rc.live ? tree.node[1][rc.k] : 0u;
+    const uint32_t inv = row_invert(rc, z);
+    if (rc.live && rc.r == 0u) tree.node[1][rc.k] = inv;
+  }
+  __syncthreads();
+  tree_down(tree, tid);
+  fe inv;
+  tree_get(inv, tree, ENC_BLOCK + tid);
+  ristretto_dc_finish(w, s, inv);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) w[k] = zero ? 0u : w[k];
+}
+
+// acc = s B for a reduced scalar over the context's table of B, as k_mul_base walks it: every lane of the wavefront takes part
+__device__ __forceinline__ void dlog_mul_base(ge_p3& acc, const uint32_t s[8], const uint4* __restrict__ table) {
+  sc red;
+#pragma unroll
+  for (int q = 0; q < 8; ++q) red.v[q] = s[q];
+  const uint32_t flip = sc_fold_sign(red.v);
+  uint32_t e[9];
+  hot_recode(e, red.v, true);
+  ge_identity(acc);
+  fixed_base_xbar(acc, e, table, true);
+  ge_cneg(acc, flip);
+}
+__device__ __forceinline__ void dlog_small_scalar(uint32_t s[8], uint64_t v) {
+  s[0] = (uint32_t)v;
+  s[1] = (uint32_t)(v >> 32);
+#pragma unroll
+  for (int q = 2; q < 8; ++q) s[q] = 0;
+}
+__device__ __forceinline__ void dlog_load_cached(ge_cached& q, const uint32_t* src) {
+  uint32_t w[36];
+  load_vec<9>(w, src);
+  fe_set(q.YpX, w); fe_set(q.YmX, w + 9); fe_set(q.Z2, w + 18); fe_set(q.T2d, w + 27);
+}
+
+// k_dlog_setup (one wavefront): consts[0] = (1/2) B, consts[1] = (m / 2) B in cached form, 36 words each
+__global__ void __launch_bounds__(64)
+k_dlog_setup(uint64_t half_m, const uint4* __restrict__ table, uint32_t* __restrict__ consts) {
+  const uint32_t lane = threadIdx.x;
+  uint32_t s[8];
+  dlog_small_scalar(s, lane == 1u ? half_m : 0ull);
+  if (lane == 0u) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) s[q] = sc_half(q);                 // (l - 1) / 2 ...
+    s[0] += 1u;                                                   // ... + 1 = 1 / 2 mod l (the low word does not wrap)
+  }
+  ge_p3 acc;
+  dlog_mul_base(acc, s, table);
+  if (lane < 2u) {
+    ge_cached c;
+    ge_to_cached(c, acc);
+    uint32_t w[36];
+    fe_get(w, c.YpX); fe_get(w + 9, c.YmX); fe_get(w + 18, c.Z2); fe_get(w + 27, c.T2d);
+    store_vec<9>(consts + 36 * lane, w);
+  }
+}
+
+// k_dlog_rows: the baby rows encode(i B), i < m.  Lane g walks i0 = g DLOG_ROW_RUN, ... from (i0 / 2) B by adding (1/2) B and the workgroup encodes the
+// doubles of one step of all its lanes with one inversion.  Lanes beyond m walk along (the crossbar and the barriers need them) and store nothing.
+__global__ void __launch_bounds__(DLOG_GROUP, 2)
+k_dlog_rows(uint32_t m, const uint4* __restrict__ table, const uint32_t* __restrict__ consts, uint32_t* __restrict__ rows) {
+  __shared__ enc_tree tree;
+  const int tid = threadIdx.x;
+  const uint64_t i0 = ((uint64_t)blockIdx.x * DLOG_GROUP + tid) * DLOG_ROW_RUN;
+  uint32_t s[8];
+  dlog_small_scalar(s, i0 < m ? i0 / 2 : 0ull);
+  ge_p3 P;
+  dlog_mul_base(P, s, table);
+#pragma unroll 1
+  for (uint32_t t = 0; t < DLOG_ROW_RUN; ++t) {
+    uint32_t w[8];
+    dlog_group_encode(w, P, tree, tid);
+    if (i0 + t < m) store_vec<2>(rows + 8 * (size_t)(i0 + t), w);
+    ge_cached hb;
+    dlog_load_cached(hb, consts);
+    ge_add_cached(P, P, hb);
+  }
+}
+
+// k_dlog_prepare: halves[i] = ((l + 1) / 2) decode(points[i]) by the variable-time ladder of k_mul_pairs, so that every later candidate is a doubled
+// point; status[i] = 1 where the encoding does not decode, 2 (not found yet) otherwise; out[i] = 0.
+__global__ void __launch_bounds__(256, 2)
+k_dlog_prepare(uint32_t n, const uint8_t* __restrict__ points, uint4* ladder_rw, dev_ext* __restrict__ halves, uint64_t* __restrict__ out,
+               uint8_t* __restrict__ status) {
+  __shared__ uint32_t ecols[8 * 256];
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint4* tbl = ladder_rw + (size_t)(i >> 6) * LADDER_GROUP_UINT4 + (i & 63u);
+  uint32_t s[8], w[8];
+#pragma unroll
+  for (int q = 0; q < 8; ++q) s[q] = sc_half(q);
+  s[0] += 1u;
+  load_vec<2>(w, points + 32 * (size_t)i);
+  ge_p3 P, acc;
+  const uint32_t ok = ristretto_decode(P, w);                    // (the identity where it fails)
+  ladder16_point<false>(acc, s, P, tbl, ecols + threadIdx.x);
+  store_ext(halves + i, acc);
+  out[i] = 0;
+  status[i] = (uint8_t)(ok ? ZKP_DLOG_NOT_FOUND : ZKP_DLOG_INVALID);
+}
+
+// k_dlog_steps: one slice of the search.  Work item = (point p, chunk c of DLOG_CHUNK giant steps), item = p span + cl with c = chunk0 + cl and span the
+// chunks of a point in this launch: the lanes of a workgroup hold neighbouring chunks of one point (and, where span is below the group size, of its
+// neighbours), so the work of a finished point vanishes workgroup by workgroup.  A lane whose point is found or invalid has no work;
+// a workgroup without work leaves, otherwise idle lanes walk the identity along (the crossbar needs every lane of a wavefront, the shared
+// inversion every lane of the workgroup) and touch no memory.  Start Q / 2 - (c DLOG_CHUNK m / 2) B from the table of B, then one encoding group and
+// one subtraction of (m / 2) B per giant step.  A confirmed hit k = j m + i below 2^bits writes out and status = 0; k is unique, so there is one
+// writer.  steps = the giant steps a chunk walks: DLOG_CHUNK, or fewer where the whole range has fewer (both powers of two: then every point has one
+// chunk, and steps past the range could only give k >= 2^bits).  Every index that reaches memory is below its array's length: p < n, the probe masks its slot and a slot names a row below m.
+__global__ void __launch_bounds__(DLOG_GROUP, 2)
+k_dlog_steps(uint32_t n, uint64_t items, uint64_t span, uint64_t chunk0, uint64_t total_chunks, uint32_t steps, uint32_t bits, uint32_t baby_bits, const dev_ext* __restrict__ halves,
+             const uint4* __restrict__ table, const uint32_t* __restrict__ consts, const dlog_slot* __restrict__ slots,
+             const uint32_t* __restrict__ rows, uint64_t* out, uint8_t* status) {
+  __shared__ enc_tree tree;
+  const int tid = threadIdx.x;
+  const uint64_t item = (uint64_t)blockIdx.x * DLOG_GROUP + tid;
+  const uint64_t p64 = item / span;
+  const uint32_t p = p64 < n ? (uint32_t)p64 : n - 1u;
+  const uint64_t c = chunk0 + item % span;
+  uint32_t live = (uint32_t)(item < items && p64 < n && c < total_chunks);
+  if (live) live = (uint32_t)(status[p] == ZKP_DLOG_NOT_FOUND);
+  if (__syncthreads_or((int)live) == 0) return;
+  const uint64_t j0 = c * DLOG_CHUNK;
+  ge_p3 P;
+  {
+    uint32_t s[8];
+    dlog_small_scalar(s, live ? j0 << (baby_bits - 1u) : 0ull);   // j0 m / 2 < 2^47
+    ge_p3 A, H;
+    dlog_mul_base(A, s, table);
+    ge_identity(H);
+    if (live) load_ext(H, halves + p);
+    ge_cached ca;
+    ge_to_cached(ca, A);
+    ge_sub_cached(P, H, ca);
+  }
+#pragma unroll 1
+  for (uint32_t t = 0; t < steps; ++t) {                            // (uniform: min(DLOG_CHUNK, giant steps of the range))
+    uint32_t w[8];
+    dlog_group_encode(w, P, tree, tid);
+    if (live) {
+      const uint32_t i = dlog_probe(w, slots, rows, baby_bits);
+      const uint64_t k = ((j0 + t) << baby_bits) + i;
+      if (i != DLOG_NONE && dlog_in_range(k, bits)) {
+        out[p] = k;
+        status[p] = (uint8_t)ZKP_DLOG_FOUND;
+        live = 0;
+      }
+    }
+    if (__syncthreads_or((int)live) == 0) break;
+    ge_cached st;
+    dlog_load_cached(st, consts + 36);
+    ge_sub_cached(P, P, st);
+  }
+}
+
 // =============================================================================================
 // host side: context, workspace, C ABI
 // =============================================================================================
@@ -1674,6 +1852,12 @@ struct zkp_ctx {
   // zkp_mul_base (section 8): the basepoint's table in one slot's format, an allocation of the context's own OUTSIDE hot_tables -- it takes no
   // LRU slot, k_hot_match never sees it; built at the first call (ensure_base_table)
   dev_niels* base_table = nullptr;
+  // zkp_dlog_base (section 10): the baby-step table, allocations of the context's own like base_table -- rows [2^baby_bits][8] words, probe slots
+  // [2^(baby_bits + 1)], and the two points of the walk ((1/2) B, (m / 2) B, cached form); dlog_baby_bits = 0: none yet (ensure_dlog_table)
+  uint32_t dlog_baby_bits = 0;
+  uint32_t* dlog_rows = nullptr;
+  dlog_slot* dlog_slots = nullptr;
+  uint32_t* dlog_consts = nullptr;
   // fused flows (fused_flows.h): compiled transcript programs and operand templates per (flow, statement, N, position)
   std::map<std::string, void*> fused_plans;
   // ragged calls (ragged_transcripts.h): uploaded class programs per (flow, statement, N, position) and position-free base plans per
@@ -1709,6 +1893,15 @@ struct zkp_ctx {
   bool hot_registry_uploaded = false;  // the device copy of the fixed-base registry matches hot_key[]
 };
 void free_fused_plans(zkp_ctx* c);
+static void free_dlog_table(zkp_ctx* c) {
+  if (c->dlog_rows) (void)hipFree(c->dlog_rows);
+  if (c->dlog_slots) (void)hipFree(c->dlog_slots);
+  if (c->dlog_consts) (void)hipFree(c->dlog_consts);
+  c->dlog_rows = nullptr;
+  c->dlog_slots = nullptr;
+  c->dlog_consts = nullptr;
+  c->dlog_baby_bits = 0;
+}
 void free_ragged_progs(zkp_ctx* c);
 
 namespace {
@@ -2533,6 +2726,94 @@ int launch_sum_points(zkp_ctx* c, uint32_t n_sums, const uint32_t* d_off, const 
   return ZKP_OK;
 }
 
+// ---- zkp_mi355x.h (10): the context's baby-step table and the launchers of the search (dlog.h) ----
+// Builds the table for baby_bits (the same size again: nothing to do).  Rows on the device, slots on the host from the downloaded rows.
+// Synchronises, so not under capture.  A replaced table makes graphs recorded over the old one stale (ws_generation).
+int ensure_dlog_table(zkp_ctx* c, uint32_t baby_bits) {
+  if (c->dlog_baby_bits == baby_bits) return ZKP_OK;
+  if (c->capturing) return fail(ZKP_ERR_ARG, "graph capture: the baby-step table is not built yet -- run zkp_ctx_prepare_dlog or one zkp_dlog_base outside the capture");
+  if (c->job.kind) return fail(ZKP_ERR_ARG, "a submitted job is pending on this context: zkp_ctx_job_wait first");
+  int rc = ensure_base_table(c);
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (c->dlog_baby_bits) {
+    free_dlog_table(c);
+    ++c->ws_generation;
+  }
+  const uint32_t m = 1u << baby_bits;
+  const size_t row_bytes = (size_t)m * 32, slot_bytes = sizeof(dlog_slot) * (size_t)dlog_slot_count(baby_bits);
+  hipError_t err = hipMalloc(&c->dlog_rows, row_bytes);
+  if (err == hipSuccess) err = hipMalloc(&c->dlog_slots, slot_bytes);
+  if (err == hipSuccess) err = hipMalloc(&c->dlog_consts, 2 * 36 * sizeof(uint32_t));
+  std::vector<uint32_t> rows;
+  std::vector<dlog_slot> slots;
+  if (err == hipSuccess) {
+    const uint4* table = reinterpret_cast<const uint4*>(c->base_table);
+    hipLaunchKernelGGL(k_dlog_setup, dim3(1), dim3(64), 0, c->stream, (uint64_t)(m / 2), table, c->dlog_consts);
+    hipLaunchKernelGGL(k_dlog_rows, grid1(((size_t)m + DLOG_ROW_RUN - 1) / DLOG_ROW_RUN, DLOG_GROUP), dim3(DLOG_GROUP), 0, c->stream, m, table,
+                       c->dlog_consts, c->dlog_rows);
+    err = hipGetLastError();
+    rows.resize((size_t)m * 8);
+    if (err == hipSuccess) err = hipMemcpyAsync(rows.data(), c->dlog_rows, row_bytes, hipMemcpyDeviceToHost, c->stream);
+    if (err == hipSuccess) err = hipStreamSynchronize(c->stream);
+  }
+  if (err == hipSuccess) {
+    slots.assign(dlog_slot_count(baby_bits), dlog_slot{0u, 0u});
+    dlog_fill_slots(slots.data(), rows.data(), baby_bits);
+    err = hipMemcpyAsync(c->dlog_slots, slots.data(), slot_bytes, hipMemcpyHostToDevice, c->stream);
+    if (err == hipSuccess) err = hipStreamSynchronize(c->stream);
+  }
+  if (err != hipSuccess) {
+    free_dlog_table(c);
+    HIP_TRY(err);
+  }
+  c->dlog_baby_bits = baby_bits;
+  return ZKP_OK;
+}
+
+int dlog_check(zkp_ctx* c, uint64_t n, uint32_t bits, bool null_buffer) {
+  const int rc = sc_call_check(c, n, null_buffer);
+  if (rc) return rc;
+  if (bits < 1 || bits > DLOG_BITS_MAX) return fail(ZKP_ERR_ARG, "bits must be 1 .. 48");
+  return ZKP_OK;
+}
+// the launches of a call on the context's table (which exists): how many k_dlog_steps launches it takes
+inline uint64_t dlog_launches(const zkp_ctx* c, uint64_t n, uint32_t bits) {
+  const uint64_t chunks = dlog_chunks(bits, c->dlog_baby_bits), per = dlog_slice_chunks(n);
+  return (chunks + per - 1) / per;
+}
+struct dlog_ws { size_t halves = 0, ladder = 0, total = 0; };
+dlog_ws dlog_base_ws(uint64_t n, size_t reserved = 0) {
+  carve cv;
+  cv.off = reserved;
+  dlog_ws w;
+  w.halves = cv.take(sizeof(dev_ext) * (size_t)n);
+  w.ladder = cv.take(mul_pairs_ws(n));
+  w.total = cv.off;
+  return w;
+}
+int launch_dlog(zkp_ctx* c, uint64_t n, const uint8_t* d_points, uint32_t bits, char* ws, const dlog_ws& w, uint64_t* d_out, uint8_t* d_status) {
+  dev_ext* halves = reinterpret_cast<dev_ext*>(ws + w.halves);
+  uint4* ladder = reinterpret_cast<uint4*>(ws + w.ladder);
+  for (uint64_t i0 = 0; i0 < n; i0 += MUL_PAIRS_MAX_LANES) {
+    const uint32_t k = (uint32_t)std::min<uint64_t>(n - i0, MUL_PAIRS_MAX_LANES);
+    hipLaunchKernelGGL(k_dlog_prepare, grid1(k, 256), dim3(256), 0, c->stream, k, d_points + 32 * (size_t)i0, ladder, halves + i0, d_out + i0, d_status + i0);
+  }
+  prof_note(c, ZKP_K_DECODE, "k_dlog_prepare");
+  prof_mark(c, ZKP_K_DECODE);
+  const uint32_t bb = c->dlog_baby_bits;
+  const uint64_t chunks = dlog_chunks(bits, bb), per = dlog_slice_chunks(n);
+  for (uint64_t c0 = 0; c0 < chunks; c0 += per) {
+    const uint64_t span = std::min<uint64_t>(per, chunks - c0), items = n * span;
+    hipLaunchKernelGGL(k_dlog_steps, grid1((size_t)items, DLOG_GROUP), dim3(DLOG_GROUP), 0, c->stream, (uint32_t)n, items, span, c0, chunks, (uint32_t)std::min<uint64_t>(DLOG_CHUNK, dlog_giant_steps(bits, bb)), bits, bb, halves,
+                       reinterpret_cast<const uint4*>(c->base_table), c->dlog_consts, c->dlog_slots, c->dlog_rows, d_out, d_status);
+  }
+  prof_note(c, ZKP_K_TERMS, "k_dlog_steps");
+  prof_mark(c, ZKP_K_TERMS);
+  HIP_TRY(hipGetLastError());
+  return ZKP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2584,6 +2865,7 @@ void zkp_ctx_destroy(zkp_ctx* c) {
   if (c->ws) hipFree(c->ws);
   if (c->hot_tables) hipFree(c->hot_tables);
   if (c->base_table) hipFree(c->base_table);
+  free_dlog_table(c);
   if (c->hot_reg_words) hipFree(c->hot_reg_words);
   if (c->hot_reg_slot) hipFree(c->hot_reg_slot);
   if (c->hot_scratch) hipFree(c->hot_scratch);
@@ -3376,6 +3658,63 @@ int zkp_sum_points(zkp_ctx* c, uint32_t n_sums, const uint32_t* off, const uint3
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)n_sums * 32, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipMemcpyAsync(status, base + o_st, (size_t)n_sums, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return ZKP_OK;
+}
+
+// ---- (10) bounded discrete logarithms to the basepoint ------------------------------------------------------------------------------------
+uint32_t zkp_dlog_group(void) { return DLOG_GROUP; }
+uint32_t zkp_dlog_chunk(void) { return DLOG_CHUNK; }
+uint32_t zkp_dlog_slice_chunks(uint64_t n) { return (uint32_t)dlog_slice_chunks(n); }
+uint32_t zkp_dlog_baby_bits(zkp_ctx* c) { return c ? c->dlog_baby_bits : 0u; }
+
+int zkp_ctx_prepare_dlog(zkp_ctx* c, uint32_t baby_bits) {
+  if (!c) return fail(ZKP_ERR_ARG, "ctx is NULL");
+  if (baby_bits < DLOG_BABY_MIN || baby_bits > DLOG_BABY_MAX) return fail(ZKP_ERR_ARG, "baby_bits must be 4 .. 22");
+  if (c->capturing) return fail(ZKP_ERR_ARG, "graph capture: zkp_ctx_prepare_dlog synchronises");
+  HIP_TRY(hipSetDevice(c->device));
+  return ensure_dlog_table(c, baby_bits);
+}
+
+int zkp_dlog_base_dev(zkp_ctx* c, uint64_t n, const uint8_t* d_points, uint32_t bits, uint64_t* d_out, uint8_t* d_status) {
+  int rc = dlog_check(c, n, bits, !d_points || !d_out || !d_status);
+  if (rc || n == 0) return rc;
+  if (!aligned16(d_points) || (reinterpret_cast<uintptr_t>(d_out) & 7)) return fail(ZKP_ERR_ARG, "d_points must be 16-byte, d_out 8-byte aligned");
+  HIP_TRY(hipSetDevice(c->device));
+  if (!c->dlog_baby_bits) {
+    rc = ensure_dlog_table(c, DLOG_BABY_DEFAULT);
+    if (rc) return rc;
+  }
+  if (dlog_launches(c, n, bits) > DLOG_MAX_LAUNCHES) return fail(ZKP_ERR_ARG, "the search would take more than 65,536 launches: prepare a larger table or split the call");
+  const dlog_ws w = dlog_base_ws(n);
+  rc = ensure_ws(c, w.total);
+  if (rc) return rc;
+  prof_begin(c);
+  return launch_dlog(c, n, d_points, bits, static_cast<char*>(c->ws), w, d_out, d_status);
+}
+int zkp_dlog_base(zkp_ctx* c, uint64_t n, const uint8_t* points, uint32_t bits, uint64_t* out, uint8_t* status) {
+  int rc = dlog_check(c, n, bits, !points || !out || !status);
+  if (rc || n == 0) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  if (!c->dlog_baby_bits) {
+    rc = ensure_dlog_table(c, DLOG_BABY_DEFAULT);
+    if (rc) return rc;
+  }
+  if (dlog_launches(c, n, bits) > DLOG_MAX_LAUNCHES) return fail(ZKP_ERR_ARG, "the search would take more than 65,536 launches: prepare a larger table or split the call");
+  carve cv;
+  const size_t o_pts = cv.take((size_t)n * 32);
+  const size_t o_out = cv.take((size_t)n * 8);
+  const size_t o_st = cv.take((size_t)n);
+  const dlog_ws w = dlog_base_ws(n, cv.off);
+  rc = ensure_ws(c, w.total);
+  if (rc) return rc;
+  char* base = static_cast<char*>(c->ws);
+  HIP_TRY(hipMemcpyAsync(base + o_pts, points, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
+  prof_begin(c);
+  rc = launch_dlog(c, n, reinterpret_cast<const uint8_t*>(base + o_pts), bits, base, w, reinterpret_cast<uint64_t*>(base + o_out), reinterpret_cast<uint8_t*>(base + o_st));
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(status, base + o_st, (size_t)n, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return ZKP_OK;
 }

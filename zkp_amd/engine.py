@@ -25,6 +25,7 @@ ZKP_OPT_WS_LIMIT_BYTES, ZKP_OPT_JOB_DEFER_D2H, ZKP_OPT_SYNC_SCHEDULE, ZKP_OPT_TR
 ZKP_VARTIME = 0
 ZKP_CT = 1
 ZKP_PT_ADD, ZKP_PT_SUB = 0, 1               # zkp_add_points' op
+ZKP_DLOG_FOUND, ZKP_DLOG_INVALID, ZKP_DLOG_NOT_FOUND = 0, 1, 2      # zkp_dlog_base's status
 ZKP_OPT_BATCH_ENCODE_MIN = 1
 (ZKP_OPT_COMB_TEETH, ZKP_OPT_CT_SINGLE_USE_TABLES, ZKP_OPT_TRANSCRIPT_LANES, ZKP_OPT_DEV_OVERLAP, ZKP_OPT_GROUPED_COMB, ZKP_OPT_TABLES_LANE,
  ZKP_OPT_FUSE_TABLES_TRANSCRIPT) = 2, 3, 4, 5, 6, 7, 8
@@ -371,6 +372,26 @@ class Engine:
                                         len(points), _ptr(out), _ptr(status)), "zkp_sum_points")
         return out, status
 
+    # ---- bounded discrete logarithms to the basepoint (include/zkp_mi355x.h section 10): variable time by nature ----
+    def prepare_dlog(self, baby_bits: int) -> None:
+        """build (or replace) the context's baby-step table: the encodings of i B for i < 2**baby_bits, baby_bits in 4 .. 22"""
+        _check(self._lib.zkp_ctx_prepare_dlog(self._h, baby_bits), "zkp_ctx_prepare_dlog")
+
+    @property
+    def dlog_baby_bits(self) -> int:
+        """the size of the baby-step table the context holds; 0 = none yet"""
+        return int(self._lib.zkp_dlog_baby_bits(self._h))
+
+    def dlog_base(self, points, bits: int) -> Tuple[np.ndarray, np.ndarray]:
+        """points [n][32] = encode(k B) -> (k uint64 [n], status uint8 [n]): status 0 = found (k < 2**bits), 1 = the encoding does not decode,
+        2 = no k in range (k = 0 for both); bits in 1 .. 48.  A context without a table builds the default size first."""
+        points = _u8(points, 32)
+        n = len(points)
+        out = np.zeros(n, np.uint64)
+        status = np.zeros(n, np.uint8)
+        _check(self._lib.zkp_dlog_base(self._h, n, _ptr(points), bits, _ptr(out), _ptr(status)), "zkp_dlog_base")
+        return out, status
+
     def debug_sha512(self, data, offsets) -> np.ndarray:
         """the SHA-512 stage alone (test-hook build): CSR batch -> digests [n][64]"""
         self._need_hooks("zkp_debug_sha512")
@@ -494,6 +515,10 @@ class Engine:
         """zkp_sum_points_dev: d_off u32 [n_sums + 1], d_pidx u32 [n_terms] or None, d_neg u8 [n_terms] or None, d_points [n_points][32] ->
         d_out [n_sums][32], d_status [n_sums]; nothing is read on the host, the launches depend on n_terms and n_sums alone"""
         _check(self._lib.zkp_sum_points_dev(self._h, n_sums, d_off, d_pidx, d_neg, d_points, n_points, n_terms, d_out, d_status), "zkp_sum_points_dev")
+
+    def dlog_base_dev(self, n, d_points, bits, d_out, d_status) -> None:
+        """zkp_dlog_base_dev: d_points [n][32] (16-byte aligned) -> d_out u64 [n], d_status u8 [n]; queued on the context's stream"""
+        _check(self._lib.zkp_dlog_base_dev(self._h, n, d_points, bits, d_out, d_status), "zkp_dlog_base_dev")
 
     def transcripts_append_message_dev(self, n, shared_initial, d_ts_in, d_ts_out, label: bytes, d_msgs, msgs_len, d_offsets) -> None:
         """zkp_transcripts_append_message_dev: blobs 16-byte aligned (d_ts_out may be d_ts_in when not shared), d_offsets u64 [n + 1] 8-byte

@@ -647,6 +647,38 @@ def point_sum(eng, off, points, pidx=None, neg=None, threads: int = 0):
     return out, status
 
 
+# ---- bounded discrete logarithms to the basepoint (include/zkp_toolbox.h): m from encode(m B), m < 2**bits; eng = None is the host backend ----
+def basepoint_dlog(eng, points, bits: int, threads: int = 0):
+    """points [n][32] -> (k uint64 [n], status uint8 [n]): status 0 and encode(k B) == points[i] with k < 2**bits, 1 where the encoding does not
+    decode, 2 where no k is in range (k = 0 for both).  bits in 1 .. 48.  Variable time: the duration depends on the logarithms."""
+    from .engine import _u8
+    points = _u8(points, 32)
+    n = len(points)
+    out = np.zeros(n, np.uint64)
+    status = np.zeros(n, np.uint8)
+    _raise(lib().zkp_basepoint_dlog_batch(None if eng is None else eng._h, n, _p(points), bits, _p(out), _p(status), threads), "zkp_basepoint_dlog_batch")
+    return out, status
+
+
+def set_dlog_baby_bits(baby_bits: int) -> None:
+    """the size of the host backend's baby-step table (2**baby_bits rows, 4 .. 22) for later basepoint_dlog calls"""
+    _raise(lib().zkp_toolbox_set_dlog_baby_bits(baby_bits), "zkp_toolbox_set_dlog_baby_bits")
+
+
+def get_dlog_baby_bits() -> int:
+    return int(lib().zkp_toolbox_get_dlog_baby_bits())
+
+
+def set_dlog_host_max_steps(steps: int) -> None:
+    """calls whose host work n * (2**(bits - host baby_bits) + 128) -- giant steps, a point counting 128 for its decode and halving -- is at most
+    `steps` per thread (threads counted up to 16) stay on the host threads even with an engine"""
+    lib().zkp_toolbox_set_dlog_host_max_steps(steps)
+
+
+def get_dlog_host_max_steps() -> int:
+    return int(lib().zkp_toolbox_get_dlog_host_max_steps())
+
+
 # ---- pipelines and device groups (include/zkp_toolbox.h, round 4) ------------------------------------------------------
 def pinned_empty(shape, dtype=np.uint8) -> np.ndarray:
     """A numpy array in pinned host memory (zkp_host_alloc): jobs copy from / to it without staging.  The memory is freed when
