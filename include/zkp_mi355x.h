@@ -700,6 +700,41 @@ uint32_t zkp_dlog_group(void);
 uint32_t zkp_dlog_chunk(void);
 uint32_t zkp_dlog_slice_chunks(uint64_t n);
 
+/* (11) Multiscalar sums with LONG segments, batched: a vector Pedersen commitment sum m_i G_i + r H (constant time, many commitments over one set
+ *     of generators), a weighted tally sum w_k C_k, an aggregated key sum a_k X_k, a caller's own random linear combination.  zkp_msm_many was
+ *     built for very many MSMs of 2 to 11 terms: after its term kernels one lane per MSM adds that MSM's products one after another, and with long
+ *     segments that serial sum is the whole call (profiles/point_sum_bench.txt: one MSM of 2^20 terms 8.9 ms of terms and 3.4 s of sum).
+ *     zkp_msm_segments: meaning, argument checks and results are those of zkp_msm_many -- out[i] = encode(sum over t in [off[i], off[i + 1]) of
+ *       scalars[t] * decode(points[pidx[t]])), scalars any 32 bytes, ZKP_CT or ZKP_VARTIME; status[i] = 1 and 32 zero bytes where a referenced point
+ *       does not decode (the neighbours are left alone), an empty range gives 32 zero bytes and status 0; bad flags, off[0] != 0, decreasing
+ *       offsets and an index >= n_points (host-pointer form) are ZKP_ERR_ARG with nothing written -- and so are its bytes.  pidx == NULL: term t
+ *       uses point t, as in zkp_sum_points, and n_points must equal the number of terms (else ZKP_ERR_ARG).
+ *       The call runs zkp_msm_many's term path unchanged up to the products (decode, classification, comb tables, "k_terms_*" under ZKP_K_TERMS:
+ *       terms on points registered with zkp_ctx_prepare_fixed_points keep their fixed-base walk) on the scalars as given -- nothing is halved, the
+ *       shared-inversion encoder is not used -- and then folds the term axis in the levels of zkp_sum_points: "k_sum_fold_parts" (level 1: item j
+ *       is the product of term j, its bad flag the decode status of point pidx[j], an index at or beyond n_points flags the sum), then
+ *       "k_sum_fold<false>@2", "@3", ... (ZKP_K_REDUCE), and k_sum_encode (ZKP_K_COMBINE).  The launch shapes follow from n_terms and n_msm alone;
+ *       no atomics, one writer per output, every index that reaches memory is below its array's length whatever off and pidx hold.
+ *       THE FOLD HAS NO BRANCH, ADDRESS OR TRIP COUNT THAT DEPENDS ON A SCALAR: it reads products, offsets and indices, and the segment structure
+ *       (off, pidx, n_points) is public, as it is for zkp_msm_many.  What ZKP_CT promises is therefore what the term kernels promise.
+ *       The _dev form takes device pointers (scalars, points, out 16-byte aligned), inspects no device array on the host, synchronises nowhere,
+ *       sizes its workspace up front and may be recorded between zkp_ctx_capture_begin / _end once the same call has run outside the capture;
+ *       n_terms MUST equal d_off[n_msm] (see zkp_sum_points_dev).
+ *     NOT the call for short segments (zkp_msm_many's shared-inversion encoder wins there; zkp_toolbox.h routes by the longest segment) and NOT
+ *       for one long variable-time MSM with an own point per term: zkp_msm_optional's bucket method does a fraction of the point operations.
+ *     Sizes (profiles/msm_segments_bench.txt, one MI355X, stream time, min / median / max over the rounds, against zkp_msm_many on the same job,
+ *       alternated in one process; variable | constant time): 64 segments of 1,024 terms 1.282 / 1.290 / 1.315 ms against 4.173 / 4.194 / 4.204 | 1.435 / 1.446 / 1.452 against 4.326 / 4.355 / 4.390; 1,024 such segments 12.63 / 12.64 / 12.66 ms against 15.87 / 15.96 / 15.98 | 13.97 / 14.04 / 14.04 against 17.23 / 17.29 / 17.31; one segment of
+ *       65,536 terms 1.285 / 1.294 / 1.313 ms against 194.5 / 239.6 / 251.4 | 1.430 / 1.449 / 1.484 against 194.7 / 213.7 / 239.9; one of 2^20 terms 12.95 / 12.99 / 13.02 ms against 3403 / 3444 / 3525 | 14.40 / 14.45 / 14.47 against 3538 / 3810 / 3820; 16 segments of 65,536 terms over 65,536 shared points 6.233 / 6.272 / 6.405 ms against 222.6 / 266.4 / 266.5 | 5.599 / 5.601 / 5.602 against 247.8 / 255.7 / 265.6.  Faster beyond the spread
+ *       at every one of these shapes, stream and synchronous call: the call is zkp_msm_many's term time plus 0.35 to 0.75 ms of fold.
+ *       NOT faster on short segments (4,096 and 65,536 MSMs of 2, 11, 32 and 128 terms: fold against msm_many, ms, medians, variable time -- 4,096 x 2: 1.086 against 0.747; 4,096 x 11: 1.176 against 0.834; 4,096 x 32: 1.920 against 1.562; 4,096 x 128: 6.521 against 6.557; 65,536 x 2: 1.948 against 1.501; 65,536 x 11: 8.745 against 8.279; 65,536 x 32: 23.45 against 23.42; 65,536 x 128: 85.10 against 84.62), and NOT faster than zkp_msm_optional for one
+ *       variable-time MSM with a point per term (65,536 terms: 1.248 ms against 0.834; 2^20 terms: 12.50 ms against 3.142): use those calls there. */
+int zkp_msm_segments(zkp_ctx* ctx, uint32_t n_msm, const uint32_t* off /*[n_msm+1]*/, const uint8_t* scalars /*[T][32]*/,
+                     const uint32_t* pidx /*[T] or NULL*/, const uint8_t* points /*[n_points][32]*/, uint32_t n_points, int flags,
+                     uint8_t* out /*[n_msm][32]*/, uint8_t* status /*[n_msm]*/);
+int zkp_msm_segments_dev(zkp_ctx* ctx, uint32_t n_msm, const uint32_t* d_off /*[n_msm+1]*/, const uint8_t* d_scalars /*[n_terms][32]*/,
+                         const uint32_t* d_pidx /*[n_terms] or NULL*/, const uint8_t* d_points /*[n_points][32]*/, uint32_t n_points,
+                         uint32_t n_terms, int flags, uint8_t* d_out /*[n_msm][32]*/, uint8_t* d_status /*uint8 [n_msm]*/);
+
 /* Timing of the last *_dev / host call on this context, measured with HIP events on the stream the
  * kernels were launched on.  kernel_ms[] is indexed by ZKP_K_*; returns the number of entries. */
 enum {

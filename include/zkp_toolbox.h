@@ -326,6 +326,28 @@ int zkp_multiscalar_mul_batch(zkp_ctx* ctx, uint32_t n_msm, const uint32_t* off 
                               const uint32_t* pidx /*[T]*/, const uint8_t* points /*[n_points][32]*/, uint32_t n_points, int flags, int n_threads,
                               uint8_t* out /*[n_msm][32]*/, uint8_t* status /*[n_msm]*/);
 
+/* Multiscalar sums with segments of ANY length (zkp_mi355x.h (11)): zkp_multiscalar_mul_batch's meaning, checks and bytes -- out[i] =
+ * encode(sum over t in [off[i], off[i + 1]) of scalars[t] * decode(points[pidx[t]])), status[i] = 1 and zeros where a referenced point does not
+ * decode, an empty range 32 zero bytes and status 0, ZKP_CT or ZKP_VARTIME -- for a vector Pedersen commitment, a weighted tally, an aggregated
+ * key.  pidx == NULL: term t uses point t and n_points must be off[n_msm].  Argument errors (as for zkp_multiscalar_mul_batch, and pidx == NULL
+ * with n_points != off[n_msm]) are ZKP_TB_BAD_STATEMENT with nothing written.  Routing, same bytes on every route:
+ *   1. ctx == NULL or off[n_msm] <= zkp_toolbox_get_host_max_terms(): the host threads.  They share the TERM axis: a segment longer than a
+ *      thread's share is cut into per-thread partial sums that are added at the end (zkp_multiscalar_mul_batch gives an MSM to one thread).
+ *   2. otherwise, the longest segment shorter than zkp_toolbox_get_msm_fold_min_segment(): zkp_msm_many, whose shared-inversion encoder wins on
+ *      short segments (with pidx == NULL the toolbox supplies 0, 1, 2, ...).
+ *   3. otherwise zkp_msm_segments.
+ * zkp_toolbox_set_msm_fold_min_segment moves the threshold of step 2 (0: always fold; 0xffffffff: never).  The default is 1,024, from
+ * profiles/msm_segments_bench.txt (stream time, medians, fold against zkp_msm_many, variable time; constant time reads the same): the rule is the
+ * shortest measured length at which the fold is ahead beyond the spread at every measured output count.  Of 2, 11, 32 and 128 terms none is:
+ * 4,096 x 2: 1.086 against 0.747; 4,096 x 11: 1.176 against 0.834; 4,096 x 32: 1.920 against 1.562; 4,096 x 128: 6.521 against 6.557; 65,536 x 2: 1.948 against 1.501; 65,536 x 11: 8.745 against 8.279; 65,536 x 32: 23.45 against 23.42; 65,536 x 128: 85.10 against 84.62.  At 1,024 terms it is: 1.290 against 4.194 ms at 64 segments, 12.64 against 15.96 ms at 1,024.  Between 128 and 1,024 terms nothing is measured; the fold's gain comes from
+ * FEW long segments (one lane per MSM already fills the chip at 65,536 outputs), so a caller with a handful of segments of a few hundred terms
+ * may lower the threshold. */
+int zkp_multiscalar_sum_batch(zkp_ctx* ctx, uint32_t n_msm, const uint32_t* off /*[n_msm+1]*/, const uint8_t* scalars /*[T][32]*/,
+                              const uint32_t* pidx /*[T] or NULL*/, const uint8_t* points /*[n_points][32]*/, uint32_t n_points, int flags,
+                              int n_threads, uint8_t* out /*[n_msm][32]*/, uint8_t* status /*[n_msm]*/);
+void zkp_toolbox_set_msm_fold_min_segment(uint32_t n);
+uint32_t zkp_toolbox_get_msm_fold_min_segment(void);
+
 /* RistrettoPoint sums, batched (zkp_mi355x.h (9)): `P + Q`, `P - Q`, `-P` (ZKP_PT_SUB from the identity, 32 zero bytes at stride 0) and
  * `iter().sum()`, each with the `compress()` that follows.  Routing is that of the calls above: ctx == NULL or n <= zkp_toolbox_get_host_max_terms()
  * (for zkp_point_sum_batch n is the number of terms, off[n_sums]) on the host threads, anything else on the device; same bytes on both routes.

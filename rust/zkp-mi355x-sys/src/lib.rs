@@ -241,6 +241,11 @@ extern "C" {
     pub fn zkp_sum_points_dev(ctx: *mut zkp_ctx, n_sums: u32, d_off: *const u32, d_pidx: *const u32, d_neg: *const u8, d_points: *const u8,
                               n_points: u32, n_terms: u32, d_out: *mut u8, d_status: *mut u8) -> c_int;
     pub fn zkp_sum_points_group() -> u32;
+    // (11) multiscalar sums with long segments: zkp_msm_many's results, the term axis folded in the levels of zkp_sum_points
+    pub fn zkp_msm_segments(ctx: *mut zkp_ctx, n_msm: u32, off: *const u32, scalars: *const u8, pidx: *const u32, points: *const u8, n_points: u32,
+                            flags: c_int, out: *mut u8, status: *mut u8) -> c_int;
+    pub fn zkp_msm_segments_dev(ctx: *mut zkp_ctx, n_msm: u32, d_off: *const u32, d_scalars: *const u8, d_pidx: *const u32, d_points: *const u8,
+                                n_points: u32, n_terms: u32, flags: c_int, d_out: *mut u8, d_status: *mut u8) -> c_int;
     // (10) bounded discrete logarithms to the basepoint (variable time by nature): the context's baby-step table and the search
     pub fn zkp_ctx_prepare_dlog(ctx: *mut zkp_ctx, baby_bits: u32) -> c_int;
     pub fn zkp_dlog_baby_bits(ctx: *mut zkp_ctx) -> u32;
@@ -378,6 +383,11 @@ extern "C" {
                                out: *mut u8, status: *mut u8) -> c_int;
     pub fn zkp_point_sum_batch(ctx: *mut zkp_ctx, n_sums: u32, off: *const u32, pidx: *const u32, neg: *const u8, points: *const u8, n_points: u32,
                                n_threads: c_int, out: *mut u8, status: *mut u8) -> c_int;
+    // multiscalar sums routed by size and by the longest segment (host threads / zkp_msm_many / zkp_msm_segments) and the segment threshold
+    pub fn zkp_multiscalar_sum_batch(ctx: *mut zkp_ctx, n_msm: u32, off: *const u32, scalars: *const u8, pidx: *const u32, points: *const u8,
+                                     n_points: u32, flags: c_int, n_threads: c_int, out: *mut u8, status: *mut u8) -> c_int;
+    pub fn zkp_toolbox_set_msm_fold_min_segment(n: u32);
+    pub fn zkp_toolbox_get_msm_fold_min_segment() -> u32;
     // bounded discrete logarithms to the basepoint behind the same routing; the host table's size and the routing threshold
     pub fn zkp_basepoint_dlog_batch(ctx: *mut zkp_ctx, n: u64, points: *const u8, bits: u32, out: *mut u64, status: *mut u8, n_threads: c_int) -> c_int;
     pub fn zkp_toolbox_set_dlog_baby_bits(baby_bits: u32) -> c_int;

@@ -1,0 +1,148 @@
+"""Multiscalar sums with long segments on the host backend (no GPU): toolbox.multiscalar_sum with eng = None is hostbk::msm_segments_n, which cuts
+the TERM axis over its threads, so a long segment becomes per-thread partial sums that are added at the end.  Byte for byte and status for status
+against the oracle's msm_many on the same job (tests/msm_segments_cases.py) for thread counts 1, 5 and more than there are segments, both flags;
+then the same code in a stand-alone program under AddressSanitizer and UBSan."""
+import os
+import shutil
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from tests import msm_segments_cases as MC
+from zkp_amd import toolbox as T
+from zkp_amd.engine import ZKP_CT, ZKP_VARTIME
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+G = 32                                        # the device fold's group size; the host has none, the lengths are the GPU tests'
+THREADS = (1, 5, 40)
+FLAGS = (ZKP_VARTIME, ZKP_CT)
+BAD_STATEMENT = -10
+
+
+def check(name, off, sc, pidx, points, flags, threads=THREADS):
+    want, want_st = MC.expected(name, off, sc, pidx, points, flags)
+    for t in threads:
+        got, st = T.multiscalar_sum(None, off, sc, points, pidx, flags, threads=t)
+        assert (st == want_st).all(), (name, t)
+        assert (got == want).all(), (name, t)
+    return want, want_st
+
+
+@pytest.mark.parametrize("flags", FLAGS)
+def test_one_segment_of_every_length_around_the_group_edges(flags):
+    for n in MC.single_lengths(G):
+        off, sc, pidx, pts = MC.job([n], seed=n)
+        check("single%d" % n, off, sc, pidx, pts, flags)
+
+
+@pytest.mark.parametrize("flags", FLAGS)
+def test_ragged_job_with_long_segments_cut_over_the_threads(flags):
+    lens = MC.ragged_lengths(G)
+    off, sc, pidx, pts = MC.job(lens, seed=2)
+    assert 750 <= off[-1] <= 950 and max(lens) > off[-1] // 5            # five threads cut the 600-term segment
+    want, st = check("ragged", off, sc, pidx, pts, flags)
+    empty = np.flatnonzero(np.diff(off.astype(np.int64)) == 0)
+    assert len(empty) == 4 and not want[empty].any() and not st.any()
+    # the same bytes as the call that gives every MSM to one thread
+    old, old_st = T.multiscalar_mul(None, off, sc, pidx, pts, flags)
+    assert (old == want).all() and (old_st == st).all()
+
+
+@pytest.mark.parametrize("flags", FLAGS)
+def test_invalid_encodings_flag_their_segments_and_no_other(flags):
+    off, sc, pidx, points, flagged = MC.with_invalid(G)
+    want, st = check("invalid", off, sc, pidx, points, flags)
+    assert np.flatnonzero(st).tolist() == flagged and not want[flagged].any()
+    # the neighbours hold what they hold in the job without the invalid rows
+    clean_off, clean_sc, clean_pidx, pts = MC.job(MC.ragged_lengths(G) + [3 * G + 7, 4, 0, 9], seed=3)
+    clean, _ = MC.expected("invalid-clean", clean_off, clean_sc, clean_pidx, pts, flags)
+    rest = [i for i in range(len(off) - 1) if i not in flagged]
+    assert (want[rest] == clean[rest]).all()
+
+
+@pytest.mark.parametrize("flags", FLAGS)
+def test_scalar_and_point_special_cases(flags):
+    off, sc, pidx, pts, identity = MC.special_cases(G)
+    want, st = check("special", off, sc, pidx, pts, flags)
+    assert not st.any() and not want[identity].any() and want[2].any() and want[4].any()
+
+
+@pytest.mark.parametrize("flags", FLAGS)
+def test_without_pidx_term_t_uses_point_t(flags):
+    off, sc, pidx, pts = MC.job(MC.ragged_lengths(G), seed=2)
+    want, want_st = MC.expected("ragged", off, sc, pidx, pts, flags)
+    _, _, rows = MC.own_points(off, sc, pidx, pts)
+    for t in THREADS:
+        got, st = T.multiscalar_sum(None, off, sc, rows, None, flags, threads=t)
+        assert (got == want).all() and (st == want_st).all()
+    with pytest.raises(Exception):
+        T.multiscalar_sum(None, off, sc, rows[:-1], None, flags)          # n_points != n_terms
+
+
+def test_argument_errors_write_nothing():
+    off, sc, pidx, pts = MC.job([3, 0, 5], seed=4)
+    out, st = np.full((3, 32), 0xEE, np.uint8), np.full(3, 0xEE, np.uint8)
+    OF, SCp, PI, P, O, ST = (a.ctypes.data for a in (off, sc, pidx, pts, out, st))
+    call = T.lib().zkp_multiscalar_sum_batch
+    assert call(None, 0, None, None, None, None, 0, 0, 0, None, None) == 0
+    assert call(None, 3, OF, SCp, PI, P, len(pts), 2, 0, O, ST) == BAD_STATEMENT           # flags
+    assert call(None, 3, OF, SCp, PI, P, len(pts), -1, 0, O, ST) == BAD_STATEMENT
+    one = np.array([1, 3, 3, 8], np.uint32)
+    assert call(None, 3, one.ctypes.data, SCp, PI, P, len(pts), 0, 0, O, ST) == BAD_STATEMENT     # off[0] != 0
+    dec = np.array([0, 5, 3, 8], np.uint32)
+    assert call(None, 3, dec.ctypes.data, SCp, PI, P, len(pts), 0, 0, O, ST) == BAD_STATEMENT     # decreasing
+    assert call(None, 3, OF, SCp, PI, P, int(pidx.max()), 0, 0, O, ST) == BAD_STATEMENT           # an index out of range
+    assert call(None, 3, OF, SCp, None, P, len(pts), 0, 0, O, ST) == BAD_STATEMENT                # no pidx: n_points must be the number of terms
+    for args in ((None, SCp, PI, P), (OF, None, PI, P), (OF, SCp, PI, None)):
+        assert call(None, 3, *args, len(pts), 0, 0, O, ST) == BAD_STATEMENT
+    assert call(None, 3, OF, SCp, PI, P, len(pts), 0, 0, None, ST) == BAD_STATEMENT
+    assert call(None, 3, OF, SCp, PI, P, len(pts), 0, 0, O, None) == BAD_STATEMENT
+    assert (out == 0xEE).all() and (st == 0xEE).all()
+
+
+def test_threshold_setter_and_the_declarations_parse():
+    from zkp_amd import cabi
+    tb, dev = cabi.signatures("zkp_toolbox.h"), cabi.signatures("zkp_mi355x.h")
+    assert {"zkp_multiscalar_sum_batch", "zkp_toolbox_set_msm_fold_min_segment", "zkp_toolbox_get_msm_fold_min_segment"} <= set(tb)
+    assert {"zkp_msm_segments", "zkp_msm_segments_dev"} <= set(dev)
+    old = T.get_msm_fold_min_segment()
+    assert old > 0
+    try:
+        T.set_msm_fold_min_segment(77)
+        assert T.get_msm_fold_min_segment() == 77
+    finally:
+        T.set_msm_fold_min_segment(old)
+
+
+def test_the_pedersen_vector_example_on_the_host():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "examples", "pedersen_vector_batch.py"), "6", "40", "--host"], cwd=ROOT,
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "agree" in r.stdout
+
+
+def test_msm_segments_n_under_sanitizers(tmp_path):
+    """tests/host/msm_segments_host_main.cpp + host/host_backend.cpp, g++ -fsanitize=address,undefined, as a child process: hostbk::msm_segments_n
+    against hostbk::msm_many on a ragged job with invalid rows, on heap blocks of exactly the size a call may touch.  Exit 0, silent sanitizers,
+    and every printed encoding equal to the oracle's."""
+    gxx = shutil.which("g++")
+    assert gxx, "g++ is needed (it builds the host library too)"
+    exe = tmp_path / "msm_segments_host_main"
+    subprocess.run([gxx, "-std=c++17", "-O1", "-g", "-pthread", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Wno-unknown-pragmas",
+                    os.path.join(ROOT, "tests", "host", "msm_segments_host_main.cpp"), os.path.join(ROOT, "zkp_amd", "csrc", "host", "host_backend.cpp"),
+                    "-o", str(exe)], check=True, capture_output=True, text=True)
+    off, sc, pidx, points, flagged = MC.with_invalid(8, seed=5)
+    want, want_st = MC.expected("invalid8", off, sc, pidx, points, ZKP_VARTIME)
+    hexrows = lambda a: "\n".join(bytes(r).hex() for r in a)
+    (tmp_path / "job.txt").write_text("%d %d %d\n%s\n%s\n%s\n%s\n" % (len(off) - 1, len(pidx), len(points), " ".join(map(str, off)), " ".join(map(str, pidx)),
+                                                                       hexrows(sc), hexrows(points)))
+    r = subprocess.run([str(exe), str(tmp_path / "job.txt")], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
+    assert "ERROR" not in r.stderr and "runtime error" not in r.stderr
+    lines = [ln.split() for ln in r.stdout.splitlines() if ln.startswith("M ")]
+    assert len(lines) == len(want)
+    for i, (_, enc, st) in enumerate(lines):
+        assert enc == bytes(want[i]).hex() and int(st, 16) == want_st[i], i
+    assert np.flatnonzero(want_st).tolist() == flagged

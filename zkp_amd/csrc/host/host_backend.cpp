@@ -13,6 +13,8 @@
 //   msm_many      per MSM a Straus walk over signed radix-16 digits, table {1..8} P per distinct point of the MSM.  flags = ZKP_CT: the
 //                 table entry is picked with masks over all eight entries and zero digits are added like any other (what
 //                 curve25519-dalek's constant-time multiscalar_mul does, prover.rs:94); ZKP_VARTIME: indexed, zeros skipped.
+//   msm_segments_n  zkp_msm_segments (11): msm_many's results with the TERM axis cut over the threads.  A thread walks the terms of its stretch segment by
+//                 segment (the same Straus walk); a segment longer than a stretch leaves one partial sum per stretch, added at the end.
 //   msm_optional  the same walk over n points with decode-or-None (verifier.rs:162-166, batch_verifier.rs:219-228).
 //   decode_check  ristretto decode.
 //   from_uniform_bytes  RFC 9496 section 4.3.4 (ristretto_from_uniform_bytes of ge25519.h: selects only, constant time), then the encoder.
@@ -32,6 +34,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <thread>
 #include <vector>
 
 #define ZKP_HOST_FE51 1        // this translation unit (and no other of the library) gets the 5 x 51-bit field under the device's point formulas
@@ -149,6 +152,114 @@ int msm_many(uint32_t n_msm, const uint32_t* off, const uint8_t* scalars, const 
     else straus<false>(acc, k, reinterpret_cast<const int8_t(*)[65]>(dig.data()), tp.data());
     encode(out + 32 * (size_t)i, acc);
   }
+  return ZKP_OK;
+}
+
+// ---- multiscalar sums with long segments (zkp_mi355x.h (11)) ----
+namespace {
+// One thread's stretch [lo, hi) of the term axis: a table per distinct point the stretch uses, and per segment it meets one Straus walk over the
+// terms the two share.  A segment that lies wholly inside is finished here (out, status); the others leave a partial sum for the caller.
+struct SegPartial { uint32_t seg; bool bad; ge_p3 sum; };
+void msm_stretch(uint32_t lo, uint32_t hi, uint32_t n_msm, const uint32_t* off, const uint8_t* scalars, const uint32_t* pidx, const uint8_t* points,
+                 uint32_t n_points, int flags, uint8_t* out, uint8_t* status, std::vector<SegPartial>& partials) {
+  std::map<uint32_t, uint32_t> slot;                 // point -> table (a stretch touches few of a large catalogue's points)
+  std::vector<Table> tabs;
+  std::vector<uint8_t> ok;
+  std::vector<uint32_t> term_slot(hi - lo);
+  for (uint32_t t = lo; t < hi; ++t) {
+    const uint32_t pi = pidx ? pidx[t] : t;
+    auto it = slot.find(pi);
+    if (it == slot.end()) {
+      ge_p3 p;
+      const uint32_t good = decode(p, points + 32 * (size_t)pi);
+      it = slot.emplace(pi, (uint32_t)tabs.size()).first;
+      tabs.emplace_back();
+      ok.push_back((uint8_t)good);
+      if (good) build_table(tabs.back(), p);
+    }
+    term_slot[t - lo] = it->second;
+  }
+  std::vector<int8_t> dig;
+  std::vector<const Table*> tp;
+  uint32_t s = (uint32_t)(std::upper_bound(off, off + n_msm + 1, lo) - off) - 1;      // the segment of term lo
+  for (; s < n_msm && off[s] < hi; ++s) {
+    const uint32_t a = std::max(off[s], lo), b = std::min(off[s + 1], hi);
+    if (a >= b) continue;                                                                // an empty segment inside the stretch
+    const size_t k = b - a;
+    dig.resize(65 * k);
+    tp.resize(k);
+    bool bad = false;
+    for (size_t j = 0; j < k; ++j) {
+      recode16(reinterpret_cast<int8_t(*)[65]>(dig.data())[j], scalars + 32 * (size_t)(a + j));
+      tp[j] = &tabs[term_slot[a + j - lo]];
+      bad |= !ok[term_slot[a + j - lo]];
+    }
+    ge_p3 acc;
+    ge_identity(acc);
+    if (!bad) {
+      if (flags == ZKP_CT) straus<true>(acc, k, reinterpret_cast<const int8_t(*)[65]>(dig.data()), tp.data());
+      else straus<false>(acc, k, reinterpret_cast<const int8_t(*)[65]>(dig.data()), tp.data());
+    }
+    if (a == off[s] && b == off[s + 1]) {
+      status[s] = bad ? 1 : 0;
+      if (bad) std::memset(out + 32 * (size_t)s, 0, 32);
+      else encode(out + 32 * (size_t)s, acc);
+    } else {
+      partials.push_back({s, bad, acc});
+    }
+  }
+}
+}  // namespace
+
+int msm_segments_n(uint32_t n_msm, const uint32_t* off, const uint8_t* scalars, const uint32_t* pidx, const uint8_t* points, uint32_t n_points, int flags,
+                   int n_threads, uint8_t* out, uint8_t* status) {
+  if (flags != ZKP_CT && flags != ZKP_VARTIME) return ZKP_ERR_ARG;
+  if (n_msm == 0) return ZKP_OK;
+  if (!off || !out || !status || off[0] != 0) return ZKP_ERR_ARG;
+  for (uint32_t i = 0; i < n_msm; ++i)
+    if (off[i + 1] < off[i]) return ZKP_ERR_ARG;
+  const uint32_t T = off[n_msm];
+  if (T && (!scalars || !points || n_points == 0)) return ZKP_ERR_ARG;
+  if (!pidx && n_points != T) return ZKP_ERR_ARG;
+  if (pidx)
+    for (uint32_t t = 0; t < T; ++t)
+      if (pidx[t] >= n_points) return ZKP_ERR_ARG;
+  for (uint32_t i = 0; i < n_msm; ++i)
+    if (off[i + 1] == off[i]) { std::memset(out + 32 * (size_t)i, 0, 32); status[i] = 0; }
+  if (T == 0) return ZKP_OK;
+  // stretches of equal numbers of terms, at least MIN_STRETCH each: a stretch pays the 256 doublings of its walks whatever its length
+  constexpr uint32_t MIN_STRETCH = 16;
+  unsigned t = n_threads > 0 ? (unsigned)n_threads : std::thread::hardware_concurrency();
+  t = std::max(1u, std::min(std::min(t, 128u), (T + MIN_STRETCH - 1) / MIN_STRETCH));
+  const uint32_t share = (uint32_t)(((uint64_t)T + t - 1) / t);
+  std::vector<std::vector<SegPartial>> partials(t);
+  auto work = [&](unsigned k) {
+    const uint32_t lo = (uint32_t)std::min<uint64_t>(T, (uint64_t)k * share), hi = (uint32_t)std::min<uint64_t>(T, (uint64_t)lo + share);
+    if (lo < hi) msm_stretch(lo, hi, n_msm, off, scalars, pidx, points, n_points, flags, out, status, partials[k]);
+  };
+  std::vector<std::thread> pool;
+  for (unsigned k = 1; k < t; ++k) pool.emplace_back(work, k);
+  work(0);
+  for (std::thread& th : pool) th.join();
+  // the cut segments: their partial sums lie in stretch order, those of one segment next to each other
+  ge_p3 acc;
+  bool bad = false, open = false;
+  uint32_t seg = 0;
+  auto finish = [&]() {
+    status[seg] = bad ? 1 : 0;
+    if (bad) std::memset(out + 32 * (size_t)seg, 0, 32);
+    else encode(out + 32 * (size_t)seg, acc);
+  };
+  for (const auto& list : partials)
+    for (const SegPartial& p : list) {
+      if (open && p.seg != seg) { finish(); open = false; }
+      if (!open) { ge_identity(acc); bad = false; seg = p.seg; open = true; }
+      ge_cached c;
+      ge_to_cached(c, p.sum);
+      ge_add_cached(acc, acc, c);
+      bad |= p.bad;
+    }
+  if (open) finish();
   return ZKP_OK;
 }
 

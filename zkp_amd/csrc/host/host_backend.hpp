@@ -10,6 +10,11 @@ namespace zkp {
 namespace hostbk {
 int msm_many(uint32_t n_msm, const uint32_t* off, const uint8_t* scalars, const uint32_t* pidx, const uint8_t* points, uint32_t n_points, int flags,
              uint8_t* out, uint8_t* status);
+// zkp_msm_segments (11): the results of msm_many (pidx == NULL: term t uses point t and n_points must be the number of terms), every argument
+// checked before anything is written.  The term axis is cut into one stretch per thread (n_threads <= 0: one per core; never less than 16 terms
+// each), so one long segment is the work of all threads where msm_many gives it to one.
+int msm_segments_n(uint32_t n_msm, const uint32_t* off, const uint8_t* scalars, const uint32_t* pidx /*or NULL*/, const uint8_t* points, uint32_t n_points,
+                   int flags, int n_threads, uint8_t* out, uint8_t* status);
 int msm_optional(uint64_t n, const uint8_t* scalars, const uint8_t* points, uint8_t out_point[32], int* status);
 int decode_check(uint64_t n, const uint8_t* points, uint8_t* status);
 int from_uniform_bytes(uint64_t n, const uint8_t* in /*[n][64]*/, uint8_t* out /*[n][32]*/);      // zkp_from_uniform_bytes (5)

@@ -1036,6 +1036,47 @@ int zkp_multiscalar_mul_batch(zkp_ctx* ctx, uint32_t n_msm, const uint32_t* off,
   return rc.load() ? ZKP_TB_BAD_STATEMENT : ZKP_TB_OK;
 }
 
+// ---- multiscalar sums with long segments (zkp_mi355x.h (11)) ------------------------------------------------------------------------------
+// The shortest longest-segment from which a device job folds its term axis (zkp_msm_segments) instead of summing each MSM in one lane
+// (zkp_msm_many).  profiles/msm_segments_bench.txt (stream medians, fold against zkp_msm_many): of the short lengths none has the fold ahead beyond the
+// spread at both output counts -- 4,096 x 2: 1.086 against 0.747; 4,096 x 11: 1.176 against 0.834; 4,096 x 32: 1.920 against 1.562; 4,096 x 128: 6.521 against 6.557; 65,536 x 2: 1.948 against 1.501; 65,536 x 11: 8.745 against 8.279; 65,536 x 32: 23.45 against 23.42; 65,536 x 128: 85.10 against 84.62 -- and 1,024 is the shortest measured length that has (1.290 against 4.194 ms at 64 segments, 12.64 against 15.96 ms at 1,024).
+static std::atomic<uint32_t> g_msm_fold_min_segment{1024};
+void zkp_toolbox_set_msm_fold_min_segment(uint32_t n) { g_msm_fold_min_segment = n; }
+uint32_t zkp_toolbox_get_msm_fold_min_segment(void) { return g_msm_fold_min_segment.load(); }
+
+// Every check is made here, before anything is written, so that the three routes refuse the same calls.
+int zkp_multiscalar_sum_batch(zkp_ctx* ctx, uint32_t n_msm, const uint32_t* off, const uint8_t* scalars, const uint32_t* pidx, const uint8_t* points,
+                              uint32_t n_points, int flags, int n_threads, uint8_t* out, uint8_t* status) {
+  if (flags != ZKP_CT && flags != ZKP_VARTIME) return ZKP_TB_BAD_STATEMENT;
+  if (n_msm == 0) return ZKP_TB_OK;
+  if (!off || !out || !status || off[0] != 0) return ZKP_TB_BAD_STATEMENT;
+  uint32_t longest = 0;
+  for (uint32_t i = 0; i < n_msm; ++i) {
+    if (off[i + 1] < off[i]) return ZKP_TB_BAD_STATEMENT;
+    longest = std::max(longest, off[i + 1] - off[i]);
+  }
+  const uint32_t n_terms = off[n_msm];
+  if (n_terms && (!scalars || !points || n_points == 0)) return ZKP_TB_BAD_STATEMENT;
+  if (!pidx && n_points != n_terms) return ZKP_TB_BAD_STATEMENT;
+  if (pidx)
+    for (uint32_t t = 0; t < n_terms; ++t)
+      if (pidx[t] >= n_points) return ZKP_TB_BAD_STATEMENT;
+  int rc;
+  if (on_host(ctx, n_terms)) {
+    rc = zkp::hostbk::msm_segments_n(n_msm, off, scalars, pidx, points, n_points, flags, n_threads, out, status);
+  } else if (longest < g_msm_fold_min_segment.load()) {
+    std::vector<uint32_t> iota;
+    if (!pidx) {
+      iota.resize(n_terms);
+      for (uint32_t t = 0; t < n_terms; ++t) iota[t] = t;
+    }
+    rc = zkp_msm_many(ctx, n_msm, off, scalars, pidx ? pidx : iota.data(), points, n_points, flags, out, status);
+  } else {
+    rc = zkp_msm_segments(ctx, n_msm, off, scalars, pidx, points, n_points, flags, out, status);
+  }
+  return rc == ZKP_ERR_ARG ? ZKP_TB_BAD_STATEMENT : rc;
+}
+
 // ---- RistrettoPoint sums (zkp_mi355x.h (9)): pairs and CSR segments behind the same routing ------------------------------------------------
 int zkp_point_add_batch(zkp_ctx* ctx, uint64_t n, const uint8_t* a, uint32_t a_stride, const uint8_t* b, uint32_t b_stride, int op, int n_threads,
                         uint8_t* out, uint8_t* status) {

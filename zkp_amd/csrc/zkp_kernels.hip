@@ -1533,6 +1533,52 @@ k_sum_fold(uint32_t n_items, uint32_t last, const uint32_t* __restrict__ off, ui
   }
 }
 
+// k_sum_fold_parts: level 1 of the fold for zkp_msm_segments (zkp_mi355x.h (11)).  Item j is part[j], the product the term kernels left for term j in
+// extended coordinates; its bad flag is the valid word of point pidx[j] (an index at or beyond n_points flags the sum and reads no point), its segment
+// comes from segment_of_term for the lane's first term and the walk along off, as in k_sum_fold<true>.  The additions are the complete ge_add_p3 and
+// the runs go where k_sum_fold sends them, so k_sum_fold<false> takes over from level 2.  Nothing here reads a scalar: branches, addresses and trip
+// counts follow from off, n_items and n_points alone, and every index that reaches memory is below its array's length whatever off and pidx hold.
+__global__ void __launch_bounds__(256, 2)
+k_sum_fold_parts(uint32_t n_items, uint32_t last, const uint32_t* __restrict__ off, uint32_t n_sums, const uint32_t* __restrict__ pidx, uint32_t n_points,
+                 const dev_affine* __restrict__ pts, const dev_ext* __restrict__ part, sum_item* __restrict__ out, sum_item* __restrict__ fin) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t b64 = (uint64_t)g * SUM_GROUP;
+  if (b64 >= n_items) return;
+  const uint32_t b = (uint32_t)b64, e = b64 + SUM_GROUP < n_items ? b + SUM_GROUP : n_items;
+  ge_p3 acc;
+  ge_identity(acc);
+  uint32_t cur = segment_of_term(off, n_sums, b), end = off[cur + 1], bad = 0, runs = 0;
+#pragma unroll 1
+  for (uint32_t j = b; j < e; ++j) {
+    uint32_t s = cur;
+    while (j >= end && s + 1 < n_sums) { ++s; end = off[s + 1]; }
+    const uint32_t pi = pidx[j];
+    const uint32_t ibad = pi < n_points ? (pts[pi].valid ^ 1u) : 1u;
+    ge_p3 q;
+    load_ext(q, part + j);
+    if (j != b && s != cur) {                                     // the run of `cur` ends here
+      store_item(runs == 0 && !last ? out + 2 * (size_t)g : fin + cur, acc, cur, bad);
+      ++runs;
+      ge_identity(acc);
+      bad = 0;
+    }
+    cur = s;
+    bad |= ibad;
+    ge_add_p3(acc, acc, q);
+  }
+  store_item(last ? fin + cur : out + 2 * (size_t)g + (runs != 0), acc, cur, bad);
+  if (!last && runs == 0) {                                       // one run: the second item is the identity under the same segment
+    ge_identity(acc);
+    store_item(out + 2 * (size_t)g + 1, acc, cur, 0u);
+  }
+}
+
+// k_iota: v[i] = i (zkp_msm_segments / _dev without pidx: the term kernels want an index per term)
+__global__ void k_iota(uint32_t n, uint32_t* __restrict__ v) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) v[i] = i;
+}
+
 // k_sum_encode: out[s] = the encoding of fin[s], zeros and status 1 where the sum met a point that does not decode; an empty segment has no slot
 // and is the identity (32 zero bytes, status 0).
 __global__ void __launch_bounds__(256, 2)
@@ -1984,6 +2030,7 @@ struct terms_cfg {
   stmt_job stmt;                   // fused flows: the statement's term structure (one-launch classifier, k_stmt_classify)
   bool canonical = false;          // constant-time calls: every scalar the term kernel reads is reduced mod l (the fused prove flows), so the walks skip the carry window
   bool rider_tables = false;       // stmt.pair: max_tables counts a table of multiples for every per-proof point whose terms all ride (stmt_pairs.h: stmt_rider)
+  bool terms_only = false;         // stop after the term kernels: part holds s_t P_t for every term (never halved), nothing is reduced or encoded (zkp_msm_segments)
 };
 inline bool stmt_classify_applies(const terms_cfg& k, uint32_t n_terms) {
   return k.stmt.on && n_terms >= 1024 && k.stmt.T <= STMT_MAX_TERMS && k.stmt.np <= STMT_MAX_POINTS && k.stmt.T && k.stmt.N;
@@ -2025,11 +2072,12 @@ terms_layout terms_carve(size_t start, uint32_t n_points, uint32_t n_terms, uint
   o.comb = cv.take(split ? (size_t)k.max_tables * comb_entries(k.teeth) * sizeof(dev_ext) : 0);
   o.ladder = cv.take(split ? (((size_t)k.max_ladder + 63) / 64) * (k.stmt.pair ? 2 : 1) * LADDER_GROUP_UINT4 * sizeof(uint4) : 0);   // wave-interleaved groups of 64 tables (comb_tables.h)
   const uint32_t enc_blocks = (n_msm + ENC_BLOCK - 1) / ENC_BLOCK;
-  o.half = cv.take(split ? (size_t)n_terms * 32 : 0);            // (batched encoder: reserved whenever it could be chosen)
-  o.states = cv.take(split ? (size_t)n_msm * 54 * 4 : 0);
-  o.xs = cv.take(split ? (size_t)n_msm * 9 * 4 : 0);
-  o.bprod = cv.take(split ? (size_t)enc_blocks * 9 * 4 * 2 : 0);
-  o.zflag = cv.take(split ? (size_t)n_msm : 0);
+  const bool enc = split && !k.terms_only;
+  o.half = cv.take(enc ? (size_t)n_terms * 32 : 0);              // (batched encoder: reserved whenever it could be chosen)
+  o.states = cv.take(enc ? (size_t)n_msm * 54 * 4 : 0);
+  o.xs = cv.take(enc ? (size_t)n_msm * 9 * 4 : 0);
+  o.bprod = cv.take(enc ? (size_t)enc_blocks * 9 * 4 * 2 : 0);
+  o.zflag = cv.take(enc ? (size_t)n_msm : 0);
   o.end = cv.off;
   return o;
 }
@@ -2087,7 +2135,7 @@ int msm_terms_path(zkp_ctx* c, uint32_t n_msm, const uint32_t* d_off, const uint
                    int phase = PH_ALL, const terms_cfg& cfg_in = terms_cfg()) {
   const terms_cfg k = terms_cfg_clamped(cfg_in, n_points, n_terms);
   const terms_layout o = terms_carve(ws_reserved, n_points, n_terms, n_msm, k);
-  const bool batched_encode = terms_batched_encode(c, n_terms, n_msm, k.throughput);
+  const bool batched_encode = !k.terms_only && terms_batched_encode(c, n_terms, n_msm, k.throughput);
   const uint32_t enc_blocks = (n_msm + ENC_BLOCK - 1) / ENC_BLOCK;
   // ensure_ws was done by the caller for ws_reserved + this much; recompute defensively
   if (o.end > c->ws_bytes) return fail(ZKP_ERR_ARG, "internal: workspace too small");
@@ -2240,6 +2288,7 @@ int msm_terms_path(zkp_ctx* c, uint32_t n_msm, const uint32_t* d_off, const uint
   }
   if (!(phase & PH_SCALARS)) { HIP_TRY(hipGetLastError()); return ZKP_OK; }
   prof_mark(c, ZKP_K_TERMS);
+  if (k.terms_only) { HIP_TRY(hipGetLastError()); return ZKP_OK; }   // the caller folds part itself
   if (n_msm && batched_encode) {
     uint32_t* states = reinterpret_cast<uint32_t*>(base + o.states);
     uint32_t* xs = reinterpret_cast<uint32_t*>(base + o.xs);
@@ -2253,11 +2302,13 @@ int msm_terms_path(zkp_ctx* c, uint32_t n_msm, const uint32_t* d_off, const uint
     hipLaunchKernelGGL(k_encode_invert, dim3(enc_groups), dim3(ENC_BLOCK), 0, c->stream, enc_blocks, bprod, binv);
     hipLaunchKernelGGL(k_encode_finish, dim3(enc_blocks), dim3(ENC_BLOCK), 0, c->stream, n_msm, d_off, d_pidx, n_points, pts, part, states, xs, binv, zflag,
                        (const uint8_t*)d_status8, (const uint32_t*)d_status32, d_out, k.map);
+    prof_note(c, ZKP_K_REDUCE, "k_encode_prepare;k_encode_invert;k_encode_finish");
   } else if (n_msm) {
     if (d_status8)
       hipLaunchKernelGGL(k_reduce_encode<uint8_t>, grid1(n_msm, 256), dim3(256), 0, c->stream, n_msm, d_off, d_pidx, n_points, pts, part, d_out, d_status8, k.map);
     else
       hipLaunchKernelGGL(k_reduce_encode<uint32_t>, grid1(n_msm, 256), dim3(256), 0, c->stream, n_msm, d_off, d_pidx, n_points, pts, part, d_out, d_status32, k.map);
+    prof_note(c, ZKP_K_REDUCE, "k_reduce_encode");
   }
   prof_mark(c, ZKP_K_REDUCE);
   HIP_TRY(hipGetLastError());
@@ -2695,13 +2746,13 @@ sum_ws sum_points_ws(uint32_t n_points, uint32_t n_terms, uint32_t n_sums, size_
   w.total = cv.off;
   return w;
 }
-int launch_sum_points(zkp_ctx* c, uint32_t n_sums, const uint32_t* d_off, const uint32_t* d_pidx, const uint8_t* d_neg, const uint8_t* d_points, uint32_t n_points,
-                      uint32_t n_terms, char* ws, const sum_ws& w, uint8_t* d_out, uint8_t* d_status) {
+// The levels of a fold over n_terms > 0 terms and the encode.  level1(grid, n, last, out) launches the kernel that reads the terms -- decoded points
+// (zkp_sum_points) or the term kernels' partials (zkp_msm_segments) -- and returns its name; levels 2 and up are k_sum_fold<false> on what it handed on.
+template <typename LEVEL1>
+int launch_sum_levels(zkp_ctx* c, uint32_t n_sums, const uint32_t* d_off, uint32_t n_terms, char* ws, const sum_ws& w, uint8_t* d_out, uint8_t* d_status,
+                      LEVEL1&& level1) {
   sum_item* fin = reinterpret_cast<sum_item*>(ws + w.fin);
   if (n_terms) {
-    dev_affine* pts = reinterpret_cast<dev_affine*>(ws + w.aff);
-    hipLaunchKernelGGL(k_decode_affine, grid1(n_points, 256), dim3(256), 0, c->stream, n_points, d_points, pts, (const uint32_t*)nullptr);
-    prof_mark(c, ZKP_K_DECODE);
     sum_item* bufs[2] = {reinterpret_cast<sum_item*>(ws + w.a), reinterpret_cast<sum_item*>(ws + w.b)};
     const sum_item* in = nullptr;
     uint32_t n = n_terms;
@@ -2709,11 +2760,13 @@ int launch_sum_points(zkp_ctx* c, uint32_t n_sums, const uint32_t* d_off, const 
       const uint32_t last = n <= SUM_GROUP;
       sum_item* out = bufs[(level - 1) & 1];
       const dim3 grid = grid1(((size_t)n + SUM_GROUP - 1) / SUM_GROUP, SUM_FOLD_BLOCK);
-      if (level == 1)
-        hipLaunchKernelGGL(k_sum_fold<true>, grid, dim3(SUM_FOLD_BLOCK), 0, c->stream, n, last, d_off, n_sums, d_pidx, d_neg, n_points, pts, in, out, fin);
-      else
-        hipLaunchKernelGGL(k_sum_fold<false>, grid, dim3(SUM_FOLD_BLOCK), 0, c->stream, n, last, d_off, n_sums, d_pidx, d_neg, n_points, pts, in, out, fin);
-      prof_note(c, ZKP_K_REDUCE, level == 1 ? std::string("k_sum_fold<true>") : "k_sum_fold<false>@" + std::to_string(level));
+      if (level == 1) {
+        prof_note(c, ZKP_K_REDUCE, level1(grid, n, last, out));
+      } else {
+        hipLaunchKernelGGL(k_sum_fold<false>, grid, dim3(SUM_FOLD_BLOCK), 0, c->stream, n, last, d_off, n_sums, (const uint32_t*)nullptr, (const uint8_t*)nullptr, 0u,
+                           (const dev_affine*)nullptr, in, out, fin);
+        prof_note(c, ZKP_K_REDUCE, "k_sum_fold<false>@" + std::to_string(level));
+      }
       if (last) break;
       n = sum_next_items(n);
       in = out;
@@ -2724,6 +2777,45 @@ int launch_sum_points(zkp_ctx* c, uint32_t n_sums, const uint32_t* d_off, const 
   prof_mark(c, ZKP_K_COMBINE);
   HIP_TRY(hipGetLastError());
   return ZKP_OK;
+}
+int launch_sum_points(zkp_ctx* c, uint32_t n_sums, const uint32_t* d_off, const uint32_t* d_pidx, const uint8_t* d_neg, const uint8_t* d_points, uint32_t n_points,
+                      uint32_t n_terms, char* ws, const sum_ws& w, uint8_t* d_out, uint8_t* d_status) {
+  dev_affine* pts = reinterpret_cast<dev_affine*>(ws + w.aff);
+  if (n_terms) {
+    hipLaunchKernelGGL(k_decode_affine, grid1(n_points, 256), dim3(256), 0, c->stream, n_points, d_points, pts, (const uint32_t*)nullptr);
+    prof_mark(c, ZKP_K_DECODE);
+  }
+  sum_item* fin = reinterpret_cast<sum_item*>(ws + w.fin);
+  return launch_sum_levels(c, n_sums, d_off, n_terms, ws, w, d_out, d_status, [&](dim3 grid, uint32_t n, uint32_t last, sum_item* out) {
+    hipLaunchKernelGGL(k_sum_fold<true>, grid, dim3(SUM_FOLD_BLOCK), 0, c->stream, n, last, d_off, n_sums, d_pidx, d_neg, n_points, pts, (const sum_item*)nullptr, out, fin);
+    return std::string("k_sum_fold<true>");
+  });
+}
+
+// ---- (11) multiscalar sums with long segments: the term path up to `part`, then the fold of point_sum.h over the term axis ----------------------
+// Workspace: [ws_reserved: the caller's staging and, without pidx, the arange] [terms_carve] [fin | A | B of the fold].  d_pidx is never NULL here.
+struct segments_ws { size_t terms = 0; sum_ws sum; };
+segments_ws msm_segments_ws(uint32_t n_points, uint32_t n_terms, uint32_t n_msm, const terms_cfg& k, size_t reserved) {
+  segments_ws w;
+  w.terms = reserved;
+  w.sum = sum_points_ws(0, n_terms, n_msm, reserved + terms_path_ws(n_points, n_terms, n_msm, k));
+  return w;
+}
+int launch_msm_segments(zkp_ctx* c, uint32_t n_msm, const uint32_t* d_off, const uint8_t* d_scalars, const uint32_t* d_pidx, const uint8_t* d_points,
+                        uint32_t n_points, uint32_t n_terms, int flags, const terms_cfg& k, const segments_ws& w, uint8_t* d_out, uint8_t* d_status) {
+  char* ws = static_cast<char*>(c->ws);
+  if (n_terms) {
+    const int rc = msm_terms_path(c, n_msm, d_off, d_scalars, d_pidx, d_points, n_points, n_terms, flags, nullptr, nullptr, nullptr, w.terms, false, PH_ALL, k);
+    if (rc) return rc;
+  }
+  const terms_layout o = terms_carve(w.terms, n_points, n_terms, n_msm, terms_cfg_clamped(k, n_points, n_terms));
+  const dev_affine* pts = reinterpret_cast<const dev_affine*>(ws + o.pts);
+  const dev_ext* part = reinterpret_cast<const dev_ext*>(ws + o.part);
+  sum_item* fin = reinterpret_cast<sum_item*>(ws + w.sum.fin);
+  return launch_sum_levels(c, n_msm, d_off, n_terms, ws, w.sum, d_out, d_status, [&](dim3 grid, uint32_t n, uint32_t last, sum_item* out) {
+    hipLaunchKernelGGL(k_sum_fold_parts, grid, dim3(SUM_FOLD_BLOCK), 0, c->stream, n, last, d_off, n_msm, d_pidx, n_points, pts, part, out, fin);
+    return std::string("k_sum_fold_parts");
+  });
 }
 
 // ---- zkp_mi355x.h (10): the context's baby-step table and the launchers of the search (dlog.h) ----
@@ -3213,6 +3305,91 @@ int zkp_msm_many(zkp_ctx* c, uint32_t n_msm, const uint32_t* off, const uint8_t*
   rc = msm_terms_path(c, n_msm, reinterpret_cast<uint32_t*>(base + o_off), reinterpret_cast<uint8_t*>(base + o_sc),
                       reinterpret_cast<uint32_t*>(base + o_pidx), reinterpret_cast<uint8_t*>(base + o_pts), n_points,
                       n_terms, flags, reinterpret_cast<uint8_t*>(base + o_out), reinterpret_cast<uint8_t*>(base + o_st), nullptr, reserved, false, PH_ALL, k);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)n_msm * 32, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(status, base + o_st, (size_t)n_msm, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return ZKP_OK;
+}
+
+// ---- (11) multiscalar sums with long segments ----
+int zkp_msm_segments_dev(zkp_ctx* c, uint32_t n_msm, const uint32_t* d_off, const uint8_t* d_scalars, const uint32_t* d_pidx, const uint8_t* d_points,
+                         uint32_t n_points, uint32_t n_terms, int flags, uint8_t* d_out, uint8_t* d_status) {
+  if (!c) return fail(ZKP_ERR_ARG, "ctx is NULL");
+  if (flags != ZKP_CT && flags != ZKP_VARTIME) return fail(ZKP_ERR_ARG, "flags must be ZKP_CT or ZKP_VARTIME");
+  if (n_msm == 0) return ZKP_OK;
+  if (!d_off || !d_out || !d_status) return fail(ZKP_ERR_ARG, "NULL device pointer");
+  if (n_terms && (!d_scalars || !d_points || n_points == 0)) return fail(ZKP_ERR_ARG, "terms without scalars/points");
+  if (!d_pidx && n_points != n_terms) return fail(ZKP_ERR_ARG, "without pidx, n_points must equal the number of terms");
+  if (!aligned16(d_scalars) || !aligned16(d_points) || !aligned16(d_out)) return fail(ZKP_ERR_ARG, "device buffers must be 16-byte aligned");
+  HIP_TRY(hipSetDevice(c->device));
+  terms_cfg k;                               // the device arrays are not inspected on the host: generic bounds, as in zkp_msm_many_dev
+  k.teeth = c->comb_teeth;
+  k.throughput = true;
+  k.comb_min = flags == ZKP_CT ? c->ct_comb_min(true, n_terms) : 2u;
+  k.terms_only = true;
+  carve cv;
+  const size_t o_iota = cv.take(d_pidx ? 0 : (size_t)n_terms * 4);
+  const segments_ws w = msm_segments_ws(n_points, n_terms, n_msm, k, cv.off);
+  const int rc = ensure_ws(c, w.sum.total);
+  if (rc) return rc;
+  prof_begin(c);
+  if (!d_pidx && n_terms) {
+    uint32_t* iota = reinterpret_cast<uint32_t*>(static_cast<char*>(c->ws) + o_iota);
+    hipLaunchKernelGGL(k_iota, grid1(n_terms, 256), dim3(256), 0, c->stream, n_terms, iota);
+    d_pidx = iota;
+  }
+  return launch_msm_segments(c, n_msm, d_off, d_scalars, d_pidx, d_points, n_points, n_terms, flags, k, w, d_out, d_status);
+}
+
+int zkp_msm_segments(zkp_ctx* c, uint32_t n_msm, const uint32_t* off, const uint8_t* scalars, const uint32_t* pidx, const uint8_t* points, uint32_t n_points,
+                     int flags, uint8_t* out, uint8_t* status) {
+  if (!c) return fail(ZKP_ERR_ARG, "ctx is NULL");
+  if (flags != ZKP_CT && flags != ZKP_VARTIME) return fail(ZKP_ERR_ARG, "flags must be ZKP_CT or ZKP_VARTIME");
+  if (n_msm == 0) return ZKP_OK;
+  if (!off || !out || !status) return fail(ZKP_ERR_ARG, "NULL pointer");
+  if (off[0] != 0) return fail(ZKP_ERR_ARG, "off[0] must be 0");
+  for (uint32_t i = 0; i < n_msm; ++i)
+    if (off[i + 1] < off[i]) return fail(ZKP_ERR_ARG, "off must be non-decreasing");
+  const uint32_t n_terms = off[n_msm];
+  if (n_terms && (!scalars || !points || n_points == 0)) return fail(ZKP_ERR_ARG, "terms without scalars/points");
+  if (!pidx && n_points != n_terms) return fail(ZKP_ERR_ARG, "without pidx, n_points must equal the number of terms");
+  if (pidx)
+    for (uint32_t t = 0; t < n_terms; ++t)
+      if (pidx[t] >= n_points) return fail(ZKP_ERR_ARG, "pidx out of range");
+  HIP_TRY(hipSetDevice(c->device));
+  std::vector<uint32_t> iota;                // without pidx: term t is point t; the exact table counts want the index written out (the device writes its own)
+  if (!pidx && n_terms >= 1024) {
+    iota.resize(n_terms);
+    for (uint32_t t = 0; t < n_terms; ++t) iota[t] = t;
+  }
+  terms_cfg k = n_terms >= 1024 ? host_terms_cfg(c, n_terms, pidx ? pidx : iota.data(), points, n_points, flags == ZKP_CT ? c->ct_comb_min(false, n_terms) : 2u) : terms_cfg();
+#ifdef ZKP_BUILD_TEST_HOOKS
+  if (c->debug_vouch_reduced && flags == ZKP_CT) k.canonical = true;
+#endif
+  k.terms_only = true;
+  carve cv;
+  const size_t o_off = cv.take((size_t)(n_msm + 1) * 4);
+  const size_t o_sc = cv.take((size_t)n_terms * 32);
+  const size_t o_pidx = cv.take((size_t)n_terms * 4);
+  const size_t o_pts = cv.take((size_t)n_points * 32);
+  const size_t o_out = cv.take((size_t)n_msm * 32);
+  const size_t o_st = cv.take((size_t)n_msm);
+  const segments_ws w = msm_segments_ws(n_points, n_terms, n_msm, k, cv.off);
+  int rc = ensure_ws(c, w.sum.total);
+  if (rc) return rc;
+  char* base = static_cast<char*>(c->ws);
+  HIP_TRY(hipMemcpyAsync(base + o_off, off, (size_t)(n_msm + 1) * 4, hipMemcpyHostToDevice, c->stream));
+  if (n_terms) {
+    HIP_TRY(hipMemcpyAsync(base + o_sc, scalars, (size_t)n_terms * 32, hipMemcpyHostToDevice, c->stream));
+    if (pidx) HIP_TRY(hipMemcpyAsync(base + o_pidx, pidx, (size_t)n_terms * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(base + o_pts, points, (size_t)n_points * 32, hipMemcpyHostToDevice, c->stream));
+  }
+  prof_begin(c);
+  if (!pidx && n_terms) hipLaunchKernelGGL(k_iota, grid1(n_terms, 256), dim3(256), 0, c->stream, n_terms, reinterpret_cast<uint32_t*>(base + o_pidx));
+  rc = launch_msm_segments(c, n_msm, reinterpret_cast<uint32_t*>(base + o_off), reinterpret_cast<uint8_t*>(base + o_sc), reinterpret_cast<uint32_t*>(base + o_pidx),
+                           reinterpret_cast<uint8_t*>(base + o_pts), n_points, n_terms, flags, k, w, reinterpret_cast<uint8_t*>(base + o_out),
+                           reinterpret_cast<uint8_t*>(base + o_st));
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)n_msm * 32, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipMemcpyAsync(status, base + o_st, (size_t)n_msm, hipMemcpyDeviceToHost, c->stream));

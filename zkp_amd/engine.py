@@ -372,6 +372,20 @@ class Engine:
                                         len(points), _ptr(out), _ptr(status)), "zkp_sum_points")
         return out, status
 
+    def msm_segments(self, off, scalars, points, pidx=None, flags: int = ZKP_VARTIME) -> Tuple[np.ndarray, np.ndarray]:
+        """zkp_msm_segments: msm_many's results -- out[i] = encode(sum over t in [off[i], off[i + 1]) of scalars[t] * decode(points[pidx[t]])) ->
+        (out [n_msm][32], status [n_msm]) -- with the term axis folded in levels, for segments of any length; pidx = None: term t uses point t"""
+        off, pidx, _, points = sum_operands(off, points, pidx, None)
+        n_msm, n_terms = len(off) - 1, int(off[-1])
+        scalars = _u8(scalars, 32) if n_terms else np.zeros((0, 32), np.uint8)
+        if len(scalars) != n_terms:
+            raise ValueError("scalars length must equal off[-1]")
+        out = np.zeros((n_msm, 32), np.uint8)
+        status = np.zeros(n_msm, np.uint8)
+        _check(self._lib.zkp_msm_segments(self._h, n_msm, _ptr(off), _ptr(scalars), None if pidx is None else _ptr(pidx), _ptr(points), len(points), flags,
+                                          _ptr(out), _ptr(status)), "zkp_msm_segments")
+        return out, status
+
     # ---- bounded discrete logarithms to the basepoint (include/zkp_mi355x.h section 10): variable time by nature ----
     def prepare_dlog(self, baby_bits: int) -> None:
         """build (or replace) the context's baby-step table: the encodings of i B for i < 2**baby_bits, baby_bits in 4 .. 22"""
@@ -515,6 +529,12 @@ class Engine:
         """zkp_sum_points_dev: d_off u32 [n_sums + 1], d_pidx u32 [n_terms] or None, d_neg u8 [n_terms] or None, d_points [n_points][32] ->
         d_out [n_sums][32], d_status [n_sums]; nothing is read on the host, the launches depend on n_terms and n_sums alone"""
         _check(self._lib.zkp_sum_points_dev(self._h, n_sums, d_off, d_pidx, d_neg, d_points, n_points, n_terms, d_out, d_status), "zkp_sum_points_dev")
+
+    def msm_segments_dev(self, n_msm, d_off, d_scalars, d_pidx, d_points, n_points, n_terms, flags, d_out, d_status) -> None:
+        """zkp_msm_segments_dev: d_off u32 [n_msm + 1], d_scalars [n_terms][32], d_pidx u32 [n_terms] or None, d_points [n_points][32] ->
+        d_out [n_msm][32], d_status [n_msm] bytes; nothing is read on the host, the launches depend on n_terms and n_msm alone"""
+        _check(self._lib.zkp_msm_segments_dev(self._h, n_msm, d_off, d_scalars, d_pidx, d_points, n_points, n_terms, flags, d_out, d_status),
+               "zkp_msm_segments_dev")
 
     def dlog_base_dev(self, n, d_points, bits, d_out, d_status) -> None:
         """zkp_dlog_base_dev: d_points [n][32] (16-byte aligned) -> d_out u64 [n], d_status u8 [n]; queued on the context's stream"""

@@ -607,6 +607,33 @@ def multiscalar_mul(eng, off, scalars, pidx, points, flags: int = 0, threads: in
     return out, status
 
 
+def multiscalar_sum(eng, off, scalars, points, pidx=None, flags: int = 0, threads: int = 0):
+    """multiscalar_mul's results for segments of ANY length -> (out [n_msm][32], status [n_msm]).  pidx = None: term t uses point t.  eng = None
+    (or at most get_host_max_terms() terms) runs on the host threads, which share the TERM axis, so one long segment is everybody's work; with an
+    Engine a job whose longest segment is below get_msm_fold_min_segment() is Engine.msm_many, anything else Engine.msm_segments.  Same bytes on
+    every route."""
+    from .engine import _u8, sum_operands
+    off, pidx, _, points = sum_operands(off, points, pidx, None)
+    n_msm, n_terms = len(off) - 1, int(off[-1])
+    scalars = _u8(scalars, 32) if n_terms else np.zeros((0, 32), np.uint8)
+    if len(scalars) != n_terms:
+        raise ValueError("scalars length must equal off[-1]")
+    out = np.zeros((n_msm, 32), np.uint8)
+    status = np.zeros(n_msm, np.uint8)
+    _raise(lib().zkp_multiscalar_sum_batch(None if eng is None else eng._h, n_msm, _p(off), _p(scalars), _p(pidx), _p(points), len(points), flags, threads,
+                                           _p(out), _p(status)), "zkp_multiscalar_sum_batch")
+    return out, status
+
+
+def set_msm_fold_min_segment(n: int) -> None:
+    """multiscalar_sum jobs on an engine whose longest segment has at least n terms fold the term axis (zkp_msm_segments); shorter ones are zkp_msm_many"""
+    lib().zkp_toolbox_set_msm_fold_min_segment(n)
+
+
+def get_msm_fold_min_segment() -> int:
+    return int(lib().zkp_toolbox_get_msm_fold_min_segment())
+
+
 # ---- RistrettoPoint sums (include/zkp_toolbox.h): `P + Q`, `P - Q`, `-P`, `iter().sum()`, each with its compress(); eng = None is the host backend ----
 def _point_pairs(eng, a, b, op: int, threads: int):
     from .engine import mul_operands
