@@ -735,6 +735,63 @@ int zkp_msm_segments_dev(zkp_ctx* ctx, uint32_t n_msm, const uint32_t* d_off /*[
                          const uint32_t* d_pidx /*[n_terms] or NULL*/, const uint8_t* d_points /*[n_points][32]*/, uint32_t n_points,
                          uint32_t n_terms, int flags, uint8_t* d_out /*[n_msm][32]*/, uint8_t* d_status /*uint8 [n_msm]*/);
 
+/* (12) Scalar sums, products and dot products over segments of any length, batched: dalek's `iter().sum()`, `iter().product()` and the inner
+ *     product sum a_i b_i -- Lagrange coefficients prod m / (m - j), Shamir shares sum c_i j^i, powers j^i, the check sum lambda_j s_j == y, a
+ *     verifier's acc_i = sum_k w_k m_ki.  zkp_sc_muladd writes one output per lane and has no reduction axis.
+ *     zkp_sc_reduce: out[i] = the fold of the terms t in [off[i], off[i + 1]):
+ *         ZKP_SC_SUM      sum  of a[ai(t)]               (an empty range: 0)
+ *         ZKP_SC_PRODUCT  prod of a[ai(t)]               (an empty range: 1)
+ *         ZKP_SC_DOT      sum  of a[ai(t)] * b[bi(t)]    (an empty range: 0)
+ *       with ai(t) = aidx ? aidx[t] : t and likewise for b.  With a NULL index array the operand must have exactly T = off[n_out] rows.  Operands are
+ *       any 32 bytes, read as Scalar::from_bytes_mod_order reads them; outputs are canonical; 0 and 1 are dalek's Sum and Product identities.  b, n_b
+ *       and bidx belong to ZKP_SC_DOT and must be NULL / 0 / NULL otherwise.  out must not overlap an input.  Index lists may repeat and skip rows:
+ *       one shared scalar, a matrix column, j^i as a product of i references to row j are all plain calls.
+ *       n_out = 0 is a no-op.  ZKP_ERR_ARG with nothing written: a NULL context, a NULL buffer the call would read or write, an unknown op, more
+ *       than 2^31 - 1 terms, and in the host-pointer form off[0] != 0, decreasing offsets, an index at or beyond its operand's length and a NULL
+ *       index array with another operand length than T.
+ *       The _dev form reads none of its arrays on the host; n_terms MUST equal d_off[n_out].  With another value, decreasing offsets or an index out
+ *       of range the outputs that depend on the bad input are unspecified, every access still stays inside the buffers (indices are clamped, a
+ *       term's segment is a binary search in d_off whose result is below n_out) and the outputs that do not reference the bad term are right.
+ *       Scalars and d_out 16-byte aligned, offsets and indices 4-byte; queued on the context's stream without synchronising; may be recorded
+ *       between zkp_ctx_capture_begin / _end once the same call has run outside the capture (it draws into the workspace).
+ *     The plan (zkp_amd/csrc/sc_reduce.h) follows from n_terms and n_out alone: 2^20 sums of two terms and one sum of 2^20 terms make the same
+ *       launches.  THE WORK UNIT IS A WORKGROUP: zkp_sc_reduce_group() (256) is both its number of lanes and the number of consecutive items of one
+ *       level it folds, one item per lane.  Rows read in order arrive as 16 bytes per lane on consecutive addresses through an LDS tile; the
+ *       stretches of the segments inside a unit are folded by a segmented scan with head flags over the lanes.  A stretch that begins and ends inside
+ *       the unit is written to its output, the first and the last are handed on through the workspace as two items of the next level (the result
+ *       does not depend on what the workspace held).  zkp_sc_reduce_levels(T) is the number of such launches: 1 up to 256 terms, 2 up to 32,768, 3
+ *       up to 2^22.  One writer per output, no atomics, no lane waits for another workgroup.
+ *       NO BRANCH, TRIP COUNT OR ADDRESS DEPENDS ON A SCALAR'S VALUE -- a zero factor does not end a product -- control flow follows off, the index
+ *       arrays and the sizes only (profiles/scalar_reduce_ct_counters.txt).
+ *       Timed under ZKP_K_SCALARS; zkp_ctx_last_kernels(ZKP_K_SCALARS) names one entry per level: "k_sc_fold<op, true>", "k_sc_fold<op, false>@2", ...
+ *       k_sc_fold: 52 VGPRs (64 for products), no scratch, 18 KiB of LDS, 8 wavefronts per SIMD.
+ *     Sizes (profiles/scalar_reduce_bench.txt, one MI355X, five rounds with the routes alternated in one process, min / median / max in ms; `stream` =
+ *       HIP events around zkp_sc_reduce_dev on resident buffers, `call` = the synchronous host-pointer call, copies included, `host` = the host
+ *       backend at 16 threads, `ints` = Python integers on the decoded rows):
+ *       SUM, one segment of 2^20 terms: stream 0.054 / 0.056 / 0.073 (33.5 MB of terms in 0.056 ms: 604 GB/s, three launches; far below the memory
+ *       system, the call is launch-bound at this size), call 0.764 / 0.767 / 0.788, host 1.648 / 1.715 / 1.751, ints 15.6.  SUM, 65,536 x 2: stream
+ *       0.040, call 0.376, host 0.830, ints 18.2.  PRODUCT, one of 2^20: stream 0.171 / 0.172 / 0.175, call 0.888, host 4.874, ints 201.7; 4,096 x 32:
+ *       stream 0.057, call 0.188, host 1.016, ints 25.1.  DOT, one of 2^20: stream 0.070 / 0.072 / 0.079, call 1.394, host 4.877, ints 93.7; 64 x
+ *       1,024: stream 0.025, call 0.168, host 0.698, ints 5.6.  The Pedersen check as a matrix-vector job (K = 1,024 weights through aidx against
+ *       1,025 columns): stream 0.084 / 0.090 / 0.101 against 3.703 / 3.861 / 4.016 for the loop of K zkp_sc_muladd_dev calls (x 43); call 1.096 / 1.129 /
+ *       1.139 against 63.73 / 63.82 / 64.74 for the loop of K synchronous scalar_muladd calls (x 57) and 5.059 / 5.092 / 5.626 for the host backend.
+ *     Where it does NOT win: the synchronous call is a bus transfer of 32 or 64 bytes per term and 32 per output for a few instructions of work.  In
+ *       the sweep of 2^12 to 2^22 terms against the host backend at 16 threads it is ahead beyond the spread at 70 of 72 cells, but SUM of 2^22 terms
+ *       in segments of 2 (2^21 outputs) is level with the host, 10.31 / 10.99 / 11.45 against 10.38 / 10.94 / 11.45, and one round of DOT at 2^14 x 32
+ *       took 7.758 ms against 0.505; zkp_toolbox.h therefore routes SUM to the host by default.  Below 4,096 terms nothing is measured.  The host
+ *       backend pays 0.37 to 0.45 ms for its 16 threads at every size up to 2^16 terms: one thread (not measured here) may well beat both. */
+#define ZKP_SC_SUM 0
+#define ZKP_SC_PRODUCT 1
+#define ZKP_SC_DOT 2
+int zkp_sc_reduce(zkp_ctx* ctx, int op, uint32_t n_out, const uint32_t* off /*[n_out+1]*/, const uint8_t* a /*[n_a][32]*/, uint32_t n_a,
+                  const uint32_t* aidx /*[T] or NULL*/, const uint8_t* b /*[n_b][32] or NULL*/, uint32_t n_b, const uint32_t* bidx /*[T] or NULL*/,
+                  uint8_t* out /*[n_out][32]*/);
+int zkp_sc_reduce_dev(zkp_ctx* ctx, int op, uint32_t n_out, const uint32_t* d_off /*[n_out+1]*/, const uint8_t* d_a /*[n_a][32]*/, uint32_t n_a,
+                      const uint32_t* d_aidx /*[n_terms] or NULL*/, const uint8_t* d_b /*[n_b][32] or NULL*/, uint32_t n_b,
+                      const uint32_t* d_bidx /*[n_terms] or NULL*/, uint32_t n_terms, uint8_t* d_out /*[n_out][32]*/);
+uint32_t zkp_sc_reduce_group(void);              /* pure arithmetic, no context */
+uint32_t zkp_sc_reduce_levels(uint32_t n_terms); /* fold launches a call of n_terms terms makes; 0 for 0 */
+
 /* Timing of the last *_dev / host call on this context, measured with HIP events on the stream the
  * kernels were launched on.  kernel_ms[] is indexed by ZKP_K_*; returns the number of entries. */
 enum {

@@ -307,6 +307,32 @@ int zkp_scalar_hash_from_bytes_sha512_batch(zkp_ctx* ctx, uint64_t n, const uint
                                             uint8_t* out /*[n][32]*/);
 int zkp_scalar_random_batch(zkp_ctx* ctx, uint64_t n, const uint8_t* key /*[32] or NULL*/, uint64_t nonce, int n_threads, uint8_t* out /*[n][32]*/);
 
+/* Scalar sums, products and dot products over segments of any length (zkp_mi355x.h (12)): out[i] = the fold of the terms [off[i], off[i + 1]) --
+ * ZKP_SC_SUM of a[ai(t)] (empty: 0), ZKP_SC_PRODUCT of a[ai(t)] (empty: 1), ZKP_SC_DOT of a[ai(t)] * b[bi(t)] (empty: 0), ai(t) = aidx ? aidx[t] : t
+ * and likewise for b; operands any 32 bytes, outputs canonical; b, n_b, bidx NULL / 0 / NULL unless ZKP_SC_DOT.  Argument errors (those of
+ * zkp_sc_reduce's host-pointer form) are ZKP_TB_BAD_STATEMENT with nothing written.  Same bytes on both routes:
+ *   ctx == NULL, or fewer than zkp_toolbox_get_scalar_reduce_min_terms(op) terms: the host threads.  They share the TERM axis: a segment longer
+ *     than a thread's share becomes per-thread partials that are combined at the end.
+ *   anything else: zkp_sc_reduce on the device.
+ * zkp_toolbox_set_scalar_reduce_min_terms(op, n): 0 = always the device, UINT64_MAX = never.  The default per op follows from
+ * profiles/scalar_reduce_bench.txt by this rule: the smallest measured term count from which the synchronous device call is ahead of the host
+ * backend at 16 threads, beyond the min-max spread of the rounds, at every measured segment mix; if there is none up to 2^22 terms: never.
+ * The sweep of that file: 2^12 .. 2^22 terms in steps of 4, in segments of 2, 32 and 1,024 terms and in one segment (device | host, ms, medians).
+ *   ZKP_SC_SUM: NEVER (UINT64_MAX).  The device call is ahead beyond the spread at 23 of the 24 cells (2^12 in one segment 0.071 | 0.375; 2^20 in one
+ *     segment 0.682 | 1.379; 2^22 in one segment 2.530 | 4.477), but at 2^22 terms in segments of 2 -- 2^21 outputs to bring back -- the two are level
+ *     (10.31 / 10.99 / 11.45 | 10.38 / 10.94 / 11.45), so there is no size from which every mix is ahead.  A caller whose sums are not millions of
+ *     pairs gains x 1.2 (2^20 terms in pairs) to x 5 (2^12 terms) by setting a threshold of 4,096.
+ *   ZKP_SC_PRODUCT: 4,096, the smallest measured size: ahead at every cell (2^12: 0.086 to 0.098 | 0.439 to 0.457; 2^20: 0.799 to 1.672 | 4.524 to
+ *     5.075; 2^22 in segments of 2: 11.16 | 23.29).  Below 4,096 terms nothing is measured.
+ *   ZKP_SC_DOT: 65,536.  Ahead at every cell from there on (2^16: 0.163 to 0.252 | 0.625 to 0.669; 2^22: 4.982 to 13.14 | 17.96 to 23.97); at 2^14 x 32
+ *     one round of five took 7.758 ms (0.105 / 0.110 / 7.758 | 0.500 / 0.505 / 0.641), which the rule counts as within the spread.
+ * zkp_sc_reduce_dev is the call for pipelines whose operands are resident either way. */
+int zkp_scalar_reduce_batch(zkp_ctx* ctx, int op, uint32_t n_out, const uint32_t* off /*[n_out+1]*/, const uint8_t* a /*[n_a][32]*/, uint32_t n_a,
+                            const uint32_t* aidx /*[T] or NULL*/, const uint8_t* b /*[n_b][32] or NULL*/, uint32_t n_b,
+                            const uint32_t* bidx /*[T] or NULL*/, int n_threads, uint8_t* out /*[n_out][32]*/);
+void zkp_toolbox_set_scalar_reduce_min_terms(int op, uint64_t n);
+size_t zkp_toolbox_get_scalar_reduce_min_terms(int op);   /* (64 bits on every platform the library builds for; SIZE_MAX = never) */
+
 /* Scalar * basepoint, Scalar * point and multiscalar products, batched (zkp_mi355x.h (8), (1)): key generation `&sk * &RISTRETTO_BASEPOINT_TABLE`
  * (tests/sig_and_vrf_example.rs:58), `&H * &x` (:112) and RistrettoPoint::[vartime_]multiscalar_mul, each with the `compress()` that follows.
  * Routing is that of the scalar calls above: ctx == NULL or n <= zkp_toolbox_get_host_max_terms() on the host threads (the kernels' point

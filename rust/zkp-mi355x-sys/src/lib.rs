@@ -246,6 +246,13 @@ extern "C" {
                             flags: c_int, out: *mut u8, status: *mut u8) -> c_int;
     pub fn zkp_msm_segments_dev(ctx: *mut zkp_ctx, n_msm: u32, d_off: *const u32, d_scalars: *const u8, d_pidx: *const u32, d_points: *const u8,
                                 n_points: u32, n_terms: u32, flags: c_int, d_out: *mut u8, d_status: *mut u8) -> c_int;
+    // (12) segmented scalar sums, products and dot products (op: 0 sum, 1 product, 2 dot); the work unit's size and the number of fold launches
+    pub fn zkp_sc_reduce(ctx: *mut zkp_ctx, op: c_int, n_out: u32, off: *const u32, a: *const u8, n_a: u32, aidx: *const u32, b: *const u8, n_b: u32,
+                         bidx: *const u32, out: *mut u8) -> c_int;
+    pub fn zkp_sc_reduce_dev(ctx: *mut zkp_ctx, op: c_int, n_out: u32, d_off: *const u32, d_a: *const u8, n_a: u32, d_aidx: *const u32, d_b: *const u8,
+                             n_b: u32, d_bidx: *const u32, n_terms: u32, d_out: *mut u8) -> c_int;
+    pub fn zkp_sc_reduce_group() -> u32;
+    pub fn zkp_sc_reduce_levels(n_terms: u32) -> u32;
     // (10) bounded discrete logarithms to the basepoint (variable time by nature): the context's baby-step table and the search
     pub fn zkp_ctx_prepare_dlog(ctx: *mut zkp_ctx, baby_bits: u32) -> c_int;
     pub fn zkp_dlog_baby_bits(ctx: *mut zkp_ctx) -> u32;
@@ -386,6 +393,11 @@ extern "C" {
     // multiscalar sums routed by size and by the longest segment (host threads / zkp_msm_many / zkp_msm_segments) and the segment threshold
     pub fn zkp_multiscalar_sum_batch(ctx: *mut zkp_ctx, n_msm: u32, off: *const u32, scalars: *const u8, pidx: *const u32, points: *const u8,
                                      n_points: u32, flags: c_int, n_threads: c_int, out: *mut u8, status: *mut u8) -> c_int;
+    // segmented scalar sums, products and dot products routed by the number of terms (host threads / zkp_sc_reduce) and the per-op threshold
+    pub fn zkp_scalar_reduce_batch(ctx: *mut zkp_ctx, op: c_int, n_out: u32, off: *const u32, a: *const u8, n_a: u32, aidx: *const u32, b: *const u8,
+                                   n_b: u32, bidx: *const u32, n_threads: c_int, out: *mut u8) -> c_int;
+    pub fn zkp_toolbox_set_scalar_reduce_min_terms(op: c_int, n: u64);
+    pub fn zkp_toolbox_get_scalar_reduce_min_terms(op: c_int) -> usize;
     pub fn zkp_toolbox_set_msm_fold_min_segment(n: u32);
     pub fn zkp_toolbox_get_msm_fold_min_segment() -> u32;
     // bounded discrete logarithms to the basepoint behind the same routing; the host table's size and the routing threshold

@@ -355,6 +355,91 @@ void sc_muladd_n(uint64_t n, const uint8_t* a, uint32_t sa, const uint8_t* b, ui
   }
 }
 
+// ---- segmented sums, products and dot products of scalars (zkp_mi355x.h (12)) ----
+namespace {
+struct ScPartial { uint32_t seg; sc v; };
+// One thread's stretch [lo, hi) of the term axis, segment by segment.  A segment that lies wholly inside is finished here; the others leave a partial.
+void sc_reduce_stretch(int op, uint32_t lo, uint32_t hi, uint32_t n_out, const uint32_t* off, const uint8_t* a, const uint32_t* aidx, const uint8_t* b,
+                       const uint32_t* bidx, uint8_t* out, std::vector<ScPartial>& partials) {
+  uint32_t s = (uint32_t)(std::upper_bound(off, off + n_out + 1, lo) - off) - 1;        // the segment of term lo
+  for (; s < n_out && off[s] < hi; ++s) {
+    const uint32_t t0 = std::max(off[s], lo), t1 = std::min(off[s + 1], hi);
+    if (t0 >= t1) continue;                                                              // an empty segment inside the stretch
+    sc acc;
+    sc_zero(acc);
+    acc.v[0] = op == ZKP_SC_PRODUCT ? 1u : 0u;
+    for (uint32_t t = t0; t < t1; ++t) {
+      sc x, y;
+      sc_load(x, a + 32 * (size_t)(aidx ? aidx[t] : t));
+      if (op == ZKP_SC_SUM) {
+        sc_reduce(x, x);
+        sc_add(acc, acc, x);
+      } else if (op == ZKP_SC_PRODUCT) {
+        sc_mul(acc, acc, x);
+      } else {
+        sc_load(y, b + 32 * (size_t)(bidx ? bidx[t] : t));
+        sc_muladd(acc, x, y, acc);
+      }
+    }
+    if (t0 == off[s] && t1 == off[s + 1]) sc_store(out + 32 * (size_t)s, acc);
+    else partials.push_back({s, acc});
+  }
+}
+}  // namespace
+
+int sc_reduce_n(int op, uint32_t n_out, const uint32_t* off, const uint8_t* a, uint32_t n_a, const uint32_t* aidx, const uint8_t* b, uint32_t n_b,
+                const uint32_t* bidx, int n_threads, uint8_t* out) {
+  if (op != ZKP_SC_SUM && op != ZKP_SC_PRODUCT && op != ZKP_SC_DOT) return ZKP_ERR_ARG;
+  if (op != ZKP_SC_DOT && (b || n_b || bidx)) return ZKP_ERR_ARG;
+  if (n_out == 0) return ZKP_OK;
+  if (!off || !out || off[0] != 0) return ZKP_ERR_ARG;
+  for (uint32_t i = 0; i < n_out; ++i)
+    if (off[i + 1] < off[i]) return ZKP_ERR_ARG;
+  const uint32_t T = off[n_out];
+  if (T > 0x7fffffffu) return ZKP_ERR_ARG;
+  if (T && (!a || n_a == 0)) return ZKP_ERR_ARG;
+  if (T && op == ZKP_SC_DOT && (!b || n_b == 0)) return ZKP_ERR_ARG;
+  if (!aidx && n_a != T) return ZKP_ERR_ARG;
+  if (op == ZKP_SC_DOT && !bidx && n_b != T) return ZKP_ERR_ARG;
+  for (uint32_t t = 0; aidx && t < T; ++t)
+    if (aidx[t] >= n_a) return ZKP_ERR_ARG;
+  for (uint32_t t = 0; bidx && t < T; ++t)
+    if (bidx[t] >= n_b) return ZKP_ERR_ARG;
+  sc ident;
+  sc_zero(ident);
+  ident.v[0] = op == ZKP_SC_PRODUCT ? 1u : 0u;
+  for (uint32_t i = 0; i < n_out; ++i)
+    if (off[i + 1] == off[i]) sc_store(out + 32 * (size_t)i, ident);
+  if (T == 0) return ZKP_OK;
+  // stretches of equal numbers of terms, at least MIN_STRETCH each: a term is a few hundred instructions, starting a thread some microseconds
+  constexpr uint32_t MIN_STRETCH = 64;
+  unsigned nt = n_threads > 0 ? (unsigned)n_threads : std::thread::hardware_concurrency();
+  nt = std::max(1u, std::min(std::min(nt, 128u), (T + MIN_STRETCH - 1) / MIN_STRETCH));
+  const uint32_t share = (uint32_t)(((uint64_t)T + nt - 1) / nt);
+  std::vector<std::vector<ScPartial>> partials(nt);
+  auto work = [&](unsigned k) {
+    const uint32_t lo = (uint32_t)std::min<uint64_t>(T, (uint64_t)k * share), hi = (uint32_t)std::min<uint64_t>(T, (uint64_t)lo + share);
+    if (lo < hi) sc_reduce_stretch(op, lo, hi, n_out, off, a, aidx, b, bidx, out, partials[k]);
+  };
+  std::vector<std::thread> pool;
+  for (unsigned k = 1; k < nt; ++k) pool.emplace_back(work, k);
+  work(0);
+  for (std::thread& th : pool) th.join();
+  // the cut segments: their partials lie in stretch order, those of one segment next to each other
+  sc acc;
+  bool open = false;
+  uint32_t seg = 0;
+  for (const auto& list : partials)
+    for (const ScPartial& p : list) {
+      if (open && p.seg != seg) { sc_store(out + 32 * (size_t)seg, acc); open = false; }
+      if (!open) { acc = ident; seg = p.seg; open = true; }
+      if (op == ZKP_SC_PRODUCT) sc_mul(acc, acc, p.v);
+      else sc_add(acc, acc, p.v);
+    }
+  if (open) sc_store(out + 32 * (size_t)seg, acc);
+  return ZKP_OK;
+}
+
 void sc_hash_sha512_n(uint64_t n, const uint8_t* msgs, const uint64_t* offsets, uint8_t* out) {
   for (uint64_t i = 0; i < n; ++i) {
     uint64_t H[8];

@@ -15,6 +15,11 @@ int msm_many(uint32_t n_msm, const uint32_t* off, const uint8_t* scalars, const 
 // each), so one long segment is the work of all threads where msm_many gives it to one.
 int msm_segments_n(uint32_t n_msm, const uint32_t* off, const uint8_t* scalars, const uint32_t* pidx /*or NULL*/, const uint8_t* points, uint32_t n_points,
                    int flags, int n_threads, uint8_t* out, uint8_t* status);
+// zkp_sc_reduce (12): segmented sums, products and dot products of scalars, every argument checked before anything is written.  The TERM axis is
+// cut into one stretch per thread (n_threads <= 0: one per core; never less than 64 terms each); a segment longer than a stretch leaves one partial
+// per stretch, combined at the end.
+int sc_reduce_n(int op, uint32_t n_out, const uint32_t* off, const uint8_t* a, uint32_t n_a, const uint32_t* aidx /*or NULL*/, const uint8_t* b /*or NULL*/,
+                uint32_t n_b, const uint32_t* bidx /*or NULL*/, int n_threads, uint8_t* out);
 int msm_optional(uint64_t n, const uint8_t* scalars, const uint8_t* points, uint8_t out_point[32], int* status);
 int decode_check(uint64_t n, const uint8_t* points, uint8_t* status);
 int from_uniform_bytes(uint64_t n, const uint8_t* in /*[n][64]*/, uint8_t* out /*[n][32]*/);      // zkp_from_uniform_bytes (5)

@@ -973,6 +973,35 @@ int zkp_scalar_muladd_batch(zkp_ctx* ctx, uint64_t n, const uint8_t* a, uint32_t
   return ZKP_TB_OK;
 }
 
+// ---- segmented scalar sums, products and dot products (zkp_mi355x.h (12)) --------------------------------------------------------------------
+// The smallest number of terms from which a call with a context runs on the device, per op.  The rule (zkp_toolbox.h): the smallest measured term
+// count from which the synchronous device call is ahead of the host backend at 16 threads beyond the min-max spread of the rounds at every
+// measured segment mix; none up to 2^22 terms: never.  profiles/scalar_reduce_bench.txt, the sweep (2^12 .. 2^22 terms in steps of 4, segments of 2, 32,
+// 1,024 terms and one segment; device | host, ms, medians):
+//   SUM      ahead at 23 of 24 cells (2^20 in one segment 0.682 | 1.379), but at 2^22 terms in segments of 2 -- 2^21 outputs to bring back -- the two are
+//            level, 10.99 | 10.94 with spreads that cover each other: no size from which every mix is ahead, so NEVER
+//   PRODUCT  ahead at every cell from the smallest measured size on (2^12: 0.086 to 0.098 | 0.439 to 0.457; 2^22 in segments of 2: 11.16 | 23.29): 4,096
+//   DOT      ahead at every cell but one round of 2^14 x 32 (0.105 / 0.110 / 7.758 | 0.505), and at every cell from 2^16 on (0.163 to 0.252 | 0.625 to 0.669): 65,536
+static std::atomic<uint64_t> g_scalar_reduce_min_terms[3] = {{UINT64_MAX}, {4096}, {65536}};
+void zkp_toolbox_set_scalar_reduce_min_terms(int op, uint64_t n) {
+  if (op >= 0 && op < 3) g_scalar_reduce_min_terms[op] = n;
+}
+static_assert(sizeof(size_t) == sizeof(uint64_t), "the getter returns the 64-bit threshold as a size_t");
+size_t zkp_toolbox_get_scalar_reduce_min_terms(int op) { return op >= 0 && op < 3 ? (size_t)g_scalar_reduce_min_terms[op].load() : SIZE_MAX; }
+
+// Every check is made by both routes before anything is written (hostbk::sc_reduce_n, zkp_sc_reduce), so they refuse the same calls.
+int zkp_scalar_reduce_batch(zkp_ctx* ctx, int op, uint32_t n_out, const uint32_t* off, const uint8_t* a, uint32_t n_a, const uint32_t* aidx, const uint8_t* b,
+                            uint32_t n_b, const uint32_t* bidx, int n_threads, uint8_t* out) {
+  if (op != ZKP_SC_SUM && op != ZKP_SC_PRODUCT && op != ZKP_SC_DOT) return ZKP_TB_BAD_STATEMENT;
+  if (n_out == 0) return ZKP_TB_OK;
+  if (!off || !out) return ZKP_TB_BAD_STATEMENT;
+  const uint64_t min_terms = g_scalar_reduce_min_terms[op].load();
+  const bool host = !ctx || min_terms == UINT64_MAX || off[n_out] < min_terms;
+  const int rc = host ? zkp::hostbk::sc_reduce_n(op, n_out, off, a, n_a, aidx, b, n_b, bidx, n_threads, out)
+                      : zkp_sc_reduce(ctx, op, n_out, off, a, n_a, aidx, b, n_b, bidx, out);
+  return rc == ZKP_ERR_ARG ? ZKP_TB_BAD_STATEMENT : rc;
+}
+
 // Scalar::hash_from_bytes::<Sha512> of n messages (CSR, checked here as zkp_hash_from_bytes_sha512_batch checks it)
 int zkp_scalar_hash_from_bytes_sha512_batch(zkp_ctx* ctx, uint64_t n, const uint8_t* msgs, const uint64_t* offsets, int n_threads, uint8_t* out) {
   if (n == 0) return ZKP_TB_OK;

@@ -58,6 +58,7 @@ __device__ __forceinline__ uint32_t sel8(const uint32_t w[8], int j) {
 #include "comb_tables.h"
 #include "point_mul.h"
 #include "point_sum.h"
+#include "sc_reduce.h"
 #include "dlog.h"
 #include "transcript_kernels.h"
 #include "sha512.h"
@@ -2553,6 +2554,76 @@ int sc_call_check(zkp_ctx* c, uint64_t n, bool null_buffer, bool stride_ok = tru
   return ZKP_OK;
 }
 
+// ---- (12) segmented sums, products and dot products of scalars (sc_reduce.h has the scheme) ----
+// Workspace of the fold from `reserved` on: the items two levels hand on, [values A | segments A | values B | segments B].
+struct sc_red_ws { size_t va = 0, sa = 0, vb = 0, sb = 0, total = 0; };
+sc_red_ws sc_reduce_ws(uint32_t n_terms, size_t reserved) {
+  sc_red_ws w;
+  carve cv;
+  cv.off = reserved;
+  const size_t n1 = n_terms > SC_RED_GROUP ? sc_red_next_items(n_terms) : 0, n2 = n1 > SC_RED_GROUP ? sc_red_next_items((uint32_t)n1) : 0;
+  w.va = cv.take(n1 * 32);
+  w.sa = cv.take(n1 * 4);
+  w.vb = cv.take(n2 * 32);
+  w.sb = cv.take(n2 * 4);
+  w.total = cv.off;
+  return w;
+}
+template <int OP>
+int launch_sc_reduce_op(zkp_ctx* c, uint32_t n_out, const uint32_t* d_off, const uint8_t* d_a, uint32_t n_a, const uint32_t* d_aidx, const uint8_t* d_b, uint32_t n_b,
+                        const uint32_t* d_bidx, uint32_t n_terms, const sc_red_ws& w, uint8_t* d_out) {
+  char* ws = static_cast<char*>(c->ws);
+  uint8_t* vals[2] = {reinterpret_cast<uint8_t*>(ws + w.va), reinterpret_cast<uint8_t*>(ws + w.vb)};
+  uint32_t* segs[2] = {reinterpret_cast<uint32_t*>(ws + w.sa), reinterpret_cast<uint32_t*>(ws + w.sb)};
+  const std::string name = "k_sc_fold<" + std::to_string(OP) + ", ";
+  constexpr int UP = OP == SC_RED_PRODUCT ? SC_RED_PRODUCT : SC_RED_SUM;      // the later levels of a dot product add
+  uint32_t n = n_terms;
+  const uint8_t* in_v = nullptr;
+  const uint32_t* in_seg = nullptr;
+  for (uint32_t level = 1;; ++level) {
+    const uint32_t last = n <= SC_RED_GROUP, units = (n + SC_RED_GROUP - 1) / SC_RED_GROUP;
+    uint8_t* hv = vals[(level - 1) & 1];
+    uint32_t* hs = segs[(level - 1) & 1];
+    if (level == 1) {
+      const uint32_t blocks = std::max(units, (n_out + SC_RED_GROUP - 1) / SC_RED_GROUP);     // (the lanes that write the empty segments)
+      hipLaunchKernelGGL((k_sc_fold<OP, true>), dim3(blocks), dim3(SC_RED_GROUP), 0, c->stream, n, units, last, d_off, n_out, d_a, n_a, d_aidx, d_b, n_b, d_bidx,
+                         (const uint8_t*)nullptr, (const uint32_t*)nullptr, hv, hs, d_out);
+      if (n) prof_note(c, ZKP_K_SCALARS, name + "true>");
+    } else {
+      hipLaunchKernelGGL((k_sc_fold<UP, false>), dim3(units), dim3(SC_RED_GROUP), 0, c->stream, n, units, last, d_off, n_out, (const uint8_t*)nullptr, 0u,
+                         (const uint32_t*)nullptr, (const uint8_t*)nullptr, 0u, (const uint32_t*)nullptr, in_v, in_seg, hv, hs, d_out);
+      prof_note(c, ZKP_K_SCALARS, "k_sc_fold<" + std::to_string(UP) + ", false>@" + std::to_string(level));
+    }
+    prof_mark(c, ZKP_K_SCALARS);
+    if (last) break;
+    n = sc_red_next_items(n);
+    in_v = hv;
+    in_seg = hs;
+  }
+  HIP_TRY(hipGetLastError());
+  return ZKP_OK;
+}
+int launch_sc_reduce(zkp_ctx* c, int op, uint32_t n_out, const uint32_t* d_off, const uint8_t* d_a, uint32_t n_a, const uint32_t* d_aidx, const uint8_t* d_b,
+                     uint32_t n_b, const uint32_t* d_bidx, uint32_t n_terms, const sc_red_ws& w, uint8_t* d_out) {
+  if (op == SC_RED_SUM) return launch_sc_reduce_op<SC_RED_SUM>(c, n_out, d_off, d_a, n_a, d_aidx, d_b, n_b, d_bidx, n_terms, w, d_out);
+  if (op == SC_RED_PRODUCT) return launch_sc_reduce_op<SC_RED_PRODUCT>(c, n_out, d_off, d_a, n_a, d_aidx, d_b, n_b, d_bidx, n_terms, w, d_out);
+  return launch_sc_reduce_op<SC_RED_DOT>(c, n_out, d_off, d_a, n_a, d_aidx, d_b, n_b, d_bidx, n_terms, w, d_out);
+}
+// the checks the two forms share (the arrays themselves are the host-pointer form's business); n_terms: off[n_out] / the argument
+int sc_reduce_check(zkp_ctx* c, int op, uint32_t n_out, const void* off, const void* a, uint32_t n_a, const void* aidx, const void* b, uint32_t n_b, const void* bidx,
+                    uint64_t n_terms, const void* out) {
+  if (!c) return fail(ZKP_ERR_ARG, "ctx is NULL");
+  if (op != ZKP_SC_SUM && op != ZKP_SC_PRODUCT && op != ZKP_SC_DOT) return fail(ZKP_ERR_ARG, "op must be ZKP_SC_SUM, ZKP_SC_PRODUCT or ZKP_SC_DOT");
+  if (op != ZKP_SC_DOT && (b || n_b || bidx)) return fail(ZKP_ERR_ARG, "b, n_b and bidx belong to ZKP_SC_DOT");
+  if (!off || !out) return fail(ZKP_ERR_ARG, "NULL pointer");
+  if (n_terms > 0x7fffffffull) return fail(ZKP_ERR_ARG, "too many terms");
+  if (n_terms && (!a || n_a == 0)) return fail(ZKP_ERR_ARG, "terms without an operand a");
+  if (n_terms && op == ZKP_SC_DOT && (!b || n_b == 0)) return fail(ZKP_ERR_ARG, "terms without an operand b");
+  if (!aidx && n_a != n_terms) return fail(ZKP_ERR_ARG, "without aidx, n_a must equal the number of terms");
+  if (op == ZKP_SC_DOT && !bidx && n_b != n_terms) return fail(ZKP_ERR_ARG, "without bidx, n_b must equal the number of terms");
+  return ZKP_OK;
+}
+
 // zkp_hash_from_bytes_sha512 and zkp_debug_sha512: checks the offsets on the host (non-decreasing), uploads msgs[offsets[0], offsets[n])
 // and the offsets rebased to 0, hashes, and (HASH_MAP) maps the digests in place of the workspace.  out: [n][32] encodings, or [n][64] digests.
 // HASH_SCALAR (zkp_sc_hash_from_bytes_sha512): the same checks and upload, k_sc_hash_sha512 instead: out = [n][32] scalars.
@@ -3655,6 +3726,72 @@ int zkp_sc_muladd(zkp_ctx* c, uint64_t n, const uint8_t* a, uint32_t a_stride, c
   rc = launch_sc_muladd(c, n, base + o_a, a_stride, base + o_b, b_stride, cc ? base + o_c : nullptr, c_stride, base + o_out);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return ZKP_OK;
+}
+
+// ---- (12) segmented scalar sums, products and dot products ----
+uint32_t zkp_sc_reduce_group(void) { return SC_RED_GROUP; }
+uint32_t zkp_sc_reduce_levels(uint32_t n_terms) { return sc_red_levels(n_terms); }
+
+int zkp_sc_reduce_dev(zkp_ctx* c, int op, uint32_t n_out, const uint32_t* d_off, const uint8_t* d_a, uint32_t n_a, const uint32_t* d_aidx, const uint8_t* d_b,
+                      uint32_t n_b, const uint32_t* d_bidx, uint32_t n_terms, uint8_t* d_out) {
+  if (!c) return fail(ZKP_ERR_ARG, "ctx is NULL");
+  if (n_out == 0) return op == ZKP_SC_SUM || op == ZKP_SC_PRODUCT || op == ZKP_SC_DOT ? ZKP_OK : fail(ZKP_ERR_ARG, "op must be ZKP_SC_SUM, ZKP_SC_PRODUCT or ZKP_SC_DOT");
+  int rc = sc_reduce_check(c, op, n_out, d_off, d_a, n_a, d_aidx, d_b, n_b, d_bidx, n_terms, d_out);
+  if (rc) return rc;
+  if (!aligned16(d_a) || !aligned16(d_b) || !aligned16(d_out)) return fail(ZKP_ERR_ARG, "device scalars must be 16-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(d_off) | reinterpret_cast<uintptr_t>(d_aidx) | reinterpret_cast<uintptr_t>(d_bidx)) & 3)
+    return fail(ZKP_ERR_ARG, "device offsets and indices must be 4-byte aligned");
+  HIP_TRY(hipSetDevice(c->device));
+  const sc_red_ws w = sc_reduce_ws(n_terms, 0);
+  rc = ensure_ws(c, w.total);
+  if (rc) return rc;
+  prof_begin(c);
+  return launch_sc_reduce(c, op, n_out, d_off, d_a, n_a, d_aidx, d_b, n_b, d_bidx, n_terms, w, d_out);
+}
+
+int zkp_sc_reduce(zkp_ctx* c, int op, uint32_t n_out, const uint32_t* off, const uint8_t* a, uint32_t n_a, const uint32_t* aidx, const uint8_t* b, uint32_t n_b,
+                  const uint32_t* bidx, uint8_t* out) {
+  if (!c) return fail(ZKP_ERR_ARG, "ctx is NULL");
+  if (n_out == 0) return op == ZKP_SC_SUM || op == ZKP_SC_PRODUCT || op == ZKP_SC_DOT ? ZKP_OK : fail(ZKP_ERR_ARG, "op must be ZKP_SC_SUM, ZKP_SC_PRODUCT or ZKP_SC_DOT");
+  if (!off || !out) return fail(ZKP_ERR_ARG, "NULL pointer");
+  if (off[0] != 0) return fail(ZKP_ERR_ARG, "off[0] must be 0");
+  for (uint32_t i = 0; i < n_out; ++i)
+    if (off[i + 1] < off[i]) return fail(ZKP_ERR_ARG, "off must be non-decreasing");
+  const uint32_t n_terms = off[n_out];
+  int rc = sc_reduce_check(c, op, n_out, off, a, n_a, aidx, b, n_b, bidx, n_terms, out);
+  if (rc) return rc;
+  for (uint32_t t = 0; aidx && t < n_terms; ++t)
+    if (aidx[t] >= n_a) return fail(ZKP_ERR_ARG, "aidx out of range");
+  for (uint32_t t = 0; bidx && t < n_terms; ++t)
+    if (bidx[t] >= n_b) return fail(ZKP_ERR_ARG, "bidx out of range");
+  HIP_TRY(hipSetDevice(c->device));
+  const bool dot = op == ZKP_SC_DOT;
+  carve cv;
+  const size_t o_off = cv.take((size_t)(n_out + 1) * 4);
+  const size_t o_a = cv.take(n_terms ? (size_t)n_a * 32 : 0);
+  const size_t o_ai = cv.take(aidx ? (size_t)n_terms * 4 : 0);
+  const size_t o_b = cv.take(dot && n_terms ? (size_t)n_b * 32 : 0);
+  const size_t o_bi = cv.take(bidx ? (size_t)n_terms * 4 : 0);
+  const size_t o_out = cv.take((size_t)n_out * 32);
+  const sc_red_ws w = sc_reduce_ws(n_terms, cv.off);
+  rc = ensure_ws(c, w.total);
+  if (rc) return rc;
+  char* base = static_cast<char*>(c->ws);
+  HIP_TRY(hipMemcpyAsync(base + o_off, off, (size_t)(n_out + 1) * 4, hipMemcpyHostToDevice, c->stream));
+  if (n_terms) {
+    HIP_TRY(hipMemcpyAsync(base + o_a, a, (size_t)n_a * 32, hipMemcpyHostToDevice, c->stream));
+    if (aidx) HIP_TRY(hipMemcpyAsync(base + o_ai, aidx, (size_t)n_terms * 4, hipMemcpyHostToDevice, c->stream));
+    if (dot) HIP_TRY(hipMemcpyAsync(base + o_b, b, (size_t)n_b * 32, hipMemcpyHostToDevice, c->stream));
+    if (bidx) HIP_TRY(hipMemcpyAsync(base + o_bi, bidx, (size_t)n_terms * 4, hipMemcpyHostToDevice, c->stream));
+  }
+  prof_begin(c);
+  rc = launch_sc_reduce(c, op, n_out, reinterpret_cast<uint32_t*>(base + o_off), reinterpret_cast<uint8_t*>(base + o_a), n_a,
+                        aidx ? reinterpret_cast<uint32_t*>(base + o_ai) : nullptr, dot ? reinterpret_cast<uint8_t*>(base + o_b) : nullptr, n_b,
+                        bidx ? reinterpret_cast<uint32_t*>(base + o_bi) : nullptr, n_terms, w, reinterpret_cast<uint8_t*>(base + o_out));
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)n_out * 32, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return ZKP_OK;
 }

@@ -25,6 +25,7 @@ ZKP_OPT_WS_LIMIT_BYTES, ZKP_OPT_JOB_DEFER_D2H, ZKP_OPT_SYNC_SCHEDULE, ZKP_OPT_TR
 ZKP_VARTIME = 0
 ZKP_CT = 1
 ZKP_PT_ADD, ZKP_PT_SUB = 0, 1               # zkp_add_points' op
+ZKP_SC_SUM, ZKP_SC_PRODUCT, ZKP_SC_DOT = 0, 1, 2     # zkp_sc_reduce's op
 ZKP_DLOG_FOUND, ZKP_DLOG_INVALID, ZKP_DLOG_NOT_FOUND = 0, 1, 2      # zkp_dlog_base's status
 ZKP_OPT_BATCH_ENCODE_MIN = 1
 (ZKP_OPT_COMB_TEETH, ZKP_OPT_CT_SINGLE_USE_TABLES, ZKP_OPT_TRANSCRIPT_LANES, ZKP_OPT_DEV_OVERLAP, ZKP_OPT_GROUPED_COMB, ZKP_OPT_TABLES_LANE,
@@ -129,6 +130,37 @@ def strobe_pos_after_append(strobe_pos: int, label_len: int, msg_len: int) -> in
     """zkp_strobe_pos_after_append (no GPU): the position word pos | pos_begin << 8 | cur_flags << 16 of a transcript after one
     append_message with a label of label_len and a message of msg_len bytes, from its position word before"""
     return int(load_library().zkp_strobe_pos_after_append(strobe_pos, label_len, msg_len))
+
+
+
+def reduce_operands(op: int, off, a, aidx=None, b=None, bidx=None):
+    """The operands of a segmented scalar fold as C-contiguous arrays: (off u32 [n_out + 1], a u8 [n_a][32], aidx u32 [T] or None, b or None,
+    bidx or None).  Shapes only: the values are the library's to check."""
+    off = np.ascontiguousarray(off, dtype=np.uint32).reshape(-1)
+    if len(off) < 1:
+        raise ValueError("off must hold n_out + 1 entries")
+    n_terms = int(off[-1])
+
+    def operand(x, idx, name):
+        x = _u8(x, 32)
+        if idx is not None:
+            idx = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
+            if len(idx) != n_terms:
+                raise ValueError(f"{name}idx must hold off[-1] entries")
+            if len(idx) == 0:
+                idx = np.zeros(1, np.uint32)                    # never a NULL pointer for an index list that was given
+        if len(x) == 0:
+            x = np.zeros((0, 32), np.uint8)
+        return x, idx
+
+    a, aidx = operand(a, aidx, "a")
+    if op == ZKP_SC_DOT:
+        if b is None:
+            raise ValueError("ZKP_SC_DOT needs b")
+        b, bidx = operand(b, bidx, "b")
+    elif b is not None or bidx is not None:
+        raise ValueError("b and bidx belong to ZKP_SC_DOT")
+    return off, a, aidx, b, bidx
 
 
 def scalar_operands(a, b, c=None):
@@ -386,6 +418,16 @@ class Engine:
                                           _ptr(out), _ptr(status)), "zkp_msm_segments")
         return out, status
 
+    def scalar_reduce(self, op: int, off, a, aidx=None, b=None, bidx=None) -> np.ndarray:
+        """zkp_sc_reduce: out[i] = the fold of the terms [off[i], off[i + 1]) -> [n_out][32] canonical scalars.  op = ZKP_SC_SUM (of a[ai(t)], empty: 0),
+        ZKP_SC_PRODUCT (empty: 1) or ZKP_SC_DOT (of a[ai(t)] * b[bi(t)], empty: 0); ai(t) = aidx[t], or t with aidx = None (a then has off[-1] rows)"""
+        off, a, aidx, b, bidx = reduce_operands(op, off, a, aidx, b, bidx)
+        n_out = len(off) - 1
+        out = np.zeros((n_out, 32), np.uint8)
+        _check(self._lib.zkp_sc_reduce(self._h, op, n_out, _ptr(off), _ptr(a) if len(a) else None, len(a), _ptr(aidx),
+                                       None if b is None or not len(b) else _ptr(b), 0 if b is None else len(b), _ptr(bidx), _ptr(out)), "zkp_sc_reduce")
+        return out
+
     # ---- bounded discrete logarithms to the basepoint (include/zkp_mi355x.h section 10): variable time by nature ----
     def prepare_dlog(self, baby_bits: int) -> None:
         """build (or replace) the context's baby-step table: the encodings of i B for i < 2**baby_bits, baby_bits in 4 .. 22"""
@@ -535,6 +577,11 @@ class Engine:
         d_out [n_msm][32], d_status [n_msm] bytes; nothing is read on the host, the launches depend on n_terms and n_msm alone"""
         _check(self._lib.zkp_msm_segments_dev(self._h, n_msm, d_off, d_scalars, d_pidx, d_points, n_points, n_terms, flags, d_out, d_status),
                "zkp_msm_segments_dev")
+
+    def scalar_reduce_dev(self, op, n_out, d_off, d_a, n_a, d_aidx, d_b, n_b, d_bidx, n_terms, d_out) -> None:
+        """zkp_sc_reduce_dev: d_off u32 [n_out + 1], d_a [n_a][32], d_aidx u32 [n_terms] or None, d_b [n_b][32] / d_bidx (ZKP_SC_DOT, else None, 0,
+        None) -> d_out [n_out][32]; nothing is read on the host, the launches depend on n_terms and n_out alone; n_terms must be d_off[n_out]"""
+        _check(self._lib.zkp_sc_reduce_dev(self._h, op, n_out, d_off, d_a, n_a, d_aidx, d_b, n_b, d_bidx, n_terms, d_out), "zkp_sc_reduce_dev")
 
     def dlog_base_dev(self, n, d_points, bits, d_out, d_status) -> None:
         """zkp_dlog_base_dev: d_points [n][32] (16-byte aligned) -> d_out u64 [n], d_status u8 [n]; queued on the context's stream"""

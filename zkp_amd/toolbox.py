@@ -536,6 +536,43 @@ def scalar_muladd(eng, a, b, c=None, threads: int = 0) -> np.ndarray:
     return out
 
 
+def scalar_reduce(eng, op: int, off, a, aidx=None, b=None, bidx=None, threads: int = 0) -> np.ndarray:
+    """zkp_scalar_reduce_batch: out[i] = the fold of the terms [off[i], off[i + 1]) -> [n_out][32] canonical scalars.  eng = None, or fewer than
+    get_scalar_reduce_min_terms(op) terms, runs on the host threads, which share the TERM axis; anything else is Engine.scalar_reduce.  Same bytes."""
+    from .engine import reduce_operands
+    off, a, aidx, b, bidx = reduce_operands(op, off, a, aidx, b, bidx)
+    n_out = len(off) - 1
+    out = np.zeros((n_out, 32), np.uint8)
+    _raise(lib().zkp_scalar_reduce_batch(None if eng is None else eng._h, op, n_out, _p(off), _p(a) if len(a) else None, len(a), _p(aidx),
+                                         None if b is None or not len(b) else _p(b), 0 if b is None else len(b), _p(bidx), threads, _p(out)),
+           "zkp_scalar_reduce_batch")
+    return out
+
+
+def scalar_sum(eng, off, a, aidx=None, threads: int = 0) -> np.ndarray:
+    """`iter().sum()` per segment: out[i] = sum over t in [off[i], off[i + 1]) of a[aidx[t]] (aidx = None: a[t]); an empty segment is 0"""
+    return scalar_reduce(eng, 0, off, a, aidx, threads=threads)
+
+
+def scalar_product(eng, off, a, aidx=None, threads: int = 0) -> np.ndarray:
+    """`iter().product()` per segment: out[i] = prod over t in [off[i], off[i + 1]) of a[aidx[t]] (aidx = None: a[t]); an empty segment is 1"""
+    return scalar_reduce(eng, 1, off, a, aidx, threads=threads)
+
+
+def scalar_dot(eng, off, a, b, aidx=None, bidx=None, threads: int = 0) -> np.ndarray:
+    """inner products per segment: out[i] = sum over t in [off[i], off[i + 1]) of a[aidx[t]] * b[bidx[t]] (an index list None: row t); empty: 0"""
+    return scalar_reduce(eng, 2, off, a, aidx, b, bidx, threads=threads)
+
+
+def set_scalar_reduce_min_terms(op: int, n: int) -> None:
+    """scalar_reduce jobs of op on an engine with at least n terms run on the device (0: always; 2**64 - 1: never)"""
+    lib().zkp_toolbox_set_scalar_reduce_min_terms(op, n)
+
+
+def get_scalar_reduce_min_terms(op: int) -> int:
+    return int(lib().zkp_toolbox_get_scalar_reduce_min_terms(op))
+
+
 def scalar_hash_from_bytes_sha512(eng, messages, threads: int = 0) -> np.ndarray:
     """Scalar::hash_from_bytes::<Sha512> of every message (a list of byte strings)"""
     from .engine import messages_csr
