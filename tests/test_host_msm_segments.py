@@ -10,7 +10,9 @@ import sys
 import numpy as np
 import pytest
 
+from oracle import model as M
 from tests import msm_segments_cases as MC
+from tests import point_mul_cases as PC
 from zkp_amd import toolbox as T
 from zkp_amd.engine import ZKP_CT, ZKP_VARTIME
 
@@ -79,6 +81,78 @@ def test_without_pidx_term_t_uses_point_t(flags):
         assert (got == want).all() and (st == want_st).all()
     with pytest.raises(Exception):
         T.multiscalar_sum(None, off, sc, rows[:-1], None, flags)          # n_points != n_terms
+
+
+# ---- the jobs of the classified term path's GPU cases (tests/test_gpu_msm_segments.py): what a CPU can say about them -----------------------------
+TERMS_SPLIT, SPLIT_COMB, ENCODE_MIN = MC.threshold("n_terms >= 1024"), MC.threshold("kSplitCombTerms"), MC.threshold("kThroughputEncodeMin")
+
+
+def _both_forms(name, off, sc, pidx, points, flags, threads=(1, 5)):
+    """host backend against the oracle with pidx, then with a row per term (pidx = None)"""
+    want, want_st = check(name, off, sc, pidx, points, flags, threads)
+    _, _, rows = MC.own_points(off, sc, pidx, points)
+    got, st = T.multiscalar_sum(None, off, sc, rows, None, flags, threads=threads[-1])
+    assert (got == want).all() and (st == want_st).all(), name
+    return want, want_st
+
+
+@pytest.mark.parametrize("flags", FLAGS)
+@pytest.mark.parametrize("T_", (TERMS_SPLIT - 1, TERMS_SPLIT, TERMS_SPLIT + 1, TERMS_SPLIT + 63, TERMS_SPLIT + 64, TERMS_SPLIT + 65))
+def test_own_rows_job(T_, flags):
+    off, sc, rows, logs = MC.own_rows_job(T_, seed=T_)
+    assert off.tolist() == [0, T_] and len({bytes(r) for r in rows}) == T_ and not rows[0].any() and (rows[1] == PC.BASEPOINT_ROW[0]).all()
+    edges = set(MC.EDGE_SCALARS)
+    assert all(int.from_bytes(sc[j].tobytes(), "little") in edges for j in range(0, T_, 5))
+    want, st = check("own%d" % T_, off, sc, None, rows, flags, threads=(1, 5))
+    # the rows have known logs: the sum is (sum s_t d_t mod l) B, from Python integers
+    total = sum(int.from_bytes(sc[t].tobytes(), "little") * d for t, d in enumerate(logs)) % MC.L
+    assert not st.any() and bytes(want[0]) == M.ristretto_encode(M.pt_mul(total, M.BASEPOINT))
+
+
+@pytest.mark.parametrize("flags", FLAGS)
+@pytest.mark.parametrize("total", (TERMS_SPLIT + 1, SPLIT_COMB - 1, SPLIT_COMB))
+def test_mixed_job(total, flags):
+    off, sc, pidx, points, info = MC.mixed_job(G, total)
+    T_ = int(off[-1])
+    assert T_ == max(total, 1382) and len(points) == 64 + info["n_pairs"] + info["n_once"]
+    counts = info["counts"]
+    assert sum(counts.values()) == T_ and all(abs(v - T_ / 4) <= 6 for v in counts.values()), counts       # a quarter each (+- the cancelling segments)
+    assert counts["twice"] == 2 * info["n_pairs"] and counts["once"] == info["n_once"]
+    uses = np.bincount(pidx, minlength=len(points))
+    assert sorted(np.unique(uses[64:]).tolist()) == [1, 2] and (uses[:64] >= 5).all()
+    lens = np.diff(off.astype(np.int64)).tolist()
+    assert lens[:12] == MC.ragged_lengths(G) and lens[12:16] == [G * G // 2 + 1, 0, 3, 2 * G + 1] and all(k == G + 1 for k in lens[16:-1])
+    assert bytes(points[pidx[info["t_hot"]]]) == bytes(points[MC.REGISTERED[0]]) and info["cls"][info["t_hot"]] == MC.CLASS_ONCE
+    want, st = _both_forms("mixed%d" % total, off, sc, pidx, points, flags)
+    assert not st.any()
+    assert not want[info["identity"]].any()                          # the empty and the two cancelling segments
+    assert sum(1 for w in want if w.any()) >= len(want) - len(info["identity"]) - 2        # (a 1-term segment may hold the scalar 0 or the identity row)
+
+
+@pytest.mark.parametrize("flags", FLAGS)
+def test_mixed_job_with_invalid_rows(flags):
+    off, sc, pidx, points, flagged, info = MC.mixed_job_with_invalid(G, TERMS_SPLIT + 1)
+    c_off, c_sc, c_pidx, c_points, _ = MC.mixed_job(G, TERMS_SPLIT + 1)
+    assert (off == c_off).all() and (sc == c_sc).all()
+    cls_of_bad = sorted({int(info["cls"][t]) for t in range(len(pidx)) if bytes(points[pidx[t]]) in {bytes(r) for r in MC.invalid_rows()}})
+    assert cls_of_bad == [MC.CLASS_SHARED, MC.CLASS_TWICE, MC.CLASS_ONCE]
+    want, st = _both_forms("mixed-invalid", off, sc, pidx, points, flags)
+    assert np.flatnonzero(st).tolist() == flagged and not want[flagged].any()
+    clean, _ = MC.expected("mixed%d" % (TERMS_SPLIT + 1), c_off, c_sc, c_pidx, c_points, flags)
+    rest = [i for i in range(len(off) - 1) if i not in flagged]
+    assert (want[rest] == clean[rest]).all()
+
+
+@pytest.mark.parametrize("flags", FLAGS)
+@pytest.mark.parametrize("n_msm", (ENCODE_MIN - 1, ENCODE_MIN))
+def test_many_segments_job(n_msm, flags):
+    off, sc, pidx, points = MC.many_segments_job(n_msm)
+    lens = np.diff(off.astype(np.int64))
+    assert len(lens) == n_msm and lens[:8].tolist() == [1, 2, 3, 0, 1, 2, 3, 0] and off[-1] > TERMS_SPLIT
+    uses = np.bincount(pidx, minlength=len(points))
+    assert (uses[64:] == 1).all() and (pidx[3::4] >= 64).all() and (np.delete(pidx, np.arange(3, len(pidx), 4)) < 64).all()
+    want, st = _both_forms("many%d" % n_msm, off, sc, pidx, points, flags)
+    assert not st.any() and not want[lens == 0].any()
 
 
 def test_argument_errors_write_nothing():
