@@ -792,6 +792,85 @@ int zkp_sc_reduce_dev(zkp_ctx* ctx, int op, uint32_t n_out, const uint32_t* d_of
 uint32_t zkp_sc_reduce_group(void);              /* pure arithmetic, no context */
 uint32_t zkp_sc_reduce_levels(uint32_t n_terms); /* fold launches a call of n_terms terms makes; 0 for 0 */
 
+/* (13) Prefix sums and prefix products over segments, batched: the running value at EVERY term where (9), (11) and (12) return one value per segment.
+ *     Tables of powers x^0 .. x^(t-1) -- the weights w^k of a random linear combination, the rows j^i of a Shamir or Feldman Vandermonde matrix,
+ *     Horner points, the prefix products behind Montgomery's inversion trick -- and running sums of points: the tally after every ballot, cumulative
+ *     balances, the multiples G, 2G, 3G, .. of a caller's own generator.  Without a scan these are T calls, or a fold over all T prefixes, which is
+ *     quadratic (j^i as zkp_sc_reduce over "i references to row j" is t (t - 1) / 2 terms for t powers).
+ *     The job is in CSR form, T = off[n_seg], every term belongs to exactly one segment.  For term t of segment s
+ *         ZKP_SCAN_INCLUSIVE  out[t] folds the terms [off[s], t]
+ *         ZKP_SCAN_EXCLUSIVE  out[t] folds the terms [off[s], t): the first row of a segment is the identity -- 0, 1, or 32 zero bytes.
+ *       A scan never crosses a segment boundary; an empty segment owns no rows.  n_seg = 0 or T = 0 is a no-op.
+ *     zkp_sc_scan: ZKP_SC_SUM or ZKP_SC_PRODUCT of a[ai(t)], ai(t) = aidx ? aidx[t] : t.  Operands are any 32 bytes, read as
+ *       Scalar::from_bytes_mod_order reads them; outputs are canonical.  aidx may repeat and skip rows, as in zkp_sc_reduce: the exclusive product
+ *       scan of t references to row j is the table j^0 .. j^(t-1).  ZKP_SC_DOT is ZKP_ERR_ARG: a running dot product is zkp_sc_muladd (the
+ *       products a_t b_t) followed by a sum scan.  out must not overlap an input.
+ *     zkp_scan_points: pidx, neg, n_points and the decode rules are those of zkp_sum_points; there is no ZKP_CT / ZKP_VARTIME flag (nothing here
+ *       reads a scalar).  status[t] = 1 and out[t] is zeros where a point among the terms out[t] depends on does not decode: a bad point flags its
+ *       own row (the next row in exclusive mode) and every later row of its segment, nothing before it and nothing in another segment.  The
+ *       additions are the complete ones: P, P, P, .. gives P, 2P, 3P, .. and P, -P the identity, with no special case.
+ *     ZKP_ERR_ARG with nothing written: a NULL context, a NULL buffer the call would read or write, an unknown op or mode, more than 2^31 - 1
+ *       terms, and in the host-pointer forms off[0] != 0, decreasing offsets, an index at or beyond its operand's length and a NULL index array
+ *       with another operand length than T.
+ *       The _dev forms read none of their arrays on the host; n_terms MUST equal d_off[n_seg].  With another value, decreasing offsets or an index
+ *       out of range the rows that depend on the bad input are unspecified, every access still stays inside the buffers (indices are clamped, a
+ *       term's segment is a binary search in d_off whose result is below n_seg) and the rows that do not depend on the bad term are right.
+ *       Scalars, points and d_out 16-byte aligned, offsets and indices 4-byte; queued on the context's stream without synchronising; may be
+ *       recorded between zkp_ctx_capture_begin / _end once the same call has run outside the capture (it draws into the workspace).
+ *     The plans (zkp_amd/csrc/sc_scan.h, point_scan.h) are REDUCE-THEN-SCAN over dependent launches and follow from n_terms alone.  Up-sweep: a
+ *       unit hands on the fold of its last run and whether a segment begins inside it, one item per unit, level by level; the top level is one
+ *       unit; down-sweep: a unit scans its items again, its carry goes into its first run when that run began in an earlier unit, and every prefix
+ *       is written.  One writer per row, no atomics, NO LANE WAITS FOR ANOTHER WORKGROUP (no look-back, no spinning), and the result does not depend
+ *       on what the workspace held.
+ *       Scalars: the unit is zkp_sc_reduce's workgroup of zkp_sc_scan_group() (256) lanes, one item per lane, rows in and out through the LDS tile
+ *       on consecutive addresses.  zkp_sc_scan_launches(T) = 2 L - 1: 1 up to 256 terms, 3 up to 65,536, 5 up to 2^24.  NO BRANCH, TRIP COUNT OR
+ *       ADDRESS DEPENDS ON A SCALAR'S VALUE -- a zero factor does not end a product scan (profiles/scalar_scan_ct_counters.txt).  Timed under
+ *       ZKP_K_SCALARS; zkp_ctx_last_kernels(ZKP_K_SCALARS) names one entry per launch: "k_sc_scan<op, true, false>@1" (terms, up),
+ *       "k_sc_scan<op, false, false>@2", .., "k_sc_scan<op, false, true>@2" (down), "k_sc_scan<op, true, true>@1".
+ *       Points: the unit is zkp_sum_points' lane with zkp_scan_points_group() (32) consecutive items.  zkp_scan_points_launches(T) = 2 L + 1: the
+ *       decode ("k_decode_affine" under ZKP_K_DECODE), "k_pt_scan<terms, down>@level" (ZKP_K_REDUCE; 1 walk up to 32 terms, 3 up to 1,024, 5 up to
+ *       32,768, 7 up to 2^20, 9 up to 2^25) and the encode, one lane and one inversion per row ("k_pt_scan_encode" under ZKP_K_COMBINE): the names
+ *       of the three kinds number zkp_scan_points_launches(T).  Workspace: 160 bytes per term and 112 per point.
+ *       k_sc_scan: 50 to 54 VGPRs (64 to 68 for products), no scratch, 18 KiB of LDS.  The point scan encodes with the body behind k_sum_encode, one
+ *       inversion per row; the shared-inversion encoder of doubled points (dlog.h) was not built or measured.
+ *     Sizes (profiles/scan_bench.txt, one MI355X, five rounds with the routes alternated in one process, min / median / max in ms; `stream` = HIP
+ *       events around the _dev call on resident buffers, `call` = the synchronous host-pointer call, copies included, `host` = the host backend at 16
+ *       threads, `folds` = what callers had before: every prefix as a segment of its own in one zkp_sc_reduce / zkp_sum_points job):
+ *       SUM, one segment of 2^20 terms: stream 0.087 / 0.090 / 0.102 (five launches; 33.5 MB read twice and written once: 1.1 TB/s), call 4.623, host
+ *       5.045.  SUM, 64 x 1,024: stream 0.030 against folds 0.804 (x 27), call 0.200 against 10.78 (x 54), host 1.045.  PRODUCT (exclusive: tables of
+ *       powers), one segment of 4,096: stream 0.053 against folds 0.988 (x 19), call 0.122 against 3.354 (x 28), host 0.935; 64 x 1,024: stream 0.060
+ *       against 3.891 (x 64), call 0.229 against 13.38 (x 58), host 1.223; one of 2^20: stream 0.305 / 0.306 / 0.308, call 2.320, host 10.88.  From
+ *       2^16 terms in one segment the folds are 2^31 terms and more and are not measured.
+ *       Points, one segment of 4,096: stream 0.544 / 0.551 / 0.570 against 0.967 for the sums over all prefixes (8.4 million terms), call 0.640
+ *       against 3.407, against 971.1 for the loop of 4,095 point_add calls and 4.278 for the host; 64 x 1,024: stream 0.779 against 2.238, call 0.978
+ *       against 11.76, 218.4 (loop) and 30.23 (host); one of 2^20: stream 2.637 / 2.707 / 2.733 (decode 0.92, walks 0.80, encode 0.92), call 7.191,
+ *       host 890.1.
+ *     Where it does NOT win: segments of two -- 65,536 x 2 scalars: stream 0.039 (SUM) and 0.092 (PRODUCT) against 0.024 and 0.047 for the folds over the
+ *       98,304 prefix terms, which are one launch where the scan is three; points: stream 0.896 against 0.699, call 1.215 against 1.167 and against
+ *       0.442 for ONE point_add call, which is all a scan of pairs is.  Points in segments of 32 (4,096 x 32): stream 0.911 against 0.869 for the sums
+ *       over all prefixes, the synchronous call still x 1.6 ahead.  The synchronous scalar call moves 32 bytes in and 32 bytes out per term for a few
+ *       instructions of work: against the host backend SUM is level at 2^20 terms and behind at 2^22 in short segments (17.25 against 16.12), and
+ *       PRODUCT at 2^20 terms took 6 to 34 ms from round to round against 9 to 14 on the host IN THE SWEEP, while the identical call in the shapes part
+ *       of the same file took 2.302 / 2.320 / 2.347 ms: the slow rows are unexplained and were not reproduced -- they are no property of the call (SUM
+ *       at that size reads 4.5 ms in both parts).  zkp_toolbox.h routes SUM to the host by default and, reading the sweep as it stands, PRODUCT below
+ *       2^22 terms.  A point scan of 64 terms takes 0.37 ms as a synchronous call (seven launches at 4,096 terms, nine at 2^20). */
+#define ZKP_SCAN_INCLUSIVE 0
+#define ZKP_SCAN_EXCLUSIVE 1
+int zkp_sc_scan(zkp_ctx* ctx, int op, int mode, uint32_t n_seg, const uint32_t* off /*[n_seg+1]*/, const uint8_t* a /*[n_a][32]*/, uint32_t n_a,
+                const uint32_t* aidx /*[T] or NULL*/, uint8_t* out /*[T][32]*/);
+int zkp_sc_scan_dev(zkp_ctx* ctx, int op, int mode, uint32_t n_seg, const uint32_t* d_off /*[n_seg+1]*/, const uint8_t* d_a /*[n_a][32]*/, uint32_t n_a,
+                    const uint32_t* d_aidx /*[n_terms] or NULL*/, uint32_t n_terms, uint8_t* d_out /*[n_terms][32]*/);
+uint32_t zkp_sc_scan_group(void);                   /* pure arithmetic, no context */
+uint32_t zkp_sc_scan_launches(uint32_t n_terms);    /* kernel launches a scalar scan of n_terms terms makes; 0 for 0 */
+int zkp_scan_points(zkp_ctx* ctx, int mode, uint32_t n_seg, const uint32_t* off /*[n_seg+1]*/, const uint32_t* pidx /*[T] or NULL*/,
+                    const uint8_t* neg /*[T] or NULL*/, const uint8_t* points /*[n_points][32]*/, uint32_t n_points, uint8_t* out /*[T][32]*/,
+                    uint8_t* status /*[T]*/);
+int zkp_scan_points_dev(zkp_ctx* ctx, int mode, uint32_t n_seg, const uint32_t* d_off /*[n_seg+1]*/, const uint32_t* d_pidx /*[n_terms] or NULL*/,
+                        const uint8_t* d_neg /*[n_terms] or NULL*/, const uint8_t* d_points /*[n_points][32]*/, uint32_t n_points, uint32_t n_terms,
+                        uint8_t* d_out /*[n_terms][32]*/, uint8_t* d_status /*uint8 [n_terms]*/);
+uint32_t zkp_scan_points_group(void);
+uint32_t zkp_scan_points_launches(uint32_t n_terms); /* decode, walks and encode of a point scan of n_terms terms; 0 for 0 */
+
 /* Timing of the last *_dev / host call on this context, measured with HIP events on the stream the
  * kernels were launched on.  kernel_ms[] is indexed by ZKP_K_*; returns the number of entries. */
 enum {

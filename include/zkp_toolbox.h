@@ -391,6 +391,47 @@ int zkp_point_sum_batch(zkp_ctx* ctx, uint32_t n_sums, const uint32_t* off /*[n_
                         const uint8_t* neg /*[T] or NULL*/, const uint8_t* points /*[n_points][32]*/, uint32_t n_points, int n_threads,
                         uint8_t* out /*[n_sums][32]*/, uint8_t* status /*[n_sums]*/);
 
+/* Prefix sums and products of scalars and running sums of points over segments (zkp_mi355x.h (13)): one row per TERM.  For term t of segment s,
+ * mode ZKP_SCAN_INCLUSIVE folds the terms [off[s], t], ZKP_SCAN_EXCLUSIVE the terms [off[s], t) -- the identity (0, 1, 32 zero bytes) at a
+ * segment's first term.  A scan never crosses a segment boundary; an empty segment owns no rows; n_seg = 0 or off[n_seg] = 0 is a no-op.
+ *   zkp_scalar_scan_batch: op ZKP_SC_SUM or ZKP_SC_PRODUCT of a[ai(t)], ai(t) = aidx ? aidx[t] : t; operands any 32 bytes, outputs canonical.  The
+ *     exclusive product scan of t references to one row j is the table j^0 .. j^(t-1).  ZKP_SC_DOT is refused: zkp_scalar_muladd_batch, then a sum scan.
+ *   zkp_point_scan_batch: pidx, neg, n_points and decoding as in zkp_point_sum_batch; status[t] = 1 and zeros where a point among the terms row t
+ *     depends on does not decode: its own row (the next in exclusive mode) and every later row of its segment, nothing else.
+ * Argument errors (those of the host-pointer forms of zkp_sc_scan / zkp_scan_points) are ZKP_TB_BAD_STATEMENT with nothing written.  Same bytes on
+ * both routes:
+ *   ctx == NULL, or fewer than zkp_toolbox_get_scalar_scan_min_terms(op) / zkp_toolbox_get_point_scan_min_terms() terms: the host threads.  They
+ *     share the TERM axis, at least 64 terms per stretch: each scans its stretch, the stretch totals are scanned serially, each fixes up its first run.
+ *   anything else: zkp_sc_scan / zkp_scan_points on the device.
+ * zkp_toolbox_set_*_scan_min_terms: 0 = always the device, UINT64_MAX = never.  The defaults follow from profiles/scan_bench.txt by the rule of
+ * zkp_toolbox_get_scalar_reduce_min_terms: the smallest measured term count from which the synchronous device call is ahead of the host backend at
+ * 16 threads, beyond the min-max spread of the rounds, at every measured segment mix; if there is none: never.
+ * The sweep of that file: scalars at 2^12 .. 2^22 terms, points at 2^6 .. 2^18, in steps of 4, in segments of 2, 32 and 1,024 terms and in one
+ * segment (device | host, ms, medians).
+ *   ZKP_SC_SUM: NEVER (UINT64_MAX).  Ahead beyond the spread at every cell up to 2^18 terms (2^12: 0.088 to 0.094 | 0.790 to 0.834; 2^18: 0.664 to
+ *     0.708 | 1.229 to 1.377), level at 2^20 (4.505 to 4.752 | 4.562 to 5.323) and behind at 2^22 in segments of 2 and of 1,024 (17.25 | 16.12 and
+ *     16.26 | 15.44): the call brings 32 bytes back for every 32 it sends.  A caller whose scans stay below a quarter of a million terms gains x 1.8
+ *     (2^18) to x 9 (2^12) by setting a threshold of 4,096.
+ *   ZKP_SC_PRODUCT: 4,194,304.  Ahead at every cell up to 2^18 (2^12: 0.116 to 0.122 | 0.859 to 0.985; 2^18: 0.725 to 0.797 | 1.882 to 2.910) and at
+ *     2^22 (16.86 to 18.29 | 27.48 to 45.17), but at 2^20 the device call took anything from 6 to 34 ms from round to round (medians 16.05 to 20.73 |
+ *     9.284 to 13.92), behind or within the spread at all four mixes; the rule therefore starts at 2^22.  THE 2^20 CELL IS UNEXPLAINED: the identical
+ *     call (one segment of 2^20 terms, exclusive) took 2.302 / 2.320 / 2.347 ms in the shapes part of the same file, x 4.7 ahead of the host, and SUM
+ *     at that size reads 4.5 ms in both parts.  The slow rows are no property of the call; they were not reproduced or traced, and the default, which
+ *     only keeps work on the host, is read off the sweep as it stands.  A caller with product scans of 2^12 to 2^20 terms gains x 2.4 to x 8 by setting
+ *     a threshold of 4,096.
+ *   points: 64, the smallest measured size: ahead at every cell (2^6: 0.365 to 0.369 | 0.400 to 0.405; 2^12: 0.632 to 0.651 | 2.538 to 4.287; 2^18:
+ *     1.780 to 1.969 | 118.2 to 220.9).  Below 64 terms nothing is measured.
+ * zkp_sc_scan_dev / zkp_scan_points_dev are the calls for pipelines whose operands are resident either way. */
+int zkp_scalar_scan_batch(zkp_ctx* ctx, int op, int mode, uint32_t n_seg, const uint32_t* off /*[n_seg+1]*/, const uint8_t* a /*[n_a][32]*/, uint32_t n_a,
+                          const uint32_t* aidx /*[T] or NULL*/, int n_threads, uint8_t* out /*[T][32]*/);
+int zkp_point_scan_batch(zkp_ctx* ctx, int mode, uint32_t n_seg, const uint32_t* off /*[n_seg+1]*/, const uint32_t* pidx /*[T] or NULL*/,
+                         const uint8_t* neg /*[T] or NULL*/, const uint8_t* points /*[n_points][32]*/, uint32_t n_points, int n_threads,
+                         uint8_t* out /*[T][32]*/, uint8_t* status /*[T]*/);
+void zkp_toolbox_set_scalar_scan_min_terms(int op, uint64_t n);
+size_t zkp_toolbox_get_scalar_scan_min_terms(int op);     /* (SIZE_MAX = never, and for an op that has no scan) */
+void zkp_toolbox_set_point_scan_min_terms(uint64_t n);
+size_t zkp_toolbox_get_point_scan_min_terms(void);
+
 /* Bounded discrete logarithms to the basepoint, batched (zkp_mi355x.h (10)): out[i] = the k in [0, 2^bits) with encode(k B) == points[i] and
  * status[i] = ZKP_DLOG_FOUND; ZKP_DLOG_INVALID and 0 where the encoding does not decode; ZKP_DLOG_NOT_FOUND and 0 where no k is in range.  bits is
  * 1 .. 48.  VARIABLE TIME: the duration depends on the logarithms.  n = 0 is a no-op; a NULL buffer with n > 0 or bits out of range is

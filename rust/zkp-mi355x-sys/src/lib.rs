@@ -253,6 +253,18 @@ extern "C" {
                              n_b: u32, d_bidx: *const u32, n_terms: u32, d_out: *mut u8) -> c_int;
     pub fn zkp_sc_reduce_group() -> u32;
     pub fn zkp_sc_reduce_levels(n_terms: u32) -> u32;
+    // (13) segmented prefix sums and products of scalars, running sums of points (mode: 0 inclusive, 1 exclusive): one row per term
+    pub fn zkp_sc_scan(ctx: *mut zkp_ctx, op: c_int, mode: c_int, n_seg: u32, off: *const u32, a: *const u8, n_a: u32, aidx: *const u32, out: *mut u8) -> c_int;
+    pub fn zkp_sc_scan_dev(ctx: *mut zkp_ctx, op: c_int, mode: c_int, n_seg: u32, d_off: *const u32, d_a: *const u8, n_a: u32, d_aidx: *const u32,
+                           n_terms: u32, d_out: *mut u8) -> c_int;
+    pub fn zkp_sc_scan_group() -> u32;
+    pub fn zkp_sc_scan_launches(n_terms: u32) -> u32;
+    pub fn zkp_scan_points(ctx: *mut zkp_ctx, mode: c_int, n_seg: u32, off: *const u32, pidx: *const u32, neg: *const u8, points: *const u8, n_points: u32,
+                           out: *mut u8, status: *mut u8) -> c_int;
+    pub fn zkp_scan_points_dev(ctx: *mut zkp_ctx, mode: c_int, n_seg: u32, d_off: *const u32, d_pidx: *const u32, d_neg: *const u8, d_points: *const u8,
+                               n_points: u32, n_terms: u32, d_out: *mut u8, d_status: *mut u8) -> c_int;
+    pub fn zkp_scan_points_group() -> u32;
+    pub fn zkp_scan_points_launches(n_terms: u32) -> u32;
     // (10) bounded discrete logarithms to the basepoint (variable time by nature): the context's baby-step table and the search
     pub fn zkp_ctx_prepare_dlog(ctx: *mut zkp_ctx, baby_bits: u32) -> c_int;
     pub fn zkp_dlog_baby_bits(ctx: *mut zkp_ctx) -> u32;
@@ -398,6 +410,15 @@ extern "C" {
                                    n_b: u32, bidx: *const u32, n_threads: c_int, out: *mut u8) -> c_int;
     pub fn zkp_toolbox_set_scalar_reduce_min_terms(op: c_int, n: u64);
     pub fn zkp_toolbox_get_scalar_reduce_min_terms(op: c_int) -> usize;
+    // segmented prefix sums and products of scalars and running sums of points, routed by the number of terms (host threads / zkp_sc_scan, zkp_scan_points)
+    pub fn zkp_scalar_scan_batch(ctx: *mut zkp_ctx, op: c_int, mode: c_int, n_seg: u32, off: *const u32, a: *const u8, n_a: u32, aidx: *const u32,
+                                 n_threads: c_int, out: *mut u8) -> c_int;
+    pub fn zkp_point_scan_batch(ctx: *mut zkp_ctx, mode: c_int, n_seg: u32, off: *const u32, pidx: *const u32, neg: *const u8, points: *const u8,
+                                n_points: u32, n_threads: c_int, out: *mut u8, status: *mut u8) -> c_int;
+    pub fn zkp_toolbox_set_scalar_scan_min_terms(op: c_int, n: u64);
+    pub fn zkp_toolbox_get_scalar_scan_min_terms(op: c_int) -> usize;
+    pub fn zkp_toolbox_set_point_scan_min_terms(n: u64);
+    pub fn zkp_toolbox_get_point_scan_min_terms() -> usize;
     pub fn zkp_toolbox_set_msm_fold_min_segment(n: u32);
     pub fn zkp_toolbox_get_msm_fold_min_segment() -> u32;
     // bounded discrete logarithms to the basepoint behind the same routing; the host table's size and the routing threshold

@@ -23,6 +23,8 @@
 //                 table {1..8} P, 256 doublings + 65 additions; ZKP_CT keeps the masked look-ups and skips no digit (mul_base_n always).
 //   add_points_n / sum_points_n  zkp_add_points / zkp_sum_points (9): decode, the complete addition of ge25519.h (a sign is a conditional negation of
 //                 the cached operand), encode.  A sum is one serial chain here; the toolbox cuts long ones (sum_points_partial / _finish).
+//   sc_scan_n / point_scan_n  zkp_sc_scan / zkp_scan_points (13): the term axis cut over the threads; a stretch is scanned from the identity, the
+//                 stretch totals serially, and the rows before a stretch's first segment start take their carry in a second pass.
 //   dlog_halve / dlog_base_range / dlog_base_n  zkp_dlog_base (10): baby-step / giant-step of dlog.h -- the point halved once, candidates walked by subtracting
 //                 (m / 2) B, encode(2 H) of DLOG_GROUP consecutive candidates from one inversion (the serial form of Montgomery's trick), the probe of
 //                 dlog.h.  The baby table is built here the same way and kept per baby_bits for the process behind a mutex.
@@ -437,6 +439,178 @@ int sc_reduce_n(int op, uint32_t n_out, const uint32_t* off, const uint8_t* a, u
       else sc_add(acc, acc, p.v);
     }
   if (open) sc_store(out + 32 * (size_t)seg, acc);
+  return ZKP_OK;
+}
+
+// ---- segmented prefix sums and products of scalars, running sums of points (zkp_mi355x.h (13)) ----
+namespace {
+// Stretches of equal numbers of terms, at least 64 each (as sc_reduce_n cuts them): the number of stretches and the terms of one.
+inline unsigned scan_stretches(uint32_t T, int n_threads, uint32_t& share) {
+  constexpr uint32_t MIN_STRETCH = 64;
+  unsigned nt = n_threads > 0 ? (unsigned)n_threads : std::thread::hardware_concurrency();
+  nt = std::max(1u, std::min(std::min(nt, 128u), (T + MIN_STRETCH - 1) / MIN_STRETCH));
+  share = (uint32_t)(((uint64_t)T + nt - 1) / nt);
+  return nt;
+}
+template <typename F>
+inline void scan_run(unsigned nt, F&& work) {
+  std::vector<std::thread> pool;
+  for (unsigned k = 1; k < nt; ++k) pool.emplace_back(work, k);
+  work(0);
+  for (std::thread& th : pool) th.join();
+}
+// the checks the two scans share, in the order of the engine's; T = off[n_seg] on success
+inline int scan_check(uint32_t n_seg, const uint32_t* off, const void* rows, uint32_t n_rows, const uint32_t* idx, const void* out, uint32_t& T) {
+  if (!off || off[0] != 0) return ZKP_ERR_ARG;
+  for (uint32_t i = 0; i < n_seg; ++i)
+    if (off[i + 1] < off[i]) return ZKP_ERR_ARG;
+  T = off[n_seg];
+  if (T > 0x7fffffffu) return ZKP_ERR_ARG;
+  if (T && (!rows || n_rows == 0 || !out)) return ZKP_ERR_ARG;
+  if (!idx && n_rows != T) return ZKP_ERR_ARG;
+  for (uint32_t t = 0; idx && t < T; ++t)
+    if (idx[t] >= n_rows) return ZKP_ERR_ARG;
+  return ZKP_OK;
+}
+struct ScanStretch { uint32_t lo = 0, hi = 0, first_head = 0; };   // first_head: the first term of [lo, hi) that opens a segment, or hi
+inline uint32_t sum_terms(ge_p3& acc, uint32_t lo, uint32_t hi, const uint32_t* pidx, const uint8_t* neg, const uint8_t* points);   // (below, with the sums)
+}  // namespace
+
+int sc_scan_n(int op, int mode, uint32_t n_seg, const uint32_t* off, const uint8_t* a, uint32_t n_a, const uint32_t* aidx, int n_threads, uint8_t* out) {
+  if (op != ZKP_SC_SUM && op != ZKP_SC_PRODUCT) return ZKP_ERR_ARG;
+  if (mode != ZKP_SCAN_INCLUSIVE && mode != ZKP_SCAN_EXCLUSIVE) return ZKP_ERR_ARG;
+  if (n_seg == 0) return ZKP_OK;
+  uint32_t T = 0;
+  const int rc = scan_check(n_seg, off, a, n_a, aidx, out, T);
+  if (rc || T == 0) return rc;
+  const bool mul = op == ZKP_SC_PRODUCT, excl = mode == ZKP_SCAN_EXCLUSIVE;
+  sc ident;
+  sc_zero(ident);
+  ident.v[0] = mul ? 1u : 0u;
+  uint32_t share = 0;
+  const unsigned nt = scan_stretches(T, n_threads, share);
+  std::vector<ScanStretch> st(nt);
+  std::vector<sc> total(nt, ident), carry(nt, ident);
+  // every thread scans its stretch from the identity; what is open at its end is its total
+  scan_run(nt, [&](unsigned k) {
+    ScanStretch& z = st[k];
+    z.lo = (uint32_t)std::min<uint64_t>(T, (uint64_t)k * share);
+    z.hi = (uint32_t)std::min<uint64_t>(T, (uint64_t)z.lo + share);
+    z.first_head = z.hi;
+    if (z.lo >= z.hi) return;
+    uint32_t s = (uint32_t)(std::upper_bound(off, off + n_seg + 1, z.lo) - off) - 1;      // the segment of term lo
+    sc acc = ident;
+    for (uint32_t t = z.lo; t < z.hi; ++t) {
+      while (t >= off[s + 1]) ++s;
+      if (t == off[s]) {
+        acc = ident;
+        if (z.first_head == z.hi) z.first_head = t;
+      }
+      if (excl) sc_store(out + 32 * (size_t)t, acc);
+      sc x;
+      sc_load(x, a + 32 * (size_t)(aidx ? aidx[t] : t));
+      if (mul) {
+        sc_mul(acc, acc, x);
+      } else {
+        sc_reduce(x, x);
+        sc_add(acc, acc, x);
+      }
+      if (!excl) sc_store(out + 32 * (size_t)t, acc);
+    }
+    total[k] = acc;
+  });
+  // the stretch totals, scanned serially: carry[k] is what is open where stretch k begins
+  sc c = ident;
+  for (unsigned k = 0; k < nt; ++k) {
+    carry[k] = c;
+    if (st[k].lo >= st[k].hi) continue;
+    if (st[k].first_head != st[k].hi) c = total[k];
+    else if (mul) sc_mul(c, c, total[k]);
+    else sc_add(c, c, total[k]);
+  }
+  // every thread fixes up its first run
+  scan_run(nt, [&](unsigned k) {
+    if (k == 0) return;
+    for (uint32_t t = st[k].lo; t < st[k].first_head; ++t) {
+      sc x;
+      sc_load(x, out + 32 * (size_t)t);
+      if (mul) sc_mul(x, carry[k], x);
+      else sc_add(x, carry[k], x);
+      sc_store(out + 32 * (size_t)t, x);
+    }
+  });
+  return ZKP_OK;
+}
+
+int point_scan_n(int mode, uint32_t n_seg, const uint32_t* off, const uint32_t* pidx, const uint8_t* neg, const uint8_t* points, uint32_t n_points, int n_threads,
+                 uint8_t* out, uint8_t* status) {
+  if (mode != ZKP_SCAN_INCLUSIVE && mode != ZKP_SCAN_EXCLUSIVE) return ZKP_ERR_ARG;
+  if (n_seg == 0) return ZKP_OK;
+  uint32_t T = 0;
+  const int rc = scan_check(n_seg, off, points, n_points, pidx, out, T);
+  if (rc || T == 0) return rc;
+  if (!status) return ZKP_ERR_ARG;
+  const bool excl = mode == ZKP_SCAN_EXCLUSIVE;
+  uint32_t share = 0;
+  const unsigned nt = scan_stretches(T, n_threads, share);
+  std::vector<ScanStretch> st(nt);
+  std::vector<ge_p3> total(nt), carry(nt);
+  std::vector<uint32_t> total_bad(nt, 0), carry_bad(nt, 0);
+  // rows [from, to), the walk starting at `from` with (acc, bad).  after_head: only the rows from the first head on are written (the others wait
+  // for their carry).  first_head: the first term of the range that opens a segment, or `to`.
+  auto walk = [&](uint32_t from, uint32_t to, bool after_head, ge_p3& acc, uint32_t& bad, uint32_t& first_head) {
+    uint32_t s = (uint32_t)(std::upper_bound(off, off + n_seg + 1, from) - off) - 1;      // the segment of term `from`
+    first_head = to;
+    auto put = [&](uint32_t t) {
+      if (after_head && first_head == to) return;
+      status[t] = (uint8_t)bad;
+      if (bad) std::memset(out + 32 * (size_t)t, 0, 32);
+      else encode(out + 32 * (size_t)t, acc);
+    };
+    for (uint32_t t = from; t < to; ++t) {
+      while (t >= off[s + 1]) ++s;
+      if (t == off[s]) {
+        ge_identity(acc);
+        bad = 0;
+        if (first_head == to) first_head = t;
+      }
+      if (excl) put(t);
+      bad |= sum_terms(acc, t, t + 1, pidx, neg, points);
+      if (!excl) put(t);
+    }
+  };
+  // every thread walks its stretch from the identity: the rows from its first head on are final, what is open at its end is its total
+  scan_run(nt, [&](unsigned k) {
+    ScanStretch& z = st[k];
+    z.lo = (uint32_t)std::min<uint64_t>(T, (uint64_t)k * share);
+    z.hi = (uint32_t)std::min<uint64_t>(T, (uint64_t)z.lo + share);
+    z.first_head = z.hi;
+    ge_identity(total[k]);
+    if (z.lo < z.hi) walk(z.lo, z.hi, true, total[k], total_bad[k], z.first_head);
+  });
+  ge_p3 c;
+  ge_identity(c);
+  uint32_t cbad = 0;
+  for (unsigned k = 0; k < nt; ++k) {
+    carry[k] = c;
+    carry_bad[k] = cbad;
+    if (st[k].lo >= st[k].hi) continue;
+    if (st[k].first_head != st[k].hi) {
+      c = total[k];
+      cbad = total_bad[k];
+    } else {
+      ge_cached q;
+      ge_to_cached(q, total[k]);
+      ge_add_cached(c, c, q);
+      cbad |= total_bad[k];
+    }
+  }
+  // every thread walks its first run again, from its carry
+  scan_run(nt, [&](unsigned k) {
+    if (k == 0 || st[k].lo >= st[k].first_head) return;
+    uint32_t none;
+    walk(st[k].lo, st[k].first_head, false, carry[k], carry_bad[k], none);
+  });
   return ZKP_OK;
 }
 

@@ -20,6 +20,14 @@ int msm_segments_n(uint32_t n_msm, const uint32_t* off, const uint8_t* scalars, 
 // per stretch, combined at the end.
 int sc_reduce_n(int op, uint32_t n_out, const uint32_t* off, const uint8_t* a, uint32_t n_a, const uint32_t* aidx /*or NULL*/, const uint8_t* b /*or NULL*/,
                 uint32_t n_b, const uint32_t* bidx /*or NULL*/, int n_threads, uint8_t* out);
+// zkp_sc_scan / zkp_scan_points (13): segmented prefix sums and products of scalars and running sums of points, every argument checked before
+// anything is written.  The threads share the TERM axis (n_threads <= 0: one per core; never less than 64 terms each): each scans its stretch from
+// the identity, the stretch totals are scanned serially, and each thread fixes up its first run -- the rows before the first segment that begins
+// inside its stretch (scalars: one operation per row; points: the rows are walked again from the carry, so a row is encoded once).
+int sc_scan_n(int op, int mode, uint32_t n_seg, const uint32_t* off, const uint8_t* a, uint32_t n_a, const uint32_t* aidx /*or NULL*/, int n_threads,
+              uint8_t* out /*[T][32]*/);
+int point_scan_n(int mode, uint32_t n_seg, const uint32_t* off, const uint32_t* pidx /*or NULL*/, const uint8_t* neg /*or NULL*/, const uint8_t* points,
+                 uint32_t n_points, int n_threads, uint8_t* out /*[T][32]*/, uint8_t* status /*[T]*/);
 int msm_optional(uint64_t n, const uint8_t* scalars, const uint8_t* points, uint8_t out_point[32], int* status);
 int decode_check(uint64_t n, const uint8_t* points, uint8_t* status);
 int from_uniform_bytes(uint64_t n, const uint8_t* in /*[n][64]*/, uint8_t* out /*[n][32]*/);      // zkp_from_uniform_bytes (5)

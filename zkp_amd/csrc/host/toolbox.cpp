@@ -1166,6 +1166,54 @@ int zkp_point_sum_batch(zkp_ctx* ctx, uint32_t n_sums, const uint32_t* off, cons
   return ZKP_TB_OK;
 }
 
+// ---- segmented prefix sums and products of scalars, running sums of points (zkp_mi355x.h (13)) ---------------------------------------------
+// The smallest number of terms from which a call with a context runs on the device (scalars: per op), by the rule of
+// g_scalar_reduce_min_terms, read off the sweep of profiles/scan_bench.txt (scalars 2^12 .. 2^22 terms, points 2^6 .. 2^18, in steps of 4, in
+// segments of 2, 32, 1,024 terms and one segment; device | host, ms, medians):
+//   SUM      ahead at every cell up to 2^18 terms (2^12: 0.088 to 0.094 | 0.790 to 0.834; 2^18: 0.664 to 0.708 | 1.229 to 1.377), level at 2^20
+//            (4.505 to 4.752 | 4.562 to 5.323, three of four mixes within the spread) and behind at 2^22 in segments of 2 and of 1,024
+//            (17.25 | 16.12; 16.26 | 15.44): 32 bytes back per term.  No size from which every mix is ahead: NEVER
+//   PRODUCT  ahead at every cell up to 2^18 (2^12: 0.116 to 0.122 | 0.859 to 0.985; 2^18: 0.725 to 0.797 | 1.882 to 2.910); at 2^20 the device call took
+//            6 to 34 ms from round to round (medians 16.05 to 20.73 | 9.284 to 13.92: behind or within the spread); ahead at every mix at 2^22
+//            (16.86 to 18.29 | 27.48 to 45.17): 4,194,304.  The 2^20 cell is unexplained -- the identical call reads 2.32 ms in the shapes part of the
+//            same file -- and no property of the call; the default only keeps work on the host (zkp_toolbox.h)
+//   points   ahead at every cell from the smallest measured size on (2^6: 0.365 to 0.369 | 0.400 to 0.405; 2^12: 0.632 to 0.651 | 2.538 to 4.287;
+//            2^18: 1.780 to 1.969 | 118.2 to 220.9): 64
+static std::atomic<uint64_t> g_scalar_scan_min_terms[2] = {{UINT64_MAX}, {4194304}};
+static std::atomic<uint64_t> g_point_scan_min_terms{64};
+void zkp_toolbox_set_scalar_scan_min_terms(int op, uint64_t n) {
+  if (op >= 0 && op < 2) g_scalar_scan_min_terms[op] = n;
+}
+size_t zkp_toolbox_get_scalar_scan_min_terms(int op) { return op >= 0 && op < 2 ? (size_t)g_scalar_scan_min_terms[op].load() : SIZE_MAX; }
+void zkp_toolbox_set_point_scan_min_terms(uint64_t n) { g_point_scan_min_terms = n; }
+size_t zkp_toolbox_get_point_scan_min_terms(void) { return (size_t)g_point_scan_min_terms.load(); }
+
+// Every check is made by both routes before anything is written (hostbk::sc_scan_n / point_scan_n, zkp_sc_scan / zkp_scan_points), so they refuse
+// the same calls.
+int zkp_scalar_scan_batch(zkp_ctx* ctx, int op, int mode, uint32_t n_seg, const uint32_t* off, const uint8_t* a, uint32_t n_a, const uint32_t* aidx, int n_threads,
+                          uint8_t* out) {
+  if (op != ZKP_SC_SUM && op != ZKP_SC_PRODUCT) return ZKP_TB_BAD_STATEMENT;
+  if (mode != ZKP_SCAN_INCLUSIVE && mode != ZKP_SCAN_EXCLUSIVE) return ZKP_TB_BAD_STATEMENT;
+  if (n_seg == 0) return ZKP_TB_OK;
+  if (!off) return ZKP_TB_BAD_STATEMENT;
+  const uint64_t min_terms = g_scalar_scan_min_terms[op].load();
+  const bool host = !ctx || min_terms == UINT64_MAX || off[n_seg] < min_terms;
+  const int rc = host ? zkp::hostbk::sc_scan_n(op, mode, n_seg, off, a, n_a, aidx, n_threads, out) : zkp_sc_scan(ctx, op, mode, n_seg, off, a, n_a, aidx, out);
+  return rc == ZKP_ERR_ARG ? ZKP_TB_BAD_STATEMENT : rc;
+}
+
+int zkp_point_scan_batch(zkp_ctx* ctx, int mode, uint32_t n_seg, const uint32_t* off, const uint32_t* pidx, const uint8_t* neg, const uint8_t* points, uint32_t n_points,
+                         int n_threads, uint8_t* out, uint8_t* status) {
+  if (mode != ZKP_SCAN_INCLUSIVE && mode != ZKP_SCAN_EXCLUSIVE) return ZKP_TB_BAD_STATEMENT;
+  if (n_seg == 0) return ZKP_TB_OK;
+  if (!off) return ZKP_TB_BAD_STATEMENT;
+  const uint64_t min_terms = g_point_scan_min_terms.load();
+  const bool host = !ctx || min_terms == UINT64_MAX || off[n_seg] < min_terms;
+  const int rc = host ? zkp::hostbk::point_scan_n(mode, n_seg, off, pidx, neg, points, n_points, n_threads, out, status)
+                      : zkp_scan_points(ctx, mode, n_seg, off, pidx, neg, points, n_points, out, status);
+  return rc == ZKP_ERR_ARG ? ZKP_TB_BAD_STATEMENT : rc;
+}
+
 // ---- bounded discrete logarithms to the basepoint (zkp_mi355x.h (10)) behind the same routing ------------------------------------------------
 int zkp_toolbox_set_dlog_baby_bits(uint32_t baby_bits) {
   if (baby_bits < 4 || baby_bits > 22) return ZKP_TB_BAD_STATEMENT;

@@ -59,6 +59,8 @@ __device__ __forceinline__ uint32_t sel8(const uint32_t w[8], int j) {
 #include "point_mul.h"
 #include "point_sum.h"
 #include "sc_reduce.h"
+#include "sc_scan.h"
+#include "point_scan.h"
 #include "dlog.h"
 #include "transcript_kernels.h"
 #include "sha512.h"
@@ -2624,6 +2626,80 @@ int sc_reduce_check(zkp_ctx* c, int op, uint32_t n_out, const void* off, const v
   return ZKP_OK;
 }
 
+// ---- (13) segmented prefix sums and products of scalars (sc_scan.h has the scheme) ----
+// Workspace from `reserved` on, per level k = 1 .. L - 1: what its units hand on [values | flags] and the inclusive prefixes of those items, which
+// the down-sweep of level k + 1 writes and the units of level k take their carries from.
+struct sc_scan_ws {
+  uint32_t levels = 0, n[SC_SCAN_MAX_LEVELS + 1] = {};
+  size_t agg_v[SC_SCAN_MAX_LEVELS] = {}, agg_f[SC_SCAN_MAX_LEVELS] = {}, inc[SC_SCAN_MAX_LEVELS] = {}, total = 0;
+};
+sc_scan_ws sc_scan_plan(uint32_t n_terms, size_t reserved) {
+  sc_scan_ws w;
+  carve cv;
+  cv.off = reserved;
+  w.levels = sc_scan_levels(n_terms);
+  w.n[0] = n_terms;                                               // n[k]: the items of level k + 1
+  for (uint32_t k = 1; k < w.levels; ++k) {
+    w.n[k] = sc_scan_next_items(w.n[k - 1]);
+    w.agg_v[k] = cv.take((size_t)w.n[k] * 32);
+    w.agg_f[k] = cv.take((size_t)w.n[k] * 4);
+    w.inc[k] = cv.take((size_t)w.n[k] * 32);
+  }
+  w.total = cv.off;
+  return w;
+}
+template <int OP>
+int launch_sc_scan_op(zkp_ctx* c, uint32_t excl, uint32_t n_seg, const uint32_t* d_off, const uint8_t* d_a, uint32_t n_a, const uint32_t* d_aidx, const sc_scan_ws& w,
+                      uint8_t* d_out) {
+  char* ws = static_cast<char*>(c->ws);
+  const std::string name = "k_sc_scan<" + std::to_string(OP) + ", ";
+  const uint32_t L = w.levels;
+  auto vals = [&](uint32_t k) { return reinterpret_cast<uint8_t*>(ws + w.agg_v[k]); };
+  auto flags = [&](uint32_t k) { return reinterpret_cast<uint32_t*>(ws + w.agg_f[k]); };
+  auto incl = [&](uint32_t k) { return reinterpret_cast<uint8_t*>(ws + w.inc[k]); };
+  for (uint32_t level = 1; level < L; ++level) {                  // up-sweep: level `level` hands on n[level] items
+    const dim3 grid(w.n[level]);
+    if (level == 1)
+      hipLaunchKernelGGL((k_sc_scan<OP, true, false>), grid, dim3(SC_SCAN_GROUP), 0, c->stream, w.n[0], 0u, d_off, n_seg, d_a, n_a, d_aidx, (const uint8_t*)nullptr,
+                         (const uint32_t*)nullptr, (const uint8_t*)nullptr, vals(1), flags(1), (uint8_t*)nullptr);
+    else
+      hipLaunchKernelGGL((k_sc_scan<OP, false, false>), grid, dim3(SC_SCAN_GROUP), 0, c->stream, w.n[level - 1], 0u, d_off, n_seg, (const uint8_t*)nullptr, 0u,
+                         (const uint32_t*)nullptr, vals(level - 1), flags(level - 1), (const uint8_t*)nullptr, vals(level), flags(level), (uint8_t*)nullptr);
+    prof_note(c, ZKP_K_SCALARS, name + (level == 1 ? "true" : "false") + ", false>@" + std::to_string(level));
+  }
+  for (uint32_t level = L; level >= 1; --level) {                 // the top and the down-sweep: level `level` takes its carries from the level above
+    const dim3 grid(level == L ? 1u : w.n[level]);
+    const uint8_t* carry = level == L ? nullptr : incl(level);
+    if (level == 1)
+      hipLaunchKernelGGL((k_sc_scan<OP, true, true>), grid, dim3(SC_SCAN_GROUP), 0, c->stream, w.n[0], excl, d_off, n_seg, d_a, n_a, d_aidx, (const uint8_t*)nullptr,
+                         (const uint32_t*)nullptr, carry, (uint8_t*)nullptr, (uint32_t*)nullptr, d_out);
+    else
+      hipLaunchKernelGGL((k_sc_scan<OP, false, true>), grid, dim3(SC_SCAN_GROUP), 0, c->stream, w.n[level - 1], 0u, d_off, n_seg, (const uint8_t*)nullptr, 0u,
+                         (const uint32_t*)nullptr, vals(level - 1), flags(level - 1), carry, (uint8_t*)nullptr, (uint32_t*)nullptr, incl(level - 1));
+    prof_note(c, ZKP_K_SCALARS, name + (level == 1 ? "true" : "false") + ", true>@" + std::to_string(level));
+  }
+  prof_mark(c, ZKP_K_SCALARS);
+  HIP_TRY(hipGetLastError());
+  return ZKP_OK;
+}
+int launch_sc_scan(zkp_ctx* c, int op, int mode, uint32_t n_seg, const uint32_t* d_off, const uint8_t* d_a, uint32_t n_a, const uint32_t* d_aidx, const sc_scan_ws& w,
+                   uint8_t* d_out) {
+  const uint32_t excl = mode == ZKP_SCAN_EXCLUSIVE;
+  if (op == ZKP_SC_SUM) return launch_sc_scan_op<SC_RED_SUM>(c, excl, n_seg, d_off, d_a, n_a, d_aidx, w, d_out);
+  return launch_sc_scan_op<SC_RED_PRODUCT>(c, excl, n_seg, d_off, d_a, n_a, d_aidx, w, d_out);
+}
+// the checks the two forms share; n_terms: off[n_seg] / the argument
+int sc_scan_check(zkp_ctx* c, int op, int mode, const void* off, const void* a, uint32_t n_a, const void* aidx, uint64_t n_terms, const void* out) {
+  if (!c) return fail(ZKP_ERR_ARG, "ctx is NULL");
+  if (op != ZKP_SC_SUM && op != ZKP_SC_PRODUCT) return fail(ZKP_ERR_ARG, "op must be ZKP_SC_SUM or ZKP_SC_PRODUCT");
+  if (mode != ZKP_SCAN_INCLUSIVE && mode != ZKP_SCAN_EXCLUSIVE) return fail(ZKP_ERR_ARG, "mode must be ZKP_SCAN_INCLUSIVE or ZKP_SCAN_EXCLUSIVE");
+  if (!off) return fail(ZKP_ERR_ARG, "NULL pointer");
+  if (n_terms > 0x7fffffffull) return fail(ZKP_ERR_ARG, "too many terms");
+  if (n_terms && (!a || n_a == 0 || !out)) return fail(ZKP_ERR_ARG, "terms without an operand a or without out");
+  if (!aidx && n_a != n_terms) return fail(ZKP_ERR_ARG, "without aidx, n_a must equal the number of terms");
+  return ZKP_OK;
+}
+
 // zkp_hash_from_bytes_sha512 and zkp_debug_sha512: checks the offsets on the host (non-decreasing), uploads msgs[offsets[0], offsets[n])
 // and the offsets rebased to 0, hashes, and (HASH_MAP) maps the digests in place of the workspace.  out: [n][32] encodings, or [n][64] digests.
 // HASH_SCALAR (zkp_sc_hash_from_bytes_sha512): the same checks and upload, k_sc_hash_sha512 instead: out = [n][32] scalars.
@@ -2861,6 +2937,79 @@ int launch_sum_points(zkp_ctx* c, uint32_t n_sums, const uint32_t* d_off, const 
     hipLaunchKernelGGL(k_sum_fold<true>, grid, dim3(SUM_FOLD_BLOCK), 0, c->stream, n, last, d_off, n_sums, d_pidx, d_neg, n_points, pts, (const sum_item*)nullptr, out, fin);
     return std::string("k_sum_fold<true>");
   });
+}
+
+// ---- (13) segmented running sums of points (point_scan.h has the scheme) ----
+// Workspace from `reserved` on: the decoded points, the prefix of every term, and per level k = 1 .. L - 1 what its lanes hand on and the inclusive
+// prefixes of those items.
+struct pt_scan_ws {
+  uint32_t levels = 0, n[PT_SCAN_MAX_LEVELS + 1] = {};
+  size_t aff = 0, pre = 0, agg[PT_SCAN_MAX_LEVELS] = {}, inc[PT_SCAN_MAX_LEVELS] = {}, total = 0;
+};
+pt_scan_ws pt_scan_plan(uint32_t n_points, uint32_t n_terms, size_t reserved) {
+  pt_scan_ws w;
+  carve cv;
+  cv.off = reserved;
+  w.levels = pt_scan_levels(n_terms);
+  w.n[0] = n_terms;
+  w.aff = cv.take(sizeof(dev_affine) * (size_t)(n_terms ? n_points : 0));
+  w.pre = cv.take(sizeof(sum_item) * (size_t)n_terms);
+  for (uint32_t k = 1; k < w.levels; ++k) {
+    w.n[k] = pt_scan_next_items(w.n[k - 1]);
+    w.agg[k] = cv.take(sizeof(sum_item) * (size_t)w.n[k]);
+    w.inc[k] = cv.take(sizeof(sum_item) * (size_t)w.n[k]);
+  }
+  w.total = cv.off;
+  return w;
+}
+int launch_scan_points(zkp_ctx* c, int mode, uint32_t n_seg, const uint32_t* d_off, const uint32_t* d_pidx, const uint8_t* d_neg, const uint8_t* d_points,
+                       uint32_t n_points, const pt_scan_ws& w, uint8_t* d_out, uint8_t* d_status) {
+  char* ws = static_cast<char*>(c->ws);
+  const uint32_t L = w.levels, excl = mode == ZKP_SCAN_EXCLUSIVE;
+  dev_affine* pts = reinterpret_cast<dev_affine*>(ws + w.aff);
+  sum_item* pre = reinterpret_cast<sum_item*>(ws + w.pre);
+  auto agg = [&](uint32_t k) { return reinterpret_cast<sum_item*>(ws + w.agg[k]); };
+  auto incl = [&](uint32_t k) { return reinterpret_cast<sum_item*>(ws + w.inc[k]); };
+  hipLaunchKernelGGL(k_decode_affine, grid1(n_points, 256), dim3(256), 0, c->stream, n_points, d_points, pts, (const uint32_t*)nullptr);
+  prof_note(c, ZKP_K_DECODE, "k_decode_affine");
+  prof_mark(c, ZKP_K_DECODE);
+  for (uint32_t level = 1; level < L; ++level) {
+    const dim3 grid = grid1(w.n[level], SUM_FOLD_BLOCK);
+    if (level == 1)
+      hipLaunchKernelGGL((k_pt_scan<true, false>), grid, dim3(SUM_FOLD_BLOCK), 0, c->stream, w.n[0], 0u, d_off, n_seg, d_pidx, d_neg, n_points, pts, (const sum_item*)nullptr,
+                         (const sum_item*)nullptr, agg(1), (sum_item*)nullptr);
+    else
+      hipLaunchKernelGGL((k_pt_scan<false, false>), grid, dim3(SUM_FOLD_BLOCK), 0, c->stream, w.n[level - 1], 0u, d_off, n_seg, (const uint32_t*)nullptr,
+                         (const uint8_t*)nullptr, 0u, (const dev_affine*)nullptr, agg(level - 1), (const sum_item*)nullptr, agg(level), (sum_item*)nullptr);
+    prof_note(c, ZKP_K_REDUCE, std::string("k_pt_scan<") + (level == 1 ? "true" : "false") + ", false>@" + std::to_string(level));
+  }
+  for (uint32_t level = L; level >= 1; --level) {
+    const dim3 grid = grid1(level == L ? 1u : w.n[level], SUM_FOLD_BLOCK);
+    const sum_item* carry = level == L ? nullptr : incl(level);
+    if (level == 1)
+      hipLaunchKernelGGL((k_pt_scan<true, true>), grid, dim3(SUM_FOLD_BLOCK), 0, c->stream, w.n[0], excl, d_off, n_seg, d_pidx, d_neg, n_points, pts, (const sum_item*)nullptr,
+                         carry, (sum_item*)nullptr, pre);
+    else
+      hipLaunchKernelGGL((k_pt_scan<false, true>), grid, dim3(SUM_FOLD_BLOCK), 0, c->stream, w.n[level - 1], 0u, d_off, n_seg, (const uint32_t*)nullptr,
+                         (const uint8_t*)nullptr, 0u, (const dev_affine*)nullptr, agg(level - 1), carry, (sum_item*)nullptr, incl(level - 1));
+    prof_note(c, ZKP_K_REDUCE, std::string("k_pt_scan<") + (level == 1 ? "true" : "false") + ", true>@" + std::to_string(level));
+  }
+  prof_mark(c, ZKP_K_REDUCE);
+  hipLaunchKernelGGL(k_pt_scan_encode, grid1(w.n[0], 256), dim3(256), 0, c->stream, w.n[0], pre, d_out, d_status);
+  prof_note(c, ZKP_K_COMBINE, "k_pt_scan_encode");
+  prof_mark(c, ZKP_K_COMBINE);
+  HIP_TRY(hipGetLastError());
+  return ZKP_OK;
+}
+int scan_points_check(zkp_ctx* c, int mode, const void* off, const void* points, uint32_t n_points, const void* pidx, uint64_t n_terms, const void* out,
+                      const void* status) {
+  if (!c) return fail(ZKP_ERR_ARG, "ctx is NULL");
+  if (mode != ZKP_SCAN_INCLUSIVE && mode != ZKP_SCAN_EXCLUSIVE) return fail(ZKP_ERR_ARG, "mode must be ZKP_SCAN_INCLUSIVE or ZKP_SCAN_EXCLUSIVE");
+  if (!off) return fail(ZKP_ERR_ARG, "NULL pointer");
+  if (n_terms > 0x7fffffffull) return fail(ZKP_ERR_ARG, "too many terms");
+  if (n_terms && (!points || n_points == 0 || !out || !status)) return fail(ZKP_ERR_ARG, "terms without points, out or status");
+  if (!pidx && n_points != n_terms) return fail(ZKP_ERR_ARG, "without pidx, n_points must equal the number of terms");
+  return ZKP_OK;
 }
 
 // ---- (11) multiscalar sums with long segments: the term path up to `part`, then the fold of point_sum.h over the term axis ----------------------
@@ -3201,12 +3350,16 @@ int zkp_ctx_last_timing(zkp_ctx* c, float* kernel_ms, float* total_ms) {
   c->total_ms = 0;
   if (c->n_ev >= 2) {
     HIP_TRY(hipEventSynchronize(c->ev[c->n_ev - 1]));
+    float sum = 0;
     for (int i = 1; i < c->n_ev; ++i) {
       float ms = 0;
       HIP_TRY(hipEventElapsedTime(&ms, c->ev[i - 1], c->ev[i]));
       if (c->ev_kind[i] >= 0) c->kernel_ms[c->ev_kind[i]] += ms;
+      sum += ms;
     }
     HIP_TRY(hipEventElapsedTime(&c->total_ms, c->ev[0], c->ev[c->n_ev - 1]));
+    // the intervals add up to the total but for float rounding: a kind that is all of a call must not come out one ulp above the total
+    c->total_ms = std::max(c->total_ms, sum);
   }
   if (kernel_ms) memcpy(kernel_ms, c->kernel_ms, sizeof(c->kernel_ms));
   if (total_ms) *total_ms = c->total_ms;
@@ -3972,6 +4125,116 @@ int zkp_sum_points(zkp_ctx* c, uint32_t n_sums, const uint32_t* off, const uint3
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)n_sums * 32, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipMemcpyAsync(status, base + o_st, (size_t)n_sums, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return ZKP_OK;
+}
+
+// ---- (13) segmented prefix sums and products of scalars, running sums of points ---------------------------------------------------------------
+uint32_t zkp_sc_scan_group(void) { return SC_SCAN_GROUP; }
+uint32_t zkp_sc_scan_launches(uint32_t n_terms) { return sc_scan_launches(n_terms); }
+uint32_t zkp_scan_points_group(void) { return PT_SCAN_GROUP; }
+uint32_t zkp_scan_points_launches(uint32_t n_terms) { return pt_scan_launches(n_terms); }
+
+int zkp_sc_scan_dev(zkp_ctx* c, int op, int mode, uint32_t n_seg, const uint32_t* d_off, const uint8_t* d_a, uint32_t n_a, const uint32_t* d_aidx, uint32_t n_terms,
+                    uint8_t* d_out) {
+  if (n_seg == 0) return sc_scan_check(c, op, mode, &n_seg, d_a, 0, &n_seg, 0, d_out);      // a no-op once the context, op and mode are checked
+  int rc = sc_scan_check(c, op, mode, d_off, d_a, n_a, d_aidx, n_terms, d_out);
+  if (rc || n_terms == 0) return rc;
+  if (!aligned16(d_a) || !aligned16(d_out)) return fail(ZKP_ERR_ARG, "device scalars must be 16-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(d_off) | reinterpret_cast<uintptr_t>(d_aidx)) & 3) return fail(ZKP_ERR_ARG, "device offsets and indices must be 4-byte aligned");
+  HIP_TRY(hipSetDevice(c->device));
+  const sc_scan_ws w = sc_scan_plan(n_terms, 0);
+  rc = ensure_ws(c, w.total);
+  if (rc) return rc;
+  prof_begin(c);
+  return launch_sc_scan(c, op, mode, n_seg, d_off, d_a, n_a, d_aidx, w, d_out);
+}
+
+int zkp_sc_scan(zkp_ctx* c, int op, int mode, uint32_t n_seg, const uint32_t* off, const uint8_t* a, uint32_t n_a, const uint32_t* aidx, uint8_t* out) {
+  if (n_seg == 0) return sc_scan_check(c, op, mode, &n_seg, a, 0, &n_seg, 0, out);
+  if (!c) return fail(ZKP_ERR_ARG, "ctx is NULL");
+  if (!off) return fail(ZKP_ERR_ARG, "NULL pointer");
+  if (off[0] != 0) return fail(ZKP_ERR_ARG, "off[0] must be 0");
+  for (uint32_t i = 0; i < n_seg; ++i)
+    if (off[i + 1] < off[i]) return fail(ZKP_ERR_ARG, "off must be non-decreasing");
+  const uint32_t n_terms = off[n_seg];
+  int rc = sc_scan_check(c, op, mode, off, a, n_a, aidx, n_terms, out);
+  if (rc || n_terms == 0) return rc;
+  for (uint32_t t = 0; aidx && t < n_terms; ++t)
+    if (aidx[t] >= n_a) return fail(ZKP_ERR_ARG, "aidx out of range");
+  HIP_TRY(hipSetDevice(c->device));
+  carve cv;
+  const size_t o_off = cv.take((size_t)(n_seg + 1) * 4);
+  const size_t o_a = cv.take((size_t)n_a * 32);
+  const size_t o_ai = cv.take(aidx ? (size_t)n_terms * 4 : 0);
+  const size_t o_out = cv.take((size_t)n_terms * 32);
+  const sc_scan_ws w = sc_scan_plan(n_terms, cv.off);
+  rc = ensure_ws(c, w.total);
+  if (rc) return rc;
+  char* base = static_cast<char*>(c->ws);
+  HIP_TRY(hipMemcpyAsync(base + o_off, off, (size_t)(n_seg + 1) * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(base + o_a, a, (size_t)n_a * 32, hipMemcpyHostToDevice, c->stream));
+  if (aidx) HIP_TRY(hipMemcpyAsync(base + o_ai, aidx, (size_t)n_terms * 4, hipMemcpyHostToDevice, c->stream));
+  prof_begin(c);
+  rc = launch_sc_scan(c, op, mode, n_seg, reinterpret_cast<uint32_t*>(base + o_off), reinterpret_cast<uint8_t*>(base + o_a), n_a,
+                      aidx ? reinterpret_cast<uint32_t*>(base + o_ai) : nullptr, w, reinterpret_cast<uint8_t*>(base + o_out));
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)n_terms * 32, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return ZKP_OK;
+}
+
+int zkp_scan_points_dev(zkp_ctx* c, int mode, uint32_t n_seg, const uint32_t* d_off, const uint32_t* d_pidx, const uint8_t* d_neg, const uint8_t* d_points,
+                        uint32_t n_points, uint32_t n_terms, uint8_t* d_out, uint8_t* d_status) {
+  if (n_seg == 0) return scan_points_check(c, mode, &n_seg, d_points, 0, &n_seg, 0, d_out, d_status);      // a no-op once the context and mode are checked
+  int rc = scan_points_check(c, mode, d_off, d_points, n_points, d_pidx, n_terms, d_out, d_status);
+  if (rc || n_terms == 0) return rc;
+  if (!aligned16(d_points) || !aligned16(d_out)) return fail(ZKP_ERR_ARG, "device buffers must be 16-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(d_off) | reinterpret_cast<uintptr_t>(d_pidx)) & 3) return fail(ZKP_ERR_ARG, "device offsets and indices must be 4-byte aligned");
+  HIP_TRY(hipSetDevice(c->device));
+  const pt_scan_ws w = pt_scan_plan(n_points, n_terms, 0);
+  rc = ensure_ws(c, w.total);
+  if (rc) return rc;
+  prof_begin(c);
+  return launch_scan_points(c, mode, n_seg, d_off, d_pidx, d_neg, d_points, n_points, w, d_out, d_status);
+}
+
+int zkp_scan_points(zkp_ctx* c, int mode, uint32_t n_seg, const uint32_t* off, const uint32_t* pidx, const uint8_t* neg, const uint8_t* points, uint32_t n_points,
+                    uint8_t* out, uint8_t* status) {
+  if (n_seg == 0) return scan_points_check(c, mode, &n_seg, points, 0, &n_seg, 0, out, status);
+  if (!c) return fail(ZKP_ERR_ARG, "ctx is NULL");
+  if (!off) return fail(ZKP_ERR_ARG, "NULL pointer");
+  if (off[0] != 0) return fail(ZKP_ERR_ARG, "off[0] must be 0");
+  for (uint32_t i = 0; i < n_seg; ++i)
+    if (off[i + 1] < off[i]) return fail(ZKP_ERR_ARG, "off must be non-decreasing");
+  const uint32_t n_terms = off[n_seg];
+  int rc = scan_points_check(c, mode, off, points, n_points, pidx, n_terms, out, status);
+  if (rc || n_terms == 0) return rc;
+  for (uint32_t t = 0; pidx && t < n_terms; ++t)
+    if (pidx[t] >= n_points) return fail(ZKP_ERR_ARG, "pidx out of range");
+  HIP_TRY(hipSetDevice(c->device));
+  carve cv;
+  const size_t o_off = cv.take((size_t)(n_seg + 1) * 4);
+  const size_t o_pidx = cv.take(pidx ? (size_t)n_terms * 4 : 0);
+  const size_t o_neg = cv.take(neg ? (size_t)n_terms : 0);
+  const size_t o_pts = cv.take((size_t)n_points * 32);
+  const size_t o_out = cv.take((size_t)n_terms * 32);
+  const size_t o_st = cv.take((size_t)n_terms);
+  const pt_scan_ws w = pt_scan_plan(n_points, n_terms, cv.off);
+  rc = ensure_ws(c, w.total);
+  if (rc) return rc;
+  char* base = static_cast<char*>(c->ws);
+  HIP_TRY(hipMemcpyAsync(base + o_off, off, (size_t)(n_seg + 1) * 4, hipMemcpyHostToDevice, c->stream));
+  if (pidx) HIP_TRY(hipMemcpyAsync(base + o_pidx, pidx, (size_t)n_terms * 4, hipMemcpyHostToDevice, c->stream));
+  if (neg) HIP_TRY(hipMemcpyAsync(base + o_neg, neg, (size_t)n_terms, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(base + o_pts, points, (size_t)n_points * 32, hipMemcpyHostToDevice, c->stream));
+  prof_begin(c);
+  rc = launch_scan_points(c, mode, n_seg, reinterpret_cast<uint32_t*>(base + o_off), pidx ? reinterpret_cast<uint32_t*>(base + o_pidx) : nullptr,
+                          neg ? reinterpret_cast<uint8_t*>(base + o_neg) : nullptr, reinterpret_cast<uint8_t*>(base + o_pts), n_points, w,
+                          reinterpret_cast<uint8_t*>(base + o_out), reinterpret_cast<uint8_t*>(base + o_st));
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)n_terms * 32, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(status, base + o_st, (size_t)n_terms, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return ZKP_OK;
 }

@@ -26,6 +26,7 @@ ZKP_VARTIME = 0
 ZKP_CT = 1
 ZKP_PT_ADD, ZKP_PT_SUB = 0, 1               # zkp_add_points' op
 ZKP_SC_SUM, ZKP_SC_PRODUCT, ZKP_SC_DOT = 0, 1, 2     # zkp_sc_reduce's op
+ZKP_SCAN_INCLUSIVE, ZKP_SCAN_EXCLUSIVE = 0, 1        # zkp_sc_scan's and zkp_scan_points' mode
 ZKP_DLOG_FOUND, ZKP_DLOG_INVALID, ZKP_DLOG_NOT_FOUND = 0, 1, 2      # zkp_dlog_base's status
 ZKP_OPT_BATCH_ENCODE_MIN = 1
 (ZKP_OPT_COMB_TEETH, ZKP_OPT_CT_SINGLE_USE_TABLES, ZKP_OPT_TRANSCRIPT_LANES, ZKP_OPT_DEV_OVERLAP, ZKP_OPT_GROUPED_COMB, ZKP_OPT_TABLES_LANE,
@@ -428,6 +429,28 @@ class Engine:
                                        None if b is None or not len(b) else _ptr(b), 0 if b is None else len(b), _ptr(bidx), _ptr(out)), "zkp_sc_reduce")
         return out
 
+    # ---- prefix sums and products over segments (include/zkp_mi355x.h section 13): one row per term ----
+    def scalar_scan(self, op: int, off, a, aidx=None, exclusive: bool = False) -> np.ndarray:
+        """zkp_sc_scan: out[t] = the fold of the terms of t's segment up to t (exclusive: before t; the identity at a segment's first term) ->
+        [off[-1]][32] canonical scalars.  op = ZKP_SC_SUM or ZKP_SC_PRODUCT of a[ai(t)]; ai(t) = aidx[t], or t with aidx = None"""
+        off, a, aidx, _, _ = reduce_operands(ZKP_SC_SUM, off, a, aidx)       # (shapes only: op is the library's to check)
+        out = np.zeros((int(off[-1]), 32), np.uint8)
+        _check(self._lib.zkp_sc_scan(self._h, op, int(bool(exclusive)), len(off) - 1, _ptr(off), _ptr(a) if len(a) else None, len(a), _ptr(aidx), _ptr(out)),
+               "zkp_sc_scan")
+        return out
+
+    def point_scan(self, off, points, pidx=None, neg=None, exclusive: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        """zkp_scan_points: out[t] = encode(the sum of +- decode(points[pidx[t']]) over the terms t' of t's segment up to t (exclusive: before t)) ->
+        (out [off[-1]][32], status [off[-1]]); status 1 and a zero row where a point the row depends on does not decode; pidx = None: term t is point t"""
+        off, pidx, neg, points = sum_operands(off, points, pidx, neg)
+        n_terms = int(off[-1])
+        out = np.zeros((n_terms, 32), np.uint8)
+        status = np.zeros(n_terms, np.uint8)
+        _check(self._lib.zkp_scan_points(self._h, int(bool(exclusive)), len(off) - 1, _ptr(off), None if pidx is None else _ptr(pidx),
+                                         None if neg is None else _ptr(neg), _ptr(points) if len(points) else None, len(points), _ptr(out), _ptr(status)),
+               "zkp_scan_points")
+        return out, status
+
     # ---- bounded discrete logarithms to the basepoint (include/zkp_mi355x.h section 10): variable time by nature ----
     def prepare_dlog(self, baby_bits: int) -> None:
         """build (or replace) the context's baby-step table: the encodings of i B for i < 2**baby_bits, baby_bits in 4 .. 22"""
@@ -582,6 +605,16 @@ class Engine:
         """zkp_sc_reduce_dev: d_off u32 [n_out + 1], d_a [n_a][32], d_aidx u32 [n_terms] or None, d_b [n_b][32] / d_bidx (ZKP_SC_DOT, else None, 0,
         None) -> d_out [n_out][32]; nothing is read on the host, the launches depend on n_terms and n_out alone; n_terms must be d_off[n_out]"""
         _check(self._lib.zkp_sc_reduce_dev(self._h, op, n_out, d_off, d_a, n_a, d_aidx, d_b, n_b, d_bidx, n_terms, d_out), "zkp_sc_reduce_dev")
+
+    def scalar_scan_dev(self, op, mode, n_seg, d_off, d_a, n_a, d_aidx, n_terms, d_out) -> None:
+        """zkp_sc_scan_dev: d_off u32 [n_seg + 1], d_a [n_a][32], d_aidx u32 [n_terms] or None -> d_out [n_terms][32]; nothing is read on the host, the
+        launches depend on n_terms alone; n_terms must be d_off[n_seg]"""
+        _check(self._lib.zkp_sc_scan_dev(self._h, op, mode, n_seg, d_off, d_a, n_a, d_aidx, n_terms, d_out), "zkp_sc_scan_dev")
+
+    def point_scan_dev(self, mode, n_seg, d_off, d_pidx, d_neg, d_points, n_points, n_terms, d_out, d_status) -> None:
+        """zkp_scan_points_dev: d_off u32 [n_seg + 1], d_pidx u32 [n_terms] or None, d_neg u8 [n_terms] or None, d_points [n_points][32] ->
+        d_out [n_terms][32], d_status [n_terms] bytes; nothing is read on the host, the launches depend on n_terms alone"""
+        _check(self._lib.zkp_scan_points_dev(self._h, mode, n_seg, d_off, d_pidx, d_neg, d_points, n_points, n_terms, d_out, d_status), "zkp_scan_points_dev")
 
     def dlog_base_dev(self, n, d_points, bits, d_out, d_status) -> None:
         """zkp_dlog_base_dev: d_points [n][32] (16-byte aligned) -> d_out u64 [n], d_status u8 [n]; queued on the context's stream"""

@@ -573,6 +573,48 @@ def get_scalar_reduce_min_terms(op: int) -> int:
     return int(lib().zkp_toolbox_get_scalar_reduce_min_terms(op))
 
 
+def scalar_scan(eng, op: int, off, a, aidx=None, exclusive: bool = False, threads: int = 0) -> np.ndarray:
+    """zkp_scalar_scan_batch: out[t] = the fold of the terms of t's segment up to t (exclusive: before t) -> [off[-1]][32] canonical scalars.  eng = None,
+    or fewer than get_scalar_scan_min_terms(op) terms, runs on the host threads, which share the TERM axis; anything else is Engine.scalar_scan."""
+    from .engine import reduce_operands
+    off, a, aidx, _, _ = reduce_operands(0, off, a, aidx)
+    out = np.zeros((int(off[-1]), 32), np.uint8)
+    _raise(lib().zkp_scalar_scan_batch(None if eng is None else eng._h, op, int(bool(exclusive)), len(off) - 1, _p(off), _p(a) if len(a) else None, len(a),
+                                       _p(aidx), threads, _p(out)), "zkp_scalar_scan_batch")
+    return out
+
+
+def scalar_cumsum(eng, off, a, aidx=None, exclusive: bool = False, threads: int = 0) -> np.ndarray:
+    """running sums per segment: out[t] = sum of a[aidx[t']] over the terms t' <= t of t's segment (exclusive: t' < t; 0 at a segment's first term)"""
+    return scalar_scan(eng, 0, off, a, aidx, exclusive, threads)
+
+
+def scalar_cumprod(eng, off, a, aidx=None, exclusive: bool = False, threads: int = 0) -> np.ndarray:
+    """running products per segment: out[t] = prod of a[aidx[t']] over the terms t' <= t of t's segment (exclusive: t' < t; 1 at a segment's first term)"""
+    return scalar_scan(eng, 1, off, a, aidx, exclusive, threads)
+
+
+def scalar_powers(eng, x, t: int, threads: int = 0) -> np.ndarray:
+    """x [n][32] -> [n][t][32]: row j holds x[j]^0 .. x[j]^(t-1), an exclusive product scan over t references to row j"""
+    from .engine import _u8
+    x = _u8(x, 32)
+    n = len(x)
+    off = np.arange(n + 1, dtype=np.uint64) * t
+    if int(off[-1]) > 0x7fffffff:
+        raise ValueError("more than 2**31 - 1 powers")
+    aidx = np.repeat(np.arange(n, dtype=np.uint32), t)
+    return scalar_cumprod(eng, off.astype(np.uint32), x, aidx, True, threads).reshape(n, t, 32)
+
+
+def set_scalar_scan_min_terms(op: int, n: int) -> None:
+    """scalar_scan jobs of op on an engine with at least n terms run on the device (0: always; 2**64 - 1: never)"""
+    lib().zkp_toolbox_set_scalar_scan_min_terms(op, n)
+
+
+def get_scalar_scan_min_terms(op: int) -> int:
+    return int(lib().zkp_toolbox_get_scalar_scan_min_terms(op))
+
+
 def scalar_hash_from_bytes_sha512(eng, messages, threads: int = 0) -> np.ndarray:
     """Scalar::hash_from_bytes::<Sha512> of every message (a list of byte strings)"""
     from .engine import messages_csr
@@ -709,6 +751,29 @@ def point_sum(eng, off, points, pidx=None, neg=None, threads: int = 0):
     _raise(lib().zkp_point_sum_batch(None if eng is None else eng._h, n_sums, _p(off), _p(pidx), _p(neg), _p(points), len(points), threads, _p(out),
                                      _p(status)), "zkp_point_sum_batch")
     return out, status
+
+
+def point_cumsum(eng, off, points, pidx=None, neg=None, exclusive: bool = False, threads: int = 0):
+    """running sums of points per segment: out[t] = encode(sum of +- decode(points[pidx[t']]) over the terms t' <= t of t's segment) (exclusive:
+    t' < t; the identity at a segment's first term) -> (out [off[-1]][32], status [off[-1]]).  pidx and neg as in point_sum.  status 1 and a zero row
+    where a point the row depends on does not decode.  eng = None, or fewer than get_point_scan_min_terms() terms, runs on the host threads."""
+    from .engine import sum_operands
+    off, pidx, neg, points = sum_operands(off, points, pidx, neg)
+    n_terms = int(off[-1])
+    out = np.zeros((n_terms, 32), np.uint8)
+    status = np.zeros(n_terms, np.uint8)
+    _raise(lib().zkp_point_scan_batch(None if eng is None else eng._h, int(bool(exclusive)), len(off) - 1, _p(off), _p(pidx), _p(neg),
+                                      _p(points) if len(points) else None, len(points), threads, _p(out), _p(status)), "zkp_point_scan_batch")
+    return out, status
+
+
+def set_point_scan_min_terms(n: int) -> None:
+    """point_cumsum jobs on an engine with at least n terms run on the device (0: always; 2**64 - 1: never)"""
+    lib().zkp_toolbox_set_point_scan_min_terms(n)
+
+
+def get_point_scan_min_terms() -> int:
+    return int(lib().zkp_toolbox_get_point_scan_min_terms())
 
 
 # ---- bounded discrete logarithms to the basepoint (include/zkp_toolbox.h): m from encode(m B), m < 2**bits; eng = None is the host backend ----
