@@ -548,7 +548,35 @@ int zkp_sc_hash_from_bytes_sha512_dev(zkp_ctx* ctx, uint64_t n, const uint8_t* d
  *     zkp_strobe_pos_after_append: pure arithmetic, no GPU: the position word pos | pos_begin << 8 | cur_flags << 16 of a transcript
  *       after one append_message with a label of label_len and a message of msg_len bytes, given its position word before.  A resident
  *       caller whose messages have one length passes d_ts_out straight to zkp_fused_prove_dev / _batch_verify_dev with it, without
- *       downloading a blob to learn strobe_pos.  (A position byte of 166 or more returns strobe_pos unchanged.) */
+ *       downloading a blob to learn strobe_pos.  (A position byte of 166 or more returns strobe_pos unchanged.)
+ *     The rest of the reference's TranscriptProtocol (src/toolbox/mod.rs:165-228) and its prover's TranscriptRng (src/toolbox/prover.rs:78-89),
+ *     for callers who write a protocol of their own out of the batched calls -- an OR-proof, another challenge structure.  The lane code
+ *     has STROBE's KEY operation for them (flags A|C: it overwrites the state where ad XORs; its begin runs the permutation when the
+ *     position is not 0, as PRF's does).  Same common rules; the host-pointer forms reject a position byte of 166 or more, the _dev forms
+ *     (blobs 16-byte aligned, every other buffer of any alignment) enqueue without synchronising, use no workspace and are recordable.
+ *     zkp_transcripts_witness_rng / _dev: for each of N transcripts, which are read and never written (build_rng clones):
+ *         for k < m:  meta_ad(label); meta_ad(u32le(wlen), more); KEY(witness k)       rekey_with_witness_bytes(label, witness k)
+ *         meta_ad("rng"); KEY(entropy j [32])                                         finalize(&mut rng)
+ *         ZKP_RNG_SCALARS: count x { meta_ad(u32le(64)); PRF(64) }, each reduced with from_bytes_mod_order_wide -> out [N][count][32],
+ *                          canonical (Scalar::random(&mut rng) per blinding)
+ *         ZKP_RNG_BYTES:   meta_ad(u32le(count)); PRF(count) -> out [N][count]         one fill_bytes
+ *       witnesses [N][m][wlen], one wlen per call; m = 0 and wlen = 0 are allowed (and are different transcripts: wlen = 0 still frames
+ *       and keys); witnesses may be NULL when m * wlen = 0 and out when count = 0.  entropy [N][32] is the caller's: what the external
+ *       RNG contributes.  The reference's label is "".  Any other mode is ZKP_ERR_ARG.  The _dev form writes zeros for a corrupt blob.
+ *       Branches and addresses depend on positions, m, wlen, count and the label's length, never on witness, entropy or state bytes.
+ *       The host-pointer form stages entropy and witnesses in the context's workspace and zeroes that region before it returns, on
+ *       error paths too; the outputs' staging is not wiped (they are the caller's secrets as much as what it receives in `out`), nor is
+ *       anything the HIP runtime stages for a copy from pageable memory.
+ *     zkp_transcripts_challenge_scalars / _dev: N x get_challenge(label) = challenge_bytes(label, 64) reduced mod l in the same lane ->
+ *       out [N][32], canonical; the blobs advance in place.  The _dev form leaves a corrupt blob as it is and writes zeros.
+ *     zkp_transcripts_append_points / _dev: N x { append_message(kind, var_label); append_message("val", points[j][32]) } in one launch:
+ *       kind = "ptvar" is append_point_var, "blindcom" append_blinding_commitment (any label works).  validate != 0 gives the validating
+ *       forms: a row of 32 zero bytes (the identity's encoding) gets status[j] = 1 and its blob stays as it was, the reference's early
+ *       return; nothing else is validated, as there.  status [N] (required when validate != 0, optional otherwise) gets 0 for every
+ *       other row.  The _dev form leaves a corrupt blob as it is, with status 0.
+ *     zkp_ctx_last_kernels names "k_strobe_witness_rng", "k_strobe_challenge_scalars" and "k_strobe_append_points". */
+#define ZKP_RNG_SCALARS 0
+#define ZKP_RNG_BYTES 1
 int zkp_transcripts_append_message(zkp_ctx* ctx, uint32_t N, int shared_initial, uint8_t* ts /*[N][208]*/, const char* label,
                                    const uint8_t* msgs, const uint64_t* offsets /*[N+1]*/);
 int zkp_transcripts_append_message_dev(zkp_ctx* ctx, uint32_t N, int shared_initial, const uint8_t* d_ts_in, uint8_t* d_ts_out,
@@ -558,6 +586,18 @@ int zkp_transcripts_challenge_bytes(zkp_ctx* ctx, uint32_t N, uint8_t* ts /*[N][
 int zkp_transcripts_challenge_bytes_dev(zkp_ctx* ctx, uint32_t N, uint8_t* d_ts /*[N][208]*/, const char* label, uint32_t len,
                                         uint8_t* d_out /*[N][len]*/);
 uint32_t zkp_strobe_pos_after_append(uint32_t strobe_pos, uint64_t label_len, uint64_t msg_len);
+int zkp_transcripts_witness_rng(zkp_ctx* ctx, uint32_t N, const uint8_t* ts /*[N][208]*/, const char* label, uint32_t m, uint32_t wlen,
+                                const uint8_t* witnesses /*[N][m][wlen]*/, const uint8_t* entropy /*[N][32]*/, int mode, uint32_t count,
+                                uint8_t* out /*[N][count][32] or [N][count]*/);
+int zkp_transcripts_witness_rng_dev(zkp_ctx* ctx, uint32_t N, const uint8_t* d_ts /*[N][208]*/, const char* label, uint32_t m, uint32_t wlen,
+                                    const uint8_t* d_witnesses /*[N][m][wlen]*/, const uint8_t* d_entropy /*[N][32]*/, int mode, uint32_t count,
+                                    uint8_t* d_out /*[N][count][32] or [N][count]*/);
+int zkp_transcripts_challenge_scalars(zkp_ctx* ctx, uint32_t N, uint8_t* ts /*[N][208]*/, const char* label, uint8_t* out /*[N][32]*/);
+int zkp_transcripts_challenge_scalars_dev(zkp_ctx* ctx, uint32_t N, uint8_t* d_ts /*[N][208]*/, const char* label, uint8_t* d_out /*[N][32]*/);
+int zkp_transcripts_append_points(zkp_ctx* ctx, uint32_t N, uint8_t* ts /*[N][208]*/, const char* kind, const char* var_label,
+                                  const uint8_t* points /*[N][32]*/, int validate, uint8_t* status /*[N]*/);
+int zkp_transcripts_append_points_dev(zkp_ctx* ctx, uint32_t N, uint8_t* d_ts /*[N][208]*/, const char* kind, const char* var_label,
+                                      const uint8_t* d_points /*[N][32]*/, int validate, uint8_t* d_status /*[N]*/);
 
 /* (8) Scalar * basepoint and Scalar * point, batched: `&sk * &RISTRETTO_BASEPOINT_TABLE` (PublicKey::from(&SecretKey), reference
  *     tests/sig_and_vrf_example.rs:58) and `&H * &x` (:112; the instance points of tests/zkp.rs and benches/dleq.rs) for n operands, each

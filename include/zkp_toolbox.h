@@ -62,6 +62,40 @@ int zkp_transcripts_append_message_batch_ctx(zkp_ctx* ctx, uint8_t* ts /*[N][208
                                              const uint8_t* msgs, const uint64_t* offsets /*[N + 1]*/, int n_threads);
 int zkp_transcripts_challenge_bytes_batch(zkp_ctx* ctx, uint8_t* ts /*[N][208]*/, uint32_t N, const char* label, uint32_t len, int n_threads,
                                           uint8_t* out /*[N][len]*/);
+/* The rest of the reference's TranscriptProtocol (src/toolbox/mod.rs:165-228) and its prover's TranscriptRng (src/toolbox/prover.rs:78-89)
+ * over N transcripts at any mix of positions, for protocols the constraint system cannot express: semantics in zkp_mi355x.h (7).
+ * (domain_sep and append_scalar_var are append_message with the labels "dom-sep" and "scvar".)
+ *   zkp_transcripts_witness_rng_batch: build_rng; rekey_with_witness_bytes(label, witness k) for k < m; finalize; then count x Scalar::random
+ *     (mode ZKP_RNG_SCALARS, out [N][count][32] canonical) or one fill_bytes(count) (ZKP_RNG_BYTES, out [N][count]).  The transcripts are
+ *     read, never written.  witnesses [N][m][wlen]; entropy [N][32], or NULL: drawn the way zkp_prove_batch draws the prover's entropy
+ *     (ZKP_TB_NO_ENTROPY if the operating system gives none).
+ *   zkp_transcripts_challenge_scalars_batch: get_challenge(label) -> out [N][32], canonical; the blobs advance in place.
+ *   zkp_transcripts_append_points_batch: append_message(kind, var_label); append_message("val", points[j]) -- kind "ptvar" is
+ *     append_point_var, "blindcom" append_blinding_commitment.  validate != 0: the validating forms, status[j] = 1 and blob j unchanged for
+ *     a row of 32 zero bytes; status [N] is required then, optional otherwise, and gets 0 for every other row.
+ * ctx == NULL runs the lane code the kernels compile (zkp_amd/csrc/strobe_lane.h) on n_threads host threads; with a context, a batch of at
+ * least zkp_toolbox_get_*_min_batch() transcripts goes to the device (UINT32_MAX = never, 0 = always).  Same bytes on both routes.  The
+ * defaults follow the toolbox's rule -- the smallest measured N from which the synchronous device call is ahead of the host backend at 16
+ * threads, beyond the spread of the rounds, at every measured shape -- over profiles/transcript_rng_bench.txt.
+ * N = 0 is a no-op.  A NULL buffer with N > 0, a NULL label, a label of more than 248 bytes, another mode, N > 2^31 - 1 or a position byte
+ * (byte 200 of a blob) of 166 or more is ZKP_TB_BAD_STATEMENT, and nothing changes on an error.
+ * Secrets: the calls wipe the entropy they drew and the keyed STROBE state of every host lane before they return, on error paths too, and
+ * make no host copy of the witnesses.  On the device route the staging of entropy and witnesses in the context's workspace is zeroed
+ * (zkp_mi355x.h); NOT wiped: the outputs' device staging, which stays in the workspace until the next call reuses it, and whatever the
+ * HIP runtime stages for its copies. */
+int zkp_transcripts_witness_rng_batch(zkp_ctx* ctx, const uint8_t* ts /*[N][208]*/, uint32_t N, const char* label, uint32_t m, uint32_t wlen,
+                                      const uint8_t* witnesses /*[N][m][wlen]*/, const uint8_t* entropy /*[N][32] or NULL*/, int mode, uint32_t count,
+                                      int n_threads, uint8_t* out);
+int zkp_transcripts_challenge_scalars_batch(zkp_ctx* ctx, uint8_t* ts /*[N][208]*/, uint32_t N, const char* label, int n_threads,
+                                            uint8_t* out /*[N][32]*/);
+int zkp_transcripts_append_points_batch(zkp_ctx* ctx, uint8_t* ts /*[N][208]*/, uint32_t N, const char* kind, const char* var_label,
+                                        const uint8_t* points /*[N][32]*/, int validate, int n_threads, uint8_t* status /*[N]*/);
+void zkp_toolbox_set_witness_rng_min_batch(uint32_t n);
+uint32_t zkp_toolbox_get_witness_rng_min_batch(void);
+void zkp_toolbox_set_challenge_scalars_min_batch(uint32_t n);
+uint32_t zkp_toolbox_get_challenge_scalars_min_batch(void);
+void zkp_toolbox_set_append_points_min_batch(uint32_t n);
+uint32_t zkp_toolbox_get_append_points_min_batch(void);
 
 /* ---- scalars mod l (curve25519_dalek::scalar::Scalar) -------------------------------------------- */
 void zkp_scalar_from_wide(uint8_t out[32], const uint8_t in[64]);   /* from_bytes_mod_order_wide */

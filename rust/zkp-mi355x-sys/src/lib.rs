@@ -281,6 +281,16 @@ extern "C" {
     pub fn zkp_transcripts_challenge_bytes(ctx: *mut zkp_ctx, n: u32, ts: *mut u8, label: *const c_char, len: u32, out: *mut u8) -> c_int;
     pub fn zkp_transcripts_challenge_bytes_dev(ctx: *mut zkp_ctx, n: u32, d_ts: *mut u8, label: *const c_char, len: u32, d_out: *mut u8) -> c_int;
     pub fn zkp_strobe_pos_after_append(strobe_pos: u32, label_len: u64, msg_len: u64) -> u32;
+    pub fn zkp_transcripts_witness_rng(ctx: *mut zkp_ctx, n: u32, ts: *const u8, label: *const c_char, m: u32, wlen: u32, witnesses: *const u8, entropy: *const u8,
+                                       mode: c_int, count: u32, out: *mut u8) -> c_int;
+    pub fn zkp_transcripts_witness_rng_dev(ctx: *mut zkp_ctx, n: u32, d_ts: *const u8, label: *const c_char, m: u32, wlen: u32, d_witnesses: *const u8,
+                                           d_entropy: *const u8, mode: c_int, count: u32, d_out: *mut u8) -> c_int;
+    pub fn zkp_transcripts_challenge_scalars(ctx: *mut zkp_ctx, n: u32, ts: *mut u8, label: *const c_char, out: *mut u8) -> c_int;
+    pub fn zkp_transcripts_challenge_scalars_dev(ctx: *mut zkp_ctx, n: u32, d_ts: *mut u8, label: *const c_char, d_out: *mut u8) -> c_int;
+    pub fn zkp_transcripts_append_points(ctx: *mut zkp_ctx, n: u32, ts: *mut u8, kind: *const c_char, var_label: *const c_char, points: *const u8,
+                                         validate: c_int, status: *mut u8) -> c_int;
+    pub fn zkp_transcripts_append_points_dev(ctx: *mut zkp_ctx, n: u32, d_ts: *mut u8, kind: *const c_char, var_label: *const c_char, d_points: *const u8,
+                                             validate: c_int, d_status: *mut u8) -> c_int;
     pub fn zkp_ctx_last_timing(ctx: *mut zkp_ctx, kernel_ms: *mut f32, total_ms: *mut f32) -> c_int;
     pub fn zkp_ctx_last_kernels(ctx: *mut zkp_ctx, kind: c_int, buf: *mut c_char, cap: usize) -> c_int;
     pub fn zkp_ctx_set_profiling(ctx: *mut zkp_ctx, enabled: c_int) -> c_int;
@@ -294,6 +304,17 @@ extern "C" {
     pub fn zkp_transcripts_append_message_batch_ctx(ctx: *mut zkp_ctx, ts: *mut u8, n: u32, shared_initial: c_int, label: *const c_char, msgs: *const u8,
                                                     offsets: *const u64, n_threads: c_int) -> c_int;
     pub fn zkp_transcripts_challenge_bytes_batch(ctx: *mut zkp_ctx, ts: *mut u8, n: u32, label: *const c_char, len: u32, n_threads: c_int, out: *mut u8) -> c_int;
+    pub fn zkp_transcripts_witness_rng_batch(ctx: *mut zkp_ctx, ts: *const u8, n: u32, label: *const c_char, m: u32, wlen: u32, witnesses: *const u8,
+                                             entropy: *const u8, mode: c_int, count: u32, n_threads: c_int, out: *mut u8) -> c_int;
+    pub fn zkp_transcripts_challenge_scalars_batch(ctx: *mut zkp_ctx, ts: *mut u8, n: u32, label: *const c_char, n_threads: c_int, out: *mut u8) -> c_int;
+    pub fn zkp_transcripts_append_points_batch(ctx: *mut zkp_ctx, ts: *mut u8, n: u32, kind: *const c_char, var_label: *const c_char, points: *const u8,
+                                               validate: c_int, n_threads: c_int, status: *mut u8) -> c_int;
+    pub fn zkp_toolbox_set_witness_rng_min_batch(n: u32);
+    pub fn zkp_toolbox_get_witness_rng_min_batch() -> u32;
+    pub fn zkp_toolbox_set_challenge_scalars_min_batch(n: u32);
+    pub fn zkp_toolbox_get_challenge_scalars_min_batch() -> u32;
+    pub fn zkp_toolbox_set_append_points_min_batch(n: u32);
+    pub fn zkp_toolbox_get_append_points_min_batch() -> u32;
     pub fn zkp_scalar_from_wide(out: *mut u8, input: *const u8);
     pub fn zkp_scalar_muladd(out: *mut u8, a: *const u8, b: *const u8, c: *const u8);
     pub fn zkp_scalar_neg(out: *mut u8, a: *const u8);

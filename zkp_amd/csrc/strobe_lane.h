@@ -2,7 +2,8 @@
 // challenge_bytes on ONE transcript whose position is only known at run time (host/merlin.cpp:61-150 restated; merlin_prog.h compiles
 // programs for batches whose positions the host knows, this header needs no program).
 //
-// g++ (a stand-alone driver, tests/host/transcript_ops_host_main.cpp) and hipcc compile the same text.  The 25 state words are a strided
+// g++ (the stand-alone drivers tests/host/transcript_ops_host_main.cpp and transcript_rng_host_main.cpp, and the host library's
+// host/transcript_rng.cpp) and hipcc compile the same text.  The 25 state words are a strided
 // column, S[i * stride]: an LDS column per lane on the device (a run-time position indexes LDS, never a register array: no scratch),
 // stride 1 on the host.  The permutation is merlin_prog.h's one-lane Keccak-f[1600] (tr_keccak_f).
 //
@@ -14,15 +15,22 @@
 // Lanes of a wavefront stand at different positions and hold different lengths; with the permutation outside the per-step loop a
 // wavefront runs max over its lanes of the lane's permutation count, not their sum.
 // Branches and addresses depend on positions, label lengths and data lengths only, never on message or state bytes.
+//
+// The second half of the header is the part walker (strobe_walk): the same loop over ANY sequence of parts, among them KEY (flags A|C:
+// it overwrites where ad XORs), the two frames of Merlin's TranscriptRng that strobe_merlin_op does not walk -- meta_ad("rng") without a
+// length, fill_bytes with a length and no label -- and a 64-byte PRF reduced mod l in the lane (sc25519.h).  On it stand the witness RNG
+// (TranscriptRng: build_rng, rekey_with_witness_bytes, finalize, fill_bytes / Scalar::random), get_challenge and the point appends of the
+// reference's TranscriptProtocol (src/toolbox/mod.rs:165-228).
 #pragma once
 #include <stdint.h>
 #include "merlin_prog.h"   // ZKP_HD, tr_keccak_f, tr_bytemask
 #include "sha512.h"        // sha512_clamp
+#include "sc25519.h"       // sc_reduce_wide
 
 namespace zkp {
 
 constexpr uint32_t STROBE_RATE = 166;
-constexpr uint32_t STROBE_I = 1, STROBE_A = 2, STROBE_C = 4, STROBE_M = 16;    // the flags Merlin uses (K and T never appear)
+constexpr uint32_t STROBE_I = 1, STROBE_A = 2, STROBE_C = 4, STROBE_M = 16;    // the flags Merlin uses: KEY is A|C (K and T never appear)
 
 // A label as a kernel argument: its bytes in little-endian words, zero padded.  One word stays free behind the last label byte, so
 // that the unaligned 8-byte fetch may read word k + 1.
@@ -231,6 +239,188 @@ ZKP_HD uint32_t strobe_pos_after_append(uint32_t strobe_pos, uint64_t label_len,
   const bool crossed = msg_len >= STROBE_RATE || at_ad + 2 + m >= STROBE_RATE;
   const uint32_t end = (uint32_t)((at_ad + 2 + m) % STROBE_RATE);
   return end | (crossed ? 0u : at_ad + 1) << 8 | STROBE_A << 16;
+}
+
+// ---- the part walker -------------------------------------------------------------------------------------------------------------------
+// A part is a run of bytes that one STROBE duplex call moves.  SP_HDR is begin_op: its two header bytes are made when the part begins
+// (they hold pos_begin), and a header whose flags carry C owes a run_f once it is absorbed if pos != 0 (Strobe128::begin_op) -- PRF's
+// and KEY's alike.  SP_PRF64 is prf(64) whose output is reduced mod l: the C flag leaves it at pos = 0, so its 64 bytes are state words
+// 0..7, read with constant indices (no byte loop, no run-time register index).
+enum : uint32_t { SP_NONE, SP_HDR, SP_VAL, SP_LABEL, SP_AD, SP_KEY, SP_PRF, SP_PRF64, SP_END };
+struct strobe_part {
+  uint32_t kind, flags;         // flags: SP_HDR's operation flags
+  uint64_t rem, val;            // bytes left; SP_VAL's bytes (little-endian, at most 8), SP_PRF64's output index, SP_LABEL's label number
+  uint64_t len;                 // SP_AD / SP_KEY: the length of the whole message (strobe_msg's bound)
+  const uint8_t* src;           // SP_AD / SP_KEY: the message
+  uint8_t* dst;                 // SP_PRF: the output
+};
+ZKP_HD strobe_part strobe_part_make(uint32_t kind, uint32_t flags, uint64_t rem, uint64_t val, const uint8_t* src, uint8_t* dst) {
+  strobe_part p;
+  p.kind = kind; p.flags = flags; p.rem = rem; p.val = val; p.len = rem; p.src = src; p.dst = dst;
+  return p;
+}
+ZKP_HD strobe_part strobe_part_hdr(uint32_t flags) { return strobe_part_make(SP_HDR, flags, 2, 0, nullptr, nullptr); }
+ZKP_HD strobe_part strobe_part_val(uint64_t val, uint32_t n) { return strobe_part_make(SP_VAL, 0, n, val, nullptr, nullptr); }
+ZKP_HD strobe_part strobe_part_label(uint32_t which, uint32_t n) { return strobe_part_make(SP_LABEL, 0, n, which, nullptr, nullptr); }
+ZKP_HD strobe_part strobe_part_end() { return strobe_part_make(SP_END, 0, 0, 0, nullptr, nullptr); }
+
+// Strobe128::overwrite of the low nb bytes of x, nb = strobe_step(pos, ..)
+ZKP_HD void strobe_overwrite_step(strobe_lane& L, uint64_t x, uint32_t nb) {
+  const uint32_t b = 8 * (L.pos & 7);
+  const uint64_t m = tr_bytemask(nb), w = L.S[(L.pos >> 3) * L.stride];
+  L.S[(L.pos >> 3) * L.stride] = (w & ~(m << b)) | (x & m) << b;
+  L.pos += nb;
+}
+
+// Walks seq.part(0), seq.part(1), .. up to its SP_END on a valid lane, in strobe_merlin_op's loop: consume up to the block boundary;
+// run_f at ONE place; repeat.  seq.label(k) = the words of label k (a pointer of the sequence's own: on the device it stays an LDS
+// pointer, a part carries no pointer that could be either LDS or global); seq.wide(k, w) receives the eight state words of the k-th SP_PRF64.
+template <class Seq>
+ZKP_HD void strobe_walk(strobe_lane& L, Seq& seq) {
+  strobe_part p = strobe_part_make(SP_NONE, 0, 0, 0, nullptr, nullptr);
+  uint32_t idx = 0;
+  uint64_t off = 0;
+  bool force = false, owes = false;                                // begin_op's run_f is due / a header with the C flag is being absorbed
+  for (;;) {
+    // 1. consume up to the block boundary
+    while (p.kind != SP_END && L.pos < STROBE_RATE && !force) {
+      if (p.rem == 0) {
+        if (owes) {                                                // the header is in, at a position below the boundary
+          owes = false;
+          force = L.pos != 0;
+          continue;
+        }
+        p = seq.part(idx++);
+        off = 0;
+        if (p.kind == SP_HDR) {
+          p.val = strobe_begin_op(L, p.flags);
+          p.rem = 2;
+          owes = (p.flags & STROBE_C) != 0;
+        }
+        continue;
+      }
+      if (p.kind == SP_PRF64) {                                    // pos = 0 here (see above)
+        uint64_t w[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          w[i] = L.S[i * L.stride];
+          L.S[i * L.stride] = 0;
+        }
+        L.pos = 64;
+        seq.wide((uint32_t)p.val, w);
+        p.rem = 0;
+        continue;
+      }
+      const uint32_t nb = strobe_step(L.pos, p.rem);
+      if (p.kind == SP_PRF) strobe_out{p.dst}.put(off, strobe_squeeze_step(L, nb), nb);
+      else if (p.kind == SP_AD) strobe_absorb_step(L, strobe_msg{p.src, p.len}.get(off), nb);
+      else if (p.kind == SP_KEY) strobe_overwrite_step(L, strobe_msg{p.src, p.len}.get(off), nb);
+      else if (p.kind == SP_LABEL) strobe_absorb_step(L, strobe_label_fetch(seq.label((uint32_t)p.val), (uint32_t)off), nb);
+      else strobe_absorb_step(L, p.val >> (8 * off), nb);         // SP_HDR, SP_VAL
+      off += nb;
+      p.rem -= nb;
+    }
+    // 2. the lanes that stand at the boundary (or owe begin_op's run_f) permute, here and nowhere else
+    if (L.pos == STROBE_RATE || force) {
+      strobe_run_f(L);
+      force = false;
+    }
+    // 3. repeat while parts are left
+    if (p.kind == SP_END) break;
+  }
+}
+
+// from_bytes_mod_order_wide of the 64 bytes in w[0..8) -> 32 canonical bytes at out (any alignment)
+ZKP_HD void strobe_wide_to_scalar(const uint64_t w[8], uint8_t* out) {
+  uint32_t x[16];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    x[2 * i] = (uint32_t)w[i];
+    x[2 * i + 1] = (uint32_t)(w[i] >> 32);
+  }
+  sc r;
+  sc_reduce_wide(r, x);
+  const strobe_out o{out};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) o.put(8 * i, r.v[2 * i] | (uint64_t)r.v[2 * i + 1] << 32, 8);
+}
+
+// TranscriptRng on a clone of the transcript in L (Transcript::build_rng):
+//   for k < m:  meta_ad(label); meta_ad(u32le(wlen), more); KEY(witness k)        -- rekey_with_witness_bytes(label, w_k)
+//   meta_ad("rng"); KEY(entropy[32])                                              -- finalize
+//   scalars:  count x { meta_ad(u32le(64)); PRF(64) -> mod l }  -> out [count][32]    -- Scalar::random
+//   bytes:    meta_ad(u32le(count)); PRF(count)                 -> out [count]        -- fill_bytes
+constexpr uint32_t STROBE_RNG_SCALARS = 0, STROBE_RNG_BYTES = 1;
+template <uint32_t MODE>
+struct strobe_rng_seq {
+  const uint64_t* lab;
+  uint32_t lab_len, m, wlen, count;
+  const uint8_t* wit;          // [m][wlen]
+  const uint8_t* entropy;      // [32]
+  uint8_t* out;
+  uint32_t g = 0, r = 0;       // the walk's place: frame g (witness g < m, finalize g = m, then the outputs), slot r of its five
+  // Every frame has the same five slots -- header of meta_ad, label, u32le(length), header of the operation, data -- of which finalize has
+  // no length and an output no label: an empty slot is a part of 0 bytes.  (The walker asks for the parts in order; its index is not used.)
+  ZKP_HD strobe_part part(uint32_t) {
+    const uint32_t rounds = MODE == STROBE_RNG_SCALARS ? count : 1u, fg = g, fr = r;
+    if (fg > m + rounds) return strobe_part_end();
+    r = fr == 4 ? 0 : fr + 1;
+    g = fg + (fr == 4);
+    const bool keyed = fg <= m, fin = fg == m;
+    if (fr == 0) return strobe_part_hdr(STROBE_M | STROBE_A);
+    if (fr == 1) return fg < m ? strobe_part_label(0, lab_len) : strobe_part_val(0x676e72u /* "rng" */, fin ? 3 : 0);
+    if (fr == 2) return strobe_part_val(fg < m ? wlen : MODE == STROBE_RNG_SCALARS ? 64u : count, fin ? 0 : 4);
+    if (fr == 3) return strobe_part_hdr(keyed ? STROBE_A | STROBE_C : STROBE_I | STROBE_A | STROBE_C);
+    if (keyed) return strobe_part_make(SP_KEY, 0, fin ? 32u : wlen, 0, fin ? entropy : wit + (size_t)fg * wlen, nullptr);
+    if (MODE == STROBE_RNG_SCALARS) return strobe_part_make(SP_PRF64, 0, 64, fg - m - 1, nullptr, nullptr);
+    return strobe_part_make(SP_PRF, 0, count, 0, nullptr, out);
+  }
+  ZKP_HD const uint64_t* label(uint32_t) const { return lab; }
+  ZKP_HD void wide(uint32_t k, const uint64_t w[8]) const { strobe_wide_to_scalar(w, out + 32 * (size_t)k); }
+};
+
+// TranscriptProtocol::get_challenge: challenge_bytes(label, 64) reduced mod l -> out[32]
+struct strobe_challenge_scalar_seq {
+  const uint64_t* lab;
+  uint32_t lab_len;
+  uint8_t* out;
+  ZKP_HD strobe_part part(uint32_t i) const {
+    if (i == 0) return strobe_part_hdr(STROBE_M | STROBE_A);
+    if (i == 1) return strobe_part_label(0, lab_len);
+    if (i == 2) return strobe_part_val(64, 4);
+    if (i == 3) return strobe_part_hdr(STROBE_I | STROBE_A | STROBE_C);
+    if (i == 4) return strobe_part_make(SP_PRF64, 0, 64, 0, nullptr, nullptr);
+    return strobe_part_end();
+  }
+  ZKP_HD const uint64_t* label(uint32_t) const { return lab; }
+  ZKP_HD void wide(uint32_t, const uint64_t w[8]) const { strobe_wide_to_scalar(w, out); }
+};
+
+// append_message(kind, var_label); append_message("val", point[32]) -- append_point_var ("ptvar") and append_blinding_commitment
+// ("blindcom"); the validating forms return early on the identity's encoding, which is the caller's check (strobe_is_identity)
+struct strobe_append_point_seq {
+  const uint64_t* kind;
+  const uint64_t* var;
+  uint32_t kind_len, var_len;
+  const uint8_t* point;
+  ZKP_HD strobe_part part(uint32_t i) const {
+    if (i == 0 || i == 5) return strobe_part_hdr(STROBE_M | STROBE_A);
+    if (i == 1) return strobe_part_label(0, kind_len);
+    if (i == 2) return strobe_part_val(var_len, 4);
+    if (i == 3 || i == 8) return strobe_part_hdr(STROBE_A);
+    if (i == 4) return strobe_part_label(1, var_len);
+    if (i == 6) return strobe_part_val(0x6c6176u /* "val" */, 3);
+    if (i == 7) return strobe_part_val(32, 4);
+    if (i == 9) return strobe_part_make(SP_AD, 0, 32, 0, point, nullptr);
+    return strobe_part_end();
+  }
+  ZKP_HD const uint64_t* label(uint32_t k) const { return k ? var : kind; }
+  ZKP_HD void wide(uint32_t, const uint64_t*) const {}
+};
+// the 32 bytes at p (any alignment) are all zero: the encoding of the identity (public data: the reference branches on it too)
+ZKP_HD bool strobe_is_identity(const uint8_t* p) {
+  const strobe_msg m{p, 32};
+  return (m.get(0) | m.get(8) | m.get(16) | m.get(24)) == 0;
 }
 
 }  // namespace zkp

@@ -471,4 +471,104 @@ k_strobe_challenge(uint32_t N, uint8_t* __restrict__ ts, const strobe_label labe
   }
 }
 
+// ---- the witness RNG, get_challenge and the point appends of TranscriptProtocol: strobe_walk, one lane per transcript --------------------
+// The same shape as the two kernels above: a wavefront per workgroup, the state an LDS column per lane (12.5 KB, plus 256 bytes per
+// label), grid-stride.  The walker keeps the permutation at one place of its loop; a part's kind, length and position decide every branch
+// and every address, witness, entropy and state bytes none.
+
+// An argument that only addresses lane j's rows is live across the walk and not used in it.  As a uniform value it would sit in scalar
+// registers, of which the walk leaves too few (Keccak's round constants take 48): such arguments are parked in vector registers, where
+// the address arithmetic happens anyway.
+template <class T>
+__device__ __forceinline__ T strobe_park(T x) {
+  asm volatile("" : "+v"(x));
+  return x;
+}
+
+// N x TranscriptRng (strobe_rng_seq) on clones: ts is only read.  witnesses [N][m][wlen], entropy [N][32], both of any alignment;
+// out [N][count][32] canonical scalars (MODE STROBE_RNG_SCALARS) or [N][count] bytes (STROBE_RNG_BYTES).  A blob whose position byte is
+// >= 166 gives zeros.  Blobs 16-byte aligned.
+template <uint32_t MODE>
+__global__ void __launch_bounds__(STROBE_BLOCK)
+k_strobe_witness_rng(uint32_t N, const uint8_t* __restrict__ ts, const strobe_label label, uint32_t m, uint32_t wlen,
+                     const uint8_t* __restrict__ witnesses, const uint8_t* __restrict__ entropy, uint32_t count, uint8_t* __restrict__ out) {
+  __shared__ uint64_t S[25 * STROBE_BLOCK];
+  __shared__ uint64_t lab[STROBE_LABEL_WORDS];
+  strobe_label_to_lds(lab, label);
+  const size_t row = strobe_park(MODE == STROBE_RNG_SCALARS ? 32 * (size_t)count : (size_t)count), wrow = strobe_park((size_t)m * wlen);
+  const uint32_t n = strobe_park(N), step = strobe_park(gridDim.x * STROBE_BLOCK);
+  const uint32_t lab_len = strobe_park(label.len);     // (the walk compares these with per-lane counters: vector operations either way)
+  m = strobe_park(m);
+  wlen = strobe_park(wlen);
+  count = strobe_park(count);
+  ts = strobe_park(ts);
+  witnesses = strobe_park(witnesses);
+  entropy = strobe_park(entropy);
+  out = strobe_park(out);
+  for (uint32_t j = blockIdx.x * STROBE_BLOCK + threadIdx.x; j < n; j += step) {
+    strobe_lane L{S + threadIdx.x, STROBE_BLOCK, 0, 0, 0};
+    uint8_t* o = out + row * j;
+    strobe_load(L, reinterpret_cast<const uint64_t*>(ts + 208 * (size_t)j));
+    if (strobe_valid(L)) {
+      strobe_rng_seq<MODE> seq{lab, lab_len, m, wlen, count, witnesses + wrow * j, entropy + 32 * (size_t)j, o};
+      strobe_walk(L, seq);
+    } else {
+      for (size_t i = 0; i < row; ++i) o[i] = 0;
+    }
+  }
+}
+
+// N x get_challenge(label) -> out [N][32] (any alignment), the transcripts advanced in place.  A blob whose position byte is >= 166 stays
+// as it is and its output is zeros.
+__global__ void __launch_bounds__(STROBE_BLOCK)
+k_strobe_challenge_scalars(uint32_t N, uint8_t* __restrict__ ts, const strobe_label label, uint8_t* __restrict__ out) {
+  __shared__ uint64_t S[25 * STROBE_BLOCK];
+  __shared__ uint64_t lab[STROBE_LABEL_WORDS];
+  strobe_label_to_lds(lab, label);
+  for (uint32_t j = blockIdx.x * STROBE_BLOCK + threadIdx.x; j < N; j += gridDim.x * STROBE_BLOCK) {
+    strobe_lane L{S + threadIdx.x, STROBE_BLOCK, 0, 0, 0};
+    uint64_t* blob = reinterpret_cast<uint64_t*>(ts + 208 * (size_t)j);
+    uint8_t* o = out + 32 * (size_t)j;
+    strobe_load(L, blob);
+    if (strobe_valid(L)) {
+      strobe_challenge_scalar_seq seq{lab, label.len, o};
+      strobe_walk(L, seq);
+      strobe_store(L, blob, strobe_tail(L));
+    } else {
+      for (uint32_t i = 0; i < 32; ++i) o[i] = 0;
+    }
+  }
+}
+
+// N x { append_message(kind, var); append_message("val", points[j]) }, the transcripts advanced in place.  validate: a row of 32 zero
+// bytes gets status 1 and its blob stays as it was.  status (NULL, or [N]) gets 0 for every other row; a blob whose position byte is
+// >= 166 stays as it is with status 0.  points [N][32] of any alignment.
+__global__ void __launch_bounds__(STROBE_BLOCK)
+k_strobe_append_points(uint32_t N, uint8_t* __restrict__ ts, const strobe_label kind, const strobe_label var, const uint8_t* __restrict__ points,
+                       uint32_t validate, uint8_t* __restrict__ status) {
+  __shared__ uint64_t S[25 * STROBE_BLOCK];
+  __shared__ uint64_t lab[2][STROBE_LABEL_WORDS];
+  strobe_label_to_lds(lab[0], kind);
+  strobe_label_to_lds(lab[1], var);
+  const uint32_t n = strobe_park(N), step = strobe_park(gridDim.x * STROBE_BLOCK);
+  ts = strobe_park(ts);
+  points = strobe_park(points);
+  status = strobe_park(status);
+  validate = strobe_park(validate);
+  for (uint32_t j = blockIdx.x * STROBE_BLOCK + threadIdx.x; j < n; j += step) {
+    strobe_lane L{S + threadIdx.x, STROBE_BLOCK, 0, 0, 0};
+    uint64_t* blob = reinterpret_cast<uint64_t*>(ts + 208 * (size_t)j);
+    const uint8_t* pt = points + 32 * (size_t)j;
+    const bool rejected = validate && strobe_is_identity(pt);
+    strobe_load(L, blob);
+    const bool valid = strobe_valid(L);
+    if (valid && !rejected) {
+      strobe_append_point_seq seq{lab[0], lab[1], kind.len, var.len, pt};
+      strobe_walk(L, seq);
+      strobe_store(L, blob, strobe_tail(L));
+    }
+    if (status) status[j] = valid && rejected ? 1 : 0;
+  }
+}
+
 }  // namespace zkp

@@ -2770,7 +2770,35 @@ int launch_strobe_challenge(zkp_ctx* c, uint32_t N, uint8_t* d_ts, const strobe_
   HIP_TRY(hipGetLastError());
   return ZKP_OK;
 }
-// what the four calls check first: the context, the label (packed into `label`), then N.  *done = nothing is left to do (N = 0)
+int launch_strobe_witness_rng(zkp_ctx* c, uint32_t N, const uint8_t* d_ts, const strobe_label& label, uint32_t m, uint32_t wlen, const uint8_t* d_wit,
+                              const uint8_t* d_entropy, uint32_t mode, uint32_t count, uint8_t* d_out) {
+  if (mode == STROBE_RNG_SCALARS)
+    hipLaunchKernelGGL(k_strobe_witness_rng<STROBE_RNG_SCALARS>, dim3(strobe_blocks(N)), dim3(STROBE_BLOCK), 0, c->stream, N, d_ts, label, m, wlen, d_wit, d_entropy,
+                       count, d_out);
+  else
+    hipLaunchKernelGGL(k_strobe_witness_rng<STROBE_RNG_BYTES>, dim3(strobe_blocks(N)), dim3(STROBE_BLOCK), 0, c->stream, N, d_ts, label, m, wlen, d_wit, d_entropy,
+                       count, d_out);
+  prof_note(c, ZKP_K_TRANSCRIPT, "zkp::k_strobe_witness_rng");
+  prof_mark(c, ZKP_K_TRANSCRIPT);
+  HIP_TRY(hipGetLastError());
+  return ZKP_OK;
+}
+int launch_strobe_challenge_scalars(zkp_ctx* c, uint32_t N, uint8_t* d_ts, const strobe_label& label, uint8_t* d_out) {
+  hipLaunchKernelGGL(k_strobe_challenge_scalars, dim3(strobe_blocks(N)), dim3(STROBE_BLOCK), 0, c->stream, N, d_ts, label, d_out);
+  prof_note(c, ZKP_K_TRANSCRIPT, "zkp::k_strobe_challenge_scalars");
+  prof_mark(c, ZKP_K_TRANSCRIPT);
+  HIP_TRY(hipGetLastError());
+  return ZKP_OK;
+}
+int launch_strobe_append_points(zkp_ctx* c, uint32_t N, uint8_t* d_ts, const strobe_label& kind, const strobe_label& var, const uint8_t* d_points,
+                                uint32_t validate, uint8_t* d_status) {
+  hipLaunchKernelGGL(k_strobe_append_points, dim3(strobe_blocks(N)), dim3(STROBE_BLOCK), 0, c->stream, N, d_ts, kind, var, d_points, validate, d_status);
+  prof_note(c, ZKP_K_TRANSCRIPT, "zkp::k_strobe_append_points");
+  prof_mark(c, ZKP_K_TRANSCRIPT);
+  HIP_TRY(hipGetLastError());
+  return ZKP_OK;
+}
+// what the calls of section 7 check first: the context, the label (packed into `label`), then N.  *done = nothing is left to do (N = 0)
 int strobe_call_check(zkp_ctx* c, uint32_t N, const char* label_text, strobe_label& label, bool* done) {
   *done = false;
   if (!c) return fail(ZKP_ERR_ARG, "ctx is NULL");
@@ -4386,6 +4414,155 @@ int zkp_transcripts_challenge_bytes(zkp_ctx* c, uint32_t N, uint8_t* ts, const c
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(ts, base + o_ts, 208 * (size_t)N, hipMemcpyDeviceToHost, c->stream));
   if (len) HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)N * len, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return ZKP_OK;
+}
+
+// the witness RNG's arguments beyond strobe_call_check's; out_bytes = the size of the whole output
+static int witness_rng_check(uint32_t N, uint32_t m, uint32_t wlen, const void* ts, const void* wit, const void* entropy, int mode, uint32_t count,
+                             const void* out, size_t* out_bytes) {
+  if (mode != ZKP_RNG_SCALARS && mode != ZKP_RNG_BYTES) return fail(ZKP_ERR_ARG, "mode is neither ZKP_RNG_SCALARS nor ZKP_RNG_BYTES");
+  if (mode == ZKP_RNG_SCALARS && count > 0x03ffffffu) return fail(ZKP_ERR_ARG, "count too large");
+  *out_bytes = (size_t)N * count * (mode == ZKP_RNG_SCALARS ? 32 : 1);
+  if (!ts || !entropy || (m && wlen && !wit) || (*out_bytes && !out)) return fail(ZKP_ERR_ARG, "NULL pointer");
+  return ZKP_OK;
+}
+
+int zkp_transcripts_witness_rng_dev(zkp_ctx* c, uint32_t N, const uint8_t* d_ts, const char* label, uint32_t m, uint32_t wlen, const uint8_t* d_witnesses,
+                                    const uint8_t* d_entropy, int mode, uint32_t count, uint8_t* d_out) {
+  strobe_label lab;
+  bool done;
+  int rc = strobe_call_check(c, N, label, lab, &done);
+  if (rc || done) return rc;
+  size_t out_bytes;
+  rc = witness_rng_check(N, m, wlen, d_ts, d_witnesses, d_entropy, mode, count, d_out, &out_bytes);
+  if (rc) return rc;
+  if (!aligned16(d_ts)) return fail(ZKP_ERR_ARG, "transcripts must be 16-byte aligned");
+  HIP_TRY(hipSetDevice(c->device));
+  prof_begin(c);
+  return launch_strobe_witness_rng(c, N, d_ts, lab, m, wlen, d_witnesses, d_entropy, (uint32_t)mode, count, d_out);
+}
+
+int zkp_transcripts_witness_rng(zkp_ctx* c, uint32_t N, const uint8_t* ts, const char* label, uint32_t m, uint32_t wlen, const uint8_t* witnesses,
+                                const uint8_t* entropy, int mode, uint32_t count, uint8_t* out) {
+  strobe_label lab;
+  bool done;
+  int rc = strobe_call_check(c, N, label, lab, &done);
+  if (rc || done) return rc;
+  size_t out_bytes;
+  rc = witness_rng_check(N, m, wlen, ts, witnesses, entropy, mode, count, out, &out_bytes);
+  if (rc) return rc;
+  if (!strobe_positions_ok(ts, N)) return fail(ZKP_ERR_ARG, "a transcript's position byte is 166 or more");
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t wit_bytes = (size_t)N * m * wlen;
+  carve cv;
+  const size_t o_ts = cv.take(208 * (size_t)N);
+  const size_t o_secret = cv.take(32 * (size_t)N + wit_bytes);       // entropy, then the witnesses: one region, wiped below
+  const size_t o_out = cv.take(out_bytes);
+  rc = ensure_ws(c, cv.off);
+  if (rc) return rc;
+  uint8_t* base = static_cast<uint8_t*>(c->ws);
+  uint8_t* d_entropy = base + o_secret;
+  uint8_t* d_wit = d_entropy + 32 * (size_t)N;
+  // from the first secret byte on the device, every way out passes the wipe of the staging region
+  hipError_t err = hipMemcpyAsync(base + o_ts, ts, 208 * (size_t)N, hipMemcpyHostToDevice, c->stream);
+  if (err == hipSuccess) err = hipMemcpyAsync(d_entropy, entropy, 32 * (size_t)N, hipMemcpyHostToDevice, c->stream);
+  if (err == hipSuccess && wit_bytes) err = hipMemcpyAsync(d_wit, witnesses, wit_bytes, hipMemcpyHostToDevice, c->stream);
+  if (err == hipSuccess) {
+    prof_begin(c);
+    rc = launch_strobe_witness_rng(c, N, base + o_ts, lab, m, wlen, d_wit, d_entropy, (uint32_t)mode, count, base + o_out);
+  }
+  const hipError_t wiped = hipMemsetAsync(d_entropy, 0, 32 * (size_t)N + wit_bytes, c->stream);
+  if (err == hipSuccess && rc == ZKP_OK && out_bytes) err = hipMemcpyAsync(out, base + o_out, out_bytes, hipMemcpyDeviceToHost, c->stream);
+  const hipError_t synced = hipStreamSynchronize(c->stream);
+  if (rc) return rc;
+  HIP_TRY(err);
+  HIP_TRY(wiped);
+  HIP_TRY(synced);
+  return ZKP_OK;
+}
+
+int zkp_transcripts_challenge_scalars_dev(zkp_ctx* c, uint32_t N, uint8_t* d_ts, const char* label, uint8_t* d_out) {
+  strobe_label lab;
+  bool done;
+  const int rc = strobe_call_check(c, N, label, lab, &done);
+  if (rc || done) return rc;
+  if (!d_ts || !d_out) return fail(ZKP_ERR_ARG, "NULL device pointer");
+  if (!aligned16(d_ts)) return fail(ZKP_ERR_ARG, "transcripts must be 16-byte aligned");
+  HIP_TRY(hipSetDevice(c->device));
+  prof_begin(c);
+  return launch_strobe_challenge_scalars(c, N, d_ts, lab, d_out);
+}
+
+int zkp_transcripts_challenge_scalars(zkp_ctx* c, uint32_t N, uint8_t* ts, const char* label, uint8_t* out) {
+  strobe_label lab;
+  bool done;
+  int rc = strobe_call_check(c, N, label, lab, &done);
+  if (rc || done) return rc;
+  if (!ts || !out) return fail(ZKP_ERR_ARG, "NULL pointer");
+  if (!strobe_positions_ok(ts, N)) return fail(ZKP_ERR_ARG, "a transcript's position byte is 166 or more");
+  HIP_TRY(hipSetDevice(c->device));
+  carve cv;
+  const size_t o_ts = cv.take(208 * (size_t)N);
+  const size_t o_out = cv.take(32 * (size_t)N);
+  rc = ensure_ws(c, cv.off);
+  if (rc) return rc;
+  uint8_t* base = static_cast<uint8_t*>(c->ws);
+  HIP_TRY(hipMemcpyAsync(base + o_ts, ts, 208 * (size_t)N, hipMemcpyHostToDevice, c->stream));
+  prof_begin(c);
+  rc = launch_strobe_challenge_scalars(c, N, base + o_ts, lab, base + o_out);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(ts, base + o_ts, 208 * (size_t)N, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(out, base + o_out, 32 * (size_t)N, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return ZKP_OK;
+}
+
+// the two labels of the point appends, checked as strobe_call_check checks its one
+static int append_points_check(zkp_ctx* c, uint32_t N, const char* kind, const char* var_label, strobe_label& k, strobe_label& v, bool* done) {
+  const int rc = strobe_call_check(c, N, kind, k, done);
+  if (rc) return rc;
+  if (!var_label) return fail(ZKP_ERR_ARG, "label is NULL");
+  if (!strobe_label_pack(v, var_label, strlen(var_label))) return fail(ZKP_ERR_ARG, "label longer than 248 bytes");
+  return ZKP_OK;
+}
+
+int zkp_transcripts_append_points_dev(zkp_ctx* c, uint32_t N, uint8_t* d_ts, const char* kind, const char* var_label, const uint8_t* d_points, int validate,
+                                      uint8_t* d_status) {
+  strobe_label k, v;
+  bool done;
+  const int rc = append_points_check(c, N, kind, var_label, k, v, &done);
+  if (rc || done) return rc;
+  if (!d_ts || !d_points || (validate && !d_status)) return fail(ZKP_ERR_ARG, "NULL device pointer");
+  if (!aligned16(d_ts)) return fail(ZKP_ERR_ARG, "transcripts must be 16-byte aligned");
+  HIP_TRY(hipSetDevice(c->device));
+  prof_begin(c);
+  return launch_strobe_append_points(c, N, d_ts, k, v, d_points, validate ? 1u : 0u, d_status);
+}
+
+int zkp_transcripts_append_points(zkp_ctx* c, uint32_t N, uint8_t* ts, const char* kind, const char* var_label, const uint8_t* points, int validate,
+                                  uint8_t* status) {
+  strobe_label k, v;
+  bool done;
+  int rc = append_points_check(c, N, kind, var_label, k, v, &done);
+  if (rc || done) return rc;
+  if (!ts || !points || (validate && !status)) return fail(ZKP_ERR_ARG, "NULL pointer");
+  if (!strobe_positions_ok(ts, N)) return fail(ZKP_ERR_ARG, "a transcript's position byte is 166 or more");
+  HIP_TRY(hipSetDevice(c->device));
+  carve cv;
+  const size_t o_ts = cv.take(208 * (size_t)N);
+  const size_t o_pts = cv.take(32 * (size_t)N);
+  const size_t o_st = cv.take(status ? (size_t)N : 0);
+  rc = ensure_ws(c, cv.off);
+  if (rc) return rc;
+  uint8_t* base = static_cast<uint8_t*>(c->ws);
+  HIP_TRY(hipMemcpyAsync(base + o_ts, ts, 208 * (size_t)N, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(base + o_pts, points, 32 * (size_t)N, hipMemcpyHostToDevice, c->stream));
+  prof_begin(c);
+  rc = launch_strobe_append_points(c, N, base + o_ts, k, v, base + o_pts, validate ? 1u : 0u, status ? base + o_st : nullptr);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(ts, base + o_ts, 208 * (size_t)N, hipMemcpyDeviceToHost, c->stream));
+  if (status) HIP_TRY(hipMemcpyAsync(status, base + o_st, (size_t)N, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return ZKP_OK;
 }

@@ -24,6 +24,8 @@ ZKP_OPT_WS_LIMIT_BYTES, ZKP_OPT_JOB_DEFER_D2H, ZKP_OPT_SYNC_SCHEDULE, ZKP_OPT_TR
 
 ZKP_VARTIME = 0
 ZKP_CT = 1
+ZKP_RNG_SCALARS = 0      # zkp_transcripts_witness_rng: count x Scalar::random
+ZKP_RNG_BYTES = 1        # ... or one fill_bytes(count)
 ZKP_PT_ADD, ZKP_PT_SUB = 0, 1               # zkp_add_points' op
 ZKP_SC_SUM, ZKP_SC_PRODUCT, ZKP_SC_DOT = 0, 1, 2     # zkp_sc_reduce's op
 ZKP_SCAN_INCLUSIVE, ZKP_SCAN_EXCLUSIVE = 0, 1        # zkp_sc_scan's and zkp_scan_points' mode
@@ -323,6 +325,40 @@ class Engine:
         out = np.zeros((len(ts), n_bytes), np.uint8)
         _check(self._lib.zkp_transcripts_challenge_bytes(self._h, len(ts), _ptr(ts), bytes(label), n_bytes, _ptr(out)), "zkp_transcripts_challenge_bytes")
         return out
+
+    def transcripts_witness_rng(self, transcripts, label: bytes, witnesses, entropy, mode: int, count: int) -> np.ndarray:
+        """N x TranscriptRng on the GPU: rekey with witnesses[j][k] (uint8 [N][m][wlen]) under label, finalize with entropy[j] (uint8 [N][32]),
+        then count scalars (mode ZKP_RNG_SCALARS -> uint8 [N][count][32]) or one fill_bytes(count) (ZKP_RNG_BYTES -> uint8 [N][count]).  The
+        transcripts (C-contiguous uint8 [N][208]) are read, never written."""
+        ts = _blobs(transcripts, len(transcripts))
+        n = len(ts)
+        wit = np.ascontiguousarray(witnesses, np.uint8)
+        ent = np.ascontiguousarray(entropy, np.uint8)
+        if wit.ndim != 3 or len(wit) != n or ent.shape != (n, 32):
+            raise ValueError("witnesses must be uint8 [N][m][wlen] and entropy uint8 [N][32]")
+        out = np.zeros((n, count, 32) if mode == ZKP_RNG_SCALARS else (n, count), np.uint8)
+        _check(self._lib.zkp_transcripts_witness_rng(self._h, n, _ptr(ts), bytes(label), wit.shape[1], wit.shape[2], _ptr(wit), _ptr(ent), mode, count, _ptr(out)),
+               "zkp_transcripts_witness_rng")
+        return out
+
+    def transcripts_challenge_scalars(self, transcripts, label: bytes) -> np.ndarray:
+        """N x get_challenge(label) on the GPU -> canonical scalars uint8 [N][32]; transcripts (C-contiguous uint8 [N][208]) advance in place"""
+        ts = _blobs(transcripts, len(transcripts))
+        out = np.zeros((len(ts), 32), np.uint8)
+        _check(self._lib.zkp_transcripts_challenge_scalars(self._h, len(ts), _ptr(ts), bytes(label), _ptr(out)), "zkp_transcripts_challenge_scalars")
+        return out
+
+    def transcripts_append_points(self, transcripts, kind: bytes, var_label: bytes, points, validate: bool = False) -> np.ndarray:
+        """N x { append_message(kind, var_label); append_message(b"val", points[j]) } on the GPU, the transcripts advanced in place -> status
+        uint8 [N]: 1 = validate and row j is the identity's encoding (32 zero bytes), whose transcript stays as it was"""
+        ts = _blobs(transcripts, len(transcripts))
+        pts = np.ascontiguousarray(points, np.uint8)
+        if pts.shape != (len(ts), 32):
+            raise ValueError("points must be uint8 [N][32]")
+        status = np.zeros(len(ts), np.uint8)
+        _check(self._lib.zkp_transcripts_append_points(self._h, len(ts), _ptr(ts), bytes(kind), bytes(var_label), _ptr(pts), int(bool(validate)), _ptr(status)),
+               "zkp_transcripts_append_points")
+        return status
 
     # ---- scalars mod l, batched (include/zkp_mi355x.h section 6): [n][32] canonical scalars out ----
     def scalar_invert(self, s) -> np.ndarray:
@@ -629,6 +665,22 @@ class Engine:
     def transcripts_challenge_bytes_dev(self, n, d_ts, label: bytes, n_bytes, d_out) -> None:
         """zkp_transcripts_challenge_bytes_dev: d_ts [n][208] (16-byte aligned) advanced in place, d_out [n][n_bytes]"""
         _check(self._lib.zkp_transcripts_challenge_bytes_dev(self._h, n, d_ts, bytes(label), n_bytes, d_out), "zkp_transcripts_challenge_bytes_dev")
+
+    def transcripts_witness_rng_dev(self, n, d_ts, label: bytes, m, wlen, d_witnesses, d_entropy, mode, count, d_out) -> None:
+        """zkp_transcripts_witness_rng_dev: d_ts [n][208] (16-byte aligned) is only read; d_witnesses [n][m][wlen], d_entropy [n][32];
+        d_out [n][count][32] (ZKP_RNG_SCALARS) or [n][count] (ZKP_RNG_BYTES)"""
+        _check(self._lib.zkp_transcripts_witness_rng_dev(self._h, n, d_ts, bytes(label), m, wlen, d_witnesses, d_entropy, mode, count, d_out),
+               "zkp_transcripts_witness_rng_dev")
+
+    def transcripts_challenge_scalars_dev(self, n, d_ts, label: bytes, d_out) -> None:
+        """zkp_transcripts_challenge_scalars_dev: d_ts [n][208] (16-byte aligned) advanced in place, d_out [n][32]"""
+        _check(self._lib.zkp_transcripts_challenge_scalars_dev(self._h, n, d_ts, bytes(label), d_out), "zkp_transcripts_challenge_scalars_dev")
+
+    def transcripts_append_points_dev(self, n, d_ts, kind: bytes, var_label: bytes, d_points, validate, d_status) -> None:
+        """zkp_transcripts_append_points_dev: d_ts [n][208] (16-byte aligned) advanced in place, d_points [n][32], d_status [n] (may be
+        None / 0 when validate is false)"""
+        _check(self._lib.zkp_transcripts_append_points_dev(self._h, n, d_ts, bytes(kind), bytes(var_label), d_points, int(bool(validate)), d_status),
+               "zkp_transcripts_append_points_dev")
 
     # ---- fused statement flows on device-resident buffers (include/zkp_mi355x.h section 2c) -------------
     def fused_prove_dev(self, fst: "FusedStatement", n, strobe_pos, d_ts, d_secrets, d_table, d_entropy, d_chal, d_resp, d_coms, d_status) -> None:

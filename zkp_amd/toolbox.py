@@ -488,6 +488,120 @@ def challenge_bytes(eng, transcripts, label: bytes, n: int, threads: int = 0) ->
     return out
 
 
+# ---- the rest of TranscriptProtocol and the prover's TranscriptRng, batched (include/zkp_toolbox.h): eng = None is the host threads ----
+RNG_SCALARS, RNG_BYTES = 0, 1        # ZKP_RNG_SCALARS, ZKP_RNG_BYTES
+
+
+def _blob_array(ts, what: str) -> np.ndarray:
+    if not (isinstance(ts, np.ndarray) and ts.dtype == np.uint8 and ts.ndim == 2 and ts.shape[1] == TRANSCRIPT_BYTES and ts.flags["C_CONTIGUOUS"]):
+        raise ValueError("%s: transcripts must be a C-contiguous uint8 array of shape [N][%d]" % (what, TRANSCRIPT_BYTES))
+    return ts
+
+
+def _witness_rng(eng, transcripts, witnesses, mode: int, count: int, entropy, label: bytes, threads: int) -> np.ndarray:
+    ts = _blob_array(transcripts, "witness_rng")
+    n = len(ts)
+    wit = np.ascontiguousarray(witnesses, np.uint8)
+    if wit.ndim != 3 or len(wit) != n:
+        raise ValueError("witness_rng: witnesses must be uint8 [N][m][wlen]")
+    ent = None if entropy is None else np.ascontiguousarray(entropy, np.uint8)
+    if ent is not None and ent.shape != (n, 32):
+        raise ValueError("witness_rng: entropy must be uint8 [N][32] (or None: drawn from the operating system)")
+    if not 0 <= count <= 0xffffffff:
+        raise ValueError("witness_rng: count must fit 32 bits")
+    out = np.zeros((n, count, 32) if mode == RNG_SCALARS else (n, count), np.uint8)
+    rc = lib().zkp_transcripts_witness_rng_batch(None if eng is None else eng._h, _p(ts), n, bytes(label), wit.shape[1], wit.shape[2], _p(wit), _p(ent), mode,
+                                                 count, threads, _p(out))
+    _raise(rc, "zkp_transcripts_witness_rng_batch")
+    return out
+
+
+def witness_rng_scalars(eng, transcripts, witnesses, count: int, entropy=None, label: bytes = b"", threads: int = 0) -> np.ndarray:
+    """The prover's synthetic nonces (reference src/toolbox/prover.rs:78-89) for every transcript: build_rng(), rekey_with_witness_bytes(label,
+    witnesses[j][k]) for every k, finalize with entropy[j] (None: 32 bytes per transcript from the operating system), then count x
+    Scalar::random -> canonical scalars uint8 [N][count][32].  transcripts: C-contiguous uint8 [N][208], read and never changed (build_rng
+    clones); witnesses: uint8 [N][m][wlen].  eng = None (or a HostEngine) runs on the host threads; with an Engine, batches of at least
+    get_witness_rng_min_batch() transcripts run on the GPU, one lane per transcript.  Same bytes either way."""
+    return _witness_rng(eng, transcripts, witnesses, RNG_SCALARS, count, entropy, label, threads)
+
+
+def witness_rng_bytes(eng, transcripts, witnesses, count: int, entropy=None, label: bytes = b"", threads: int = 0) -> np.ndarray:
+    """witness_rng_scalars with one fill_bytes(count) in place of the scalars -> uint8 [N][count]"""
+    return _witness_rng(eng, transcripts, witnesses, RNG_BYTES, count, entropy, label, threads)
+
+
+def challenge_scalars(eng, transcripts, label: bytes, threads: int = 0) -> np.ndarray:
+    """TranscriptProtocol::get_challenge(label) of every transcript: challenge_bytes(label, 64) reduced mod l -> canonical scalars uint8
+    [N][32]; transcripts (C-contiguous uint8 [N][208]) advance in place.  Routed by get_challenge_scalars_min_batch()."""
+    ts = _blob_array(transcripts, "challenge_scalars")
+    out = np.zeros((len(ts), 32), np.uint8)
+    rc = lib().zkp_transcripts_challenge_scalars_batch(None if eng is None else eng._h, _p(ts), len(ts), bytes(label), threads, _p(out))
+    _raise(rc, "zkp_transcripts_challenge_scalars_batch")
+    return out
+
+
+def _append_points(eng, transcripts, kind: bytes, label: bytes, points, validate: bool, threads: int) -> np.ndarray:
+    ts = _blob_array(transcripts, "append_points")
+    pts = np.ascontiguousarray(points, np.uint8)
+    if pts.shape != (len(ts), 32):
+        raise ValueError("append_points: points must be uint8 [N][32]")
+    status = np.zeros(len(ts), np.uint8)
+    rc = lib().zkp_transcripts_append_points_batch(None if eng is None else eng._h, _p(ts), len(ts), kind, bytes(label), _p(pts), int(bool(validate)), threads,
+                                                   _p(status))
+    _raise(rc, "zkp_transcripts_append_points_batch")
+    return status
+
+
+def append_point_vars(eng, transcripts, label: bytes, points, validate: bool = False, threads: int = 0) -> np.ndarray:
+    """TranscriptProtocol::append_point_var(label, points[j]) on every transcript (C-contiguous uint8 [N][208], advanced in place); validate:
+    validate_and_append_point_var, which refuses the identity's encoding.  -> status uint8 [N]: 1 = refused, that transcript is unchanged.
+    Routed by get_append_points_min_batch()."""
+    return _append_points(eng, transcripts, b"ptvar", label, points, validate, threads)
+
+
+def append_blinding_commitments(eng, transcripts, label: bytes, points, validate: bool = False, threads: int = 0) -> np.ndarray:
+    """TranscriptProtocol::append_blinding_commitment / validate_and_append_blinding_commitment, as append_point_vars"""
+    return _append_points(eng, transcripts, b"blindcom", label, points, validate, threads)
+
+
+def domain_sep(ts, label: bytes, threads: int = 0, eng=None) -> np.ndarray:
+    """TranscriptProtocol::domain_sep(label) on every transcript of ts (uint8 [N][208], advanced in place)"""
+    append_messages(ts, b"dom-sep", [b"schnorrzkp/1.0/ristretto255"] * len(ts), threads=threads, eng=eng)
+    return append_messages(ts, b"dom-sep", [bytes(label)] * len(ts), threads=threads, eng=eng)
+
+
+def append_scalar_vars(ts, label: bytes, threads: int = 0, eng=None) -> np.ndarray:
+    """TranscriptProtocol::append_scalar_var(label) on every transcript of ts (uint8 [N][208], advanced in place)"""
+    return append_messages(ts, b"scvar", [bytes(label)] * len(ts), threads=threads, eng=eng)
+
+
+def set_witness_rng_min_batch(n: int) -> None:
+    """witness_rng_* calls on an engine with at least n transcripts run on the device (0: always; 2**32 - 1: never)"""
+    lib().zkp_toolbox_set_witness_rng_min_batch(n)
+
+
+def get_witness_rng_min_batch() -> int:
+    return int(lib().zkp_toolbox_get_witness_rng_min_batch())
+
+
+def set_challenge_scalars_min_batch(n: int) -> None:
+    """challenge_scalars calls on an engine with at least n transcripts run on the device (0: always; 2**32 - 1: never)"""
+    lib().zkp_toolbox_set_challenge_scalars_min_batch(n)
+
+
+def get_challenge_scalars_min_batch() -> int:
+    return int(lib().zkp_toolbox_get_challenge_scalars_min_batch())
+
+
+def set_append_points_min_batch(n: int) -> None:
+    """append_point_vars / append_blinding_commitments calls on an engine with at least n transcripts run on the device (0: always; 2**32 - 1: never)"""
+    lib().zkp_toolbox_set_append_points_min_batch(n)
+
+
+def get_append_points_min_batch() -> int:
+    return int(lib().zkp_toolbox_get_append_points_min_batch())
+
+
 def hash_from_bytes_sha512(eng, messages, threads: int = 0) -> np.ndarray:
     """RistrettoPoint::hash_from_bytes::<Sha512> (reference tests/zkp.rs:35) of every message (a list of byte strings) -> encodings
     [n][32].  eng = None (or a HostEngine) hashes and maps on the host threads; with an Engine, calls above get_host_max_terms()
