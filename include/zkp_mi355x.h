@@ -740,6 +740,59 @@ uint32_t zkp_dlog_group(void);
 uint32_t zkp_dlog_chunk(void);
 uint32_t zkp_dlog_slice_chunks(uint64_t n);
 
+/* (10, continued) ... to ANY base, and over SIGNED ranges: the amount sits on a generator G of the caller's (a second generator from
+ *     hash-to-group, a per-election or per-asset generator, the value generator of a Pedersen scheme whose B carries the blinding), and net
+ *     balances, score differences and tallies with retractions are signed.  The search is the one above -- the same kernels, which take their
+ *     fixed-base table and their walk points as arguments -- over a SLOT: a table the context owns for one base.  ONE base per call; per-point
+ *     bases are out of scope.
+ *     zkp_ctx_prepare_dlog_point: builds slot `slot` (below ZKP_DLOG_SLOTS) for the base with encoding `base`: G's fixed-base table in the layout of
+ *       the context's table of B ("k_decode_affine", "k_hot_bases", "k_hot_rows" over the one encoding), the rows encode(i G), i < 2^baby_bits
+ *       (baby_bits 4 .. 22), their probe slots and the walk points (1/2) G and (2^baby_bits / 2) G, as zkp_ctx_prepare_dlog builds them for B.  The
+ *       slots take none of the 64 slots of zkp_ctx_prepare_fixed_points, touch neither the context's own dlog table nor its table of B, and are
+ *       freed with the context.  Synchronous; ZKP_ERR_ARG inside a capture.  The same base and size again is a no-op; anything else replaces the
+ *       slot, and graphs recorded over a replaced or released slot are refused by zkp_graph_launch.  ZKP_ERR_ARG with the slot left as it was: a
+ *       base that does not decode, the identity (32 zero bytes: every point is a multiple of any other element of the group, but of the
+ *       identity only itself), slot >= ZKP_DLOG_SLOTS, baby_bits outside 4 .. 22, a NULL pointer.  A failed allocation is ZKP_ERR_OOM and leaves
+ *       the slot empty.
+ *     zkp_ctx_release_dlog_point: frees the slot (an empty one: no-op).  Synchronous; ZKP_ERR_ARG inside a capture.
+ *     zkp_dlog_point_baby_bits: the slot's size, 0 = empty (or no such slot, or a NULL context).  zkp_dlog_point_base: the encoding the slot was
+ *       built from (ZKP_ERR_ARG for an empty slot).  zkp_dlog_point_find: the slot that holds this base, or -1.  zkp_dlog_point_last_use: the
+ *       context counts prepares and searches over its slots; this is the count at the slot's last one, 0 for an empty slot -- the slot with the
+ *       smallest is the least recently used (what zkp_point_dlog_batch of zkp_toolbox.h replaces when no slot is free).
+ *     zkp_dlog_point[_dev]: zkp_dlog_base[_dev] with the slot's G for B: the same meaning of out and status, the same checks and limits (bits
+ *       1 .. 48, n <= 2^31 - 1, at most 65,536 step launches, n = 0 a no-op, nothing written on an argument error) and the same recording rules.
+ *       An empty slot is ZKP_ERR_ARG: there is no default base to build.  A slot prepared with the encoding of B returns exactly what
+ *       zkp_dlog_base returns.  flags = 0: k in [0, 2^bits).  flags = ZKP_DLOG_SIGNED: k in [-2^(bits - 1), 2^(bits - 1)), written to out as a
+ *       two's-complement int64 in the uint64 row (bits = 1: {-1, 0}); any other bit is ZKP_ERR_ARG.  The signed search is the unsigned one on
+ *       Q + 2^(bits - 1) G: the prepare step adds 2^(bits - 1) (G / 2) to the halved point -- one point per call, computed by "k_dlog_setup" from the
+ *       slot's fixed-base table, not a ladder per lane -- and a hit k' is written as k' - 2^(bits - 1).
+ *     LAUNCH ORDER of a signed call: the slices of the chunk axis go on the stream in ascending distance from the slice that starts at k = 0,
+ *       not in ascending k', so small magnitudes of either sign are found by the first two launches.  zkp_dlog_slice_order(n_slices, flags, i) is the
+ *       slice launched i-th, pure arithmetic: i when unsigned; when signed, z = n_slices / 2 first, then z - 1, z + 1, z - 2, ... and the rest
+ *       of the longer side once the shorter one is used up -- a permutation of 0 .. n_slices - 1.  For slice z to start at k = 0 exactly, a signed
+ *       call's slice length is zkp_dlog_slice_chunks_signed(n): zkp_dlog_slice_chunks(n) rounded down to a power of two (the chunks of a point
+ *       are a power of two as well).  Nothing else differs: same work items, same kernels.
+ *       Both counts are returned as size_t, the 64-bit return type this header uses (a slice index is a count of slices).
+ *     Timed under ZKP_K_DECODE ("k_dlog_prepare", or "k_dlog_prepare<shift>" for a signed call: the same text with the one addition) and
+ *       ZKP_K_TERMS ("k_dlog_steps").
+ *     Sizes: profiles/dlog_point_bench.txt (CHANGELOG.md has the summary).  The search costs what zkp_dlog_base costs -- group operations do not
+ *       depend on the base -- so everything said above holds, including where the device does NOT win: small calls belong on the host
+ *       (zkp_point_dlog_batch routes them there by the rule measured on B), and the first call on a new base pays one table build on top. */
+#define ZKP_DLOG_SLOTS 8
+#define ZKP_DLOG_SIGNED 1
+int zkp_ctx_prepare_dlog_point(zkp_ctx* ctx, uint32_t slot, const uint8_t base[32], uint32_t baby_bits);
+int zkp_ctx_release_dlog_point(zkp_ctx* ctx, uint32_t slot);
+uint32_t zkp_dlog_point_baby_bits(zkp_ctx* ctx, uint32_t slot);
+int zkp_dlog_point_base(zkp_ctx* ctx, uint32_t slot, uint8_t out[32]);
+int zkp_dlog_point_find(zkp_ctx* ctx, const uint8_t base[32]);
+size_t zkp_dlog_point_last_use(zkp_ctx* ctx, uint32_t slot);
+int zkp_dlog_point(zkp_ctx* ctx, uint32_t slot, uint64_t n, const uint8_t* points /*[n][32]*/, uint32_t bits, int flags, uint64_t* out /*[n]*/,
+                   uint8_t* status /*[n]*/);
+int zkp_dlog_point_dev(zkp_ctx* ctx, uint32_t slot, uint64_t n, const uint8_t* d_points /*[n][32]*/, uint32_t bits, int flags, uint64_t* d_out /*[n]*/,
+                       uint8_t* d_status /*[n]*/);
+size_t zkp_dlog_slice_order(uint64_t n_slices, int flags, uint64_t i);
+uint32_t zkp_dlog_slice_chunks_signed(uint64_t n);
+
 /* (11) Multiscalar sums with LONG segments, batched: a vector Pedersen commitment sum m_i G_i + r H (constant time, many commitments over one set
  *     of generators), a weighted tally sum w_k C_k, an aggregated key sum a_k X_k, a caller's own random linear combination.  zkp_msm_many was
  *     built for very many MSMs of 2 to 11 terms: after its term kernels one lane per MSM adds that MSM's products one after another, and with long

@@ -486,6 +486,19 @@ int zkp_toolbox_set_dlog_baby_bits(uint32_t baby_bits);
 uint32_t zkp_toolbox_get_dlog_baby_bits(void);
 void zkp_toolbox_set_dlog_host_max_steps(uint32_t steps);
 uint32_t zkp_toolbox_get_dlog_host_max_steps(void);
+/* The same to a base of the caller's and over signed ranges (zkp_mi355x.h (10): zkp_dlog_point): out[i] = the k with
+ * encode(k G) == points[i], G = decode(base); flags = 0: k in [0, 2^bits); flags = ZKP_DLOG_SIGNED: k in [-2^(bits - 1), 2^(bits - 1)) as a
+ * two's-complement int64 in the uint64 row.  status as above.  A base that does not decode is ZKP_TB_INVALID_POINT; the identity as base (32 zero
+ * bytes), a NULL buffer with n > 0, bits outside 1 .. 48 or an unknown flag is ZKP_TB_BAD_STATEMENT; nothing is written on an error; n = 0 is a
+ * no-op.  ROUTING is the rule above word for word -- the host work n (2^(bits - host baby_bits) + 128) per thread against
+ * zkp_toolbox_get_dlog_host_max_steps(), zkp_toolbox_set_dlog_baby_bits for the host table's size: the rule counts group operations, and those
+ * do not depend on the base.  The 2,048 was measured on B; a first call on a new base additionally pays one table build on either route (the
+ * host keeps up to 8 tables per process keyed by base and size, least recently used out).  On the device route the call looks the base up with
+ * zkp_dlog_point_find; a base without a slot gets a free slot, else the least recently used one (zkp_dlog_point_last_use), prepared with 2^16
+ * rows: a caller who wants another size prepares the slot first (zkp_ctx_prepare_dlog_point).  In signed mode both routes search outward from
+ * k = 0 (zkp_dlog_slice_order: the device over its slices, the host over its groups of giant steps).  Same results on both routes. */
+int zkp_point_dlog_batch(zkp_ctx* ctx, const uint8_t base[32], uint64_t n, const uint8_t* points /*[n][32]*/, uint32_t bits, int flags,
+                         uint64_t* out /*[n]*/, uint8_t* status /*[n]*/, int n_threads);
 
 /* The ChaCha20 block function (RFC 8439 section 2.3; state words 12-13 = counter, 14-15 = nonce) behind the default
  * entropy / weights of the calls above (`entropy == NULL`, `weights16 == NULL`): like the reference's `thread_rng()`, a

@@ -41,6 +41,8 @@ pub const ZKP_PT_SUB: c_int = 1; //  zkp_add_points: a - b
 pub const ZKP_DLOG_FOUND: u8 = 0; //      zkp_dlog_base status: out[i] B == points[i]
 pub const ZKP_DLOG_INVALID: u8 = 1; //    the encoding does not decode
 pub const ZKP_DLOG_NOT_FOUND: u8 = 2; //  no logarithm below 2^bits
+pub const ZKP_DLOG_SLOTS: u32 = 8; //     zkp_ctx_prepare_dlog_point: slots per context
+pub const ZKP_DLOG_SIGNED: c_int = 1; //  zkp_dlog_point flags: k in [-2^(bits-1), 2^(bits-1)) as i64
 pub const ZKP_OPT_BATCH_ENCODE_MIN: c_int = 1;
 pub const ZKP_OPT_COMB_TEETH: c_int = 2;
 pub const ZKP_OPT_CT_SINGLE_USE_TABLES: c_int = 3;
@@ -273,6 +275,16 @@ extern "C" {
     pub fn zkp_dlog_group() -> u32;
     pub fn zkp_dlog_chunk() -> u32;
     pub fn zkp_dlog_slice_chunks(n: u64) -> u32;
+    pub fn zkp_ctx_prepare_dlog_point(ctx: *mut zkp_ctx, slot: u32, base: *const u8, baby_bits: u32) -> c_int;
+    pub fn zkp_ctx_release_dlog_point(ctx: *mut zkp_ctx, slot: u32) -> c_int;
+    pub fn zkp_dlog_point_baby_bits(ctx: *mut zkp_ctx, slot: u32) -> u32;
+    pub fn zkp_dlog_point_base(ctx: *mut zkp_ctx, slot: u32, out: *mut u8) -> c_int;
+    pub fn zkp_dlog_point_find(ctx: *mut zkp_ctx, base: *const u8) -> c_int;
+    pub fn zkp_dlog_point_last_use(ctx: *mut zkp_ctx, slot: u32) -> usize;
+    pub fn zkp_dlog_point(ctx: *mut zkp_ctx, slot: u32, n: u64, points: *const u8, bits: u32, flags: c_int, out: *mut u64, status: *mut u8) -> c_int;
+    pub fn zkp_dlog_point_dev(ctx: *mut zkp_ctx, slot: u32, n: u64, d_points: *const u8, bits: u32, flags: c_int, d_out: *mut u64, d_status: *mut u8) -> c_int;
+    pub fn zkp_dlog_slice_order(n_slices: u64, flags: c_int, i: u64) -> usize;
+    pub fn zkp_dlog_slice_chunks_signed(n: u64) -> u32;
     // (7) Merlin operations on N transcripts at any mix of positions
     pub fn zkp_transcripts_append_message(ctx: *mut zkp_ctx, n: u32, shared_initial: c_int, ts: *mut u8, label: *const c_char, msgs: *const u8,
                                           offsets: *const u64) -> c_int;
@@ -444,6 +456,7 @@ extern "C" {
     pub fn zkp_toolbox_get_msm_fold_min_segment() -> u32;
     // bounded discrete logarithms to the basepoint behind the same routing; the host table's size and the routing threshold
     pub fn zkp_basepoint_dlog_batch(ctx: *mut zkp_ctx, n: u64, points: *const u8, bits: u32, out: *mut u64, status: *mut u8, n_threads: c_int) -> c_int;
+    pub fn zkp_point_dlog_batch(ctx: *mut zkp_ctx, base: *const u8, n: u64, points: *const u8, bits: u32, flags: c_int, out: *mut u64, status: *mut u8, n_threads: c_int) -> c_int;
     pub fn zkp_toolbox_set_dlog_baby_bits(baby_bits: u32) -> c_int;
     pub fn zkp_toolbox_get_dlog_baby_bits() -> u32;
     pub fn zkp_toolbox_set_dlog_host_max_steps(steps: u32);

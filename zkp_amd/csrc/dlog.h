@@ -1,4 +1,4 @@
-// Bounded discrete logarithms to the basepoint (zkp_mi355x.h (10): zkp_dlog_base): the plan and the probe of baby-step / giant-step on ristretto255.
+// Bounded discrete logarithms to the basepoint (zkp_mi355x.h (10): zkp_dlog_base) and to a base of the caller's (zkp_dlog_point): the plan and the probe of baby-step / giant-step on ristretto255.
 //
 // With m = 2^baby_bits, k = j m + i: candidate j of a point Q is Q - j m B, and k is found when the ENCODING of a candidate equals the encoding of a
 // baby step i B (equality in the group is equality of canonical encodings).  An encoding costs an inverse square root (~265 field products, 40
@@ -93,6 +93,30 @@ inline void dlog_fill_slots(dlog_slot* slots, const uint32_t* rows, uint32_t bab
     slots[h].tag = dlog_tag(w);
     slots[h].idx1 = i + 1u;
   }
+}
+
+// Any base, signed ranges (zkp_mi355x.h (10): zkp_dlog_point).  A SLOT is the same table for a base G of the caller's: G's fixed-base table, the rows
+// encode(i G), their probe slots and the walk points (1/2) G and (m / 2) G; nothing in the search knows which base it walks.  A signed range
+// [-2^(bits - 1), 2^(bits - 1)) is the unsigned search on Q + 2^(bits - 1) G: the prepare step adds 2^(bits - 1) (G / 2) to the halved point (one
+// point per call, from the slot's fixed-base table), a hit k' is written as k' - 2^(bits - 1).  What keeps small magnitudes early is the ORDER of
+// the launches alone: slices go on the stream in ascending distance from the slice that starts at k = 0 (dlog_slice_order).  For that slice to
+// exist, a signed call's slice length is rounded down to a power of two (dlog_slice_chunks_signed): the chunks of a point are a power of two as
+// well, so k' = 2^(bits - 1) is the first step of slice n_slices / 2 whenever there is more than one slice.
+constexpr uint32_t DLOG_POINT_SLOTS = 8;
+ZKP_HD uint64_t dlog_slice_chunks_signed(uint64_t n) {
+  uint64_t c = dlog_slice_chunks(n), p = 1;
+  while (p * 2 <= c) p *= 2;
+  return p;
+}
+// The slice launched i-th of n_slices.  Unsigned: i.  Signed: z = n_slices / 2 first, then z - 1, z + 1, z - 2, ... and, once one end is reached,
+// the rest of the other side outward.  A permutation of 0 .. n_slices - 1; i >= n_slices is answered with i.
+ZKP_HD uint64_t dlog_slice_order(uint64_t n_slices, bool is_signed, uint64_t i) {
+  if (!is_signed || i >= n_slices) return i;
+  const uint64_t z = n_slices / 2, below = z, above = n_slices - 1 - z, both = below < above ? below : above;
+  if (i == 0) return z;
+  if (i <= 2 * both) return (i & 1) ? z - (i + 1) / 2 : z + i / 2;
+  const uint64_t r = i - 2 * both;
+  return below > above ? z - both - r : z + both + r;
 }
 
 // k = j m + i is an answer only below 2^bits (bits < baby_bits: the table is longer than the range)

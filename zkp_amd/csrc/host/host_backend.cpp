@@ -27,7 +27,8 @@
 //                 stretch totals serially, and the rows before a stretch's first segment start take their carry in a second pass.
 //   dlog_halve / dlog_base_range / dlog_base_n  zkp_dlog_base (10): baby-step / giant-step of dlog.h -- the point halved once, candidates walked by subtracting
 //                 (m / 2) B, encode(2 H) of DLOG_GROUP consecutive candidates from one inversion (the serial form of Montgomery's trick), the probe of
-//                 dlog.h.  The baby table is built here the same way and kept per baby_bits for the process behind a mutex.
+//                 dlog.h.  The baby table is built here the same way and kept per (base, baby_bits) for the process behind a mutex; the dlog_point_*
+//                 forms take the base and a signed flag (zkp_dlog_point), the others are those with B.
 //   sc_*          the scalar kernels' bodies: sc25519.h (sc_invert, sc_from_wide, sc_mont) compiled for the host, element by element.
 #include "host_backend.hpp"
 
@@ -803,16 +804,19 @@ struct DoubleEncoder {
 
 struct DlogTable {
   uint32_t baby_bits = 0;
+  uint8_t enc[32] = {};                              // the base's encoding (the cache's key with baby_bits)
   std::vector<uint32_t> rows;
   std::vector<dlog_slot> slots;
   ge_p3 base;
-  ge_cached step;                                    // (m / 2) B
+  ge_cached step;                                    // (m / 2) G
+  ge_cached group_step;                              // DLOG_GROUP (m / 2) G: from the first candidate of one group to that of the next
+  uint64_t used = 0;
 };
 
-void build_dlog_table(DlogTable& t, uint32_t baby_bits) {
+void build_dlog_table(DlogTable& t, const ge_p3& base, uint32_t baby_bits) {
   const uint32_t m = 1u << baby_bits;
   t.baby_bits = baby_bits;
-  decode(t.base, kBasepoint);
+  t.base = base;
   uint8_t s[32];
   ge_p3 hb, sp;
   half_scalar(s);
@@ -822,6 +826,9 @@ void build_dlog_table(DlogTable& t, uint32_t baby_bits) {
   small_scalar(s, m / 2);
   mul_p3(sp, s, t.base);
   ge_to_cached(t.step, sp);
+  small_scalar(s, (uint64_t)(m / 2) * DLOG_GROUP);
+  mul_p3(sp, s, t.base);
+  ge_to_cached(t.group_step, sp);
   t.rows.resize((size_t)m * 8);
   DoubleEncoder enc;
   std::vector<ge_p3> cand(DLOG_GROUP);
@@ -839,22 +846,71 @@ void build_dlog_table(DlogTable& t, uint32_t baby_bits) {
   dlog_fill_slots(t.slots.data(), t.rows.data(), baby_bits);
 }
 
-std::shared_ptr<const DlogTable> dlog_table(uint32_t baby_bits) {
+// the table of (base, baby_bits), built at its first use; NULL where the base does not decode.  At most DLOG_POINT_SLOTS tables are kept, the
+// least recently used one leaves (callers that still search it hold their own reference).
+std::shared_ptr<const DlogTable> dlog_table(const uint8_t base[32], uint32_t baby_bits) {
   static std::mutex mu;
-  static std::map<uint32_t, std::shared_ptr<const DlogTable>> tables;
+  static std::vector<std::shared_ptr<DlogTable>> tables;
+  static uint64_t tick = 0;
   std::lock_guard<std::mutex> lk(mu);
-  auto it = tables.find(baby_bits);
-  if (it != tables.end()) return it->second;
+  for (auto& t : tables)
+    if (t->baby_bits == baby_bits && std::memcmp(t->enc, base, 32) == 0) {
+      t->used = ++tick;
+      return t;
+    }
+  ge_p3 G;
+  if (!decode(G, base)) return nullptr;
   auto t = std::make_shared<DlogTable>();
-  build_dlog_table(*t, baby_bits);
-  tables[baby_bits] = t;
+  build_dlog_table(*t, G, baby_bits);
+  std::memcpy(t->enc, base, 32);
+  t->used = ++tick;
+  if (tables.size() >= DLOG_POINT_SLOTS) {
+    size_t lru = 0;
+    for (size_t i = 1; i < tables.size(); ++i)
+      if (tables[i]->used < tables[lru]->used) lru = i;
+    tables[lru] = t;
+  } else {
+    tables.push_back(t);
+  }
   return t;
+}
+
+inline void half_store(uint8_t half[DLOG_HALF_BYTES], const ge_p3& P) {
+  const fe* co[4] = {&P.X, &P.Y, &P.Z, &P.T};
+  for (int k = 0; k < 4; ++k) {
+    uint32_t w[8];
+    fe_towords(w, *co[k]);
+    std::memcpy(half + 32 * k, w, 32);
+  }
+}
+inline void half_load(ge_p3& P, const uint8_t half[DLOG_HALF_BYTES]) {
+  fe* co[4] = {&P.X, &P.Y, &P.Z, &P.T};
+  for (int c = 0; c < 4; ++c) {
+    uint32_t w[8];
+    std::memcpy(w, half + 32 * c, 32);
+    fe_fromwords(*co[c], w);
+  }
 }
 }  // namespace
 
-void dlog_prepare_table(uint32_t baby_bits) { (void)dlog_table(baby_bits); }
+bool dlog_point_decodes(const uint8_t base[32]) {
+  ge_p3 G;
+  return decode(G, base);
+}
+int dlog_point_prepare_table(const uint8_t base[32], uint32_t baby_bits) { return dlog_table(base, baby_bits) ? 0 : ZKP_DLOG_INVALID; }
+void dlog_prepare_table(uint32_t baby_bits) { (void)dlog_table(kBasepoint, baby_bits); }
 
-int dlog_halve(const uint8_t point[32], uint8_t half[DLOG_HALF_BYTES]) {
+void dlog_point_shift(const uint8_t base[32], uint32_t bits, uint8_t shift[DLOG_HALF_BYTES]) {
+  ge_p3 G, S;
+  uint8_t s[32];
+  if (!decode(G, base)) ge_identity(G);
+  if (bits >= 2) small_scalar(s, 1ull << (bits - 2));                  // 2^(bits - 1) / 2
+  else half_scalar(s);                                                 // bits = 1: (1/2) G
+  mul_p3(S, s, G);
+  half_store(shift, S);
+}
+
+int dlog_point_halve(const uint8_t point[32], const uint8_t* shift, uint8_t half[DLOG_HALF_BYTES]) {
   ge_p3 Q, P;
   if (!decode(Q, point)) {
     std::memset(half, 0, DLOG_HALF_BYTES);
@@ -863,67 +919,100 @@ int dlog_halve(const uint8_t point[32], uint8_t half[DLOG_HALF_BYTES]) {
   uint8_t s[32];
   half_scalar(s);
   mul_p3(P, s, Q);                                   // Q / 2: every candidate of the search is a half, its bytes come from the encoder of doubles
-  const fe* co[4] = {&P.X, &P.Y, &P.Z, &P.T};
-  for (int k = 0; k < 4; ++k) {
-    uint32_t w[8];
-    fe_towords(w, *co[k]);
-    std::memcpy(half + 32 * k, w, 32);
+  if (shift) {
+    ge_p3 S;
+    ge_cached cs;
+    half_load(S, shift);
+    ge_to_cached(cs, S);
+    ge_add_cached(P, P, cs);
   }
+  half_store(half, P);
   return ZKP_DLOG_NOT_FOUND;
 }
+int dlog_halve(const uint8_t point[32], uint8_t half[DLOG_HALF_BYTES]) { return dlog_point_halve(point, nullptr, half); }
 
-int dlog_base_range(const uint8_t half[DLOG_HALF_BYTES], uint32_t bits, uint32_t baby_bits, uint64_t j_lo, uint64_t j_hi, uint64_t* k) {
+int dlog_point_range(const uint8_t base[32], const uint8_t half[DLOG_HALF_BYTES], uint32_t bits, uint32_t baby_bits, bool is_signed, uint64_t j_lo,
+                     uint64_t j_hi, uint64_t* k) {
   *k = 0;
-  ge_p3 P;
-  {
-    fe* co[4] = {&P.X, &P.Y, &P.Z, &P.T};
-    for (int c = 0; c < 4; ++c) {
-      uint32_t w[8];
-      std::memcpy(w, half + 32 * c, 32);
-      fe_fromwords(*co[c], w);
-    }
-  }
-  const std::shared_ptr<const DlogTable> tab = dlog_table(baby_bits);
+  const std::shared_ptr<const DlogTable> tab = dlog_table(base, baby_bits);
+  if (!tab || j_lo >= j_hi) return ZKP_DLOG_NOT_FOUND;
   const DlogTable& t = *tab;
-  uint8_t s[32];
-  if (j_lo) {
+  // Groups of DLOG_GROUP giant steps, numbered over the whole range of the call; this range holds [g_lo, g_hi), the first and the last of them
+  // in part where j_lo or j_hi is no multiple of the group.  The order visits the groups above its first one in ascending and those below it in
+  // descending order, so two cursors follow it: `up` stands on the next candidate going up and simply walks on, `down` on the first candidate of
+  // group g_down - 1 and moves by one addition per group.
+  const uint64_t n_groups = (dlog_giant_steps(bits, baby_bits) + DLOG_GROUP - 1) / DLOG_GROUP;
+  const uint64_t g_lo = j_lo / DLOG_GROUP, g_hi = (j_hi + DLOG_GROUP - 1) / DLOG_GROUP;
+  uint64_t g_up = std::min(std::max(dlog_slice_order(n_groups, is_signed, 0), g_lo), g_hi), g_down = g_up;
+  ge_p3 up, down;
+  half_load(up, half);
+  if (g_up || j_lo) {                                // (above g_lo the start is the group's own; in g_lo it is j_lo)
+    uint8_t s[32];
     ge_p3 A;
     ge_cached ca;
-    small_scalar(s, j_lo << (baby_bits - 1u));
+    small_scalar(s, std::max(g_up * DLOG_GROUP, j_lo) << (baby_bits - 1u));
     mul_p3(A, s, t.base);
     ge_to_cached(ca, A);
-    ge_sub_cached(P, P, ca);
+    ge_sub_cached(up, up, ca);
   }
+  ge_add_cached(down, up, t.group_step);
+  const uint64_t bias = is_signed ? 1ull << (bits - 1) : 0ull;
   DoubleEncoder enc;
   std::vector<ge_p3> cand(DLOG_GROUP);
   std::vector<uint32_t> w((size_t)DLOG_GROUP * 8);
-  for (uint64_t j0 = j_lo; j0 < j_hi; j0 += DLOG_GROUP) {
-    const size_t g = (size_t)std::min<uint64_t>(DLOG_GROUP, j_hi - j0);
-    for (size_t i = 0; i < g; ++i) {
-      cand[i] = P;
+  for (uint64_t i = 0; i < n_groups && (g_up < g_hi || g_down > g_lo); ++i) {
+    const uint64_t g = dlog_slice_order(n_groups, is_signed, i);
+    if (g < g_lo || g >= g_hi) continue;
+    const bool going_up = g == g_up;                 // (else g == g_down - 1)
+    const uint64_t j0 = std::max(g * DLOG_GROUP, j_lo);
+    ge_p3 P;
+    if (going_up) {
+      P = up;
+    } else {
+      P = down;
+      ge_add_cached(down, down, t.group_step);
+      --g_down;
+      for (uint64_t j = g * DLOG_GROUP; j < j0; ++j) ge_sub_cached(P, P, t.step);
+    }
+    const size_t n = (size_t)(std::min<uint64_t>((g + 1) * DLOG_GROUP, j_hi) - j0);
+    for (size_t c = 0; c < n; ++c) {
+      cand[c] = P;
       ge_sub_cached(P, P, t.step);
     }
-    enc.run(reinterpret_cast<uint32_t(*)[8]>(w.data()), cand.data(), g);
-    for (size_t i = 0; i < g; ++i) {
-      const uint32_t b = dlog_probe(w.data() + 8 * i, t.slots.data(), t.rows.data(), baby_bits);
-      const uint64_t v = ((j0 + i) << baby_bits) + b;
+    if (going_up) {
+      up = P;
+      ++g_up;
+    }
+    enc.run(reinterpret_cast<uint32_t(*)[8]>(w.data()), cand.data(), n);
+    for (size_t c = 0; c < n; ++c) {
+      const uint32_t b = dlog_probe(w.data() + 8 * c, t.slots.data(), t.rows.data(), baby_bits);
+      const uint64_t v = ((j0 + c) << baby_bits) + b;
       if (b != DLOG_NONE && dlog_in_range(v, bits)) {
-        *k = v;
+        *k = v - bias;
         return ZKP_DLOG_FOUND;
       }
     }
   }
   return ZKP_DLOG_NOT_FOUND;
 }
+int dlog_base_range(const uint8_t half[DLOG_HALF_BYTES], uint32_t bits, uint32_t baby_bits, uint64_t j_lo, uint64_t j_hi, uint64_t* k) {
+  return dlog_point_range(kBasepoint, half, bits, baby_bits, false, j_lo, j_hi, k);
+}
 
-void dlog_base_n(uint64_t n, const uint8_t* points, uint32_t bits, uint32_t baby_bits, uint64_t* out, uint8_t* status) {
+void dlog_point_n(const uint8_t base[32], uint64_t n, const uint8_t* points, uint32_t bits, uint32_t baby_bits, bool is_signed, uint64_t* out,
+                  uint8_t* status) {
   const uint64_t J = dlog_giant_steps(bits, baby_bits);
+  uint8_t shift[DLOG_HALF_BYTES];
+  if (is_signed) dlog_point_shift(base, bits, shift);
   for (uint64_t i = 0; i < n; ++i) {
     uint8_t half[DLOG_HALF_BYTES];
     out[i] = 0;
-    status[i] = (uint8_t)dlog_halve(points + 32 * i, half);
-    if (status[i] != ZKP_DLOG_INVALID) status[i] = (uint8_t)dlog_base_range(half, bits, baby_bits, 0, J, out + i);
+    status[i] = (uint8_t)dlog_point_halve(points + 32 * i, is_signed ? shift : nullptr, half);
+    if (status[i] != ZKP_DLOG_INVALID) status[i] = (uint8_t)dlog_point_range(base, half, bits, baby_bits, is_signed, 0, J, out + i);
   }
+}
+void dlog_base_n(uint64_t n, const uint8_t* points, uint32_t bits, uint32_t baby_bits, uint64_t* out, uint8_t* status) {
+  dlog_point_n(kBasepoint, n, points, bits, baby_bits, false, out, status);
 }
 
 }  // namespace hostbk

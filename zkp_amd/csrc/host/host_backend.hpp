@@ -67,5 +67,21 @@ void dlog_prepare_table(uint32_t baby_bits);
 int dlog_halve(const uint8_t point[32], uint8_t half[DLOG_HALF_BYTES]);
 int dlog_base_range(const uint8_t half[DLOG_HALF_BYTES], uint32_t bits, uint32_t baby_bits, uint64_t j_lo, uint64_t j_hi, uint64_t* k);
 void dlog_base_n(uint64_t n, const uint8_t* points /*[n][32]*/, uint32_t bits, uint32_t baby_bits, uint64_t* out /*[n]*/, uint8_t* status /*[n]*/);
+// zkp_dlog_point (10): the same to a base of the caller's and over signed ranges; the functions above are these with the encoding of B and
+// is_signed = false.  The process keeps at most 8 tables keyed by (base encoding, baby_bits), least recently used out, behind the same mutex.
+// dlog_point_decodes: whether an encoding is a base at all.  dlog_point_prepare_table returns ZKP_DLOG_INVALID for one that does not decode (every
+// function below assumes one that does), else 0.
+// dlog_point_shift: the point a signed call adds to every half, 2^(bits - 1) (G / 2), in the format of a half -- computed once per call.
+// dlog_point_halve is dlog_halve plus that point (shift = NULL: unsigned).  dlog_point_range with is_signed walks its groups of giant steps in
+// ascending distance from the group that starts at k = 0 (dlog_slice_order of dlog.h over the groups of the whole range, those outside
+// [j_lo, j_hi) passed over) and returns k less the bias 2^(bits - 1) as a two's-complement int64.
+bool dlog_point_decodes(const uint8_t base[32]);
+int dlog_point_prepare_table(const uint8_t base[32], uint32_t baby_bits);
+void dlog_point_shift(const uint8_t base[32], uint32_t bits, uint8_t shift[DLOG_HALF_BYTES]);
+int dlog_point_halve(const uint8_t point[32], const uint8_t* shift /*[DLOG_HALF_BYTES] or NULL*/, uint8_t half[DLOG_HALF_BYTES]);
+int dlog_point_range(const uint8_t base[32], const uint8_t half[DLOG_HALF_BYTES], uint32_t bits, uint32_t baby_bits, bool is_signed, uint64_t j_lo,
+                     uint64_t j_hi, uint64_t* k);
+void dlog_point_n(const uint8_t base[32], uint64_t n, const uint8_t* points /*[n][32]*/, uint32_t bits, uint32_t baby_bits, bool is_signed,
+                  uint64_t* out /*[n]*/, uint8_t* status /*[n]*/);
 }  // namespace hostbk
 }  // namespace zkp

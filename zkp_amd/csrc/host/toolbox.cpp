@@ -1230,24 +1230,31 @@ uint32_t zkp_toolbox_get_dlog_host_max_steps(void) { return g_dlog_host_max_step
 // Routing: the host work of a call is n (J + 128) giant steps -- J = 2^(bits - host baby_bits) for a point that is not found, and 128 for its decode and
 // halving, a 253-bit ladder.  A call with a context stays on the host while that work is at most host_max_steps PER THREAD, the threads counted up to 16
 // (what was measured: profiles/dlog_bench.txt).
-int zkp_basepoint_dlog_batch(zkp_ctx* ctx, uint64_t n, const uint8_t* points, uint32_t bits, uint64_t* out, uint8_t* status, int n_threads) {
-  if (bits < 1 || bits > 48) return ZKP_TB_BAD_STATEMENT;
-  if (n == 0) return ZKP_TB_OK;
-  if (!points || !out || !status || n > 0x7fffffffull) return ZKP_TB_BAD_STATEMENT;
+namespace {
+const uint8_t kDlogBasepoint[32] = {0xe2, 0xf2, 0xae, 0x0a, 0x6a, 0xbc, 0x4e, 0x71, 0xa8, 0x84, 0xa9, 0x61, 0xc5, 0x00, 0x51, 0x5f,
+                                    0x58, 0xe3, 0x0b, 0x6a, 0xa5, 0x82, 0xdd, 0x8d, 0xb6, 0xa6, 0x59, 0x45, 0xe0, 0x8d, 0x2d, 0x76};
+unsigned dlog_threads(int n_threads) {
+  const unsigned t = n_threads > 0 ? (unsigned)n_threads : std::thread::hardware_concurrency();
+  return std::max(1u, std::min(t, 128u));
+}
+// the routing rule of both calls: group operations do not depend on the base
+bool dlog_on_device(zkp_ctx* ctx, uint64_t n, uint32_t bits, unsigned t) {
   const uint32_t bb = g_dlog_host_baby_bits.load();
   const uint64_t J = bits <= bb ? 1ull : 1ull << (bits - bb);
-  unsigned t = n_threads > 0 ? (unsigned)n_threads : std::thread::hardware_concurrency();
-  t = std::max(1u, std::min(t, 128u));
-  if (ctx && n * (J + 128) > (uint64_t)g_dlog_host_max_steps.load() * std::min(t, 16u)) {
-    const int rc = zkp_dlog_base(ctx, n, points, bits, out, status);
-    return rc == ZKP_ERR_ARG ? ZKP_TB_BAD_STATEMENT : rc;
-  }
-  zkp::hostbk::dlog_prepare_table(bb);               // (built once, before the threads ask for it)
+  return ctx && n * (J + 128) > (uint64_t)g_dlog_host_max_steps.load() * std::min(t, 16u);
+}
+// the host route over a base that decodes (its table exists: built once, before the threads ask for it)
+void dlog_host_route(const uint8_t base[32], uint64_t n, const uint8_t* points, uint32_t bits, bool is_signed, uint64_t* out, uint8_t* status, unsigned t) {
+  const uint32_t bb = g_dlog_host_baby_bits.load();
+  const uint64_t J = bits <= bb ? 1ull : 1ull << (bits - bb);
   constexpr size_t HB = zkp::hostbk::DLOG_HALF_BYTES;
   std::vector<uint8_t> halves(HB * (size_t)n), bad(n);
+  uint8_t shift[HB];
+  if (is_signed) zkp::hostbk::dlog_point_shift(base, bits, shift);
   const unsigned tp = (unsigned)std::min<uint64_t>(t, n);
   auto halve = [&](unsigned k) {
-    for (uint64_t p = k; p < n; p += tp) bad[p] = zkp::hostbk::dlog_halve(points + 32 * (size_t)p, halves.data() + HB * (size_t)p) == ZKP_DLOG_INVALID;
+    for (uint64_t p = k; p < n; p += tp)
+      bad[p] = zkp::hostbk::dlog_point_halve(points + 32 * (size_t)p, is_signed ? shift : nullptr, halves.data() + HB * (size_t)p) == ZKP_DLOG_INVALID;
   };
   if (tp <= 1) halve(0);
   else Pool::instance().run(tp, halve);
@@ -1262,7 +1269,7 @@ int zkp_basepoint_dlog_batch(zkp_ctx* ctx, uint64_t n, const uint8_t* points, ui
     for (uint64_t it = k; it < items; it += ts) {
       const uint64_t p = it / segs, lo = (it % segs) * seg_len, hi = std::min<uint64_t>(J, lo + seg_len);
       sts[it] = (uint8_t)ZKP_DLOG_NOT_FOUND;
-      if (!bad[p] && lo < hi) sts[it] = (uint8_t)zkp::hostbk::dlog_base_range(halves.data() + HB * (size_t)p, bits, bb, lo, hi, &ks[it]);
+      if (!bad[p] && lo < hi) sts[it] = (uint8_t)zkp::hostbk::dlog_point_range(base, halves.data() + HB * (size_t)p, bits, bb, is_signed, lo, hi, &ks[it]);
     }
   };
   if (ts <= 1) work(0);
@@ -1273,6 +1280,51 @@ int zkp_basepoint_dlog_batch(zkp_ctx* ctx, uint64_t n, const uint8_t* points, ui
     for (uint64_t s2 = 0; s2 < segs; ++s2)
       if (sts[p * segs + s2] == ZKP_DLOG_FOUND) { out[p] = ks[p * segs + s2]; status[p] = ZKP_DLOG_FOUND; }
   }
+}
+}  // namespace
+
+int zkp_basepoint_dlog_batch(zkp_ctx* ctx, uint64_t n, const uint8_t* points, uint32_t bits, uint64_t* out, uint8_t* status, int n_threads) {
+  if (bits < 1 || bits > 48) return ZKP_TB_BAD_STATEMENT;
+  if (n == 0) return ZKP_TB_OK;
+  if (!points || !out || !status || n > 0x7fffffffull) return ZKP_TB_BAD_STATEMENT;
+  const unsigned t = dlog_threads(n_threads);
+  if (dlog_on_device(ctx, n, bits, t)) {
+    const int rc = zkp_dlog_base(ctx, n, points, bits, out, status);
+    return rc == ZKP_ERR_ARG ? ZKP_TB_BAD_STATEMENT : rc;
+  }
+  zkp::hostbk::dlog_prepare_table(g_dlog_host_baby_bits.load());
+  dlog_host_route(kDlogBasepoint, n, points, bits, false, out, status, t);
+  return ZKP_TB_OK;
+}
+
+// The same to a base of the caller's and over signed ranges (zkp_dlog_point).  The routing rule is the one above word for word.  On the device
+// route the base's slot is the one the context already holds for it, else a free one, else the least recently used one
+// (zkp_dlog_point_last_use), prepared with the default size of 2^16 rows.
+int zkp_point_dlog_batch(zkp_ctx* ctx, const uint8_t base[32], uint64_t n, const uint8_t* points, uint32_t bits, int flags, uint64_t* out, uint8_t* status,
+                         int n_threads) {
+  if (bits < 1 || bits > 48 || (flags & ~ZKP_DLOG_SIGNED)) return ZKP_TB_BAD_STATEMENT;
+  if (n == 0) return ZKP_TB_OK;
+  if (!base || !points || !out || !status || n > 0x7fffffffull) return ZKP_TB_BAD_STATEMENT;
+  static const uint8_t identity[32] = {};
+  if (std::memcmp(base, identity, 32) == 0) return ZKP_TB_BAD_STATEMENT;
+  const unsigned t = dlog_threads(n_threads);
+  if (dlog_on_device(ctx, n, bits, t)) {
+    int slot = zkp_dlog_point_find(ctx, base);
+    if (slot < 0) {
+      if (!zkp::hostbk::dlog_point_decodes(base)) return ZKP_TB_INVALID_POINT;       // (told apart from the context's other ZKP_ERR_ARG causes)
+      uint64_t oldest = UINT64_MAX;
+      for (uint32_t s = 0; s < ZKP_DLOG_SLOTS; ++s) {
+        const uint64_t used = zkp_dlog_point_last_use(ctx, s);                 // (0: empty)
+        if (used < oldest) { oldest = used; slot = (int)s; }
+      }
+      const int rc = zkp_ctx_prepare_dlog_point(ctx, (uint32_t)slot, base, 16);
+      if (rc) return rc == ZKP_ERR_ARG ? ZKP_TB_BAD_STATEMENT : rc;
+    }
+    const int rc = zkp_dlog_point(ctx, (uint32_t)slot, n, points, bits, flags, out, status);
+    return rc == ZKP_ERR_ARG ? ZKP_TB_BAD_STATEMENT : rc;
+  }
+  if (zkp::hostbk::dlog_point_prepare_table(base, g_dlog_host_baby_bits.load())) return ZKP_TB_INVALID_POINT;
+  dlog_host_route(base, n, points, bits, (flags & ZKP_DLOG_SIGNED) != 0, out, status, t);
   return ZKP_TB_OK;
 }
 

@@ -1604,7 +1604,8 @@ k_sum_encode(uint32_t n_sums, const uint32_t* __restrict__ off, const sum_item* 
   status[s] = (uint8_t)(bad != 0);
 }
 
-// Bounded discrete logarithms to the basepoint (zkp_mi355x.h (10); dlog.h has the scheme).
+// Bounded discrete logarithms to the basepoint and to bases of the caller's (zkp_mi355x.h (10); dlog.h has the scheme).  `table` is the fixed-base
+// table of the base B or G in the layout of the context's table of B, `consts` its two walk points: no kernel knows which base it walks.
 //
 // dlog_group_encode: w = encode(2 P) for the candidate of every lane of a DLOG_GROUP-lane workgroup from ONE field inversion: the product tree of the
 // batched encoder over the lanes' x = e g f h, the root inverted by the first wavefront (one limb per lane, rowfe.h), the tree walked down.  Every
@@ -1706,10 +1707,13 @@ k_dlog_rows(uint32_t m, const uint4* __restrict__ table, const uint32_t* __restr
 }
 
 // k_dlog_prepare: halves[i] = ((l + 1) / 2) decode(points[i]) by the variable-time ladder of k_mul_pairs, so that every later candidate is a doubled
-// point; status[i] = 1 where the encoding does not decode, 2 (not found yet) otherwise; out[i] = 0.
+// point; status[i] = 1 where the encoding does not decode, 2 (not found yet) otherwise; out[i] = 0.  SHIFT (a signed range, dlog.h): the cached point
+// at `shift`, 2^(bits - 1) (G / 2), is added to every half, so that the search that follows is the unsigned one on Q + 2^(bits - 1) G.  The addition
+// comes after the ladder, whose table and accumulator are dead by then.
+template <bool SHIFT>
 __global__ void __launch_bounds__(256, 2)
 k_dlog_prepare(uint32_t n, const uint8_t* __restrict__ points, uint4* ladder_rw, dev_ext* __restrict__ halves, uint64_t* __restrict__ out,
-               uint8_t* __restrict__ status) {
+               uint8_t* __restrict__ status, const uint32_t* __restrict__ shift) {
   __shared__ uint32_t ecols[8 * 256];
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -1722,6 +1726,11 @@ k_dlog_prepare(uint32_t n, const uint8_t* __restrict__ points, uint4* ladder_rw,
   ge_p3 P, acc;
   const uint32_t ok = ristretto_decode(P, w);                    // (the identity where it fails)
   ladder16_point<false>(acc, s, P, tbl, ecols + threadIdx.x);
+  if (SHIFT) {
+    ge_cached sh;
+    dlog_load_cached(sh, shift);
+    ge_add_cached(acc, acc, sh);
+  }
   store_ext(halves + i, acc);
   out[i] = 0;
   status[i] = (uint8_t)(ok ? ZKP_DLOG_NOT_FOUND : ZKP_DLOG_INVALID);
@@ -1733,10 +1742,10 @@ k_dlog_prepare(uint32_t n, const uint8_t* __restrict__ points, uint4* ladder_rw,
 // a workgroup without work leaves, otherwise idle lanes walk the identity along (the crossbar needs every lane of a wavefront, the shared
 // inversion every lane of the workgroup) and touch no memory.  Start Q / 2 - (c DLOG_CHUNK m / 2) B from the table of B, then one encoding group and
 // one subtraction of (m / 2) B per giant step.  A confirmed hit k = j m + i below 2^bits writes out and status = 0; k is unique, so there is one
-// writer.  steps = the giant steps a chunk walks: DLOG_CHUNK, or fewer where the whole range has fewer (both powers of two: then every point has one
+// writer.  bias (a signed range): what is written is k - bias, a two's-complement int64 in the same row; 0 for an unsigned call.  steps = the giant steps a chunk walks: DLOG_CHUNK, or fewer where the whole range has fewer (both powers of two: then every point has one
 // chunk, and steps past the range could only give k >= 2^bits).  Every index that reaches memory is below its array's length: p < n, the probe masks its slot and a slot names a row below m.
 __global__ void __launch_bounds__(DLOG_GROUP, 2)
-k_dlog_steps(uint32_t n, uint64_t items, uint64_t span, uint64_t chunk0, uint64_t total_chunks, uint32_t steps, uint32_t bits, uint32_t baby_bits, const dev_ext* __restrict__ halves,
+k_dlog_steps(uint32_t n, uint64_t items, uint64_t span, uint64_t chunk0, uint64_t total_chunks, uint32_t steps, uint32_t bits, uint32_t baby_bits, uint64_t bias, const dev_ext* __restrict__ halves,
              const uint4* __restrict__ table, const uint32_t* __restrict__ consts, const dlog_slot* __restrict__ slots,
              const uint32_t* __restrict__ rows, uint64_t* out, uint8_t* status) {
   __shared__ enc_tree tree;
@@ -1769,7 +1778,7 @@ k_dlog_steps(uint32_t n, uint64_t items, uint64_t span, uint64_t chunk0, uint64_
       const uint32_t i = dlog_probe(w, slots, rows, baby_bits);
       const uint64_t k = ((j0 + t) << baby_bits) + i;
       if (i != DLOG_NONE && dlog_in_range(k, bits)) {
-        out[p] = k;
+        out[p] = k - bias;
         status[p] = (uint8_t)ZKP_DLOG_FOUND;
         live = 0;
       }
@@ -1902,11 +1911,21 @@ struct zkp_ctx {
   // LRU slot, k_hot_match never sees it; built at the first call (ensure_base_table)
   dev_niels* base_table = nullptr;
   // zkp_dlog_base (section 10): the baby-step table, allocations of the context's own like base_table -- rows [2^baby_bits][8] words, probe slots
-  // [2^(baby_bits + 1)], and the two points of the walk ((1/2) B, (m / 2) B, cached form); dlog_baby_bits = 0: none yet (ensure_dlog_table)
-  uint32_t dlog_baby_bits = 0;
-  uint32_t* dlog_rows = nullptr;
-  dlog_slot* dlog_slots = nullptr;
-  uint32_t* dlog_consts = nullptr;
+  // [2^(baby_bits + 1)], and the two points of the walk ((1/2) B, (m / 2) B, cached form); baby_bits = 0: none yet
+  // (ensure_dlog_table, build_dlog_table).  `table` is the base's fixed-base table: the context's own struct borrows base_table, a slot of zkp_ctx_prepare_dlog_point
+  // owns one built from the caller's encoding (build_point_table).
+  struct dlog_tab {
+    uint32_t baby_bits = 0;
+    dev_niels* table = nullptr;
+    uint32_t* rows = nullptr;
+    dlog_slot* slots = nullptr;
+    uint32_t* consts = nullptr;
+    uint8_t base[32] = {};             // slots: the encoding the table was built from
+    uint64_t used = 0;                 // slots: dlog_tick at the last prepare or search (zkp_dlog_point_last_use; the toolbox replaces the smallest)
+  };
+  dlog_tab dlog;
+  dlog_tab dlog_pt[DLOG_POINT_SLOTS];
+  uint64_t dlog_tick = 0;
   // fused flows (fused_flows.h): compiled transcript programs and operand templates per (flow, statement, N, position)
   std::map<std::string, void*> fused_plans;
   // ragged calls (ragged_transcripts.h): uploaded class programs per (flow, statement, N, position) and position-free base plans per
@@ -1942,14 +1961,13 @@ struct zkp_ctx {
   bool hot_registry_uploaded = false;  // the device copy of the fixed-base registry matches hot_key[]
 };
 void free_fused_plans(zkp_ctx* c);
-static void free_dlog_table(zkp_ctx* c) {
-  if (c->dlog_rows) (void)hipFree(c->dlog_rows);
-  if (c->dlog_slots) (void)hipFree(c->dlog_slots);
-  if (c->dlog_consts) (void)hipFree(c->dlog_consts);
-  c->dlog_rows = nullptr;
-  c->dlog_slots = nullptr;
-  c->dlog_consts = nullptr;
-  c->dlog_baby_bits = 0;
+// frees rows, slots and walk points; the fixed-base table as well where the struct owns it (a slot), and forgets it either way
+static void free_dlog_table(zkp_ctx::dlog_tab& t, bool owns_table) {
+  if (t.rows) (void)hipFree(t.rows);
+  if (t.slots) (void)hipFree(t.slots);
+  if (t.consts) (void)hipFree(t.consts);
+  if (owns_table && t.table) (void)hipFree(t.table);
+  t = zkp_ctx::dlog_tab();
 }
 void free_ragged_progs(zkp_ctx* c);
 
@@ -2823,10 +2841,17 @@ const uint8_t kBasepointEncoding[32] = {0xe2, 0xf2, 0xae, 0x0a, 0x6a, 0xbc, 0x4e
 // The context's table of B for k_mul_base: k_decode_affine, k_hot_bases and k_hot_rows over ONE point into an allocation of its own, with slot
 // number 0 of that allocation.  Built once, at the first zkp_mul_base[_dev]; synchronises, so not under capture.  The registry of
 // zkp_ctx_prepare_fixed_points (hot_key / hot_used / hot_reg_*) is not touched.
+// build_point_table is the same over any encoding (the slots of zkp_ctx_prepare_dlog_point): *out = the table, *valid = what k_decode_affine
+// reported for the encoding (0: it does not decode, and no table is returned).
+int build_point_table(zkp_ctx* c, const uint8_t enc[32], dev_niels** out, uint32_t* valid);
 int ensure_base_table(zkp_ctx* c) {
   if (c->base_table) return ZKP_OK;
   if (c->capturing) return fail(ZKP_ERR_ARG, "graph capture: the basepoint table is not built yet -- run zkp_mul_base once outside the capture");
   if (c->job.kind) return fail(ZKP_ERR_ARG, "a submitted job is pending on this context: zkp_ctx_job_wait first");
+  uint32_t valid = 0;
+  return build_point_table(c, kBasepointEncoding, &c->base_table, &valid);
+}
+int build_point_table(zkp_ctx* c, const uint8_t enc[32], dev_niels** out, uint32_t* valid) {
   carve cv;
   const size_t o_enc = cv.take(32), o_aff = cv.take(sizeof(dev_affine)), o_slot = cv.take(4), o_bases = cv.take(sizeof(dev_ext) * HOT_WINDOWS);
   const size_t o_mult = cv.take(sizeof(dev_ext) * (size_t)HOT_WINDOWS * HOT_HALF);
@@ -2834,7 +2859,7 @@ int ensure_base_table(zkp_ctx* c) {
   dev_niels* table = nullptr;
   HIP_TRY(hipMalloc(&tmp, cv.off));
   hipError_t err = hipMalloc(&table, sizeof(dev_niels) * HOT_SLOT_NIELS);
-  if (err == hipSuccess) err = hipMemcpyAsync(tmp + o_enc, kBasepointEncoding, 32, hipMemcpyHostToDevice, c->stream);
+  if (err == hipSuccess) err = hipMemcpyAsync(tmp + o_enc, enc, 32, hipMemcpyHostToDevice, c->stream);
   if (err == hipSuccess) err = hipMemsetAsync(tmp + o_slot, 0, 4, c->stream);
   if (err == hipSuccess) {
     dev_affine* d_aff = reinterpret_cast<dev_affine*>(tmp + o_aff);
@@ -2844,6 +2869,7 @@ int ensure_base_table(zkp_ctx* c) {
     hipLaunchKernelGGL(k_hot_rows, grid1(HOT_WINDOWS, 64), dim3(64), 0, c->stream, 1u, reinterpret_cast<const uint32_t*>(tmp + o_slot), d_bases,
                        reinterpret_cast<dev_ext*>(tmp + o_mult), table);
     err = hipGetLastError();
+    if (err == hipSuccess) err = hipMemcpyAsync(valid, &d_aff->valid, 4, hipMemcpyDeviceToHost, c->stream);
   }
   const hipError_t sync_err = hipStreamSynchronize(c->stream);
   (void)hipFree(tmp);
@@ -2852,7 +2878,11 @@ int ensure_base_table(zkp_ctx* c) {
     HIP_TRY(err);
     HIP_TRY(sync_err);
   }
-  c->base_table = table;
+  if (!*valid) {
+    (void)hipFree(table);
+    return ZKP_OK;
+  }
+  *out = table;
   return ZKP_OK;
 }
 
@@ -3067,48 +3097,57 @@ int launch_msm_segments(zkp_ctx* c, uint32_t n_msm, const uint32_t* d_off, const
 }
 
 // ---- zkp_mi355x.h (10): the context's baby-step table and the launchers of the search (dlog.h) ----
-// Builds the table for baby_bits (the same size again: nothing to do).  Rows on the device, slots on the host from the downloaded rows.
-// Synchronises, so not under capture.  A replaced table makes graphs recorded over the old one stale (ws_generation).
-int ensure_dlog_table(zkp_ctx* c, uint32_t baby_bits) {
-  if (c->dlog_baby_bits == baby_bits) return ZKP_OK;
-  if (c->capturing) return fail(ZKP_ERR_ARG, "graph capture: the baby-step table is not built yet -- run zkp_ctx_prepare_dlog or one zkp_dlog_base outside the capture");
-  if (c->job.kind) return fail(ZKP_ERR_ARG, "a submitted job is pending on this context: zkp_ctx_job_wait first");
-  int rc = ensure_base_table(c);
-  if (rc) return rc;
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  if (c->dlog_baby_bits) {
-    free_dlog_table(c);
-    ++c->ws_generation;
-  }
+// build_dlog_table: rows, probe slots and walk points of t for baby_bits over t.table, the fixed-base table of the base (of B for the context's own
+// struct, of G for a slot).  Rows on the device, slots on the host from the downloaded rows.  Synchronises.  t holds no rows on entry; on an error
+// it holds none again and keeps t.table.
+int build_dlog_table(zkp_ctx* c, zkp_ctx::dlog_tab& t, uint32_t baby_bits) {
   const uint32_t m = 1u << baby_bits;
   const size_t row_bytes = (size_t)m * 32, slot_bytes = sizeof(dlog_slot) * (size_t)dlog_slot_count(baby_bits);
-  hipError_t err = hipMalloc(&c->dlog_rows, row_bytes);
-  if (err == hipSuccess) err = hipMalloc(&c->dlog_slots, slot_bytes);
-  if (err == hipSuccess) err = hipMalloc(&c->dlog_consts, 2 * 36 * sizeof(uint32_t));
+  hipError_t err = hipMalloc(&t.rows, row_bytes);
+  if (err == hipSuccess) err = hipMalloc(&t.slots, slot_bytes);
+  if (err == hipSuccess) err = hipMalloc(&t.consts, 2 * 36 * sizeof(uint32_t));
   std::vector<uint32_t> rows;
   std::vector<dlog_slot> slots;
   if (err == hipSuccess) {
-    const uint4* table = reinterpret_cast<const uint4*>(c->base_table);
-    hipLaunchKernelGGL(k_dlog_setup, dim3(1), dim3(64), 0, c->stream, (uint64_t)(m / 2), table, c->dlog_consts);
+    const uint4* table = reinterpret_cast<const uint4*>(t.table);
+    hipLaunchKernelGGL(k_dlog_setup, dim3(1), dim3(64), 0, c->stream, (uint64_t)(m / 2), table, t.consts);
     hipLaunchKernelGGL(k_dlog_rows, grid1(((size_t)m + DLOG_ROW_RUN - 1) / DLOG_ROW_RUN, DLOG_GROUP), dim3(DLOG_GROUP), 0, c->stream, m, table,
-                       c->dlog_consts, c->dlog_rows);
+                       t.consts, t.rows);
     err = hipGetLastError();
     rows.resize((size_t)m * 8);
-    if (err == hipSuccess) err = hipMemcpyAsync(rows.data(), c->dlog_rows, row_bytes, hipMemcpyDeviceToHost, c->stream);
+    if (err == hipSuccess) err = hipMemcpyAsync(rows.data(), t.rows, row_bytes, hipMemcpyDeviceToHost, c->stream);
     if (err == hipSuccess) err = hipStreamSynchronize(c->stream);
   }
   if (err == hipSuccess) {
     slots.assign(dlog_slot_count(baby_bits), dlog_slot{0u, 0u});
     dlog_fill_slots(slots.data(), rows.data(), baby_bits);
-    err = hipMemcpyAsync(c->dlog_slots, slots.data(), slot_bytes, hipMemcpyHostToDevice, c->stream);
+    err = hipMemcpyAsync(t.slots, slots.data(), slot_bytes, hipMemcpyHostToDevice, c->stream);
     if (err == hipSuccess) err = hipStreamSynchronize(c->stream);
   }
   if (err != hipSuccess) {
-    free_dlog_table(c);
+    dev_niels* keep = t.table;
+    free_dlog_table(t, false);
+    t.table = keep;
     HIP_TRY(err);
   }
-  c->dlog_baby_bits = baby_bits;
+  t.baby_bits = baby_bits;
   return ZKP_OK;
+}
+// The context's own table, of B, for baby_bits (the same size again: nothing to do).  Not under capture (build_dlog_table synchronises).  A replaced
+// table makes graphs recorded over the old one stale (ws_generation).
+int ensure_dlog_table(zkp_ctx* c, uint32_t baby_bits) {
+  if (c->dlog.baby_bits == baby_bits) return ZKP_OK;
+  if (c->capturing) return fail(ZKP_ERR_ARG, "graph capture: the baby-step table is not built yet -- run zkp_ctx_prepare_dlog or one zkp_dlog_base outside the capture");
+  if (c->job.kind) return fail(ZKP_ERR_ARG, "a submitted job is pending on this context: zkp_ctx_job_wait first");
+  int rc = ensure_base_table(c);
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (c->dlog.baby_bits) {
+    free_dlog_table(c->dlog, false);
+    ++c->ws_generation;
+  }
+  c->dlog.table = c->base_table;
+  return build_dlog_table(c, c->dlog, baby_bits);
 }
 
 int dlog_check(zkp_ctx* c, uint64_t n, uint32_t bits, bool null_buffer) {
@@ -3117,40 +3156,70 @@ int dlog_check(zkp_ctx* c, uint64_t n, uint32_t bits, bool null_buffer) {
   if (bits < 1 || bits > DLOG_BITS_MAX) return fail(ZKP_ERR_ARG, "bits must be 1 .. 48");
   return ZKP_OK;
 }
-// the launches of a call on the context's table (which exists): how many k_dlog_steps launches it takes
-inline uint64_t dlog_launches(const zkp_ctx* c, uint64_t n, uint32_t bits) {
-  const uint64_t chunks = dlog_chunks(bits, c->dlog_baby_bits), per = dlog_slice_chunks(n);
+// the launches of a call on a table (which exists): how many k_dlog_steps launches it takes
+inline uint64_t dlog_launches(const zkp_ctx::dlog_tab& t, uint64_t n, uint32_t bits, bool is_signed = false) {
+  const uint64_t chunks = dlog_chunks(bits, t.baby_bits), per = is_signed ? dlog_slice_chunks_signed(n) : dlog_slice_chunks(n);
   return (chunks + per - 1) / per;
 }
-struct dlog_ws { size_t halves = 0, ladder = 0, total = 0; };
+struct dlog_ws { size_t shift = 0, halves = 0, ladder = 0, total = 0; };
 dlog_ws dlog_base_ws(uint64_t n, size_t reserved = 0) {
   carve cv;
   cv.off = reserved;
   dlog_ws w;
+  w.shift = cv.take(2 * 36 * sizeof(uint32_t));                // (a signed call's shift point, k_dlog_setup's two outputs)
   w.halves = cv.take(sizeof(dev_ext) * (size_t)n);
   w.ladder = cv.take(mul_pairs_ws(n));
   w.total = cv.off;
   return w;
 }
-int launch_dlog(zkp_ctx* c, uint64_t n, const uint8_t* d_points, uint32_t bits, char* ws, const dlog_ws& w, uint64_t* d_out, uint8_t* d_status) {
+// The launches of one call over table t.  is_signed: k_dlog_setup over t.table leaves 2^(bits - 2) G = 2^(bits - 1) (G / 2) as its second point in the
+// workspace (bits = 1: the table's own (1/2) G), k_dlog_prepare<true> adds it, the slices are launched in dlog_slice_order and hits written less the bias.
+int launch_dlog(zkp_ctx* c, const zkp_ctx::dlog_tab& t, uint64_t n, const uint8_t* d_points, uint32_t bits, bool is_signed, char* ws, const dlog_ws& w,
+                uint64_t* d_out, uint8_t* d_status) {
   dev_ext* halves = reinterpret_cast<dev_ext*>(ws + w.halves);
   uint4* ladder = reinterpret_cast<uint4*>(ws + w.ladder);
+  const uint4* table = reinterpret_cast<const uint4*>(t.table);
+  const uint32_t* shift = t.consts;
+  if (is_signed && bits >= 2) {
+    uint32_t* d_shift = reinterpret_cast<uint32_t*>(ws + w.shift);
+    hipLaunchKernelGGL(k_dlog_setup, dim3(1), dim3(64), 0, c->stream, 1ull << (bits - 2), table, d_shift);
+    shift = d_shift + 36;
+  }
   for (uint64_t i0 = 0; i0 < n; i0 += MUL_PAIRS_MAX_LANES) {
     const uint32_t k = (uint32_t)std::min<uint64_t>(n - i0, MUL_PAIRS_MAX_LANES);
-    hipLaunchKernelGGL(k_dlog_prepare, grid1(k, 256), dim3(256), 0, c->stream, k, d_points + 32 * (size_t)i0, ladder, halves + i0, d_out + i0, d_status + i0);
+    if (is_signed)
+      hipLaunchKernelGGL(k_dlog_prepare<true>, grid1(k, 256), dim3(256), 0, c->stream, k, d_points + 32 * (size_t)i0, ladder, halves + i0, d_out + i0, d_status + i0, shift);
+    else
+      hipLaunchKernelGGL(k_dlog_prepare<false>, grid1(k, 256), dim3(256), 0, c->stream, k, d_points + 32 * (size_t)i0, ladder, halves + i0, d_out + i0, d_status + i0,
+                         (const uint32_t*)nullptr);
   }
-  prof_note(c, ZKP_K_DECODE, "k_dlog_prepare");
+  prof_note(c, ZKP_K_DECODE, is_signed ? "k_dlog_prepare<shift>" : "k_dlog_prepare");
   prof_mark(c, ZKP_K_DECODE);
-  const uint32_t bb = c->dlog_baby_bits;
-  const uint64_t chunks = dlog_chunks(bits, bb), per = dlog_slice_chunks(n);
-  for (uint64_t c0 = 0; c0 < chunks; c0 += per) {
+  const uint32_t bb = t.baby_bits;
+  const uint64_t chunks = dlog_chunks(bits, bb), per = is_signed ? dlog_slice_chunks_signed(n) : dlog_slice_chunks(n), n_slices = (chunks + per - 1) / per;
+  const uint64_t bias = is_signed ? 1ull << (bits - 1) : 0ull;
+  for (uint64_t i = 0; i < n_slices; ++i) {
+    const uint64_t c0 = dlog_slice_order(n_slices, is_signed, i) * per;
     const uint64_t span = std::min<uint64_t>(per, chunks - c0), items = n * span;
-    hipLaunchKernelGGL(k_dlog_steps, grid1((size_t)items, DLOG_GROUP), dim3(DLOG_GROUP), 0, c->stream, (uint32_t)n, items, span, c0, chunks, (uint32_t)std::min<uint64_t>(DLOG_CHUNK, dlog_giant_steps(bits, bb)), bits, bb, halves,
-                       reinterpret_cast<const uint4*>(c->base_table), c->dlog_consts, c->dlog_slots, c->dlog_rows, d_out, d_status);
+    hipLaunchKernelGGL(k_dlog_steps, grid1((size_t)items, DLOG_GROUP), dim3(DLOG_GROUP), 0, c->stream, (uint32_t)n, items, span, c0, chunks, (uint32_t)std::min<uint64_t>(DLOG_CHUNK, dlog_giant_steps(bits, bb)), bits, bb, bias, halves,
+                       table, t.consts, t.slots, t.rows, d_out, d_status);
   }
   prof_note(c, ZKP_K_TERMS, "k_dlog_steps");
   prof_mark(c, ZKP_K_TERMS);
   HIP_TRY(hipGetLastError());
+  return ZKP_OK;
+}
+
+// zkp_dlog_point[_dev]: the checks of zkp_dlog_base plus the slot and the flags; *t = the slot's table
+int dlog_point_check(zkp_ctx* c, uint32_t slot, uint64_t n, uint32_t bits, int flags, bool null_buffer, zkp_ctx::dlog_tab** t) {
+  const int rc = dlog_check(c, n, bits, null_buffer);
+  if (rc) return rc;
+  if (flags & ~ZKP_DLOG_SIGNED) return fail(ZKP_ERR_ARG, "flags: ZKP_DLOG_SIGNED or 0");
+  if (slot >= DLOG_POINT_SLOTS) return fail(ZKP_ERR_ARG, "slot must be below ZKP_DLOG_SLOTS");
+  *t = &c->dlog_pt[slot];
+  if (n && !(*t)->baby_bits) return fail(ZKP_ERR_ARG, "the slot is empty: zkp_ctx_prepare_dlog_point first");
+  if (n && dlog_launches(**t, n, bits, flags & ZKP_DLOG_SIGNED) > DLOG_MAX_LAUNCHES)
+    return fail(ZKP_ERR_ARG, "the search would take more than 65,536 launches: prepare a larger table or split the call");
   return ZKP_OK;
 }
 
@@ -3205,7 +3274,8 @@ void zkp_ctx_destroy(zkp_ctx* c) {
   if (c->ws) hipFree(c->ws);
   if (c->hot_tables) hipFree(c->hot_tables);
   if (c->base_table) hipFree(c->base_table);
-  free_dlog_table(c);
+  free_dlog_table(c->dlog, false);
+  for (auto& t : c->dlog_pt) free_dlog_table(t, true);
   if (c->hot_reg_words) hipFree(c->hot_reg_words);
   if (c->hot_reg_slot) hipFree(c->hot_reg_slot);
   if (c->hot_scratch) hipFree(c->hot_scratch);
@@ -4271,7 +4341,7 @@ int zkp_scan_points(zkp_ctx* c, int mode, uint32_t n_seg, const uint32_t* off, c
 uint32_t zkp_dlog_group(void) { return DLOG_GROUP; }
 uint32_t zkp_dlog_chunk(void) { return DLOG_CHUNK; }
 uint32_t zkp_dlog_slice_chunks(uint64_t n) { return (uint32_t)dlog_slice_chunks(n); }
-uint32_t zkp_dlog_baby_bits(zkp_ctx* c) { return c ? c->dlog_baby_bits : 0u; }
+uint32_t zkp_dlog_baby_bits(zkp_ctx* c) { return c ? c->dlog.baby_bits : 0u; }
 
 int zkp_ctx_prepare_dlog(zkp_ctx* c, uint32_t baby_bits) {
   if (!c) return fail(ZKP_ERR_ARG, "ctx is NULL");
@@ -4286,26 +4356,26 @@ int zkp_dlog_base_dev(zkp_ctx* c, uint64_t n, const uint8_t* d_points, uint32_t 
   if (rc || n == 0) return rc;
   if (!aligned16(d_points) || (reinterpret_cast<uintptr_t>(d_out) & 7)) return fail(ZKP_ERR_ARG, "d_points must be 16-byte, d_out 8-byte aligned");
   HIP_TRY(hipSetDevice(c->device));
-  if (!c->dlog_baby_bits) {
+  if (!c->dlog.baby_bits) {
     rc = ensure_dlog_table(c, DLOG_BABY_DEFAULT);
     if (rc) return rc;
   }
-  if (dlog_launches(c, n, bits) > DLOG_MAX_LAUNCHES) return fail(ZKP_ERR_ARG, "the search would take more than 65,536 launches: prepare a larger table or split the call");
+  if (dlog_launches(c->dlog, n, bits) > DLOG_MAX_LAUNCHES) return fail(ZKP_ERR_ARG, "the search would take more than 65,536 launches: prepare a larger table or split the call");
   const dlog_ws w = dlog_base_ws(n);
   rc = ensure_ws(c, w.total);
   if (rc) return rc;
   prof_begin(c);
-  return launch_dlog(c, n, d_points, bits, static_cast<char*>(c->ws), w, d_out, d_status);
+  return launch_dlog(c, c->dlog, n, d_points, bits, false, static_cast<char*>(c->ws), w, d_out, d_status);
 }
 int zkp_dlog_base(zkp_ctx* c, uint64_t n, const uint8_t* points, uint32_t bits, uint64_t* out, uint8_t* status) {
   int rc = dlog_check(c, n, bits, !points || !out || !status);
   if (rc || n == 0) return rc;
   HIP_TRY(hipSetDevice(c->device));
-  if (!c->dlog_baby_bits) {
+  if (!c->dlog.baby_bits) {
     rc = ensure_dlog_table(c, DLOG_BABY_DEFAULT);
     if (rc) return rc;
   }
-  if (dlog_launches(c, n, bits) > DLOG_MAX_LAUNCHES) return fail(ZKP_ERR_ARG, "the search would take more than 65,536 launches: prepare a larger table or split the call");
+  if (dlog_launches(c->dlog, n, bits) > DLOG_MAX_LAUNCHES) return fail(ZKP_ERR_ARG, "the search would take more than 65,536 launches: prepare a larger table or split the call");
   carve cv;
   const size_t o_pts = cv.take((size_t)n * 32);
   const size_t o_out = cv.take((size_t)n * 8);
@@ -4316,7 +4386,118 @@ int zkp_dlog_base(zkp_ctx* c, uint64_t n, const uint8_t* points, uint32_t bits, 
   char* base = static_cast<char*>(c->ws);
   HIP_TRY(hipMemcpyAsync(base + o_pts, points, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
   prof_begin(c);
-  rc = launch_dlog(c, n, reinterpret_cast<const uint8_t*>(base + o_pts), bits, base, w, reinterpret_cast<uint64_t*>(base + o_out), reinterpret_cast<uint8_t*>(base + o_st));
+  rc = launch_dlog(c, c->dlog, n, reinterpret_cast<const uint8_t*>(base + o_pts), bits, false, base, w, reinterpret_cast<uint64_t*>(base + o_out), reinterpret_cast<uint8_t*>(base + o_st));
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(status, base + o_st, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return ZKP_OK;
+}
+
+// ---- (10) ... to a base of the caller's: the slots, and the search over one of them ----------------------------------------------------------
+static_assert(DLOG_POINT_SLOTS == ZKP_DLOG_SLOTS, "the header's slot count");
+size_t zkp_dlog_slice_order(uint64_t n_slices, int flags, uint64_t i) { return (size_t)dlog_slice_order(n_slices, (flags & ZKP_DLOG_SIGNED) != 0, i); }
+uint32_t zkp_dlog_slice_chunks_signed(uint64_t n) { return (uint32_t)dlog_slice_chunks_signed(n); }
+uint32_t zkp_dlog_point_baby_bits(zkp_ctx* c, uint32_t slot) { return c && slot < DLOG_POINT_SLOTS ? c->dlog_pt[slot].baby_bits : 0u; }
+size_t zkp_dlog_point_last_use(zkp_ctx* c, uint32_t slot) { return c && slot < DLOG_POINT_SLOTS && c->dlog_pt[slot].baby_bits ? (size_t)c->dlog_pt[slot].used : (size_t)0; }
+int zkp_dlog_point_base(zkp_ctx* c, uint32_t slot, uint8_t out[32]) {
+  if (!c || !out) return fail(ZKP_ERR_ARG, "NULL pointer");
+  if (slot >= DLOG_POINT_SLOTS || !c->dlog_pt[slot].baby_bits) return fail(ZKP_ERR_ARG, "no such slot, or the slot is empty");
+  std::memcpy(out, c->dlog_pt[slot].base, 32);
+  return ZKP_OK;
+}
+int zkp_dlog_point_find(zkp_ctx* c, const uint8_t base[32]) {
+  if (!c || !base) return -1;
+  for (uint32_t s = 0; s < DLOG_POINT_SLOTS; ++s)
+    if (c->dlog_pt[s].baby_bits && std::memcmp(c->dlog_pt[s].base, base, 32) == 0) return (int)s;
+  return -1;
+}
+
+int zkp_ctx_release_dlog_point(zkp_ctx* c, uint32_t slot) {
+  if (!c) return fail(ZKP_ERR_ARG, "ctx is NULL");
+  if (slot >= DLOG_POINT_SLOTS) return fail(ZKP_ERR_ARG, "slot must be below ZKP_DLOG_SLOTS");
+  if (c->capturing) return fail(ZKP_ERR_ARG, "graph capture: zkp_ctx_release_dlog_point synchronises");
+  if (c->job.kind) return fail(ZKP_ERR_ARG, "a submitted job is pending on this context: zkp_ctx_job_wait first");
+  if (!c->dlog_pt[slot].baby_bits) return ZKP_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  free_dlog_table(c->dlog_pt[slot], true);
+  ++c->ws_generation;
+  return ZKP_OK;
+}
+
+// The new table is built aside and takes the slot only when all of it exists: a base that does not decode leaves the slot as it was.  (A failed
+// allocation is met after the old table was given back -- the two need not fit side by side -- and leaves the slot empty.)
+int zkp_ctx_prepare_dlog_point(zkp_ctx* c, uint32_t slot, const uint8_t base[32], uint32_t baby_bits) {
+  if (!c || !base) return fail(ZKP_ERR_ARG, "NULL pointer");
+  if (slot >= DLOG_POINT_SLOTS) return fail(ZKP_ERR_ARG, "slot must be below ZKP_DLOG_SLOTS");
+  if (baby_bits < DLOG_BABY_MIN || baby_bits > DLOG_BABY_MAX) return fail(ZKP_ERR_ARG, "baby_bits must be 4 .. 22");
+  if (c->capturing) return fail(ZKP_ERR_ARG, "graph capture: zkp_ctx_prepare_dlog_point synchronises");
+  if (c->job.kind) return fail(ZKP_ERR_ARG, "a submitted job is pending on this context: zkp_ctx_job_wait first");
+  static const uint8_t kIdentity[32] = {};
+  if (std::memcmp(base, kIdentity, 32) == 0) return fail(ZKP_ERR_ARG, "the identity is no base: only the identity is a multiple of it");
+  zkp_ctx::dlog_tab& t = c->dlog_pt[slot];
+  if (t.baby_bits == baby_bits && std::memcmp(t.base, base, 32) == 0) {
+    t.used = ++c->dlog_tick;
+    return ZKP_OK;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  zkp_ctx::dlog_tab fresh;
+  uint32_t valid = 0;
+  int rc = build_point_table(c, base, &fresh.table, &valid);
+  if (rc == ZKP_ERR_OOM && t.baby_bits) {
+    free_dlog_table(t, true);
+    ++c->ws_generation;
+  }
+  if (rc) return rc;
+  if (!valid) return fail(ZKP_ERR_ARG, "the base does not decode");
+  if (t.baby_bits) {
+    free_dlog_table(t, true);
+    ++c->ws_generation;
+  }
+  rc = build_dlog_table(c, fresh, baby_bits);
+  if (rc) {
+    free_dlog_table(fresh, true);
+    return rc;
+  }
+  std::memcpy(fresh.base, base, 32);
+  fresh.used = ++c->dlog_tick;
+  t = fresh;
+  return ZKP_OK;
+}
+
+int zkp_dlog_point_dev(zkp_ctx* c, uint32_t slot, uint64_t n, const uint8_t* d_points, uint32_t bits, int flags, uint64_t* d_out, uint8_t* d_status) {
+  zkp_ctx::dlog_tab* t = nullptr;
+  int rc = dlog_point_check(c, slot, n, bits, flags, !d_points || !d_out || !d_status, &t);
+  if (rc || n == 0) return rc;
+  if (!aligned16(d_points) || (reinterpret_cast<uintptr_t>(d_out) & 7)) return fail(ZKP_ERR_ARG, "d_points must be 16-byte, d_out 8-byte aligned");
+  HIP_TRY(hipSetDevice(c->device));
+  const dlog_ws w = dlog_base_ws(n);
+  rc = ensure_ws(c, w.total);
+  if (rc) return rc;
+  t->used = ++c->dlog_tick;
+  prof_begin(c);
+  return launch_dlog(c, *t, n, d_points, bits, (flags & ZKP_DLOG_SIGNED) != 0, static_cast<char*>(c->ws), w, d_out, d_status);
+}
+int zkp_dlog_point(zkp_ctx* c, uint32_t slot, uint64_t n, const uint8_t* points, uint32_t bits, int flags, uint64_t* out, uint8_t* status) {
+  zkp_ctx::dlog_tab* t = nullptr;
+  int rc = dlog_point_check(c, slot, n, bits, flags, !points || !out || !status, &t);
+  if (rc || n == 0) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  carve cv;
+  const size_t o_pts = cv.take((size_t)n * 32);
+  const size_t o_out = cv.take((size_t)n * 8);
+  const size_t o_st = cv.take((size_t)n);
+  const dlog_ws w = dlog_base_ws(n, cv.off);
+  rc = ensure_ws(c, w.total);
+  if (rc) return rc;
+  t->used = ++c->dlog_tick;
+  char* base = static_cast<char*>(c->ws);
+  HIP_TRY(hipMemcpyAsync(base + o_pts, points, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
+  prof_begin(c);
+  rc = launch_dlog(c, *t, n, reinterpret_cast<const uint8_t*>(base + o_pts), bits, (flags & ZKP_DLOG_SIGNED) != 0, base, w, reinterpret_cast<uint64_t*>(base + o_out),
+                   reinterpret_cast<uint8_t*>(base + o_st));
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipMemcpyAsync(status, base + o_st, (size_t)n, hipMemcpyDeviceToHost, c->stream));

@@ -30,6 +30,7 @@ ZKP_PT_ADD, ZKP_PT_SUB = 0, 1               # zkp_add_points' op
 ZKP_SC_SUM, ZKP_SC_PRODUCT, ZKP_SC_DOT = 0, 1, 2     # zkp_sc_reduce's op
 ZKP_SCAN_INCLUSIVE, ZKP_SCAN_EXCLUSIVE = 0, 1        # zkp_sc_scan's and zkp_scan_points' mode
 ZKP_DLOG_FOUND, ZKP_DLOG_INVALID, ZKP_DLOG_NOT_FOUND = 0, 1, 2      # zkp_dlog_base's status
+ZKP_DLOG_SLOTS, ZKP_DLOG_SIGNED = 8, 1           # zkp_ctx_prepare_dlog_point's slots, zkp_dlog_point's flag
 ZKP_OPT_BATCH_ENCODE_MIN = 1
 (ZKP_OPT_COMB_TEETH, ZKP_OPT_CT_SINGLE_USE_TABLES, ZKP_OPT_TRANSCRIPT_LANES, ZKP_OPT_DEV_OVERLAP, ZKP_OPT_GROUPED_COMB, ZKP_OPT_TABLES_LANE,
  ZKP_OPT_FUSE_TABLES_TRANSCRIPT) = 2, 3, 4, 5, 6, 7, 8
@@ -80,6 +81,14 @@ def _u8(a, shape_last: int) -> np.ndarray:
     if a.ndim != 2 or a.shape[1] != shape_last:
         raise ValueError(f"expected uint8 array of shape [n][{shape_last}], got {a.shape}")
     return a
+
+
+def _base32(base) -> np.ndarray:
+    """one encoding, bytes or a uint8 row, as a contiguous uint8 [32]"""
+    a = np.frombuffer(bytes(base), np.uint8) if isinstance(base, (bytes, bytearray)) else np.ascontiguousarray(base, dtype=np.uint8).reshape(-1)
+    if a.shape != (32,):
+        raise ValueError(f"expected one encoding of 32 bytes, got {a.shape}")
+    return a.copy()
 
 
 def _ptr(a: Optional[np.ndarray]):
@@ -507,6 +516,37 @@ class Engine:
         _check(self._lib.zkp_dlog_base(self._h, n, _ptr(points), bits, _ptr(out), _ptr(status)), "zkp_dlog_base")
         return out, status
 
+    # ---- ... to a base of the caller's, signed ranges: one table per slot, ZKP_DLOG_SLOTS slots per context ----
+    def prepare_dlog_point(self, slot: int, base, baby_bits: int) -> None:
+        """build (or replace) slot `slot` for the base with encoding `base` (32 bytes): the encodings of i G for i < 2**baby_bits, baby_bits in
+        4 .. 22.  The same base and size again is a no-op."""
+        base = _base32(base)
+        _check(self._lib.zkp_ctx_prepare_dlog_point(self._h, slot, _ptr(base), baby_bits), "zkp_ctx_prepare_dlog_point")
+
+    def release_dlog_point(self, slot: int) -> None:
+        _check(self._lib.zkp_ctx_release_dlog_point(self._h, slot), "zkp_ctx_release_dlog_point")
+
+    def dlog_point_slots(self):
+        """[(base bytes or None, baby_bits)] for every slot; (None, 0) is an empty one"""
+        out = []
+        for slot in range(ZKP_DLOG_SLOTS):
+            bb = int(self._lib.zkp_dlog_point_baby_bits(self._h, slot))
+            base = np.zeros(32, np.uint8)
+            if bb:
+                _check(self._lib.zkp_dlog_point_base(self._h, slot, _ptr(base)), "zkp_dlog_point_base")
+            out.append((base.tobytes() if bb else None, bb))
+        return out
+
+    def dlog_point(self, slot: int, points, bits: int, signed: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        """points [n][32] = encode(k G), G the slot's base -> (k [n], status uint8 [n]) as dlog_base; signed: k in [-2**(bits - 1), 2**(bits - 1))
+        as np.int64, else k < 2**bits as np.uint64"""
+        points = _u8(points, 32)
+        n = len(points)
+        out = np.zeros(n, np.uint64)
+        status = np.zeros(n, np.uint8)
+        _check(self._lib.zkp_dlog_point(self._h, slot, n, _ptr(points), bits, ZKP_DLOG_SIGNED if signed else 0, _ptr(out), _ptr(status)), "zkp_dlog_point")
+        return (out.view(np.int64) if signed else out), status
+
     def debug_sha512(self, data, offsets) -> np.ndarray:
         """the SHA-512 stage alone (test-hook build): CSR batch -> digests [n][64]"""
         self._need_hooks("zkp_debug_sha512")
@@ -655,6 +695,10 @@ class Engine:
     def dlog_base_dev(self, n, d_points, bits, d_out, d_status) -> None:
         """zkp_dlog_base_dev: d_points [n][32] (16-byte aligned) -> d_out u64 [n], d_status u8 [n]; queued on the context's stream"""
         _check(self._lib.zkp_dlog_base_dev(self._h, n, d_points, bits, d_out, d_status), "zkp_dlog_base_dev")
+
+    def dlog_point_dev(self, slot, n, d_points, bits, d_out, d_status, signed: bool = False) -> None:
+        """zkp_dlog_point_dev: as dlog_base_dev over the slot's base; signed: d_out holds int64"""
+        _check(self._lib.zkp_dlog_point_dev(self._h, slot, n, d_points, bits, ZKP_DLOG_SIGNED if signed else 0, d_out, d_status), "zkp_dlog_point_dev")
 
     def transcripts_append_message_dev(self, n, shared_initial, d_ts_in, d_ts_out, label: bytes, d_msgs, msgs_len, d_offsets) -> None:
         """zkp_transcripts_append_message_dev: blobs 16-byte aligned (d_ts_out may be d_ts_in when not shared), d_offsets u64 [n + 1] 8-byte

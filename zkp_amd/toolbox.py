@@ -903,6 +903,21 @@ def basepoint_dlog(eng, points, bits: int, threads: int = 0):
     return out, status
 
 
+def point_dlog(eng, base, points, bits: int, signed: bool = False, threads: int = 0):
+    """basepoint_dlog to the base with encoding `base` (32 bytes): points [n][32] -> (k [n], status uint8 [n]) with encode(k G) == points[i]; signed:
+    k in [-2**(bits - 1), 2**(bits - 1)) as np.int64, else k < 2**bits as np.uint64.  On an engine the base takes one of the context's slots
+    (Engine.prepare_dlog_point picks the size first; the default is 2**16 rows)."""
+    from .engine import _base32, _u8
+    points = _u8(points, 32)
+    base = _base32(base)
+    n = len(points)
+    out = np.zeros(n, np.uint64)
+    status = np.zeros(n, np.uint8)
+    _raise(lib().zkp_point_dlog_batch(None if eng is None else eng._h, _p(base), n, _p(points), bits, 1 if signed else 0, _p(out), _p(status), threads),
+           "zkp_point_dlog_batch")
+    return (out.view(np.int64) if signed else out), status
+
+
 def set_dlog_baby_bits(baby_bits: int) -> None:
     """the size of the host backend's baby-step table (2**baby_bits rows, 4 .. 22) for later basepoint_dlog calls"""
     _raise(lib().zkp_toolbox_set_dlog_baby_bits(baby_bits), "zkp_toolbox_set_dlog_baby_bits")
