@@ -1037,6 +1037,11 @@ int zkp_debug_ragged_blocks(const uint8_t* transcripts, uint32_t N, uint32_t* id
 int zkp_debug_fill_workspace(zkp_ctx* ctx, size_t min_bytes, uint32_t word);
 /* zkp_debug_ws_bytes: the size of the device workspace as it stands (0 before the first call): grow-only, the largest call's need plus an eighth. */
 size_t zkp_debug_ws_bytes(zkp_ctx* ctx);
+/* zkp_debug_ws_count: waits for both of the context's streams, copies the whole workspace to the host and returns how often the len bytes at
+ * `needle` occur in it (at any byte offset, overlapping occurrences counted).  What "zeroes the staging on every way out" promises can be read
+ * back with it.  (size_t)ZKP_ERR_ARG for a NULL argument, len = 0, during a capture or with a job pending; (size_t)ZKP_ERR_HIP when a stream
+ * reports an error or the copy fails; 0 while there is no workspace. */
+size_t zkp_debug_ws_count(zkp_ctx* ctx, const uint8_t* needle, size_t len);
 enum { ZKP_TESTOPT_DUMMY_LAUNCHES = 1001, ZKP_TESTOPT_GENERIC_CLASSIFIER = 1002, ZKP_TESTOPT_WAVE_CYCLES = 1003, ZKP_TESTOPT_PIP_MERGE = 1004, ZKP_TESTOPT_VOUCH_REDUCED = 1005 };
 #endif
 

@@ -1,7 +1,8 @@
 """The witness RNG, challenge scalars and point appends on the MI355X: k_strobe_witness_rng, k_strobe_challenge_scalars and
 k_strobe_append_points behind their host-pointer and _dev entry points, the toolbox routing, graph capture, and the transcripts they leave
 going into the fused prover.  Every result equals the host route (the same lane code on the host threads, which
-tests/test_host_transcript_rng.py holds against the oracle model and host Merlin) byte for byte.  Inputs: tests/transcript_rng_cases.py."""
+tests/test_host_transcript_rng.py holds against the oracle model and host Merlin) byte for byte.  Inputs: tests/transcript_rng_cases.py.
+The host-pointer witness RNG's promise to zero its staging of entropy and witnesses is read back from the workspace (zkp_debug_ws_count)."""
 import os
 import subprocess
 import sys
@@ -317,6 +318,49 @@ def test_device_appended_points_feed_fused_prove_dev_and_verify(eng):
     assert not d_st.cpu().numpy().any() and not d_rej.cpu().numpy().any()
     assert (d_chal.cpu().numpy() == chal).all() and (d_resp.cpu().numpy() == resp).all() and (d_coms.cpu().numpy() == coms).all()
     assert (d_ts.cpu().numpy()[:, :203] == ts[:, :203]).all()
+
+
+def _windows_found(e, rows, offsets=(0, 16)):
+    """(row, offset) of every 16-byte window of `rows` that occurs somewhere in the workspace of e"""
+    return [(i, o) for i, r in enumerate(rows) for o in offsets if e.debug_ws_count(r[o:o + 16].tobytes())]
+
+
+@pytest.mark.parametrize("mode,count", ((ZKP_RNG_SCALARS, 2), (ZKP_RNG_BYTES, 64)), ids=("scalars", "bytes"))
+def test_witness_rng_wipes_its_staging_of_entropy_and_witnesses_and_not_the_outputs(mode, count):
+    """include/zkp_mi355x.h, zkp_transcripts_witness_rng (host-pointer form): the staging of entropy and witnesses is zeroed on every way out,
+    the outputs' staging is not.  Read back with zkp_debug_ws_count (test-hook build): after the call no half of any witness or entropy row is
+    in the workspace, while output rows are (the control: a search of the wrong place finds neither), and a fill with zeros removes those too.
+    The success path is the only way out that valid arguments reach once secrets are on the device: after the uploads the call can fail only
+    where the HIP runtime does."""
+    from zkp_amd.engine import Engine, ZkpError
+    n, m, wlen = 65, 2, 32
+    rng = np.random.default_rng(4656 + mode)
+    S = tiled_states(n)
+    wit = rng.integers(0, 256, size=(n, m, wlen), dtype=np.uint8)
+    ent = rng.integers(0, 256, size=(n, 32), dtype=np.uint8)
+    secret_rows = np.concatenate([wit.reshape(-1, wlen), ent])
+    f = T.witness_rng_scalars if mode == ZKP_RNG_SCALARS else T.witness_rng_bytes
+    want = f(None, S, wit, count, ent, b"w")
+    e = Engine(0, test_hooks=True)
+    try:
+        assert e.debug_ws_count(bytes(16)) == 0                                # no workspace yet
+        got = e.transcripts_witness_rng(S.copy(), b"w", wit, ent, mode, count)
+        assert (got == want).all()
+        assert e.debug_ws_bytes() >= 208 * n + secret_rows.size + got.size
+        assert _windows_found(e, secret_rows) == []
+        out_rows = got.reshape(n, -1)
+        assert len(_windows_found(e, out_rows, (0,))) == n                     # every output row is still there ...
+        assert e.debug_ws_count(bytes(16)) >= 1                                # ... and zeros stand where the secrets stood
+        e.debug_fill_workspace(0, 0)
+        assert _windows_found(e, out_rows, (0,)) == []
+        e.capture_begin()
+        try:
+            with pytest.raises(ZkpError):
+                e.debug_ws_count(bytes(16))
+        finally:
+            e.capture_abort()
+    finally:
+        e.close()
 
 
 def test_or_ballot_example_runs_as_a_child_process():

@@ -14,7 +14,46 @@ each call, and the call must still give
 
 The shapes are the smallest that reach each layout ("Workspace regions and their first writers").  The fill is sized so that
 no case grows the workspace after it -- a call that had to reallocate would see fresh memory again -- and zkp_debug_ws_bytes is compared
-after every call with its value right after the fill."""
+after every call with its value right after the fill.
+
+Entry point that calls ensure_ws (include/zkp_mi355x.h sections 1 to 13) -> the test that fills the workspace in front of it.  "here" is this
+module; the other files hold a test_results_do_not_depend_on_what_the_workspace_held of their own.
+
+  zkp_msm_many                                                    here: test_msm_many
+  zkp_msm_optional, zkp_msm_optional_dev (msm_optional_impl)      here: test_msm_optional (the host-pointer form; _dev carves through the same function)
+  zkp_decode_check, zkp_encode_many                               here: test_decode_check_and_encode_many
+  zkp_fused_prove_dev                                             here: test_prove
+  zkp_fused_verify_compact_dev, zkp_fused_verify_batchable_dev    here: test_verify
+  zkp_fused_batch_verify_dev, zkp_fused_batch_verify_many_dev     here: test_batch_verify_one_batch, test_batch_verify_three_batches
+  zkp_batch_check                                                 here: test_batch_check (the raw call on the test-hook context)
+  the host-buffer jobs (prove_job, verify_compact_job,            here: test_ragged (the _ragged calls are these jobs over class programs)
+    verify_batchable_job, batch_verify_job)
+  zkp_fused_hash_to_group_ragged                                  here: test_ragged[hash]
+  zkp_fused_hash_to_group (aligned)                               here: test_aligned_hash_to_group
+  zkp_from_uniform_bytes, zkp_hash_from_bytes_sha512,             here: test_other_calls
+    zkp_sc_hash_from_bytes_sha512 (hash_from_bytes_host),
+    zkp_sc_random
+  zkp_sc_invert, zkp_sc_from_wide, zkp_sc_muladd                  here: test_scalar_calls (every stride combination at n = 257)
+  zkp_transcripts_append_message, _challenge_bytes,               here: test_transcript_calls
+    _witness_rng, _challenge_scalars, _append_points
+  zkp_mul_base, zkp_mul_points                                    tests/test_gpu_point_mul.py
+  zkp_add_points, zkp_sum_points                                  tests/test_gpu_point_sum.py
+  zkp_msm_segments                                                tests/test_gpu_msm_segments.py
+  zkp_sc_reduce                                                   tests/test_gpu_scalar_reduce.py
+  zkp_sc_scan, zkp_scan_points                                    tests/test_gpu_scan.py
+  zkp_dlog_base                                                   tests/test_gpu_dlog.py
+  zkp_dlog_point                                                  tests/test_gpu_dlog_point.py
+  zkp_mul_points_dev, zkp_sum_points_dev, zkp_msm_segments_dev,   not filled directly: each carves the layout of its host-pointer form (above) less
+    zkp_sc_reduce_dev, zkp_sc_scan_dev, zkp_scan_points_dev,      the staging of the operands, which the caller owns, and launches through the same
+    zkp_dlog_base_dev, zkp_dlog_point_dev, zkp_msm_many_dev,      launcher; those files fill the workspace in front of the host-pointer form only
+    zkp_sc_random_dev, zkp_hash_from_bytes_sha512_dev             (zkp_msm_many_dev: test_msm_many[outputs2048_dev] here does run the _dev form)
+  zkp_debug_quad_selftest, zkp_debug_row_selftest                 test-hook probes: every word they read they uploaded in the same call
+  carve nothing (not tested): the _dev forms of section 7 (zkp_transcripts_*_dev) and of zkp_sc_invert / _from_wide / _muladd /
+    _sc_hash_from_bytes_sha512, zkp_from_uniform_bytes_dev, zkp_mul_base_dev, zkp_add_points_dev; zkp_ctx_prepare_fixed_points,
+    zkp_ctx_prepare_dlog and zkp_ctx_prepare_dlog_point build into allocations of their own
+
+The transcript calls are checked against oracle.model's Merlin in Python started from the blob (tests/product_history_cases.py), the scalar
+calls against Python integers."""
 import hashlib
 
 import numpy as np
@@ -22,6 +61,7 @@ import pytest
 
 from oracle import cbind as C
 from oracle import model as M
+from tests import product_history_cases as PH
 from tests import test_gpu_thresholds as TH
 from tests.test_host_scalar_ops import chacha_block, ints, want_hash
 
@@ -488,6 +528,90 @@ def test_batch_verify_three_batches(engines, word):
         assert (a == f).all(), "%s differs from a fresh context's" % what
 
 
+# ---- zkp_batch_check: the coefficient build on the device with a carve of its own (partial sums, incidence words, n + 1 rows of operands) ----
+def _batch_check(eng, b, n, minus_c, responses, coms, w):
+    """-> (out [32], status, coefficient vector [n_static + (n_instance + n_constraints) n][32]); out and status start as nonzero garbage"""
+    import ctypes
+    fst = b["fst"]
+    total = fst.n_static + (fst.n_instance + len(fst._lhs)) * n
+    out, status, coeffs = np.full(32, 5, np.uint8), ctypes.c_int(5), np.full((total, 32), 5, np.uint8)
+    keep = [np.ascontiguousarray(a, np.uint8) for a in (minus_c, responses, w, b["common"], b["inst"], coms)]
+    rc = eng._lib.zkp_batch_check(eng._h, ctypes.byref(fst.c.shape), n, *(a.ctypes.data for a in keep), out.ctypes.data, ctypes.byref(status), coeffs.ctypes.data)
+    assert rc == 0, eng._lib.zkp_last_error()
+    return out, status.value, coeffs
+
+
+def _batch_coefficients(fst, n, minus_c, responses, w):
+    """batch_verifier.rs:173-223 in Python integers: static coefficients, then the matrix row-major (instance rows, then one row -r_ij per constraint)"""
+    ns, ni, nc = fst.n_static, fst.n_instance, len(fst._lhs)
+    val = lambda row: int.from_bytes(bytes(row), "little")
+    static, mat = [0] * ns, [[0] * n for _ in range(ni + nc)]
+
+    def add(pid, j, v):
+        if pid < ns:
+            static[pid] = (static[pid] + v) % M.L
+        else:
+            mat[pid - ns][j] = (mat[pid - ns][j] + v) % M.L
+    for j in range(n):
+        mc = val(minus_c[j])
+        for i in range(nc):
+            r = val(w[i][j])
+            add(int(fst._lhs[i]), j, r * mc)
+            for t in range(int(fst._off[i]), int(fst._off[i + 1])):
+                add(int(fst._pt[t]), j, r * val(responses[j][int(fst._sc[t])]))
+            mat[ni + i][j] = (M.L - r) % M.L
+    return static + [v for row in mat for v in row]
+
+
+@pytest.mark.parametrize("word", WORDS, ids=lambda w: "fill%x" % w)
+@pytest.mark.parametrize("n,pip", ((38, 0), (39, 1), (257, 1)))
+def test_batch_check(engines, n, pip, word):
+    """N = 38 (191 operands: the term path), 39 (196: Pippenger) and 257 (two blocks of partial sums for the static coefficient): the coefficient
+    vector equals Python integers, the point is the C oracle's MSM over it, the verdicts are the C oracle's batch verifier's"""
+    eh, es = engines
+    b = _batch(es, "dleq", n)
+    fst = b["fst"]
+
+    def make():
+        from tests.test_host_scalar_ops import rows
+        rng = np.random.default_rng(n + 4)
+        w = rng.integers(0, 256, size=(2, n, 16), dtype=np.uint8)
+        minus_c = rows([(M.L - int.from_bytes(bytes(c), "little")) % M.L for c in b["chal"]])
+        bad = b["resp"].copy()
+        bad[n // 2, 0, 0] ^= 1
+        junk = b["coms"].copy()
+        junk[n - 1, 1] = JUNK
+        runs = {"good": (b["resp"], b["coms"]), "bad response": (bad, b["coms"]), "undecodable commitment": (b["resp"], junk)}
+        want = {}
+        for k, (r, c) in runs.items():
+            verdict = C.batch_verify(b["cst"], b"thresholds", n, b["inst"], b["common"], c, r, w)
+            coeffs = rows(_batch_coefficients(fst, n, minus_c, r, w))
+            pts = np.concatenate([b["common"], b["inst"].reshape(-1, 32), np.ascontiguousarray(c.transpose(1, 0, 2)).reshape(-1, 32)])
+            want[k] = (verdict, coeffs, C.msm_optional(coeffs, pts))
+        assert want["good"][0] == 0 and want["good"][2] == IDENTITY and want["bad response"][0] != 0 and want["bad response"][2] not in (None, IDENTITY)
+        assert want["undecodable commitment"][0] != 0 and want["undecodable commitment"][2] is None
+        ef = _fresh()
+        try:
+            fresh = {k: _batch_check(ef, b, n, minus_c, r, c, w) for k, (r, c) in runs.items()}
+        finally:
+            ef.close()
+        return w, minus_c, runs, want, fresh
+
+    w, minus_c, runs, want, fresh = _once(("batch_check", n), make)
+    for name, (r, c) in runs.items():
+        _fill(eh, CAP, word)
+        out, st, coeffs = _batch_check(eh, b, n, minus_c, r, c, w)
+        assert eh.last_schedule().get("opt_pip") == pip, eh.last_schedule()
+        _, want_coeffs, want_pt = want[name]
+        assert (coeffs == want_coeffs).all(), "%s: coefficients differ in rows %s" % (name, np.flatnonzero((coeffs != want_coeffs).any(axis=1))[:8])
+        if want_pt is None:
+            assert st == 1 and not out.any(), (name, st, out)
+        else:
+            assert st == 0 and out.tobytes() == want_pt, (name, st, out)
+        for what, a, f in zip(("output", "status", "coefficients"), (out, st, coeffs), fresh[name]):
+            assert np.array_equal(a, f), "%s: %s differs from a fresh context's" % (name, what)
+
+
 # ---- one ragged call per flow: 65 proofs, three STROBE position classes ---------------------------------------------------------------
 def _ragged_inputs(es):
     def make():
@@ -616,6 +740,205 @@ def test_other_calls(engines, op, word):
     else:
         assert (got == want[op]).all()
     assert (got == fresh).all(), "a fresh context computes other bytes"
+
+
+# ---- the transcript calls, the rest of the scalar calls and the aligned hash to group: staged through the workspace by their host-pointer forms ----
+def _strobe_inputs(n):
+    """n transcripts at a mix of positions (row 0 at 165, the last byte of a block) and what the calls below take besides them"""
+    def make():
+        rng = np.random.default_rng(1000 + n)
+        msgs = [rng.bytes((0, 60, 167)[j % 3]) for j in range(n)]
+        wit, ent = rng.integers(0, 256, size=(n, 2, 32), dtype=np.uint8), rng.integers(0, 256, size=(n, 32), dtype=np.uint8)
+        pts = rng.integers(0, 256, size=(n, 32), dtype=np.uint8)
+        pts[:, 0] |= 1
+        pts[[1, n // 2]] = 0                                                     # the identity's encoding: refused under validate
+        ts = PH.states(n, n)
+        assert ts[0, 200] == 165 and len(set(ts[:, 200].tolist())) >= 40
+        return dict(ts=ts, msgs=msgs, wit=wit, ent=ent, pts=pts)
+    return _once(("strobe", n), make)
+
+
+STROBE_OPS = ("append_message", "challenge_bytes_0", "challenge_bytes_32", "challenge_bytes_200", "witness_rng_scalars", "witness_rng_bytes",
+              "challenge_scalars", "append_points", "append_points_validate")
+
+
+def _strobe_want(op, d):
+    """oracle.model's Merlin in Python, from the blob: -> the tuple _strobe_call returns"""
+    ts = d["ts"]
+    if op == "append_message":
+        return (PH.model_append(ts, b"msg", d["msgs"]),)
+    if op.startswith("challenge_bytes"):
+        return PH.model_challenge(ts, b"chal", int(op.rsplit("_", 1)[1]))
+    if op.startswith("witness_rng"):
+        mode, count = (0, 2) if op.endswith("scalars") else (1, 200)
+        return PH.model_rng(ts, b"w", d["wit"], d["ent"], mode, count), ts
+    if op == "challenge_scalars":
+        return PH.model_challenge_scalars(ts, b"chal")
+    return PH.model_append_points(ts, b"blindcom", b"A", d["pts"], op.endswith("validate"))
+
+
+def _strobe_call(eng, op, d):
+    from zkp_amd.engine import messages_csr
+    ts = d["ts"].copy()
+    if op == "append_message":
+        return (eng.transcripts_append_message(ts, b"msg", *messages_csr(d["msgs"])),)
+    if op.startswith("challenge_bytes"):
+        return eng.transcripts_challenge_bytes(ts, b"chal", int(op.rsplit("_", 1)[1])), ts
+    if op.startswith("witness_rng"):
+        mode, count = (0, 2) if op.endswith("scalars") else (1, 200)
+        return eng.transcripts_witness_rng(ts, b"w", d["wit"], d["ent"], mode, count), ts
+    if op == "challenge_scalars":
+        return eng.transcripts_challenge_scalars(ts, b"chal"), ts
+    return eng.transcripts_append_points(ts, b"blindcom", b"A", d["pts"], op.endswith("validate")), ts
+
+
+@pytest.mark.parametrize("word", WORDS, ids=lambda w: "fill%x" % w)
+@pytest.mark.parametrize("n", (65, 257))
+@pytest.mark.parametrize("op", STROBE_OPS)
+def test_transcript_calls(engines, op, n, word):
+    eh, _ = engines
+    d = _strobe_inputs(n)
+
+    def make():
+        ef = _fresh()
+        try:
+            return _strobe_want(op, d), _strobe_call(ef, op, d)
+        finally:
+            ef.close()
+
+    want, fresh = _once(("strobe", op, n), make)
+    if op == "append_points_validate":
+        assert np.flatnonzero(want[0]).tolist() == [1, n // 2]
+    _fill(eh, CAP, word)
+    got = _strobe_call(eh, op, d)
+    for what, a, e, f in zip(("result", "transcripts"), got, want, fresh):
+        assert a.shape == e.shape and (a == e).all(), "%s differs from oracle.model: rows %s" % (what, np.flatnonzero((a != e).reshape(n, -1).any(axis=1))[:8])
+        assert (a == f).all(), "%s: a fresh context computes other bytes" % what
+
+
+SCALAR_OPS = ["invert", "from_wide"] + ["muladd_%d%d%d" % s for s in ((0, 0, 0), (0, 0, 1), (0, 1, 0), (0, 1, 1), (1, 0, 0), (1, 0, 1), (1, 1, 0), (1, 1, 1))]
+
+
+def _scalar_inputs(n):
+    def make():
+        from tests.scalar_edge_cases import VALUES, random_256
+        from tests.test_host_scalar_ops import WIDE_EDGES, muladd_operands, rows
+        inv = ([0, 1, M.L - 1, M.L, M.L + 1, 2**256 - 1] + VALUES + random_256(n, n))[:n]
+        rng = np.random.default_rng(n)
+        wide = (WIDE_EDGES + [int.from_bytes(rng.bytes(64), "little") for _ in range(n)])[:n]
+        recs = muladd_operands()[:n]
+        return dict(inv=inv, wide=wide, recs=recs, a=rows([r[0] for r in recs]), b=rows([r[1] for r in recs]), c=rows([r[2] for r in recs]),
+                    inv_rows=rows(inv), wide_rows=rows(wide, 64))
+    return _once(("scalars", n), make)
+
+
+def _scalar_call(eng, op, d):
+    if op == "invert":
+        return eng.scalar_invert(d["inv_rows"])
+    if op == "from_wide":
+        return eng.scalar_from_wide(d["wide_rows"])
+    sa, sb, sc = (int(ch) for ch in op[-3:])
+    n = len(d["a"])
+    out = np.zeros((n, 32), np.uint8)
+    p = lambda x: x.ctypes.data
+    assert eng._lib.zkp_sc_muladd(eng._h, n, p(d["a"]), sa, p(d["b"]), sb, p(d["c"]), sc, p(out)) == 0
+    return out
+
+
+def _scalar_want(op, d):
+    if op == "invert":
+        return [pow(v % M.L, M.L - 2, M.L) for v in d["inv"]]
+    if op == "from_wide":
+        return [v % M.L for v in d["wide"]]
+    sa, sb, sc = (int(ch) for ch in op[-3:])
+    r = d["recs"]
+    return [(r[i * sa][0] * r[i * sb][1] + r[i * sc][2]) % M.L for i in range(len(r))]
+
+
+SCALAR_PARAMS = [(op, n) for op in SCALAR_OPS for n in (65, 257) if n == 257 or op in ("invert", "from_wide", "muladd_111")]
+
+
+@pytest.mark.parametrize("word", WORDS, ids=lambda w: "fill%x" % w)
+@pytest.mark.parametrize("op,n", SCALAR_PARAMS, ids=["%s-%d" % p for p in SCALAR_PARAMS])
+def test_scalar_calls(engines, op, n, word):
+    eh, _ = engines
+    d = _scalar_inputs(n)
+
+    def make():
+        ef = _fresh()
+        try:
+            return _scalar_call(ef, op, d)
+        finally:
+            ef.close()
+
+    fresh = _once(("scalars", op, n), make)
+    _fill(eh, CAP, word)
+    got = _scalar_call(eh, op, d)
+    assert ints(got) == _scalar_want(op, d)
+    assert (got == fresh).all(), "a fresh context computes other bytes"
+
+
+def _aligned_hash(eng, ts0):
+    ts, out = ts0.copy(), np.zeros((len(ts0), 32), np.uint8)
+    assert eng._lib.zkp_fused_hash_to_group(eng._h, len(ts), ts.ctypes.data, b"output", out.ctypes.data) == 0
+    return out, ts
+
+
+@pytest.mark.parametrize("word", WORDS, ids=lambda w: "fill%x" % w)
+@pytest.mark.parametrize("n", (65, 257))
+def test_aligned_hash_to_group(engines, n, word):
+    """zkp_fused_hash_to_group on transcripts that stand at ONE position (test_ragged has the ragged form), above the toolbox's fused threshold"""
+    eh, _ = engines
+
+    def make():
+        from zkp_amd import toolbox as T
+        assert n >= T.get_fused_min_batch()
+        rng = np.random.default_rng(n + 11)
+        ts0 = T.append_messages(b"residue", b"msg", [rng.bytes(20) for _ in range(n)])
+        assert len({bytes(r[200:203]) for r in ts0}) == 1 and len({bytes(r) for r in ts0}) == n
+        wide, adv = PH.model_challenge(ts0, b"output", 64)
+        want = np.frombuffer(b"".join(C.from_uniform_bytes(w.tobytes()) for w in wide), np.uint8).reshape(n, 32)
+        ef = _fresh()
+        try:
+            fresh = _aligned_hash(ef, ts0)
+        finally:
+            ef.close()
+        return ts0, (want, adv), fresh
+
+    ts0, want, fresh = _once(("aligned_hash", n), make)
+    _fill(eh, CAP, word)
+    got = _aligned_hash(eh, ts0)
+    for what, a, e, f in zip(("points", "transcripts"), got, want, fresh):
+        assert (a[:, :203] == e[:, :203]).all(), "%s differ from oracle.model and the C oracle's map" % what
+        assert (a == f).all(), "%s: a fresh context computes other bytes" % what
+
+
+@pytest.mark.parametrize("word", WORDS, ids=lambda w: "fill%x" % w)
+def test_decode_check_and_encode_many(engines, word):
+    """valid encodings with the ones RFC 9496 rejects between them: statuses = the C oracle's, and encode(decode(P)) = P"""
+    eh, _ = engines
+
+    def make():
+        from tests import point_mul_cases as PC
+        pts = PC.tiled(PC.pair_operands()[1][-120:], 257)
+        want = C.decode_check(pts)
+        assert 0 < int(want.sum()) < len(pts)
+        ef = _fresh()
+        try:
+            st, xyzt = ef.decode_check(pts, want_coords=True)
+            fresh = (st, ef.encode_many(xyzt))
+        finally:
+            ef.close()
+        return pts, want, fresh
+
+    pts, want, fresh = _once(("decode_encode",), make)
+    _fill(eh, CAP, word)
+    st, xyzt = eh.decode_check(pts, want_coords=True)
+    assert (st == want).all() and (st == fresh[0]).all()
+    _fill(eh, CAP, word)
+    enc = eh.encode_many(xyzt)
+    ok = want == 0
+    assert (enc[ok] == pts[ok]).all() and (enc[ok] == fresh[1][ok]).all()     # (the coordinates of a row that does not decode are unspecified)
 
 
 def test_fill_is_refused_during_a_capture_and_moves_the_workspace_generation(engines):

@@ -4838,6 +4838,28 @@ int zkp_debug_fill_workspace(zkp_ctx* c, size_t min_bytes, uint32_t word) {
 }
 // the bytes of the workspace as it stands (what the largest call so far asked for, plus ensure_ws's eighth)
 size_t zkp_debug_ws_bytes(zkp_ctx* c) { return c ? c->ws_bytes : 0; }
+// how often the len bytes at needle occur in the workspace as it stands (read back to the host; nothing on the device changes)
+size_t zkp_debug_ws_count(zkp_ctx* c, const uint8_t* needle, size_t len) {
+  const size_t bad = (size_t)(ptrdiff_t)ZKP_ERR_ARG;
+  if (!c || !needle || !len) return fail(ZKP_ERR_ARG, "bad argument"), bad;
+  if (c->capturing) return fail(ZKP_ERR_ARG, "graph capture: zkp_debug_ws_count synchronises"), bad;
+  if (c->job.kind) return fail(ZKP_ERR_ARG, "a submitted job is pending on this context: zkp_ctx_job_wait first"), bad;
+  if (!c->ws_bytes || len > c->ws_bytes) return 0;
+  if (hipSetDevice(c->device) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess ||
+      (c->side_stream && hipStreamSynchronize(c->side_stream) != hipSuccess))
+    return fail(ZKP_ERR_HIP, "zkp_debug_ws_count: the context's streams report an error"), (size_t)(ptrdiff_t)ZKP_ERR_HIP;
+  std::vector<uint8_t> host(c->ws_bytes);
+  if (hipMemcpy(host.data(), c->ws, c->ws_bytes, hipMemcpyDeviceToHost) != hipSuccess)
+    return fail(ZKP_ERR_HIP, "zkp_debug_ws_count: hipMemcpy"), (size_t)(ptrdiff_t)ZKP_ERR_HIP;
+  size_t count = 0;
+  const uint8_t *p = host.data(), *end = host.data() + host.size();
+  while ((p = static_cast<const uint8_t*>(memchr(p, needle[0], (size_t)(end - p) - (len - 1))) ) != nullptr) {
+    if (memcmp(p, needle, len) == 0) ++count;
+    ++p;
+    if ((size_t)(end - p) < len) break;
+  }
+  return count;
+}
 #endif
 
 int zkp_encode_many(zkp_ctx* c, uint64_t n, const uint8_t* xyzt, uint8_t* out) {

@@ -603,6 +603,16 @@ class Engine:
         self._need_hooks("zkp_debug_ws_bytes")
         return int(self._lib.zkp_debug_ws_bytes(self._h))
 
+    def debug_ws_count(self, needle) -> int:
+        """(test-hook build) how often the bytes of `needle` occur in the device workspace as it stands, read back to the host
+        (zkp_debug_ws_count); raises inside a capture"""
+        self._need_hooks("zkp_debug_ws_count")
+        buf = np.frombuffer(bytes(needle), np.uint8).copy()
+        n = int(self._lib.zkp_debug_ws_count(self._h, _ptr(buf), len(buf)))
+        if n >= 1 << 63:                                      # (size_t)ZKP_ERR_*
+            raise ZkpError(f"zkp_debug_ws_count failed with code {n - (1 << 64)}: {self._lib.zkp_last_error().decode()}")
+        return n
+
     def prepare_fixed_points(self, encodings) -> None:
         """Hint: these points (the statement's common / static points) will be referenced by many terms."""
         encodings = _u8(encodings, 32)
