@@ -964,6 +964,65 @@ int zkp_scan_points_dev(zkp_ctx* ctx, int mode, uint32_t n_seg, const uint32_t* 
 uint32_t zkp_scan_points_group(void);
 uint32_t zkp_scan_points_launches(uint32_t n_terms); /* decode, walks and encode of a point scan of n_terms terms; 0 for 0 */
 
+/* (14) MANY variable-time multiscalar sums with LONG segments by the bucket method: dalek's RistrettoPoint::optional_multiscalar_mul for a batch of
+ *     segments -- K independent random-linear-combination checks that each need their own verdict, the weighted tallies of K contests, the
+ *     aggregated keys of K committees, a Feldman check per dealer.  zkp_msm_segments walks a ladder, comb or fixed-base table for EVERY term, so
+ *     its work per term does not shrink with the segment's length; zkp_msm_optional runs Pippenger's bucket method, but is one MSM per call.
+ *     zkp_msm_optional_many: meaning, argument checks and bytes are those of zkp_msm_many with ZKP_VARTIME, per segment -- out[i] = encode(sum over t
+ *       in [off[i], off[i + 1]) of scalars[t] * decode(points[pidx ? pidx[t] : t])), scalars any 32 bytes; an empty segment gives the identity (32
+ *       zero bytes) and status 0; status[i] = 1 and 32 zero bytes where a referenced point does not decode: a bad point flags the segments that
+ *       reference it and no other.  pidx == NULL: a point per term, and n_points must equal the number of terms.  ZKP_ERR_ARG with nothing written
+ *       for what zkp_msm_segments refuses: a NULL context or buffer, off[0] != 0, decreasing offsets, an index >= n_points, terms without scalars
+ *       or points.  THERE IS NO FLAGS ARGUMENT: THE CALL IS VARIABLE TIME BY DEFINITION -- bucket indices, list lengths and addresses follow the
+ *       scalars.  Public scalars only.
+ *     The plan.  A RUN is zkp_msm_optional's kernels on K segments side by side ("k_pip_tile_hist" through "k_pip_combine", the batch index one more
+ *       window coordinate), K MSMs of n slots each with n the longest segment of the run and the window width picked from n as zkp_msm_optional
+ *       picks it.  "k_pip_prepare_csr<C>" reads segment seg(b) of the job for MSM b: lane i < len decodes its point and recodes its scalar as
+ *       zkp_msm_optional does; a slot beyond the segment's length is PADDING -- the identity record and all-zero digits, which the histogram skips, so
+ *       padding costs the prepare and sort passes their reads and no point addition.  "k_pip_rows" then takes the run's K rows and status words to
+ *       out[seg(b)] and status[seg(b)].  K is bounded by K * windows <= 65535 and by a cap of 2^20 padded terms (K * n) per run, which also bounds
+ *       the workspace; a segment longer than the cap is a run of its own.  Runs follow each other on the context's stream without host
+ *       synchronisation in one workspace sized for the largest.  zkp_ctx_last_kernels(ZKP_K_DECODE) names every run with its shape and its place in
+ *       the run order: "k_pip_prepare_csr<11>@K=16,n=65536,at=0".
+ *       Runs are used for segments of MORE than zkp_msm_optional_many_min_segment() = 192 terms, the sizes the bucket kernels have ever run at;
+ *       shorter work takes zkp_msm_many's term path in variable time and gives the same bytes.
+ *     The host-pointer form reads off and plans: segments of 0 terms are written directly; segments of at most 192 terms go through the term
+ *       path together as one job; the others are ordered by falling length into CLASSES -- the longest segment not yet placed and every segment
+ *       more than half as long -- and each class is one sequence of runs, so no run pads a member by a factor of two or more.
+ *     The _dev form reads no array on the host and cannot classify: it is ONE class.  All n_seg segments are padded to max_seg, THE CALLER'S PROMISE
+ *       that no segment is longer, and chunked over K by the two limits; max_seg <= 192 takes the term path.  n_terms MUST equal d_off[n_seg].  A
+ *       segment longer than max_seg leaves its own row unspecified; with that, with decreasing offsets or with an index out of range every access
+ *       still stays inside the buffers (segment bounds and indices are clamped below their arrays' lengths) and the other rows are right.  Scalars,
+ *       points and d_out 16-byte aligned, offsets and indices 4-byte; queued on the context's stream without synchronising; may be recorded between
+ *       zkp_ctx_capture_begin / _end once the same call has run outside the capture.
+ *     Sizes (profiles/msm_optional_many_bench.txt, one MI355X, stream time between HIP events, medians of five rounds, ms, routes alternated in one
+ *       process, a point per term; the call | zkp_msm_segments with ZKP_VARTIME | a loop of zkp_msm_optional_dev per segment on resident buffers):
+ *       16 x 65,536 terms 3.022 | 12.43 | 12.96; 64 x 16,384 3.625 | 12.44 | 35.21; 256 x 4,096 5.084 | 12.48 | 104.7; 1,024 x 1,024 5.301 | 12.39 |
+ *       358.4 (zkp_msm_many: 16.62); 4,096 x 256 9.009 | 12.35 | - (zkp_msm_many: 12.74); a ragged mix of 1,000 segments of 200 to 2,000 terms and
+ *       one of 2^18 7.631 | 16.02 | 354.8, its classes padding 1.35 M terms to 1.69 M slots (x 1.26); 16 x 65,536 over 65,536 shared points 2.975 |
+ *       5.845.  Ahead beyond the spread of the rounds at every one of these, as a synchronous call too (16 x 65,536: 4.26 against 14.64 ms).
+ *     WHERE IT DOES NOT WIN: one segment is zkp_msm_optional's time, because it is the same kernels (2^20 terms: 3.139 against 3.109 ms); the time
+ *       per term rises as the segments get shorter (2.9 ns at 65,536 terms a segment, 5.1 ns at 1,024, 8.6 ns at 256: every segment pays its own
+ *       bucket tree and Horner tail); FEW segments of moderate length are a narrow launch whose floor is the Horner tail: 4 x 256, 4 x 1,024 and
+ *       16 x 256 terms all take 0.37 to 0.39 ms (0.24 ms of it k_pip_combine) -- still ahead of the fold (0.97 to 1.03 ms) and of zkp_msm_many
+ *       (1.6 to 4.0 ms) at every shape measured, 4 and 16 segments of 256, 1,024 and 4,096 terms included, so no measured shape has the call
+ *       behind; nothing is measured between 193 and 255 terms.
+ *     What padding costs: no point addition (histogram and scatter skip magnitude 0: nothing is summed for bin 0), only the prepare and sort
+ *       passes' work on the extra slots.  Every segment padded to twice its length (_dev, max_seg = 2 x length): x 1.16 at 64 x 16,384 (3.32 ->
+ *       3.83 ms), x 1.21 at 1,024 x 1,024 (5.00 -> 6.05), x 1.10 at 4,096 x 256 (8.58 -> 9.47).
+ *     The run cap: equal-length jobs of 2^21 terms at caps 2^21 / 2^20 / 2^19 / 2^18 / 2^17 / 2^16 (1, 2, 4, 8, 16, 32 runs), ns per term: 32 x 65,536
+ *       2.75 / 2.90 / 3.48 / 4.81 / 7.19 / 12.39; 128 x 16,384 3.16 / 3.31 / 3.84 / 4.40 / 6.46 / 10.46; 512 x 4,096 4.65 / 4.74 / 5.06 / 5.61 /
+ *       6.76 / 9.70; 2,048 x 1,024 5.00 / 4.78 / 4.93 / 5.41 / 6.57 / 9.06 -- level down to 2^20, which is the cap, and worse with every halving
+ *       below it.
+ *     zkp_ctx_last_timing on a call of more than seven runs: see there (the total spans the call; the per-kind split lumps the tail). */
+int zkp_msm_optional_many(zkp_ctx* ctx, uint32_t n_seg, const uint32_t* off /*[n_seg+1]*/, const uint8_t* scalars /*[T][32]*/,
+                          const uint32_t* pidx /*[T] or NULL*/, const uint8_t* points /*[n_points][32]*/, uint32_t n_points,
+                          uint8_t* out /*[n_seg][32]*/, uint8_t* status /*[n_seg]*/);
+int zkp_msm_optional_many_dev(zkp_ctx* ctx, uint32_t n_seg, const uint32_t* d_off /*[n_seg+1]*/, const uint8_t* d_scalars /*[n_terms][32]*/,
+                              const uint32_t* d_pidx /*[n_terms] or NULL*/, const uint8_t* d_points /*[n_points][32]*/, uint32_t n_points,
+                              uint32_t n_terms, uint32_t max_seg, uint8_t* d_out /*[n_seg][32]*/, uint8_t* d_status /*uint8 [n_seg]*/);
+uint32_t zkp_msm_optional_many_min_segment(void);   /* 192: runs are used above it; pure arithmetic */
+
 /* Timing of the last *_dev / host call on this context, measured with HIP events on the stream the
  * kernels were launched on.  kernel_ms[] is indexed by ZKP_K_*; returns the number of entries. */
 enum {
@@ -978,6 +1037,8 @@ enum {
   ZKP_K_TABLES = 8,      /* small-MSM path: comb tables of the per-proof points (k_comb_tables*)                      */
   ZKP_K_COUNT = 9
 };
+/* A call records at most 32 timing marks.  One with more (zkp_msm_optional_many records four per run: more than seven runs) keeps moving its last
+ * mark, so total_ms still spans the whole call, while kernel_ms files everything behind the 31st mark under the kind of the call's last mark. */
 int zkp_ctx_last_timing(zkp_ctx* ctx, float* kernel_ms /*[ZKP_K_COUNT]*/, float* total_ms);
 /* With profiling on: which VARIANT of a kind's kernel the last call launched, by the name rocprofv3 prints -- the kernels whose template
  * arguments depend on the call's size, flags or options (ZKP_K_TERMS: "k_terms_split<true, 16, true, false>", ZKP_K_TABLES:
@@ -1006,6 +1067,7 @@ int zkp_ctx_set_profiling(zkp_ctx* ctx, int enabled);
  *   ZKP_TESTOPT_VOUCH_REDUCED = 1: constant-time zkp_msm_many calls vouch that every scalar is reduced mod l, as the fused prove flows do for
  *   their blindings: the term kernel skips the carry window and walks sign-folded scalars (same bytes for reduced scalars; anything else is the
  *   caller's error);
+ *   ZKP_TESTOPT_PIP_RUN_CAP = the cap on the padded terms of one run of zkp_msm_optional_many (0: the library's), for measuring it;
  *   ZKP_TESTOPT_WAVE_CYCLES = 1 switches on a per-wavefront cycle recorder in the term kernel (s_memtime at entry and exit);
  * zkp_debug_wave_cycles copies out (and clears) up to cap records, [block][wavefront 0..3] = block class << 56 | cycles (class 1 =
  *   ladder, 2 = comb scan, 3 = grouped comb walk, 4 = fixed-base; 0 = no record): the timing side of the constant-time evidence.
@@ -1042,7 +1104,7 @@ size_t zkp_debug_ws_bytes(zkp_ctx* ctx);
  * back with it.  (size_t)ZKP_ERR_ARG for a NULL argument, len = 0, during a capture or with a job pending; (size_t)ZKP_ERR_HIP when a stream
  * reports an error or the copy fails; 0 while there is no workspace. */
 size_t zkp_debug_ws_count(zkp_ctx* ctx, const uint8_t* needle, size_t len);
-enum { ZKP_TESTOPT_DUMMY_LAUNCHES = 1001, ZKP_TESTOPT_GENERIC_CLASSIFIER = 1002, ZKP_TESTOPT_WAVE_CYCLES = 1003, ZKP_TESTOPT_PIP_MERGE = 1004, ZKP_TESTOPT_VOUCH_REDUCED = 1005 };
+enum { ZKP_TESTOPT_DUMMY_LAUNCHES = 1001, ZKP_TESTOPT_GENERIC_CLASSIFIER = 1002, ZKP_TESTOPT_WAVE_CYCLES = 1003, ZKP_TESTOPT_PIP_MERGE = 1004, ZKP_TESTOPT_VOUCH_REDUCED = 1005, ZKP_TESTOPT_PIP_RUN_CAP = 1006 };
 #endif
 
 #ifdef __cplusplus

@@ -408,6 +408,25 @@ int zkp_multiscalar_sum_batch(zkp_ctx* ctx, uint32_t n_msm, const uint32_t* off 
 void zkp_toolbox_set_msm_fold_min_segment(uint32_t n);
 uint32_t zkp_toolbox_get_msm_fold_min_segment(void);
 
+/* MANY variable-time multiscalar sums, each with its own verdict (zkp_mi355x.h (14)): dalek's RistrettoPoint::optional_multiscalar_mul for a batch
+ * of segments.  zkp_multiscalar_sum_batch's meaning, checks and bytes with ZKP_VARTIME; there is no flags argument, THE CALL IS VARIABLE TIME BY
+ * DEFINITION (public scalars only).  pidx == NULL: a point per term, n_points must be off[n_seg].  Routing, same bytes on every route:
+ *   1. ctx == NULL or off[n_seg] <= zkp_toolbox_get_host_max_terms(): the host threads (the host backend has no bucket method: the CSR MSM behind
+ *      zkp_multiscalar_sum_batch, variable time).
+ *   2. otherwise, the longest segment shorter than zkp_toolbox_get_msm_bucket_min_segment(): the route zkp_multiscalar_sum_batch gives the job.
+ *   3. otherwise zkp_msm_optional_many, the bucket method on the device.
+ * zkp_toolbox_set_msm_bucket_min_segment moves the threshold of step 2 (0: always the bucket method; 0xffffffff: never).  Its default follows the
+ * toolbox's standing rule: the smallest measured segment length from which the new call is ahead beyond the spread of the rounds at every
+ * measured segment count, "never" if there is none.  The default is 256, from
+ * profiles/msm_optional_many_bench.txt (stream medians, ms, the call against zkp_msm_segments | zkp_msm_many, ahead beyond the spread in every row): 256
+ * terms at 4 segments 0.377 against 0.974 | 1.615, at 16 0.394 against 1.024 | 1.659, at 4,096 9.009 against 12.35 | 12.74; 1,024 terms at 4 segments
+ * 0.375 against 1.025 | 3.958, at 1,024 5.301 against 12.39 | 16.62.  256 is the shortest length measured: between 193 and 255 terms nothing is. */
+int zkp_multiscalar_optional_batch(zkp_ctx* ctx, uint32_t n_seg, const uint32_t* off /*[n_seg+1]*/, const uint8_t* scalars /*[T][32]*/,
+                                   const uint32_t* pidx /*[T] or NULL*/, const uint8_t* points /*[n_points][32]*/, uint32_t n_points, int n_threads,
+                                   uint8_t* out /*[n_seg][32]*/, uint8_t* status /*[n_seg]*/);
+void zkp_toolbox_set_msm_bucket_min_segment(uint32_t n);
+uint32_t zkp_toolbox_get_msm_bucket_min_segment(void);
+
 /* RistrettoPoint sums, batched (zkp_mi355x.h (9)): `P + Q`, `P - Q`, `-P` (ZKP_PT_SUB from the identity, 32 zero bytes at stride 0) and
  * `iter().sum()`, each with the `compress()` that follows.  Routing is that of the calls above: ctx == NULL or n <= zkp_toolbox_get_host_max_terms()
  * (for zkp_point_sum_batch n is the number of terms, off[n_sums]) on the host threads, anything else on the device; same bytes on both routes.

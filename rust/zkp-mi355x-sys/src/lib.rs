@@ -248,6 +248,13 @@ extern "C" {
                             flags: c_int, out: *mut u8, status: *mut u8) -> c_int;
     pub fn zkp_msm_segments_dev(ctx: *mut zkp_ctx, n_msm: u32, d_off: *const u32, d_scalars: *const u8, d_pidx: *const u32, d_points: *const u8,
                                 n_points: u32, n_terms: u32, flags: c_int, d_out: *mut u8, d_status: *mut u8) -> c_int;
+    // (14) many variable-time multiscalar sums with long segments by the bucket method (no flags: variable time by definition); the segment length
+    // above which bucket runs are used
+    pub fn zkp_msm_optional_many(ctx: *mut zkp_ctx, n_seg: u32, off: *const u32, scalars: *const u8, pidx: *const u32, points: *const u8, n_points: u32,
+                                 out: *mut u8, status: *mut u8) -> c_int;
+    pub fn zkp_msm_optional_many_dev(ctx: *mut zkp_ctx, n_seg: u32, d_off: *const u32, d_scalars: *const u8, d_pidx: *const u32, d_points: *const u8,
+                                     n_points: u32, n_terms: u32, max_seg: u32, d_out: *mut u8, d_status: *mut u8) -> c_int;
+    pub fn zkp_msm_optional_many_min_segment() -> u32;
     // (12) segmented scalar sums, products and dot products (op: 0 sum, 1 product, 2 dot); the work unit's size and the number of fold launches
     pub fn zkp_sc_reduce(ctx: *mut zkp_ctx, op: c_int, n_out: u32, off: *const u32, a: *const u8, n_a: u32, aidx: *const u32, b: *const u8, n_b: u32,
                          bidx: *const u32, out: *mut u8) -> c_int;
@@ -454,6 +461,11 @@ extern "C" {
     pub fn zkp_toolbox_get_point_scan_min_terms() -> usize;
     pub fn zkp_toolbox_set_msm_fold_min_segment(n: u32);
     pub fn zkp_toolbox_get_msm_fold_min_segment() -> u32;
+    // the same sums, variable time, routed by size and by the longest segment (host threads / zkp_multiscalar_sum_batch's route / zkp_msm_optional_many)
+    pub fn zkp_multiscalar_optional_batch(ctx: *mut zkp_ctx, n_seg: u32, off: *const u32, scalars: *const u8, pidx: *const u32, points: *const u8,
+                                          n_points: u32, n_threads: c_int, out: *mut u8, status: *mut u8) -> c_int;
+    pub fn zkp_toolbox_set_msm_bucket_min_segment(n: u32);
+    pub fn zkp_toolbox_get_msm_bucket_min_segment() -> u32;
     // bounded discrete logarithms to the basepoint behind the same routing; the host table's size and the routing threshold
     pub fn zkp_basepoint_dlog_batch(ctx: *mut zkp_ctx, n: u64, points: *const u8, bits: u32, out: *mut u64, status: *mut u8, n_threads: c_int) -> c_int;
     pub fn zkp_point_dlog_batch(ctx: *mut zkp_ctx, base: *const u8, n: u64, points: *const u8, bits: u32, flags: c_int, out: *mut u64, status: *mut u8, n_threads: c_int) -> c_int;

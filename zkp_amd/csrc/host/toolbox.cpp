@@ -1106,6 +1106,37 @@ int zkp_multiscalar_sum_batch(zkp_ctx* ctx, uint32_t n_msm, const uint32_t* off,
   return rc == ZKP_ERR_ARG ? ZKP_TB_BAD_STATEMENT : rc;
 }
 
+// ---- many variable-time multiscalar sums with long segments (zkp_mi355x.h (14)) ------------------------------------------------------------
+// The shortest longest-segment from which a device job takes the bucket method (zkp_msm_optional_many) instead of the route
+// zkp_multiscalar_sum_batch gives it.  The toolbox's standing rule: the smallest measured segment length from which the new call is ahead beyond the
+// spread of the rounds at every measured segment count; 0xffffffff ("never") if there is none.  profiles/msm_optional_many_bench.txt:
+// (stream medians, ms, the call against zkp_msm_segments | zkp_msm_many, all ahead beyond the spread): 256 terms at 4 segments 0.377 against 0.974 | 1.615, at 16 0.394 against 1.024 | 1.659, at 4,096 9.009 against 12.35 | 12.74; 1,024 terms at 4 segments 0.375 against 1.025 | 3.958, at 16 0.425 against 1.108 | 4.395, at 1,024 5.301 against 12.39 | 16.62.  256 is the shortest measured length; 193 to 255 terms are not measured.
+static std::atomic<uint32_t> g_msm_bucket_min_segment{256};
+void zkp_toolbox_set_msm_bucket_min_segment(uint32_t n) { g_msm_bucket_min_segment = n; }
+uint32_t zkp_toolbox_get_msm_bucket_min_segment(void) { return g_msm_bucket_min_segment.load(); }
+
+// zkp_multiscalar_sum_batch's checks, made before anything is written; variable time on every route.
+int zkp_multiscalar_optional_batch(zkp_ctx* ctx, uint32_t n_seg, const uint32_t* off, const uint8_t* scalars, const uint32_t* pidx, const uint8_t* points,
+                                   uint32_t n_points, int n_threads, uint8_t* out, uint8_t* status) {
+  if (n_seg == 0) return ZKP_TB_OK;
+  if (!off || !out || !status || off[0] != 0) return ZKP_TB_BAD_STATEMENT;
+  uint32_t longest = 0;
+  for (uint32_t i = 0; i < n_seg; ++i) {
+    if (off[i + 1] < off[i]) return ZKP_TB_BAD_STATEMENT;
+    longest = std::max(longest, off[i + 1] - off[i]);
+  }
+  const uint32_t n_terms = off[n_seg];
+  if (n_terms && (!scalars || !points || n_points == 0)) return ZKP_TB_BAD_STATEMENT;
+  if (!pidx && n_points != n_terms) return ZKP_TB_BAD_STATEMENT;
+  if (pidx)
+    for (uint32_t t = 0; t < n_terms; ++t)
+      if (pidx[t] >= n_points) return ZKP_TB_BAD_STATEMENT;
+  if (on_host(ctx, n_terms) || longest < g_msm_bucket_min_segment.load())
+    return zkp_multiscalar_sum_batch(ctx, n_seg, off, scalars, pidx, points, n_points, ZKP_VARTIME, n_threads, out, status);
+  const int rc = zkp_msm_optional_many(ctx, n_seg, off, scalars, pidx, points, n_points, out, status);
+  return rc == ZKP_ERR_ARG ? ZKP_TB_BAD_STATEMENT : rc;
+}
+
 // ---- RistrettoPoint sums (zkp_mi355x.h (9)): pairs and CSR segments behind the same routing ------------------------------------------------
 int zkp_point_add_batch(zkp_ctx* ctx, uint64_t n, const uint8_t* a, uint32_t a_stride, const uint8_t* b, uint32_t b_stride, int op, int n_threads,
                         uint8_t* out, uint8_t* status) {

@@ -34,6 +34,7 @@
 #include <mutex>
 #include <set>
 #include <string>
+#include <unordered_map>
 #include <vector>
 #include "../../include/zkp_mi355x.h"
 #include "dev_layout.h"
@@ -593,32 +594,11 @@ __device__ __forceinline__ void pip_seg_src(const pip_seg& seg, uint32_t b, uint
   }
 }
 
-// PHASE: 3 = both halves; 1 = the points only (decode -> niels: nothing here depends on a scalar, so the latency schedule of the batch verifier runs it on the
-// side stream next to the transcripts); 2 = the digits only
-template <int C, int PHASE = 3>
-__global__ void __launch_bounds__(256, 2)
-k_pip_prepare(uint32_t n, const pip_seg seg, const uint8_t* __restrict__ scalars, const uint8_t* __restrict__ points,
-              dev_niels* __restrict__ niels, uint32_t* __restrict__ digits, uint32_t* __restrict__ invalid) {
+// the signed radix-2^C digits of the scalar s (any 256 bits) for slot i of an MSM of n slots: digits[w * n + i], w < W1
+template <int C>
+__device__ __forceinline__ void pip_digits(uint32_t (&s)[8], uint32_t* __restrict__ digits, uint32_t n, uint32_t i) {
   using cfg = pip_cfg<C>;
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
-  if (i >= n) return;
-  size_t si, pi;
-  pip_seg_src(seg, b, i, si, pi);
-  niels += (size_t)b * n;
-  digits += (size_t)b * cfg::W1 * n;
-  if constexpr (PHASE & 1) {
-    uint32_t w[8];
-    load_vec<2>(w, points + 32 * pi);
-    ge_p3 p;
-    const uint32_t ok = ristretto_decode(p, w);
-    ge_niels q;
-    ge_affine_to_niels(q, p);
-    store_niels(niels + i, q, ok);
-    if (!ok) atomicOr(invalid + b, 1u);
-  }
-  if constexpr (!(PHASE & 2)) return;
-  uint32_t s[8], e[10];
-  load_vec<2>(s, scalars + 32 * si);
+  uint32_t e[10];
   const uint32_t flip = sc_fold_sign(s);      // s * P = (l - s) * (-P): the point's sign moves into the digits
   {
     uint64_t c = 0;
@@ -646,6 +626,103 @@ k_pip_prepare(uint32_t n, const pip_seg seg, const uint8_t* __restrict__ scalars
     }
     digits[(size_t)w * n + i] = mag | ((neg ^ flip) << 31);
   }
+}
+
+// PHASE: 3 = both halves; 1 = the points only (decode -> niels: nothing here depends on a scalar, so the latency schedule of the batch verifier runs it on the
+// side stream next to the transcripts); 2 = the digits only
+template <int C, int PHASE = 3>
+__global__ void __launch_bounds__(256, 2)
+k_pip_prepare(uint32_t n, const pip_seg seg, const uint8_t* __restrict__ scalars, const uint8_t* __restrict__ points,
+              dev_niels* __restrict__ niels, uint32_t* __restrict__ digits, uint32_t* __restrict__ invalid) {
+  using cfg = pip_cfg<C>;
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+  if (i >= n) return;
+  size_t si, pi;
+  pip_seg_src(seg, b, i, si, pi);
+  niels += (size_t)b * n;
+  digits += (size_t)b * cfg::W1 * n;
+  if constexpr (PHASE & 1) {
+    uint32_t w[8];
+    load_vec<2>(w, points + 32 * pi);
+    ge_p3 p;
+    const uint32_t ok = ristretto_decode(p, w);
+    ge_niels q;
+    ge_affine_to_niels(q, p);
+    store_niels(niels + i, q, ok);
+    if (!ok) atomicOr(invalid + b, 1u);
+  }
+  if constexpr (!(PHASE & 2)) return;
+  uint32_t s[8];
+  load_vec<2>(s, scalars + 32 * si);
+  pip_digits<C>(s, digits, n, i);
+}
+
+// The CSR source of a run (zkp_msm_optional_many, pip_segments.h): MSM b of the run is segment seg(b) = seg_ids ? seg_ids[b] : first + b of a CSR job, term i
+// of it scalars[off[seg] + i] on points[pidx ? pidx[off[seg] + i] : off[seg] + i].  Every index that reaches memory is clamped below its array's
+// length, whatever off, pidx and seg_ids hold.  at: the run's place in the call's run order (a note for zkp_ctx_last_kernels, not read on the device).
+struct pip_csr {
+  const uint32_t* off = nullptr;
+  const uint32_t* pidx = nullptr;
+  const uint32_t* seg_ids = nullptr;
+  uint32_t first = 0, n_seg = 1, n_points = 1, n_terms = 0, at = 0;
+};
+__device__ __forceinline__ uint32_t pip_csr_seg(const pip_csr& job, uint32_t b) {
+  const uint32_t sg = job.seg_ids ? job.seg_ids[b] : job.first + b;
+  return min(sg, job.n_seg - 1u);
+}
+
+// k_pip_prepare for a CSR job: one lane per SLOT of the run's K MSMs of n slots each, n the longest segment of the run.  A slot beyond its segment's length
+// is padding: the identity record, marked valid, and digits of magnitude 0 and sign 0 in every window -- bin 0, which the histogram skips and the tree
+// never reads.  The same niels records and digits as k_pip_prepare's for the slots of the segment.
+template <int C>
+__global__ void __launch_bounds__(256, 2)
+k_pip_prepare_csr(uint32_t n, const pip_csr job, const uint8_t* __restrict__ scalars, const uint8_t* __restrict__ points,
+                  dev_niels* __restrict__ niels, uint32_t* __restrict__ digits, uint32_t* __restrict__ invalid) {
+  using cfg = pip_cfg<C>;
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+  if (i >= n) return;
+  const uint32_t sg = pip_csr_seg(job, b);
+  const uint32_t lo = min(job.off[sg], job.n_terms), hi = min(max(job.off[sg + 1], lo), job.n_terms);
+  niels += (size_t)b * n;
+  digits += (size_t)b * cfg::W1 * n;
+  if (i >= hi - lo) {
+    ge_niels q;
+    ge_niels_identity(q);
+    store_niels(niels + i, q, 1u);
+#pragma unroll
+    for (int w = 0; w < cfg::W1; ++w) digits[(size_t)w * n + i] = 0u;
+    return;
+  }
+  const uint32_t t = lo + i;                         // < hi <= n_terms
+  const uint32_t pi = min(job.pidx ? job.pidx[t] : t, job.n_points - 1u);
+  uint32_t w[8];
+  load_vec<2>(w, points + 32 * (size_t)pi);
+  ge_p3 p;
+  const uint32_t ok = ristretto_decode(p, w);
+  ge_niels q;
+  ge_affine_to_niels(q, p);
+  store_niels(niels + i, q, ok);
+  if (!ok) atomicOr(invalid + b, 1u);
+  uint32_t s[8];
+  load_vec<2>(s, scalars + 32 * (size_t)t);
+  pip_digits<C>(s, digits, n, i);
+}
+
+// one lane per MSM of a run: k_pip_combine (or the term path) left K rows and K status words in run order; row b goes to out[seg(b)], its status to
+// status[seg(b)] as a byte, 32 zero bytes where the status is 1.  Only seg_ids / first / n_seg of the job are read.
+__global__ void __launch_bounds__(256)
+k_pip_rows(uint32_t K, const pip_csr job, const uint8_t* __restrict__ rows, const uint32_t* __restrict__ st, uint8_t* __restrict__ out,
+           uint8_t* __restrict__ status) {
+  const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= K) return;
+  const uint32_t sg = pip_csr_seg(job, b);
+  uint32_t w[8];
+  load_vec<2>(w, rows + 32 * (size_t)b);
+  const uint32_t bad = st[b] & 1u;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) w[k] = bad ? 0u : w[k];
+  store_vec<2>(out + 32 * (size_t)sg, w);
+  status[sg] = (uint8_t)bad;
 }
 
 // Entries per part of a bucket with cnt entries: about sqrt(cnt) -- a part is one lane's sequential chain, the merge of a bucket's
@@ -1861,6 +1938,7 @@ struct zkp_ctx {
          SCH_LADDER_INTERLEAVE, SCH_RIDERS, SCH_STRAUS_LANES, SCH_STRAUS_WINS, SCH_TR_LANES, SCH_TR_STEPS, SCH_FUSE_TT, SCH_TERMS_SPLIT,
          SCH_RAGGED_CLASSES, SCH_RAGGED_COMPILED, SCH_RAGGED_BASE, SCH_FUSED_PLANS, SCH_PIP_MERGE, SCH_PIP_BUCKETS, SCH_NO_CARRY, SCH_SIGN_FOLD, SCH_COUNT };
   int64_t sched[SCH_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+  uint64_t debug_pip_run_cap = 0;    // ZKP_TESTOPT_PIP_RUN_CAP: padded terms per run of zkp_msm_optional_many (0: pip_segments.h's)
   int debug_pip_merge = 0;           // ZKP_TESTOPT_PIP_MERGE: 0 = by the call's bucket count, 1 = a quad per bucket, 2 = a lane per bucket
   bool debug_vouch_reduced = false;  // ZKP_TESTOPT_VOUCH_REDUCED: constant-time zkp_msm_many calls vouch that their scalars are reduced mod l (terms_cfg::canonical)
 #endif
@@ -2022,8 +2100,11 @@ void prof_begin(zkp_ctx* c) {
   if (c->profiling && !c->capturing) for (auto& s : c->kernel_names) s.clear();
   if (c->profiling && !c->capturing) { hipEventRecord(c->ev[0], c->stream); c->ev_kind[0] = -1; c->n_ev = 1; }
 }
+// A call with more marks than events (zkp_msm_optional_many: four per run) keeps moving its LAST event: the total still ends at the call's last mark, and the
+// per-kind split files everything behind mark kMaxEvents - 2 under the kind of the last mark.
 void prof_mark(zkp_ctx* c, int kind) {
-  if (c->profiling && !c->capturing && !c->prof_suspended && c->n_ev < kMaxEvents) {
+  if (c->profiling && !c->capturing && !c->prof_suspended) {
+    if (c->n_ev == kMaxEvents) --c->n_ev;
     hipEventRecord(c->ev[c->n_ev], c->stream);
     c->ev_kind[c->n_ev] = kind;
     c->n_ev++;
@@ -2367,7 +2448,7 @@ size_t pip_ws(uint64_t n, uint32_t K = 1) {
 // d_out [K][32]; d_status [K] words, or [K][2] with shared_flags (the caller's K zeroed flag words: bit 0 ours, bit 1 the caller's)
 template <int C>
 int pip_run(zkp_ctx* c, uint32_t n, const uint8_t* d_scalars, const uint8_t* d_points, uint8_t* d_out,
-            uint32_t* d_status, size_t ws_reserved, uint32_t* shared_flags, const pip_seg seg = pip_seg(), int phases = 3) {
+            uint32_t* d_status, size_t ws_reserved, uint32_t* shared_flags, const pip_seg seg = pip_seg(), int phases = 3, const pip_csr* csr = nullptr) {
   using cfg = pip_cfg<C>;
   const uint32_t K = seg.K;
   const size_t WK = (size_t)cfg::W1 * K;
@@ -2408,9 +2489,14 @@ int pip_run(zkp_ctx* c, uint32_t n, const uint8_t* d_scalars, const uint8_t* d_p
     return ZKP_OK;
   }
   if (!shared_flags) HIP_TRY(hipMemsetAsync(invalid, 0, (size_t)K * 4, c->stream));
-  prof_note(c, ZKP_K_DECODE, "k_pip_prepare<" + std::to_string(C) + ">");
-  if (phases == 2) hipLaunchKernelGGL((k_pip_prepare<C, 2>), dim3((n + 255) / 256, K), dim3(256), 0, c->stream, n, seg, d_scalars, d_points, niels, digits, invalid);
-  else hipLaunchKernelGGL((k_pip_prepare<C, 3>), dim3((n + 255) / 256, K), dim3(256), 0, c->stream, n, seg, d_scalars, d_points, niels, digits, invalid);
+  if (csr) {                                         // a run of zkp_msm_optional_many: the operands are segments of a CSR job (d_scalars / d_points are the job's arrays)
+    prof_note(c, ZKP_K_DECODE, "k_pip_prepare_csr<" + std::to_string(C) + ">@K=" + std::to_string(K) + ",n=" + std::to_string(n) + ",at=" + std::to_string(csr->at));
+    hipLaunchKernelGGL(k_pip_prepare_csr<C>, dim3((n + 255) / 256, K), dim3(256), 0, c->stream, n, *csr, d_scalars, d_points, niels, digits, invalid);
+  } else {
+    prof_note(c, ZKP_K_DECODE, "k_pip_prepare<" + std::to_string(C) + ">");
+    if (phases == 2) hipLaunchKernelGGL((k_pip_prepare<C, 2>), dim3((n + 255) / 256, K), dim3(256), 0, c->stream, n, seg, d_scalars, d_points, niels, digits, invalid);
+    else hipLaunchKernelGGL((k_pip_prepare<C, 3>), dim3((n + 255) / 256, K), dim3(256), 0, c->stream, n, seg, d_scalars, d_points, niels, digits, invalid);
+  }
   prof_mark(c, ZKP_K_DECODE);
   hipLaunchKernelGGL(k_pip_tile_hist<C>, dim3(tiles, (unsigned)WK), dim3(sort_cfg<C>::THREADS), 0, c->stream, n, digits, tilehist);
   hipLaunchKernelGGL(k_pip_tile_total, grid1(nb, 256), dim3(256), 0, c->stream, cfg::B1, tiles, (uint32_t)nb, tilehist, hist);
@@ -3307,6 +3393,7 @@ int zkp_ctx_set_option(zkp_ctx* c, int option, uint64_t value) {
     case ZKP_TESTOPT_GENERIC_CLASSIFIER: c->stmt_classify = value == 0; return ZKP_OK;
     case ZKP_TESTOPT_PIP_MERGE: c->debug_pip_merge = value <= 2 ? (int)value : 0; return ZKP_OK;
     case ZKP_TESTOPT_VOUCH_REDUCED: c->debug_vouch_reduced = value != 0; return ZKP_OK;
+    case ZKP_TESTOPT_PIP_RUN_CAP: c->debug_pip_run_cap = value; return ZKP_OK;
     case ZKP_TESTOPT_DUMMY_LAUNCHES: c->debug_dummy_launches = (int)std::min<uint64_t>(value, 1000); return ZKP_OK;
     case ZKP_TESTOPT_WAVE_CYCLES: {
       HIP_TRY(hipSetDevice(c->device));
@@ -4889,3 +4976,4 @@ int zkp_encode_many(zkp_ctx* c, uint64_t n, const uint8_t* xyzt, uint8_t* out) {
 #include "fused_flows.h"
 #include "ragged_transcripts.h"
 #include "host_jobs.h"
+#include "pip_segments.h"

@@ -17,6 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libzkp_mi355x.so")
 TESTHOOKS_LIB_PATH = os.path.join(_HERE, "libzkp_mi355x_testhooks.so")     # -DZKP_BUILD_TEST_HOOKS build (tests / A-B tools)
 ZKP_TESTOPT_DUMMY_LAUNCHES, ZKP_TESTOPT_GENERIC_CLASSIFIER, ZKP_TESTOPT_WAVE_CYCLES, ZKP_TESTOPT_PIP_MERGE, ZKP_TESTOPT_VOUCH_REDUCED = 1001, 1002, 1003, 1004, 1005
+ZKP_TESTOPT_PIP_RUN_CAP = 1006
 ZKP_OPT_CT_LOOKUP, ZKP_OPT_EACH_STRAUS, ZKP_OPT_LADDER_INTERLEAVE = 9, 10, 11
 ZKP_OPT_CT_MASKED_SCANS = ZKP_OPT_CT_LOOKUP           # the round-3 name (value 1 = masked scans)
 ZKP_CT_LOOKUP_XBAR, ZKP_CT_LOOKUP_SCAN, ZKP_CT_LOOKUP_LDS = 0, 1, 2
@@ -464,6 +465,21 @@ class Engine:
                                           _ptr(out), _ptr(status)), "zkp_msm_segments")
         return out, status
 
+    def msm_optional_many(self, off, scalars, points, pidx=None) -> Tuple[np.ndarray, np.ndarray]:
+        """zkp_msm_optional_many: msm_many's variable-time results per segment -- out[i] = encode(sum over t in [off[i], off[i + 1]) of scalars[t] *
+        decode(points[pidx[t]])) -> (out [n_seg][32], status [n_seg]) -- by the bucket method, many segments to a run; pidx = None: a point per term.
+        VARIABLE TIME: public scalars only"""
+        off, pidx, _, points = sum_operands(off, points, pidx, None)
+        n_seg, n_terms = len(off) - 1, int(off[-1])
+        scalars = _u8(scalars, 32) if n_terms else np.zeros((0, 32), np.uint8)
+        if len(scalars) != n_terms:
+            raise ValueError("scalars length must equal off[-1]")
+        out = np.zeros((n_seg, 32), np.uint8)
+        status = np.zeros(n_seg, np.uint8)
+        _check(self._lib.zkp_msm_optional_many(self._h, n_seg, _ptr(off), _ptr(scalars), None if pidx is None else _ptr(pidx), _ptr(points), len(points),
+                                               _ptr(out), _ptr(status)), "zkp_msm_optional_many")
+        return out, status
+
     def scalar_reduce(self, op: int, off, a, aidx=None, b=None, bidx=None) -> np.ndarray:
         """zkp_sc_reduce: out[i] = the fold of the terms [off[i], off[i + 1]) -> [n_out][32] canonical scalars.  op = ZKP_SC_SUM (of a[ai(t)], empty: 0),
         ZKP_SC_PRODUCT (empty: 1) or ZKP_SC_DOT (of a[ai(t)] * b[bi(t)], empty: 0); ai(t) = aidx[t], or t with aidx = None (a then has off[-1] rows)"""
@@ -687,6 +703,13 @@ class Engine:
         _check(self._lib.zkp_msm_segments_dev(self._h, n_msm, d_off, d_scalars, d_pidx, d_points, n_points, n_terms, flags, d_out, d_status),
                "zkp_msm_segments_dev")
 
+    def msm_optional_many_dev(self, n_seg, d_off, d_scalars, d_pidx, d_points, n_points, n_terms, max_seg, d_out, d_status) -> None:
+        """zkp_msm_optional_many_dev: d_off u32 [n_seg + 1], d_scalars [n_terms][32], d_pidx u32 [n_terms] or None, d_points [n_points][32] ->
+        d_out [n_seg][32], d_status [n_seg] bytes; nothing is read on the host: one class, every segment padded to max_seg, the caller's promise that
+        no segment is longer; n_terms must be d_off[n_seg]"""
+        _check(self._lib.zkp_msm_optional_many_dev(self._h, n_seg, d_off, d_scalars, d_pidx, d_points, n_points, n_terms, max_seg, d_out, d_status),
+               "zkp_msm_optional_many_dev")
+
     def scalar_reduce_dev(self, op, n_out, d_off, d_a, n_a, d_aidx, d_b, n_b, d_bidx, n_terms, d_out) -> None:
         """zkp_sc_reduce_dev: d_off u32 [n_out + 1], d_a [n_a][32], d_aidx u32 [n_terms] or None, d_b [n_b][32] / d_bidx (ZKP_SC_DOT, else None, 0,
         None) -> d_out [n_out][32]; nothing is read on the host, the launches depend on n_terms and n_out alone; n_terms must be d_off[n_out]"""
@@ -899,7 +922,11 @@ class Engine:
         out = {}
         buf = ctypes.create_string_buffer(512)
         for i, k in enumerate(K_NAMES):
-            if self._lib.zkp_ctx_last_kernels(self._h, i, buf, 512) > 0:
+            n = self._lib.zkp_ctx_last_kernels(self._h, i, buf, len(buf))
+            if n >= len(buf):                                        # (a call of many runs names every one of them: zkp_msm_optional_many)
+                buf = ctypes.create_string_buffer(n + 1)
+                n = self._lib.zkp_ctx_last_kernels(self._h, i, buf, len(buf))
+            if n > 0:
                 out[k] = buf.value.decode().split(";")
         return out
 

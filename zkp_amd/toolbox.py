@@ -827,6 +827,34 @@ def get_msm_fold_min_segment() -> int:
     return int(lib().zkp_toolbox_get_msm_fold_min_segment())
 
 
+def optional_multiscalar_mul(eng, off, scalars, points, pidx=None, threads: int = 0):
+    """dalek's RistrettoPoint::optional_multiscalar_mul for a batch of segments, VARIABLE TIME (public scalars only): multiscalar_sum's results with
+    ZKP_VARTIME -> (out [n_seg][32], status [n_seg]).  pidx = None: a point per term.  eng = None (or at most get_host_max_terms() terms) runs on the
+    host threads; with an Engine a job whose longest segment is below get_msm_bucket_min_segment() takes multiscalar_sum's route, anything else
+    Engine.msm_optional_many (the bucket method).  Same bytes on every route."""
+    from .engine import _u8, sum_operands
+    off, pidx, _, points = sum_operands(off, points, pidx, None)
+    n_seg, n_terms = len(off) - 1, int(off[-1])
+    scalars = _u8(scalars, 32) if n_terms else np.zeros((0, 32), np.uint8)
+    if len(scalars) != n_terms:
+        raise ValueError("scalars length must equal off[-1]")
+    out = np.zeros((n_seg, 32), np.uint8)
+    status = np.zeros(n_seg, np.uint8)
+    _raise(lib().zkp_multiscalar_optional_batch(None if eng is None else eng._h, n_seg, _p(off), _p(scalars), _p(pidx), _p(points), len(points), threads,
+                                                _p(out), _p(status)), "zkp_multiscalar_optional_batch")
+    return out, status
+
+
+def set_msm_bucket_min_segment(n: int) -> None:
+    """optional_multiscalar_mul jobs on an engine whose longest segment has at least n terms take the bucket method (zkp_msm_optional_many); shorter
+    ones go where multiscalar_sum sends them.  0xffffffff: never"""
+    lib().zkp_toolbox_set_msm_bucket_min_segment(n)
+
+
+def get_msm_bucket_min_segment() -> int:
+    return int(lib().zkp_toolbox_get_msm_bucket_min_segment())
+
+
 # ---- RistrettoPoint sums (include/zkp_toolbox.h): `P + Q`, `P - Q`, `-P`, `iter().sum()`, each with its compress(); eng = None is the host backend ----
 def _point_pairs(eng, a, b, op: int, threads: int):
     from .engine import mul_operands
