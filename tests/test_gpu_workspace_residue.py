@@ -16,7 +16,7 @@ The shapes are the smallest that reach each layout ("Workspace region
 no case grows the workspace after it -- a call that had to reallocate would see fresh memory again -- and zkp_debug_ws_bytes is compared
 after every call with its value right after the fill.
 
-Entry point that calls ensure_ws (include/zkp_mi355x.h sections 1 to 13) -> the test that fills the workspace in front of it.  "here" is this
+Entry point that calls ensure_ws (include/zkp_mi355x.h sections 1 to 14) -> the test that fills the workspace in front of it.  "here" is this
 module; the other files hold a test_results_do_not_depend_on_what_the_workspace_held of their own.
 
   zkp_msm_many                                                    here: test_msm_many
@@ -39,14 +39,20 @@ module; the other files hold a test_results_do_not_depend_on_what_the_workspace_
   zkp_mul_base, zkp_mul_points                                    tests/test_gpu_point_mul.py
   zkp_add_points, zkp_sum_points                                  tests/test_gpu_point_sum.py
   zkp_msm_segments                                                tests/test_gpu_msm_segments.py
+  zkp_msm_segments_dev                                            here: test_msm_segments_dev (the generic-bounds terms_cfg, not host_terms_cfg, and an index
+                                                                  k_iota writes into the workspace); tests/test_gpu_msm_segments.py fills in front of it too
+  zkp_msm_optional_many                                           tests/test_gpu_msm_optional_many.py, tests/test_gpu_msm_optional_many_edges.py
+  zkp_msm_optional_many_dev                                       tests/test_gpu_msm_optional_many_edges.py: test_results_do_not_depend_on_what_the_workspace_held
+                                                                  (one class padded to max_seg, and the term path under generic bounds up to max_seg = S: neither
+                                                                  is the plan of its host-pointer form)
   zkp_sc_reduce                                                   tests/test_gpu_scalar_reduce.py
   zkp_sc_scan, zkp_scan_points                                    tests/test_gpu_scan.py
   zkp_dlog_base                                                   tests/test_gpu_dlog.py
   zkp_dlog_point                                                  tests/test_gpu_dlog_point.py
-  zkp_mul_points_dev, zkp_sum_points_dev, zkp_msm_segments_dev,   not filled directly: each carves the layout of its host-pointer form (above) less
-    zkp_sc_reduce_dev, zkp_sc_scan_dev, zkp_scan_points_dev,      the staging of the operands, which the caller owns, and launches through the same
-    zkp_dlog_base_dev, zkp_dlog_point_dev, zkp_msm_many_dev,      launcher; those files fill the workspace in front of the host-pointer form only
-    zkp_sc_random_dev, zkp_hash_from_bytes_sha512_dev             (zkp_msm_many_dev: test_msm_many[outputs2048_dev] here does run the _dev form)
+  zkp_mul_points_dev, zkp_sum_points_dev, zkp_sc_reduce_dev,      not filled directly: each carves the layout of its host-pointer form (above) less
+    zkp_sc_scan_dev, zkp_scan_points_dev, zkp_dlog_base_dev,      the staging of the operands, which the caller owns, and launches through the same
+    zkp_dlog_point_dev, zkp_msm_many_dev, zkp_sc_random_dev,      launcher; those files fill the workspace in front of the host-pointer form only
+    zkp_hash_from_bytes_sha512_dev                                (zkp_msm_many_dev: test_msm_many[outputs2048_dev] here does run the _dev form)
   zkp_debug_quad_selftest, zkp_debug_row_selftest                 test-hook probes: every word they read they uploaded in the same call
   carve nothing (not tested): the _dev forms of section 7 (zkp_transcripts_*_dev) and of zkp_sc_invert / _from_wide / _muladd /
     _sc_hash_from_bytes_sha512, zkp_from_uniform_bytes_dev, zkp_mul_base_dev, zkp_add_points_dev; zkp_ctx_prepare_fixed_points,
@@ -274,13 +280,67 @@ def test_msm_optional(engines, case, word):
     assert got == fresh, "a fresh context computes another point"
 
 
-# ---- the fused flows ------------------------------------------------------------------------------------------------------------------
 def _torch():
     return TH._torch()
 
 
 def _dev(a):
     return _torch().from_numpy(np.ascontiguousarray(a)).to("cuda:0")
+
+
+# ---- msm_segments_dev: the generic bounds of arrays the host has not inspected, and an index the device writes itself ------------------------
+SEGMENTS_DEV_LENS = [0, 1, 600, 33, 0, 466]       # 1,100 terms: the host-pointer form would count the uses (host_terms_cfg, from 1,024 terms on); the _dev form cannot
+
+
+def _segments_dev(eng, off, sc, pidx, points, flags):
+    """zkp_msm_segments_dev on torch buffers, the outputs poisoned beforehand -> (out, status)"""
+    torch = _torch()
+    n_msm, n_terms = len(off) - 1, int(off[-1])
+    d_off, d_sc, d_pts = _dev(off.view(np.int32)), _dev(sc), _dev(points)
+    d_pidx = None if pidx is None else _dev(pidx.view(np.int32))
+    d_out = torch.full((n_msm, 32), 0xAB, dtype=torch.uint8, device="cuda:0")
+    d_st = torch.full((n_msm,), 0xAB, dtype=torch.uint8, device="cuda:0")
+    torch.cuda.synchronize()
+    eng.msm_segments_dev(n_msm, d_off.data_ptr(), d_sc.data_ptr(), None if d_pidx is None else d_pidx.data_ptr(), d_pts.data_ptr(), len(points), n_terms, flags,
+                         d_out.data_ptr(), d_st.data_ptr())
+    eng.synchronize()
+    return d_out.cpu().numpy(), d_st.cpu().numpy()
+
+
+@pytest.mark.parametrize("word", WORDS, ids=lambda w: "fill%x" % w)
+@pytest.mark.parametrize("own_rows", (False, True), ids=("pidx", "own_rows"))
+@pytest.mark.parametrize("flags", (ZKP_CT, ZKP_VARTIME), ids=("ct", "vartime"))
+def test_msm_segments_dev(engines, flags, own_rows, word):
+    """1,100 terms over the 64 shared points of tests/msm_segments_cases.py, through d_pidx and with a row per term (d_pidx = NULL: k_iota writes the
+    index into the workspace in front of the fold's regions)"""
+    from tests import msm_segments_cases as MC
+    eh, _ = engines
+
+    def make():
+        off, sc, pidx, pts = MC.job(SEGMENTS_DEV_LENS, seed=1100)
+        assert int(off[-1]) >= 1024
+        want, want_st = MC.expected("residue-segments-dev", off, sc, pidx, pts, flags)
+        assert not want_st.any() and not want[[0, 4]].any() and want[[2, 3, 5]].any(axis=1).all()
+        if own_rows:
+            pidx, pts = None, np.ascontiguousarray(pts[pidx])
+        ef = _fresh()
+        try:
+            fresh = _segments_dev(ef, off, sc, pidx, pts, flags)
+        finally:
+            ef.close()
+        return off, sc, pidx, pts, want, want_st, fresh
+
+    off, sc, pidx, pts, want, want_st, fresh = _once(("segments_dev", flags, own_rows), make)
+    _fill(eh, CAP, word)
+    out, st = _segments_dev(eh, off, sc, pidx, pts, flags)
+    sched = eh.last_schedule()
+    assert sched.get("terms_split") == 1 and sched.get("batch_encode") == 0, sched      # the classified term path, the fold behind it
+    assert (st == want_st).all(), np.flatnonzero(st != want_st)
+    assert (out == want).all(), np.flatnonzero((out != want).any(axis=1))
+    assert (out == fresh[0]).all() and (st == fresh[1]).all(), "a fresh context computes other bytes"
+
+
+# ---- the fused flows ------------------------------------------------------------------------------------------------------------------
 
 
 def _prove_dev(eng, fst, n, ts0, pos, secrets, table, entropy, m, nc):
