@@ -610,15 +610,6 @@ void launch_coeff_build(zkp_ctx* c, const fused_shape& s, uint32_t N_each, const
     hipMemsetAsync(d_sc, 0, (size_t)K * s.ns * 32, c->stream);
   }
 }
-size_t optional_ws(uint64_t total) {
-  if (total <= kSmallOptional) return 1024 + (total + 1) * 4 + terms_path_ws((uint32_t)total, (uint32_t)total, 1);
-  switch (pick_c(total)) {
-    case 7: return pip_ws<7>(total);
-    case 10: return pip_ws<10>(total);
-    case 11: return pip_ws<11>(total);
-    default: return pip_ws<16>(total);
-  }
-}
 
 // ---- plans: everything about (flow, statement, N, STROBE position) that does not depend on the data -----------------
 enum { SRC_TABLE = 0, SRC_SECRETS = 1, SRC_ENTROPY = 2, SRC_COMS = 3 };
@@ -1315,14 +1306,7 @@ batch_inter batch_carve(const fused_plan& pl, size_t start, uint32_t K = 1) {
   o.end = cv.off;
   return o;
 }
-size_t optional_many_ws(uint64_t n_each, uint32_t K) {
-  switch (pick_c(n_each)) {
-    case 7: return pip_ws<7>(n_each, K);
-    case 10: return pip_ws<10>(n_each, K);
-    case 11: return pip_ws<11>(n_each, K);
-    default: return pip_ws<16>(n_each, K);
-  }
-}
+size_t optional_many_ws(uint64_t n_each, uint32_t K) { return pip_ws_for(pick_c(n_each), n_each, K); }
 int batch_core(zkp_ctx* c, const fused_plan& pl, const batch_inter& o, uint8_t* d_ts, uint8_t* d_pts, const uint8_t* d_coms,
                const uint8_t* d_resp, const uint8_t* d_w, uint8_t* d_out /*[K][32]*/,
                uint32_t* d_status /*[K][2]: MSM decode failure | transcript rejection or non-canonical response*/, bool throughput, uint32_t K = 1,

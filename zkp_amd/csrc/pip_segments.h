@@ -39,14 +39,6 @@ inline uint32_t pip_b1(int cbits) {
     default: return pip_cfg<16>::B1;
   }
 }
-inline size_t pip_ws_c(int cbits, uint64_t n, uint32_t K) {
-  switch (cbits) {
-    case 7: return pip_ws<7>(n, K);
-    case 10: return pip_ws<10>(n, K);
-    case 11: return pip_ws<11>(n, K);
-    default: return pip_ws<16>(n, K);
-  }
-}
 
 inline uint64_t pip_run_cap(const zkp_ctx* c) {
 #ifdef ZKP_BUILD_TEST_HOOKS
@@ -87,7 +79,7 @@ inline std::vector<pip_many_run> pip_many_plan(uint32_t count, const uint32_t* l
 
 inline size_t pip_many_runs_ws(const std::vector<pip_many_run>& runs) {
   size_t need = 0;
-  for (const pip_many_run& r : runs) need = std::max(need, pip_ws_c(pick_c(r.n), r.n, r.K));
+  for (const pip_many_run& r : runs) need = std::max(need, pip_ws_for(pick_c(r.n), r.n, r.K));
   return need;
 }
 
@@ -190,15 +182,12 @@ int zkp_msm_optional_many(zkp_ctx* c, uint32_t n_seg, const uint32_t* off, const
   if (!c) return fail(ZKP_ERR_ARG, "ctx is NULL");
   if (n_seg == 0) return ZKP_OK;
   if (!off || !out || !status) return fail(ZKP_ERR_ARG, "NULL pointer");
-  if (off[0] != 0) return fail(ZKP_ERR_ARG, "off[0] must be 0");
-  for (uint32_t i = 0; i < n_seg; ++i)
-    if (off[i + 1] < off[i]) return fail(ZKP_ERR_ARG, "off must be non-decreasing");
-  const uint32_t n_terms = off[n_seg];
+  uint32_t n_terms;
+  int rc = csr_check(off, n_seg, &n_terms);
+  if (rc) return rc;
   if (n_terms && (!scalars || !points || n_points == 0)) return fail(ZKP_ERR_ARG, "terms without scalars/points");
   if (!pidx && n_points != n_terms) return fail(ZKP_ERR_ARG, "without pidx, n_points must equal the number of terms");
-  if (pidx)
-    for (uint32_t t = 0; t < n_terms; ++t)
-      if (pidx[t] >= n_points) return fail(ZKP_ERR_ARG, "pidx out of range");
+  if (!idx_in_range(pidx, n_terms, n_points)) return fail(ZKP_ERR_ARG, "pidx out of range");
   HIP_TRY(hipSetDevice(c->device));
   // the plan: empty segments are the zeroed output; short ones one CSR job of their own for the term path; the long ones in falling length
   std::vector<uint32_t> short_ids, long_ids;
@@ -253,7 +242,7 @@ int zkp_msm_optional_many(zkp_ctx* c, uint32_t n_seg, const uint32_t* off, const
   const size_t o_rows = cv.take(32 * (size_t)kmax);
   const size_t o_st = cv.take(4 * (size_t)kmax);
   const size_t reserved = cv.off;
-  int rc = ensure_ws(c, reserved + std::max(pip_many_runs_ws(runs), n_short ? terms_path_ws(s_npts, s_terms, n_short, k) : 0));
+  rc = ensure_ws(c, reserved + std::max(pip_many_runs_ws(runs), n_short ? terms_path_ws(s_npts, s_terms, n_short, k) : 0));
   if (rc) return rc;
   char* base = static_cast<char*>(c->ws);
   auto up = [&](size_t o, const void* src, size_t bytes) { return bytes ? hipMemcpyAsync(base + o, src, bytes, hipMemcpyHostToDevice, c->stream) : hipSuccess; };

@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 #include <sys/syscall.h>
 #include <unistd.h>
+#include <cassert>
 #include <cctype>
 #include <cstdio>
 #include <cstring>
@@ -2111,6 +2112,103 @@ void prof_mark(zkp_ctx* c, int kind) {
   }
 }
 
+// What a synchronous host-pointer call declares once per workspace region: the carve, the upload and the download of a region come from ONE byte count, so what
+// a kernel reads of an `in` region is what was uploaded this call, whole, and what is downloaded of an `out` region is the region, whole.  Regions are carved in
+// declaration order (a zero-size one advances nothing), uploads and downloads are queued in declaration order.  Nothing happens at destruction: an early return
+// leaves the stream as it stands.
+struct staging {
+  static constexpr size_t absent = ~(size_t)0;                  // the offset of an optional region that was not given
+  struct copy { size_t off, bytes; const void* src; void* dst; };
+  zkp_ctx* c;
+  carve cv;
+  copy copies[8];                                               // (the most any call stages is six)
+  int n_copies = 0;
+  bool reserved = false;
+  explicit staging(zkp_ctx* ctx) : c(ctx) {}
+
+  // a region of bytes + pad, of which `bytes` come from src before the launch (nothing where src is NULL or bytes 0) and go to dst after it (the same)
+  size_t inout(const void* src, void* dst, size_t bytes, size_t pad = 0) {
+    const size_t o = cv.take(bytes + pad);
+    if (bytes && (src || dst)) {
+      assert(n_copies < (int)(sizeof(copies) / sizeof(copies[0])));
+      copies[n_copies++] = {o, bytes, src, dst};
+    }
+    return o;
+  }
+  size_t in(const void* src, size_t bytes, size_t pad = 0) { return inout(src, nullptr, bytes, pad); }
+  size_t out(void* dst, size_t bytes) { return inout(nullptr, dst, bytes); }
+  size_t scratch(size_t bytes) { return cv.take(bytes); }
+  // an optional argument: without it no region at all, and at() gives the launcher its NULL
+  size_t in_opt(const void* src, size_t bytes) { return src ? in(src, bytes) : absent; }
+  size_t out_opt(void* dst, size_t bytes) { return dst ? out(dst, bytes) : absent; }
+  size_t carved() const { return cv.off; }
+  template <typename T>
+  T* at(size_t off) const { return off == absent ? nullptr : reinterpret_cast<T*>(static_cast<char*>(c->ws) + off); }
+
+  // total: what a *_ws(.., carved()) plan returns for the call (regions and the launcher's own space behind them)
+  int reserve(size_t total = 0) {
+    reserved = true;
+    return ensure_ws(c, std::max(total, cv.off));
+  }
+  int upload(size_t total = 0) {
+    if (!reserved) {
+      const int rc = reserve(total);
+      if (rc) return rc;
+    }
+    for (int i = 0; i < n_copies; ++i)
+      if (copies[i].src) HIP_TRY(hipMemcpyAsync(at<char>(copies[i].off), copies[i].src, copies[i].bytes, hipMemcpyHostToDevice, c->stream));
+    return ZKP_OK;
+  }
+  int begin(size_t total = 0) {
+    const int rc = upload(total);
+    if (rc) return rc;
+    prof_begin(c);
+    return ZKP_OK;
+  }
+  // rc: the launcher's; an error is returned before any download
+  int end(int rc) {
+    if (rc) return rc;
+    for (int i = 0; i < n_copies; ++i)
+      if (copies[i].dst) HIP_TRY(hipMemcpyAsync(copies[i].dst, at<char>(copies[i].off), copies[i].bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return ZKP_OK;
+  }
+};
+
+// 32-bit CSR offsets as every segmented call takes them: off[0] = 0, non-decreasing.  *n_terms = off[n]
+int csr_check(const uint32_t* off, uint32_t n, uint32_t* n_terms) {
+  if (off[0] != 0) return fail(ZKP_ERR_ARG, "off[0] must be 0");
+  for (uint32_t i = 0; i < n; ++i)
+    if (off[i + 1] < off[i]) return fail(ZKP_ERR_ARG, "off must be non-decreasing");
+  *n_terms = off[n];
+  return ZKP_OK;
+}
+// an optional index array of a CSR call against its bound (the caller reports which array it was)
+bool idx_in_range(const uint32_t* idx, uint32_t n_terms, uint32_t bound) {
+  for (uint32_t t = 0; idx && t < n_terms; ++t)
+    if (idx[t] >= bound) return false;
+  return true;
+}
+
+// msgs[offsets[0] .. offsets[n]) and the offsets rebased to 0, as the hash and append kernels take them (64-bit offsets, checked non-decreasing here)
+struct msg_slice {
+  std::vector<uint64_t> rebased;
+  uint64_t total = 0;
+  size_t o_msgs = 0, o_off = 0;
+  int check(const uint64_t* offsets, uint64_t n) {
+    for (uint64_t i = 0; i < n; ++i)
+      if (offsets[i + 1] < offsets[i]) return fail(ZKP_ERR_ARG, "offsets must be non-decreasing");
+    total = offsets[n] - offsets[0];
+    rebased.resize(n + 1);
+    for (uint64_t i = 0; i <= n; ++i) rebased[i] = offsets[i] - offsets[0];
+    return ZKP_OK;
+  }
+  void stage(staging& st, const uint8_t* msgs, const uint64_t* offsets) {
+    o_msgs = st.in(total ? msgs + offsets[0] : nullptr, (size_t)total);
+    o_off = st.in(rebased.data(), rebased.size() * 8);
+  }
+};
+
 inline dim3 grid1(size_t n, int block) { return dim3((unsigned)((n + block - 1) / block)); }
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
@@ -2566,6 +2664,22 @@ int pick_c(uint64_t n) {
   return 16;
 }
 constexpr uint64_t kSmallOptional = 192;   // below this, zkp_msm_optional uses the per-term path
+// pip_ws of the window size pick_c gave
+inline size_t pip_ws_for(int cbits, uint64_t n, uint32_t K = 1) {
+  switch (cbits) {
+    case 7: return pip_ws<7>(n, K);
+    case 10: return pip_ws<10>(n, K);
+    case 11: return pip_ws<11>(n, K);
+    default: return pip_ws<16>(n, K);
+  }
+}
+// What msm_optional_impl may take behind its `reserved`: a caller that sizes the workspace before it stages its inputs (zkp_msm_optional, the fused flows) asks
+// for this much, and the workspace does not grow under them.  Small sizes: the term path's need plus msm_optional_impl's two index arrays (whose padding stays
+// under the 1024: it asserts so).
+inline size_t optional_ws(uint64_t n) {
+  if (n <= kSmallOptional) return 1024 + (n + 1) * 4 + terms_path_ws((uint32_t)n, (uint32_t)n, 1);
+  return pip_ws_for(pick_c(n), n);
+}
 
 // Exact table / ladder counts of a host-side CSR job: uses per point, minus the points served by a fixed-base table.
 terms_cfg host_terms_cfg(const zkp_ctx* c, uint32_t n_terms, const uint32_t* pidx, const uint8_t* points, uint32_t n_points, uint32_t comb_min) {
@@ -2813,43 +2927,22 @@ int hash_from_bytes_host(zkp_ctx* c, uint64_t n, const uint8_t* msgs, const uint
   if (n == 0) return ZKP_OK;
   if (!msgs || !offsets || !out) return fail(ZKP_ERR_ARG, "NULL pointer");
   if (n > 0x7fffffffull) return fail(ZKP_ERR_ARG, "n too large");
-  for (uint64_t i = 0; i < n; ++i)
-    if (offsets[i + 1] < offsets[i]) return fail(ZKP_ERR_ARG, "offsets must be non-decreasing");
-  const uint64_t base_off = offsets[0], total = offsets[n] - offsets[0];
-  std::vector<uint64_t> rebased(n + 1);
-  for (uint64_t i = 0; i <= n; ++i) rebased[i] = offsets[i] - base_off;
+  msg_slice m;
+  int rc = m.check(offsets, n);
+  if (rc) return rc;
   HIP_TRY(hipSetDevice(c->device));
-  carve cv;
-  const size_t o_msgs = cv.take((size_t)total);
-  const size_t o_off = cv.take((size_t)(n + 1) * 8);
-  const size_t o_wide = cv.take(mode == HASH_SCALAR ? 0 : (size_t)n * 64);
-  const size_t o_out = cv.take((size_t)n * 32);
-  int rc = ensure_ws(c, cv.off);
+  staging st(c);
+  m.stage(st, msgs, offsets);
+  const size_t o_wide = st.out(mode == HASH_DIGEST ? out : nullptr, mode == HASH_SCALAR ? 0 : (size_t)n * 64);      // the digests: the output, or what the map reads
+  const size_t o_out = st.out(mode == HASH_DIGEST ? nullptr : out, (size_t)n * 32);
+  rc = st.begin();
   if (rc) return rc;
-  char* base = static_cast<char*>(c->ws);
-  if (total) HIP_TRY(hipMemcpyAsync(base + o_msgs, msgs + base_off, (size_t)total, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(base + o_off, rebased.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-  prof_begin(c);
-  if (mode == HASH_SCALAR) {
-    rc = launch_sc_hash_sha512(c, n, reinterpret_cast<const uint8_t*>(base + o_msgs), total, reinterpret_cast<const uint64_t*>(base + o_off),
-                               reinterpret_cast<uint8_t*>(base + o_out));
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return ZKP_OK;
-  }
-  uint8_t* d_wide = reinterpret_cast<uint8_t*>(base + o_wide);
-  rc = launch_sha512(c, n, reinterpret_cast<const uint8_t*>(base + o_msgs), total, reinterpret_cast<const uint64_t*>(base + o_off), d_wide);
-  if (rc) return rc;
-  if (mode == HASH_MAP) {
-    rc = launch_from_uniform(c, n, d_wide, reinterpret_cast<uint8_t*>(base + o_out));
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
-  } else {
-    HIP_TRY(hipMemcpyAsync(out, d_wide, (size_t)n * 64, hipMemcpyDeviceToHost, c->stream));
-  }
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return ZKP_OK;
+  const uint8_t* d_msgs = st.at<const uint8_t>(m.o_msgs);
+  const uint64_t* d_off = st.at<const uint64_t>(m.o_off);
+  if (mode == HASH_SCALAR) return st.end(launch_sc_hash_sha512(c, n, d_msgs, m.total, d_off, st.at<uint8_t>(o_out)));
+  rc = launch_sha512(c, n, d_msgs, m.total, d_off, st.at<uint8_t>(o_wide));
+  if (rc == ZKP_OK && mode == HASH_MAP) rc = launch_from_uniform(c, n, st.at<uint8_t>(o_wide), st.at<uint8_t>(o_out));
+  return st.end(rc);
 }
 
 // ---- batched Merlin operations (zkp_mi355x.h (7)): k_strobe_append_csr / k_strobe_challenge, a wavefront per workgroup, grid-stride from
@@ -3681,44 +3774,28 @@ int zkp_msm_many(zkp_ctx* c, uint32_t n_msm, const uint32_t* off, const uint8_t*
   if (flags != ZKP_CT && flags != ZKP_VARTIME) return fail(ZKP_ERR_ARG, "flags must be ZKP_CT or ZKP_VARTIME");
   if (n_msm == 0) return ZKP_OK;
   if (!off || !out || !status) return fail(ZKP_ERR_ARG, "NULL pointer");
-  if (off[0] != 0) return fail(ZKP_ERR_ARG, "off[0] must be 0");
-  for (uint32_t i = 0; i < n_msm; ++i)
-    if (off[i + 1] < off[i]) return fail(ZKP_ERR_ARG, "off must be non-decreasing");
-  const uint32_t n_terms = off[n_msm];
+  uint32_t n_terms;
+  int rc = csr_check(off, n_msm, &n_terms);
+  if (rc) return rc;
   if (n_terms && (!scalars || !pidx || !points || n_points == 0)) return fail(ZKP_ERR_ARG, "terms without scalars/points");
-  for (uint32_t t = 0; t < n_terms; ++t)
-    if (pidx[t] >= n_points) return fail(ZKP_ERR_ARG, "pidx out of range");
+  if (!idx_in_range(pidx, n_terms, n_points)) return fail(ZKP_ERR_ARG, "pidx out of range");
   HIP_TRY(hipSetDevice(c->device));
   terms_cfg k = n_terms >= 1024 ? host_terms_cfg(c, n_terms, pidx, points, n_points, flags == ZKP_CT ? c->ct_comb_min(false, n_terms) : 2u) : terms_cfg();
 #ifdef ZKP_BUILD_TEST_HOOKS
   if (c->debug_vouch_reduced && flags == ZKP_CT) k.canonical = true;
 #endif
-  carve cv;
-  const size_t o_off = cv.take((size_t)(n_msm + 1) * 4);
-  const size_t o_sc = cv.take((size_t)n_terms * 32);
-  const size_t o_pidx = cv.take((size_t)n_terms * 4);
-  const size_t o_pts = cv.take((size_t)n_points * 32);
-  const size_t o_out = cv.take((size_t)n_msm * 32);
-  const size_t o_st = cv.take((size_t)n_msm);
-  const size_t reserved = cv.off;
-  int rc = ensure_ws(c, reserved + terms_path_ws(n_points, n_terms, n_msm, k));
+  staging st(c);
+  const size_t o_off = st.in(off, (size_t)(n_msm + 1) * 4);
+  const size_t o_sc = st.in(scalars, (size_t)n_terms * 32);
+  const size_t o_pidx = st.in(pidx, (size_t)n_terms * 4);
+  const size_t o_pts = st.in(points, (size_t)n_points * 32);
+  const size_t o_out = st.out(out, (size_t)n_msm * 32);
+  const size_t o_st = st.out(status, (size_t)n_msm);
+  const size_t reserved = st.carved();
+  rc = st.begin(reserved + terms_path_ws(n_points, n_terms, n_msm, k));
   if (rc) return rc;
-  char* base = static_cast<char*>(c->ws);
-  HIP_TRY(hipMemcpyAsync(base + o_off, off, (size_t)(n_msm + 1) * 4, hipMemcpyHostToDevice, c->stream));
-  if (n_terms) {
-    HIP_TRY(hipMemcpyAsync(base + o_sc, scalars, (size_t)n_terms * 32, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(base + o_pidx, pidx, (size_t)n_terms * 4, hipMemcpyHostToDevice, c->stream));
-  }
-  if (n_points) HIP_TRY(hipMemcpyAsync(base + o_pts, points, (size_t)n_points * 32, hipMemcpyHostToDevice, c->stream));
-  prof_begin(c);
-  rc = msm_terms_path(c, n_msm, reinterpret_cast<uint32_t*>(base + o_off), reinterpret_cast<uint8_t*>(base + o_sc),
-                      reinterpret_cast<uint32_t*>(base + o_pidx), reinterpret_cast<uint8_t*>(base + o_pts), n_points,
-                      n_terms, flags, reinterpret_cast<uint8_t*>(base + o_out), reinterpret_cast<uint8_t*>(base + o_st), nullptr, reserved, false, PH_ALL, k);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)n_msm * 32, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(status, base + o_st, (size_t)n_msm, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return ZKP_OK;
+  return st.end(msm_terms_path(c, n_msm, st.at<uint32_t>(o_off), st.at<uint8_t>(o_sc), st.at<uint32_t>(o_pidx), st.at<uint8_t>(o_pts), n_points, n_terms, flags,
+                               st.at<uint8_t>(o_out), st.at<uint8_t>(o_st), nullptr, reserved, false, PH_ALL, k));
 }
 
 // ---- (11) multiscalar sums with long segments ----
@@ -3757,15 +3834,12 @@ int zkp_msm_segments(zkp_ctx* c, uint32_t n_msm, const uint32_t* off, const uint
   if (flags != ZKP_CT && flags != ZKP_VARTIME) return fail(ZKP_ERR_ARG, "flags must be ZKP_CT or ZKP_VARTIME");
   if (n_msm == 0) return ZKP_OK;
   if (!off || !out || !status) return fail(ZKP_ERR_ARG, "NULL pointer");
-  if (off[0] != 0) return fail(ZKP_ERR_ARG, "off[0] must be 0");
-  for (uint32_t i = 0; i < n_msm; ++i)
-    if (off[i + 1] < off[i]) return fail(ZKP_ERR_ARG, "off must be non-decreasing");
-  const uint32_t n_terms = off[n_msm];
+  uint32_t n_terms;
+  int rc = csr_check(off, n_msm, &n_terms);
+  if (rc) return rc;
   if (n_terms && (!scalars || !points || n_points == 0)) return fail(ZKP_ERR_ARG, "terms without scalars/points");
   if (!pidx && n_points != n_terms) return fail(ZKP_ERR_ARG, "without pidx, n_points must equal the number of terms");
-  if (pidx)
-    for (uint32_t t = 0; t < n_terms; ++t)
-      if (pidx[t] >= n_points) return fail(ZKP_ERR_ARG, "pidx out of range");
+  if (!idx_in_range(pidx, n_terms, n_points)) return fail(ZKP_ERR_ARG, "pidx out of range");
   HIP_TRY(hipSetDevice(c->device));
   std::vector<uint32_t> iota;                // without pidx: term t is point t; the exact table counts want the index written out (the device writes its own)
   if (!pidx && n_terms >= 1024) {
@@ -3777,33 +3851,19 @@ int zkp_msm_segments(zkp_ctx* c, uint32_t n_msm, const uint32_t* off, const uint
   if (c->debug_vouch_reduced && flags == ZKP_CT) k.canonical = true;
 #endif
   k.terms_only = true;
-  carve cv;
-  const size_t o_off = cv.take((size_t)(n_msm + 1) * 4);
-  const size_t o_sc = cv.take((size_t)n_terms * 32);
-  const size_t o_pidx = cv.take((size_t)n_terms * 4);
-  const size_t o_pts = cv.take((size_t)n_points * 32);
-  const size_t o_out = cv.take((size_t)n_msm * 32);
-  const size_t o_st = cv.take((size_t)n_msm);
-  const segments_ws w = msm_segments_ws(n_points, n_terms, n_msm, k, cv.off);
-  int rc = ensure_ws(c, w.sum.total);
+  staging st(c);
+  const size_t o_off = st.in(off, (size_t)(n_msm + 1) * 4);
+  const size_t o_sc = st.in(scalars, (size_t)n_terms * 32);
+  const size_t o_pidx = st.in(pidx, (size_t)n_terms * 4);                   // without pidx: k_iota's, below
+  const size_t o_pts = st.in(n_terms ? points : nullptr, (size_t)n_points * 32);
+  const size_t o_out = st.out(out, (size_t)n_msm * 32);
+  const size_t o_st = st.out(status, (size_t)n_msm);
+  const segments_ws w = msm_segments_ws(n_points, n_terms, n_msm, k, st.carved());
+  rc = st.begin(w.sum.total);
   if (rc) return rc;
-  char* base = static_cast<char*>(c->ws);
-  HIP_TRY(hipMemcpyAsync(base + o_off, off, (size_t)(n_msm + 1) * 4, hipMemcpyHostToDevice, c->stream));
-  if (n_terms) {
-    HIP_TRY(hipMemcpyAsync(base + o_sc, scalars, (size_t)n_terms * 32, hipMemcpyHostToDevice, c->stream));
-    if (pidx) HIP_TRY(hipMemcpyAsync(base + o_pidx, pidx, (size_t)n_terms * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(base + o_pts, points, (size_t)n_points * 32, hipMemcpyHostToDevice, c->stream));
-  }
-  prof_begin(c);
-  if (!pidx && n_terms) hipLaunchKernelGGL(k_iota, grid1(n_terms, 256), dim3(256), 0, c->stream, n_terms, reinterpret_cast<uint32_t*>(base + o_pidx));
-  rc = launch_msm_segments(c, n_msm, reinterpret_cast<uint32_t*>(base + o_off), reinterpret_cast<uint8_t*>(base + o_sc), reinterpret_cast<uint32_t*>(base + o_pidx),
-                           reinterpret_cast<uint8_t*>(base + o_pts), n_points, n_terms, flags, k, w, reinterpret_cast<uint8_t*>(base + o_out),
-                           reinterpret_cast<uint8_t*>(base + o_st));
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)n_msm * 32, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(status, base + o_st, (size_t)n_msm, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return ZKP_OK;
+  if (!pidx && n_terms) hipLaunchKernelGGL(k_iota, grid1(n_terms, 256), dim3(256), 0, c->stream, n_terms, st.at<uint32_t>(o_pidx));
+  return st.end(launch_msm_segments(c, n_msm, st.at<uint32_t>(o_off), st.at<uint8_t>(o_sc), st.at<uint32_t>(o_pidx), st.at<uint8_t>(o_pts), n_points, n_terms, flags, k,
+                                    w, st.at<uint8_t>(o_out), st.at<uint8_t>(o_st)));
 }
 
 // shared_flags (optional, Pippenger sizes only): a zeroed device word that replaces the path's own decode-failure flag (bit 0) and
@@ -3818,6 +3878,7 @@ static int msm_optional_impl(zkp_ctx* c, uint64_t n, const uint8_t* d_scalars, c
     const size_t o_pidx = cv.take((size_t)(n + 1) * 4);
     const size_t o_off = cv.take(256);
     const size_t inner = cv.off;
+    assert(inner - reserved + terms_path_ws((uint32_t)n, (uint32_t)n, 1) <= optional_ws(n));
     int rc = ensure_ws(c, inner + terms_path_ws((uint32_t)n, (uint32_t)n, 1));
     if (rc) return rc;
     char* base = static_cast<char*>(c->ws);
@@ -3827,17 +3888,9 @@ static int msm_optional_impl(zkp_ctx* c, uint64_t n, const uint8_t* d_scalars, c
     return msm_terms_path(c, 1, off, d_scalars, pidx, d_points, (uint32_t)n, (uint32_t)n, ZKP_VARTIME, d_out, nullptr, d_status, inner);
   }
   if (n > 0x7fffffffull) return fail(ZKP_ERR_ARG, "n too large (max 2^31-1 terms per call)");
-  const int cbits = pick_c(n);
-  size_t need = 0;
-  switch (cbits) {
-    case 7: need = pip_ws<7>(n); break;
-    case 10: need = pip_ws<10>(n); break;
-    case 11: need = pip_ws<11>(n); break;
-    default: need = pip_ws<16>(n); break;
-  }
-  int rc = ensure_ws(c, reserved + need);
+  int rc = ensure_ws(c, reserved + optional_ws(n));
   if (rc) return rc;
-  switch (cbits) {
+  switch (pick_c(n)) {
     case 7: return pip_run<7>(c, (uint32_t)n, d_scalars, d_points, d_out, d_status, reserved, shared_flags, pip_seg(), phases);
     case 10: return pip_run<10>(c, (uint32_t)n, d_scalars, d_points, d_out, d_status, reserved, shared_flags, pip_seg(), phases);
     case 11: return pip_run<11>(c, (uint32_t)n, d_scalars, d_points, d_out, d_status, reserved, shared_flags, pip_seg(), phases);
@@ -3861,40 +3914,19 @@ int zkp_msm_optional(zkp_ctx* c, uint64_t n, const uint8_t* scalars, const uint8
   if (!out_point || !status) return fail(ZKP_ERR_ARG, "NULL output pointer");
   if (n && (!scalars || !points)) return fail(ZKP_ERR_ARG, "NULL input pointer");
   HIP_TRY(hipSetDevice(c->device));
-  carve cv;
-  const size_t o_sc = cv.take((size_t)n * 32 + 32);
-  const size_t o_pts = cv.take((size_t)n * 32 + 32);
-  const size_t o_out = cv.take(32);
-  const size_t o_st = cv.take(4);
-  const size_t reserved = cv.off;
+  uint32_t word = 1;
+  staging st(c);
+  const size_t o_sc = st.in(scalars, (size_t)n * 32, 32);
+  const size_t o_pts = st.in(points, (size_t)n * 32, 32);
+  const size_t o_out = st.out(out_point, 32);
+  const size_t o_st = st.out(&word, 4);
+  const size_t reserved = st.carved();
   // size the workspace once, up front (inputs are copied before the kernels are enqueued)
-  size_t need = 0;
-  if (n <= kSmallOptional) {
-    need = 1024 + (n + 1) * 4 + terms_path_ws((uint32_t)n, (uint32_t)n, 1);
-  } else {
-    switch (pick_c(n)) {
-      case 7: need = pip_ws<7>(n); break;
-      case 10: need = pip_ws<10>(n); break;
-      case 11: need = pip_ws<11>(n); break;
-        default: need = pip_ws<16>(n); break;
-    }
-  }
-  int rc = ensure_ws(c, reserved + need);
+  int rc = st.begin(reserved + optional_ws(n));
   if (rc) return rc;
-  char* base = static_cast<char*>(c->ws);
-  if (n) {
-    HIP_TRY(hipMemcpyAsync(base + o_sc, scalars, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(base + o_pts, points, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
-  }
-  prof_begin(c);
-  rc = msm_optional_impl(c, n, reinterpret_cast<uint8_t*>(base + o_sc), reinterpret_cast<uint8_t*>(base + o_pts),
-                         reinterpret_cast<uint8_t*>(base + o_out), reinterpret_cast<uint32_t*>(base + o_st), reserved);
+  rc = st.end(msm_optional_impl(c, n, st.at<uint8_t>(o_sc), st.at<uint8_t>(o_pts), st.at<uint8_t>(o_out), st.at<uint32_t>(o_st), reserved));
   if (rc) return rc;
-  uint32_t st = 1;
-  HIP_TRY(hipMemcpyAsync(out_point, static_cast<char*>(c->ws) + o_out, 32, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(&st, static_cast<char*>(c->ws) + o_st, 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  *status = (int)st;
+  *status = (int)word;
   return ZKP_OK;
 }
 
@@ -3904,23 +3936,16 @@ int zkp_decode_check(zkp_ctx* c, uint64_t n, const uint8_t* points, uint8_t* sta
   if (!points || !status) return fail(ZKP_ERR_ARG, "NULL pointer");
   if (n > 0x7fffffffull) return fail(ZKP_ERR_ARG, "n too large");
   HIP_TRY(hipSetDevice(c->device));
-  carve cv;
-  const size_t o_pts = cv.take((size_t)n * 32);
-  const size_t o_st = cv.take((size_t)n);
-  const size_t o_xyzt = cv.take(xyzt ? (size_t)n * 128 : 0);
-  const int rc = ensure_ws(c, cv.off);
+  staging st(c);
+  const size_t o_pts = st.in(points, (size_t)n * 32);
+  const size_t o_st = st.out(status, (size_t)n);
+  const size_t o_xyzt = st.out_opt(xyzt, (size_t)n * 128);
+  const int rc = st.begin();
   if (rc) return rc;
-  char* base = static_cast<char*>(c->ws);
-  HIP_TRY(hipMemcpyAsync(base + o_pts, points, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
-  prof_begin(c);
-  hipLaunchKernelGGL(k_decode_check, grid1(n, 256), dim3(256), 0, c->stream, (uint32_t)n, reinterpret_cast<uint8_t*>(base + o_pts),
-                     reinterpret_cast<uint8_t*>(base + o_st), xyzt ? reinterpret_cast<uint8_t*>(base + o_xyzt) : nullptr);
+  hipLaunchKernelGGL(k_decode_check, grid1(n, 256), dim3(256), 0, c->stream, (uint32_t)n, st.at<uint8_t>(o_pts), st.at<uint8_t>(o_st), st.at<uint8_t>(o_xyzt));
   prof_mark(c, ZKP_K_DECODE);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(status, base + o_st, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-  if (xyzt) HIP_TRY(hipMemcpyAsync(xyzt, base + o_xyzt, (size_t)n * 128, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return ZKP_OK;
+  return st.end(ZKP_OK);
 }
 
 int zkp_from_uniform_bytes_dev(zkp_ctx* c, uint64_t n, const uint8_t* d_in, uint8_t* d_out) {
@@ -3940,19 +3965,12 @@ int zkp_from_uniform_bytes(zkp_ctx* c, uint64_t n, const uint8_t* in, uint8_t* o
   if (!in || !out) return fail(ZKP_ERR_ARG, "NULL pointer");
   if (n > 0x7fffffffull) return fail(ZKP_ERR_ARG, "n too large");
   HIP_TRY(hipSetDevice(c->device));
-  carve cv;
-  const size_t o_in = cv.take((size_t)n * 64);
-  const size_t o_out = cv.take((size_t)n * 32);
-  int rc = ensure_ws(c, cv.off);
+  staging st(c);
+  const size_t o_in = st.in(in, (size_t)n * 64);
+  const size_t o_out = st.out(out, (size_t)n * 32);
+  const int rc = st.begin();
   if (rc) return rc;
-  char* base = static_cast<char*>(c->ws);
-  HIP_TRY(hipMemcpyAsync(base + o_in, in, (size_t)n * 64, hipMemcpyHostToDevice, c->stream));
-  prof_begin(c);
-  rc = launch_from_uniform(c, n, reinterpret_cast<uint8_t*>(base + o_in), reinterpret_cast<uint8_t*>(base + o_out));
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return ZKP_OK;
+  return st.end(launch_from_uniform(c, n, st.at<uint8_t>(o_in), st.at<uint8_t>(o_out)));
 }
 
 int zkp_hash_from_bytes_sha512(zkp_ctx* c, uint64_t n, const uint8_t* msgs, const uint64_t* offsets, uint8_t* out) {
@@ -3993,18 +4011,11 @@ int zkp_sc_invert(zkp_ctx* c, uint64_t n, const uint8_t* in, uint8_t* out) {
   int rc = sc_call_check(c, n, !in || !out);
   if (rc || n == 0) return rc;
   HIP_TRY(hipSetDevice(c->device));
-  carve cv;
-  const size_t o_io = cv.take((size_t)n * 32);
-  rc = ensure_ws(c, cv.off);
+  staging st(c);
+  const size_t o_io = st.inout(in, out, (size_t)n * 32);
+  rc = st.begin();
   if (rc) return rc;
-  uint8_t* d_io = static_cast<uint8_t*>(c->ws) + o_io;
-  HIP_TRY(hipMemcpyAsync(d_io, in, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
-  prof_begin(c);
-  rc = launch_sc_invert(c, n, d_io, d_io);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(out, d_io, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return ZKP_OK;
+  return st.end(launch_sc_invert(c, n, st.at<uint8_t>(o_io), st.at<uint8_t>(o_io)));
 }
 
 int zkp_sc_from_wide_dev(zkp_ctx* c, uint64_t n, const uint8_t* d_in, uint8_t* d_out) {
@@ -4019,19 +4030,12 @@ int zkp_sc_from_wide(zkp_ctx* c, uint64_t n, const uint8_t* in, uint8_t* out) {
   int rc = sc_call_check(c, n, !in || !out);
   if (rc || n == 0) return rc;
   HIP_TRY(hipSetDevice(c->device));
-  carve cv;
-  const size_t o_in = cv.take((size_t)n * 64);
-  const size_t o_out = cv.take((size_t)n * 32);
-  rc = ensure_ws(c, cv.off);
+  staging st(c);
+  const size_t o_in = st.in(in, (size_t)n * 64);
+  const size_t o_out = st.out(out, (size_t)n * 32);
+  rc = st.begin();
   if (rc) return rc;
-  uint8_t* base = static_cast<uint8_t*>(c->ws);
-  HIP_TRY(hipMemcpyAsync(base + o_in, in, (size_t)n * 64, hipMemcpyHostToDevice, c->stream));
-  prof_begin(c);
-  rc = launch_sc_from_wide(c, n, base + o_in, base + o_out);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return ZKP_OK;
+  return st.end(launch_sc_from_wide(c, n, st.at<uint8_t>(o_in), st.at<uint8_t>(o_out)));
 }
 
 int zkp_sc_muladd_dev(zkp_ctx* c, uint64_t n, const uint8_t* d_a, uint32_t a_stride, const uint8_t* d_b, uint32_t b_stride, const uint8_t* d_c, uint32_t c_stride,
@@ -4048,24 +4052,14 @@ int zkp_sc_muladd(zkp_ctx* c, uint64_t n, const uint8_t* a, uint32_t a_stride, c
   int rc = sc_call_check(c, n, !a || !b || !out, a_stride <= 1 && b_stride <= 1 && c_stride <= 1);
   if (rc || n == 0) return rc;
   HIP_TRY(hipSetDevice(c->device));
-  const size_t na = a_stride ? (size_t)n : 1, nb = b_stride ? (size_t)n : 1, nc = !cc ? 0 : c_stride ? (size_t)n : 1;
-  carve cv;
-  const size_t o_a = cv.take(na * 32);
-  const size_t o_b = cv.take(nb * 32);
-  const size_t o_c = cv.take(nc * 32);
-  const size_t o_out = cv.take((size_t)n * 32);
-  rc = ensure_ws(c, cv.off);
+  staging st(c);
+  const size_t o_a = st.in(a, (a_stride ? (size_t)n : 1) * 32);
+  const size_t o_b = st.in(b, (b_stride ? (size_t)n : 1) * 32);
+  const size_t o_c = st.in_opt(cc, (c_stride ? (size_t)n : 1) * 32);
+  const size_t o_out = st.out(out, (size_t)n * 32);
+  rc = st.begin();
   if (rc) return rc;
-  uint8_t* base = static_cast<uint8_t*>(c->ws);
-  HIP_TRY(hipMemcpyAsync(base + o_a, a, na * 32, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(base + o_b, b, nb * 32, hipMemcpyHostToDevice, c->stream));
-  if (cc) HIP_TRY(hipMemcpyAsync(base + o_c, cc, nc * 32, hipMemcpyHostToDevice, c->stream));
-  prof_begin(c);
-  rc = launch_sc_muladd(c, n, base + o_a, a_stride, base + o_b, b_stride, cc ? base + o_c : nullptr, c_stride, base + o_out);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return ZKP_OK;
+  return st.end(launch_sc_muladd(c, n, st.at<uint8_t>(o_a), a_stride, st.at<uint8_t>(o_b), b_stride, st.at<uint8_t>(o_c), c_stride, st.at<uint8_t>(o_out)));
 }
 
 // ---- (12) segmented scalar sums, products and dot products ----
@@ -4094,44 +4088,26 @@ int zkp_sc_reduce(zkp_ctx* c, int op, uint32_t n_out, const uint32_t* off, const
   if (!c) return fail(ZKP_ERR_ARG, "ctx is NULL");
   if (n_out == 0) return op == ZKP_SC_SUM || op == ZKP_SC_PRODUCT || op == ZKP_SC_DOT ? ZKP_OK : fail(ZKP_ERR_ARG, "op must be ZKP_SC_SUM, ZKP_SC_PRODUCT or ZKP_SC_DOT");
   if (!off || !out) return fail(ZKP_ERR_ARG, "NULL pointer");
-  if (off[0] != 0) return fail(ZKP_ERR_ARG, "off[0] must be 0");
-  for (uint32_t i = 0; i < n_out; ++i)
-    if (off[i + 1] < off[i]) return fail(ZKP_ERR_ARG, "off must be non-decreasing");
-  const uint32_t n_terms = off[n_out];
-  int rc = sc_reduce_check(c, op, n_out, off, a, n_a, aidx, b, n_b, bidx, n_terms, out);
+  uint32_t n_terms;
+  int rc = csr_check(off, n_out, &n_terms);
   if (rc) return rc;
-  for (uint32_t t = 0; aidx && t < n_terms; ++t)
-    if (aidx[t] >= n_a) return fail(ZKP_ERR_ARG, "aidx out of range");
-  for (uint32_t t = 0; bidx && t < n_terms; ++t)
-    if (bidx[t] >= n_b) return fail(ZKP_ERR_ARG, "bidx out of range");
+  rc = sc_reduce_check(c, op, n_out, off, a, n_a, aidx, b, n_b, bidx, n_terms, out);
+  if (rc) return rc;
+  if (!idx_in_range(aidx, n_terms, n_a)) return fail(ZKP_ERR_ARG, "aidx out of range");
+  if (!idx_in_range(bidx, n_terms, n_b)) return fail(ZKP_ERR_ARG, "bidx out of range");
   HIP_TRY(hipSetDevice(c->device));
-  const bool dot = op == ZKP_SC_DOT;
-  carve cv;
-  const size_t o_off = cv.take((size_t)(n_out + 1) * 4);
-  const size_t o_a = cv.take(n_terms ? (size_t)n_a * 32 : 0);
-  const size_t o_ai = cv.take(aidx ? (size_t)n_terms * 4 : 0);
-  const size_t o_b = cv.take(dot && n_terms ? (size_t)n_b * 32 : 0);
-  const size_t o_bi = cv.take(bidx ? (size_t)n_terms * 4 : 0);
-  const size_t o_out = cv.take((size_t)n_out * 32);
-  const sc_red_ws w = sc_reduce_ws(n_terms, cv.off);
-  rc = ensure_ws(c, w.total);
+  staging st(c);
+  const size_t o_off = st.in(off, (size_t)(n_out + 1) * 4);
+  const size_t o_a = st.in(a, n_terms ? (size_t)n_a * 32 : 0);
+  const size_t o_ai = st.in_opt(aidx, (size_t)n_terms * 4);
+  const size_t o_b = st.in_opt(b, n_terms ? (size_t)n_b * 32 : 0);           // (sc_reduce_check: b is NULL unless the op is ZKP_SC_DOT)
+  const size_t o_bi = st.in_opt(bidx, (size_t)n_terms * 4);
+  const size_t o_out = st.out(out, (size_t)n_out * 32);
+  const sc_red_ws w = sc_reduce_ws(n_terms, st.carved());
+  rc = st.begin(w.total);
   if (rc) return rc;
-  char* base = static_cast<char*>(c->ws);
-  HIP_TRY(hipMemcpyAsync(base + o_off, off, (size_t)(n_out + 1) * 4, hipMemcpyHostToDevice, c->stream));
-  if (n_terms) {
-    HIP_TRY(hipMemcpyAsync(base + o_a, a, (size_t)n_a * 32, hipMemcpyHostToDevice, c->stream));
-    if (aidx) HIP_TRY(hipMemcpyAsync(base + o_ai, aidx, (size_t)n_terms * 4, hipMemcpyHostToDevice, c->stream));
-    if (dot) HIP_TRY(hipMemcpyAsync(base + o_b, b, (size_t)n_b * 32, hipMemcpyHostToDevice, c->stream));
-    if (bidx) HIP_TRY(hipMemcpyAsync(base + o_bi, bidx, (size_t)n_terms * 4, hipMemcpyHostToDevice, c->stream));
-  }
-  prof_begin(c);
-  rc = launch_sc_reduce(c, op, n_out, reinterpret_cast<uint32_t*>(base + o_off), reinterpret_cast<uint8_t*>(base + o_a), n_a,
-                        aidx ? reinterpret_cast<uint32_t*>(base + o_ai) : nullptr, dot ? reinterpret_cast<uint8_t*>(base + o_b) : nullptr, n_b,
-                        bidx ? reinterpret_cast<uint32_t*>(base + o_bi) : nullptr, n_terms, w, reinterpret_cast<uint8_t*>(base + o_out));
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)n_out * 32, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return ZKP_OK;
+  return st.end(launch_sc_reduce(c, op, n_out, st.at<uint32_t>(o_off), st.at<uint8_t>(o_a), n_a, st.at<uint32_t>(o_ai), st.at<uint8_t>(o_b), n_b, st.at<uint32_t>(o_bi),
+                                 n_terms, w, st.at<uint8_t>(o_out)));
 }
 
 int zkp_sc_hash_from_bytes_sha512(zkp_ctx* c, uint64_t n, const uint8_t* msgs, const uint64_t* offsets, uint8_t* out) {
@@ -4165,21 +4141,16 @@ int zkp_mul_base(zkp_ctx* c, uint64_t n, const uint8_t* scalars, uint8_t* out) {
   int rc = sc_call_check(c, n, !scalars || !out);
   if (rc || n == 0) return rc;
   HIP_TRY(hipSetDevice(c->device));
-  carve cv;
-  const size_t o_sc = cv.take((size_t)n * 32);
-  const size_t o_out = cv.take((size_t)n * 32);
-  rc = ensure_ws(c, cv.off);
+  staging st(c);
+  const size_t o_sc = st.in(scalars, (size_t)n * 32);
+  const size_t o_out = st.out(out, (size_t)n * 32);
+  rc = st.reserve();
   if (rc) return rc;
   rc = ensure_base_table(c);
   if (rc) return rc;
-  uint8_t* base = static_cast<uint8_t*>(c->ws);
-  HIP_TRY(hipMemcpyAsync(base + o_sc, scalars, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
-  prof_begin(c);
-  rc = launch_mul_base(c, n, base + o_sc, base + o_out);
+  rc = st.begin();
   if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return ZKP_OK;
+  return st.end(launch_mul_base(c, n, st.at<uint8_t>(o_sc), st.at<uint8_t>(o_out)));
 }
 
 int zkp_mul_points_dev(zkp_ctx* c, uint64_t n, const uint8_t* d_scalars, uint32_t s_stride, const uint8_t* d_points, uint32_t p_stride, int flags,
@@ -4198,25 +4169,16 @@ int zkp_mul_points(zkp_ctx* c, uint64_t n, const uint8_t* scalars, uint32_t s_st
   int rc = mul_points_check(c, n, s_stride, p_stride, flags, !scalars || !points || !out || !status);
   if (rc || n == 0) return rc;
   HIP_TRY(hipSetDevice(c->device));
-  const size_t ns = s_stride ? (size_t)n : 1, np = p_stride ? (size_t)n : 1;
-  carve cv;
-  const size_t o_sc = cv.take(ns * 32);
-  const size_t o_pt = cv.take(np * 32);
-  const size_t o_out = cv.take((size_t)n * 32);
-  const size_t o_st = cv.take((size_t)n);
-  const size_t o_ladder = cv.take(mul_pairs_ws(n));
-  rc = ensure_ws(c, cv.off);
+  staging st(c);
+  const size_t o_sc = st.in(scalars, (s_stride ? (size_t)n : 1) * 32);
+  const size_t o_pt = st.in(points, (p_stride ? (size_t)n : 1) * 32);
+  const size_t o_out = st.out(out, (size_t)n * 32);
+  const size_t o_st = st.out(status, (size_t)n);
+  const size_t o_ladder = st.scratch(mul_pairs_ws(n));
+  rc = st.begin();
   if (rc) return rc;
-  uint8_t* base = static_cast<uint8_t*>(c->ws);
-  HIP_TRY(hipMemcpyAsync(base + o_sc, scalars, ns * 32, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(base + o_pt, points, np * 32, hipMemcpyHostToDevice, c->stream));
-  prof_begin(c);
-  rc = launch_mul_pairs(c, n, base + o_sc, s_stride, base + o_pt, p_stride, flags, reinterpret_cast<uint4*>(base + o_ladder), base + o_out, base + o_st);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(status, base + o_st, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return ZKP_OK;
+  return st.end(launch_mul_pairs(c, n, st.at<uint8_t>(o_sc), s_stride, st.at<uint8_t>(o_pt), p_stride, flags, st.at<uint4>(o_ladder), st.at<uint8_t>(o_out),
+                                 st.at<uint8_t>(o_st)));
 }
 
 // ---- (9) batched RistrettoPoint sums: pairs and CSR segments -------------------------------------------------------------------------------
@@ -4235,24 +4197,14 @@ int zkp_add_points(zkp_ctx* c, uint64_t n, const uint8_t* a, uint32_t a_stride, 
   int rc = add_points_check(c, n, a_stride, b_stride, op, !a || !b || !out || !status);
   if (rc || n == 0) return rc;
   HIP_TRY(hipSetDevice(c->device));
-  const size_t na = a_stride ? (size_t)n : 1, nb = b_stride ? (size_t)n : 1;
-  carve cv;
-  const size_t o_a = cv.take(na * 32);
-  const size_t o_b = cv.take(nb * 32);
-  const size_t o_out = cv.take((size_t)n * 32);
-  const size_t o_st = cv.take((size_t)n);
-  rc = ensure_ws(c, cv.off);
+  staging st(c);
+  const size_t o_a = st.in(a, (a_stride ? (size_t)n : 1) * 32);
+  const size_t o_b = st.in(b, (b_stride ? (size_t)n : 1) * 32);
+  const size_t o_out = st.out(out, (size_t)n * 32);
+  const size_t o_st = st.out(status, (size_t)n);
+  rc = st.begin();
   if (rc) return rc;
-  uint8_t* base = static_cast<uint8_t*>(c->ws);
-  HIP_TRY(hipMemcpyAsync(base + o_a, a, na * 32, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(base + o_b, b, nb * 32, hipMemcpyHostToDevice, c->stream));
-  prof_begin(c);
-  rc = launch_add_pairs(c, n, base + o_a, a_stride, base + o_b, b_stride, op, base + o_out, base + o_st);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(status, base + o_st, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return ZKP_OK;
+  return st.end(launch_add_pairs(c, n, st.at<uint8_t>(o_a), a_stride, st.at<uint8_t>(o_b), b_stride, op, st.at<uint8_t>(o_out), st.at<uint8_t>(o_st)));
 }
 
 int zkp_sum_points_dev(zkp_ctx* c, uint32_t n_sums, const uint32_t* d_off, const uint32_t* d_pidx, const uint8_t* d_neg, const uint8_t* d_points,
@@ -4275,43 +4227,26 @@ int zkp_sum_points(zkp_ctx* c, uint32_t n_sums, const uint32_t* off, const uint3
   if (!c) return fail(ZKP_ERR_ARG, "ctx is NULL");
   if (n_sums == 0) return ZKP_OK;
   if (!off || !out || !status) return fail(ZKP_ERR_ARG, "NULL pointer");
-  if (off[0] != 0) return fail(ZKP_ERR_ARG, "off[0] must be 0");
-  for (uint32_t i = 0; i < n_sums; ++i)
-    if (off[i + 1] < off[i]) return fail(ZKP_ERR_ARG, "off must be non-decreasing");
-  const uint32_t n_terms = off[n_sums];
+  uint32_t n_terms;
+  int rc = csr_check(off, n_sums, &n_terms);
+  if (rc) return rc;
   if (n_terms && (!points || n_points == 0)) return fail(ZKP_ERR_ARG, "terms without points");
   if (!pidx && n_points != n_terms) return fail(ZKP_ERR_ARG, "without pidx, n_points must equal the number of terms");
-  if (pidx)
-    for (uint32_t t = 0; t < n_terms; ++t)
-      if (pidx[t] >= n_points) return fail(ZKP_ERR_ARG, "pidx out of range");
+  if (!idx_in_range(pidx, n_terms, n_points)) return fail(ZKP_ERR_ARG, "pidx out of range");
   HIP_TRY(hipSetDevice(c->device));
-  const bool with_pts = n_terms != 0;
-  carve cv;
-  const size_t o_off = cv.take((size_t)(n_sums + 1) * 4);
-  const size_t o_pidx = cv.take(pidx ? (size_t)n_terms * 4 : 0);
-  const size_t o_neg = cv.take(neg ? (size_t)n_terms : 0);
-  const size_t o_pts = cv.take(with_pts ? (size_t)n_points * 32 : 0);
-  const size_t o_out = cv.take((size_t)n_sums * 32);
-  const size_t o_st = cv.take((size_t)n_sums);
-  const sum_ws w = sum_points_ws(with_pts ? n_points : 0, n_terms, n_sums, cv.off);
-  int rc = ensure_ws(c, w.total);
+  const uint32_t n_pts = n_terms ? n_points : 0;                      // without terms the points are neither staged nor decoded
+  staging st(c);
+  const size_t o_off = st.in(off, (size_t)(n_sums + 1) * 4);
+  const size_t o_pidx = st.in_opt(pidx, (size_t)n_terms * 4);
+  const size_t o_neg = st.in_opt(neg, (size_t)n_terms);
+  const size_t o_pts = st.in(points, (size_t)n_pts * 32);
+  const size_t o_out = st.out(out, (size_t)n_sums * 32);
+  const size_t o_st = st.out(status, (size_t)n_sums);
+  const sum_ws w = sum_points_ws(n_pts, n_terms, n_sums, st.carved());
+  rc = st.begin(w.total);
   if (rc) return rc;
-  char* base = static_cast<char*>(c->ws);
-  HIP_TRY(hipMemcpyAsync(base + o_off, off, (size_t)(n_sums + 1) * 4, hipMemcpyHostToDevice, c->stream));
-  if (n_terms) {
-    if (pidx) HIP_TRY(hipMemcpyAsync(base + o_pidx, pidx, (size_t)n_terms * 4, hipMemcpyHostToDevice, c->stream));
-    if (neg) HIP_TRY(hipMemcpyAsync(base + o_neg, neg, (size_t)n_terms, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(base + o_pts, points, (size_t)n_points * 32, hipMemcpyHostToDevice, c->stream));
-  }
-  prof_begin(c);
-  rc = launch_sum_points(c, n_sums, reinterpret_cast<uint32_t*>(base + o_off), pidx ? reinterpret_cast<uint32_t*>(base + o_pidx) : nullptr,
-                         neg ? reinterpret_cast<uint8_t*>(base + o_neg) : nullptr, reinterpret_cast<uint8_t*>(base + o_pts), n_points, n_terms, base, w,
-                         reinterpret_cast<uint8_t*>(base + o_out), reinterpret_cast<uint8_t*>(base + o_st));
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)n_sums * 32, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(status, base + o_st, (size_t)n_sums, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return ZKP_OK;
+  return st.end(launch_sum_points(c, n_sums, st.at<uint32_t>(o_off), st.at<uint32_t>(o_pidx), st.at<uint8_t>(o_neg), st.at<uint8_t>(o_pts), n_points, n_terms,
+                                  st.at<char>(0), w, st.at<uint8_t>(o_out), st.at<uint8_t>(o_st)));
 }
 
 // ---- (13) segmented prefix sums and products of scalars, running sums of points ---------------------------------------------------------------
@@ -4339,34 +4274,22 @@ int zkp_sc_scan(zkp_ctx* c, int op, int mode, uint32_t n_seg, const uint32_t* of
   if (n_seg == 0) return sc_scan_check(c, op, mode, &n_seg, a, 0, &n_seg, 0, out);
   if (!c) return fail(ZKP_ERR_ARG, "ctx is NULL");
   if (!off) return fail(ZKP_ERR_ARG, "NULL pointer");
-  if (off[0] != 0) return fail(ZKP_ERR_ARG, "off[0] must be 0");
-  for (uint32_t i = 0; i < n_seg; ++i)
-    if (off[i + 1] < off[i]) return fail(ZKP_ERR_ARG, "off must be non-decreasing");
-  const uint32_t n_terms = off[n_seg];
-  int rc = sc_scan_check(c, op, mode, off, a, n_a, aidx, n_terms, out);
+  uint32_t n_terms;
+  int rc = csr_check(off, n_seg, &n_terms);
+  if (rc) return rc;
+  rc = sc_scan_check(c, op, mode, off, a, n_a, aidx, n_terms, out);
   if (rc || n_terms == 0) return rc;
-  for (uint32_t t = 0; aidx && t < n_terms; ++t)
-    if (aidx[t] >= n_a) return fail(ZKP_ERR_ARG, "aidx out of range");
+  if (!idx_in_range(aidx, n_terms, n_a)) return fail(ZKP_ERR_ARG, "aidx out of range");
   HIP_TRY(hipSetDevice(c->device));
-  carve cv;
-  const size_t o_off = cv.take((size_t)(n_seg + 1) * 4);
-  const size_t o_a = cv.take((size_t)n_a * 32);
-  const size_t o_ai = cv.take(aidx ? (size_t)n_terms * 4 : 0);
-  const size_t o_out = cv.take((size_t)n_terms * 32);
-  const sc_scan_ws w = sc_scan_plan(n_terms, cv.off);
-  rc = ensure_ws(c, w.total);
+  staging st(c);
+  const size_t o_off = st.in(off, (size_t)(n_seg + 1) * 4);
+  const size_t o_a = st.in(a, (size_t)n_a * 32);
+  const size_t o_ai = st.in_opt(aidx, (size_t)n_terms * 4);
+  const size_t o_out = st.out(out, (size_t)n_terms * 32);
+  const sc_scan_ws w = sc_scan_plan(n_terms, st.carved());
+  rc = st.begin(w.total);
   if (rc) return rc;
-  char* base = static_cast<char*>(c->ws);
-  HIP_TRY(hipMemcpyAsync(base + o_off, off, (size_t)(n_seg + 1) * 4, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(base + o_a, a, (size_t)n_a * 32, hipMemcpyHostToDevice, c->stream));
-  if (aidx) HIP_TRY(hipMemcpyAsync(base + o_ai, aidx, (size_t)n_terms * 4, hipMemcpyHostToDevice, c->stream));
-  prof_begin(c);
-  rc = launch_sc_scan(c, op, mode, n_seg, reinterpret_cast<uint32_t*>(base + o_off), reinterpret_cast<uint8_t*>(base + o_a), n_a,
-                      aidx ? reinterpret_cast<uint32_t*>(base + o_ai) : nullptr, w, reinterpret_cast<uint8_t*>(base + o_out));
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)n_terms * 32, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return ZKP_OK;
+  return st.end(launch_sc_scan(c, op, mode, n_seg, st.at<uint32_t>(o_off), st.at<uint8_t>(o_a), n_a, st.at<uint32_t>(o_ai), w, st.at<uint8_t>(o_out)));
 }
 
 int zkp_scan_points_dev(zkp_ctx* c, int mode, uint32_t n_seg, const uint32_t* d_off, const uint32_t* d_pidx, const uint8_t* d_neg, const uint8_t* d_points,
@@ -4389,39 +4312,25 @@ int zkp_scan_points(zkp_ctx* c, int mode, uint32_t n_seg, const uint32_t* off, c
   if (n_seg == 0) return scan_points_check(c, mode, &n_seg, points, 0, &n_seg, 0, out, status);
   if (!c) return fail(ZKP_ERR_ARG, "ctx is NULL");
   if (!off) return fail(ZKP_ERR_ARG, "NULL pointer");
-  if (off[0] != 0) return fail(ZKP_ERR_ARG, "off[0] must be 0");
-  for (uint32_t i = 0; i < n_seg; ++i)
-    if (off[i + 1] < off[i]) return fail(ZKP_ERR_ARG, "off must be non-decreasing");
-  const uint32_t n_terms = off[n_seg];
-  int rc = scan_points_check(c, mode, off, points, n_points, pidx, n_terms, out, status);
+  uint32_t n_terms;
+  int rc = csr_check(off, n_seg, &n_terms);
+  if (rc) return rc;
+  rc = scan_points_check(c, mode, off, points, n_points, pidx, n_terms, out, status);
   if (rc || n_terms == 0) return rc;
-  for (uint32_t t = 0; pidx && t < n_terms; ++t)
-    if (pidx[t] >= n_points) return fail(ZKP_ERR_ARG, "pidx out of range");
+  if (!idx_in_range(pidx, n_terms, n_points)) return fail(ZKP_ERR_ARG, "pidx out of range");
   HIP_TRY(hipSetDevice(c->device));
-  carve cv;
-  const size_t o_off = cv.take((size_t)(n_seg + 1) * 4);
-  const size_t o_pidx = cv.take(pidx ? (size_t)n_terms * 4 : 0);
-  const size_t o_neg = cv.take(neg ? (size_t)n_terms : 0);
-  const size_t o_pts = cv.take((size_t)n_points * 32);
-  const size_t o_out = cv.take((size_t)n_terms * 32);
-  const size_t o_st = cv.take((size_t)n_terms);
-  const pt_scan_ws w = pt_scan_plan(n_points, n_terms, cv.off);
-  rc = ensure_ws(c, w.total);
+  staging st(c);
+  const size_t o_off = st.in(off, (size_t)(n_seg + 1) * 4);
+  const size_t o_pidx = st.in_opt(pidx, (size_t)n_terms * 4);
+  const size_t o_neg = st.in_opt(neg, (size_t)n_terms);
+  const size_t o_pts = st.in(points, (size_t)n_points * 32);
+  const size_t o_out = st.out(out, (size_t)n_terms * 32);
+  const size_t o_st = st.out(status, (size_t)n_terms);
+  const pt_scan_ws w = pt_scan_plan(n_points, n_terms, st.carved());
+  rc = st.begin(w.total);
   if (rc) return rc;
-  char* base = static_cast<char*>(c->ws);
-  HIP_TRY(hipMemcpyAsync(base + o_off, off, (size_t)(n_seg + 1) * 4, hipMemcpyHostToDevice, c->stream));
-  if (pidx) HIP_TRY(hipMemcpyAsync(base + o_pidx, pidx, (size_t)n_terms * 4, hipMemcpyHostToDevice, c->stream));
-  if (neg) HIP_TRY(hipMemcpyAsync(base + o_neg, neg, (size_t)n_terms, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(base + o_pts, points, (size_t)n_points * 32, hipMemcpyHostToDevice, c->stream));
-  prof_begin(c);
-  rc = launch_scan_points(c, mode, n_seg, reinterpret_cast<uint32_t*>(base + o_off), pidx ? reinterpret_cast<uint32_t*>(base + o_pidx) : nullptr,
-                          neg ? reinterpret_cast<uint8_t*>(base + o_neg) : nullptr, reinterpret_cast<uint8_t*>(base + o_pts), n_points, w,
-                          reinterpret_cast<uint8_t*>(base + o_out), reinterpret_cast<uint8_t*>(base + o_st));
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)n_terms * 32, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(status, base + o_st, (size_t)n_terms, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return ZKP_OK;
+  return st.end(launch_scan_points(c, mode, n_seg, st.at<uint32_t>(o_off), st.at<uint32_t>(o_pidx), st.at<uint8_t>(o_neg), st.at<uint8_t>(o_pts), n_points, w,
+                                   st.at<uint8_t>(o_out), st.at<uint8_t>(o_st)));
 }
 
 // ---- (10) bounded discrete logarithms to the basepoint ------------------------------------------------------------------------------------
@@ -4438,16 +4347,23 @@ int zkp_ctx_prepare_dlog(zkp_ctx* c, uint32_t baby_bits) {
   return ensure_dlog_table(c, baby_bits);
 }
 
+// the basepoint's table for a search of n points over `bits` bits: the default one unless the caller prepared another, and within the launch limit
+static int dlog_base_table(zkp_ctx* c, uint64_t n, uint32_t bits) {
+  if (!c->dlog.baby_bits) {
+    const int rc = ensure_dlog_table(c, DLOG_BABY_DEFAULT);
+    if (rc) return rc;
+  }
+  if (dlog_launches(c->dlog, n, bits) > DLOG_MAX_LAUNCHES) return fail(ZKP_ERR_ARG, "the search would take more than 65,536 launches: prepare a larger table or split the call");
+  return ZKP_OK;
+}
+
 int zkp_dlog_base_dev(zkp_ctx* c, uint64_t n, const uint8_t* d_points, uint32_t bits, uint64_t* d_out, uint8_t* d_status) {
   int rc = dlog_check(c, n, bits, !d_points || !d_out || !d_status);
   if (rc || n == 0) return rc;
   if (!aligned16(d_points) || (reinterpret_cast<uintptr_t>(d_out) & 7)) return fail(ZKP_ERR_ARG, "d_points must be 16-byte, d_out 8-byte aligned");
   HIP_TRY(hipSetDevice(c->device));
-  if (!c->dlog.baby_bits) {
-    rc = ensure_dlog_table(c, DLOG_BABY_DEFAULT);
-    if (rc) return rc;
-  }
-  if (dlog_launches(c->dlog, n, bits) > DLOG_MAX_LAUNCHES) return fail(ZKP_ERR_ARG, "the search would take more than 65,536 launches: prepare a larger table or split the call");
+  rc = dlog_base_table(c, n, bits);
+  if (rc) return rc;
   const dlog_ws w = dlog_base_ws(n);
   rc = ensure_ws(c, w.total);
   if (rc) return rc;
@@ -4458,27 +4374,16 @@ int zkp_dlog_base(zkp_ctx* c, uint64_t n, const uint8_t* points, uint32_t bits, 
   int rc = dlog_check(c, n, bits, !points || !out || !status);
   if (rc || n == 0) return rc;
   HIP_TRY(hipSetDevice(c->device));
-  if (!c->dlog.baby_bits) {
-    rc = ensure_dlog_table(c, DLOG_BABY_DEFAULT);
-    if (rc) return rc;
-  }
-  if (dlog_launches(c->dlog, n, bits) > DLOG_MAX_LAUNCHES) return fail(ZKP_ERR_ARG, "the search would take more than 65,536 launches: prepare a larger table or split the call");
-  carve cv;
-  const size_t o_pts = cv.take((size_t)n * 32);
-  const size_t o_out = cv.take((size_t)n * 8);
-  const size_t o_st = cv.take((size_t)n);
-  const dlog_ws w = dlog_base_ws(n, cv.off);
-  rc = ensure_ws(c, w.total);
+  rc = dlog_base_table(c, n, bits);
   if (rc) return rc;
-  char* base = static_cast<char*>(c->ws);
-  HIP_TRY(hipMemcpyAsync(base + o_pts, points, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
-  prof_begin(c);
-  rc = launch_dlog(c, c->dlog, n, reinterpret_cast<const uint8_t*>(base + o_pts), bits, false, base, w, reinterpret_cast<uint64_t*>(base + o_out), reinterpret_cast<uint8_t*>(base + o_st));
+  staging st(c);
+  const size_t o_pts = st.in(points, (size_t)n * 32);
+  const size_t o_out = st.out(out, (size_t)n * 8);
+  const size_t o_st = st.out(status, (size_t)n);
+  const dlog_ws w = dlog_base_ws(n, st.carved());
+  rc = st.begin(w.total);
   if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(status, base + o_st, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return ZKP_OK;
+  return st.end(launch_dlog(c, c->dlog, n, st.at<const uint8_t>(o_pts), bits, false, st.at<char>(0), w, st.at<uint64_t>(o_out), st.at<uint8_t>(o_st)));
 }
 
 // ---- (10) ... to a base of the caller's: the slots, and the search over one of them ----------------------------------------------------------
@@ -4572,24 +4477,18 @@ int zkp_dlog_point(zkp_ctx* c, uint32_t slot, uint64_t n, const uint8_t* points,
   int rc = dlog_point_check(c, slot, n, bits, flags, !points || !out || !status, &t);
   if (rc || n == 0) return rc;
   HIP_TRY(hipSetDevice(c->device));
-  carve cv;
-  const size_t o_pts = cv.take((size_t)n * 32);
-  const size_t o_out = cv.take((size_t)n * 8);
-  const size_t o_st = cv.take((size_t)n);
-  const dlog_ws w = dlog_base_ws(n, cv.off);
-  rc = ensure_ws(c, w.total);
+  staging st(c);
+  const size_t o_pts = st.in(points, (size_t)n * 32);
+  const size_t o_out = st.out(out, (size_t)n * 8);
+  const size_t o_st = st.out(status, (size_t)n);
+  const dlog_ws w = dlog_base_ws(n, st.carved());
+  rc = st.reserve(w.total);
   if (rc) return rc;
   t->used = ++c->dlog_tick;
-  char* base = static_cast<char*>(c->ws);
-  HIP_TRY(hipMemcpyAsync(base + o_pts, points, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
-  prof_begin(c);
-  rc = launch_dlog(c, *t, n, reinterpret_cast<const uint8_t*>(base + o_pts), bits, (flags & ZKP_DLOG_SIGNED) != 0, base, w, reinterpret_cast<uint64_t*>(base + o_out),
-                   reinterpret_cast<uint8_t*>(base + o_st));
+  rc = st.begin();
   if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(status, base + o_st, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return ZKP_OK;
+  return st.end(launch_dlog(c, *t, n, st.at<const uint8_t>(o_pts), bits, (flags & ZKP_DLOG_SIGNED) != 0, st.at<char>(0), w, st.at<uint64_t>(o_out),
+                            st.at<uint8_t>(o_st)));
 }
 
 // ---- (7) batched Merlin operations on transcripts at any mix of positions ------------------------------------------------------------
@@ -4621,33 +4520,21 @@ int zkp_transcripts_append_message(zkp_ctx* c, uint32_t N, int shared_initial, u
   int rc = strobe_call_check(c, N, label, lab, &done);
   if (rc || done) return rc;
   if (!ts || !offsets || (offsets[N] > offsets[0] && !msgs)) return fail(ZKP_ERR_ARG, "NULL pointer");
-  for (uint32_t j = 0; j < N; ++j) {
-    if (offsets[j + 1] < offsets[j]) return fail(ZKP_ERR_ARG, "offsets must be non-decreasing");
+  for (uint32_t j = 0; j < N && offsets[j + 1] >= offsets[j]; ++j)      // (up to the first decreasing pair, which msg_slice::check reports)
     if (offsets[j + 1] - offsets[j] > 0xffffffffull) return fail(ZKP_ERR_ARG, "a message is longer than 2^32 - 1 bytes");
-  }
+  msg_slice m;
+  rc = m.check(offsets, N);
+  if (rc) return rc;
   if (!strobe_positions_ok(ts, shared_initial ? 1 : N)) return fail(ZKP_ERR_ARG, "a transcript's position byte is 166 or more");
-  const uint64_t base_off = offsets[0], total = offsets[N] - offsets[0];
-  std::vector<uint64_t> rebased((size_t)N + 1);
-  for (uint32_t j = 0; j <= N; ++j) rebased[j] = offsets[j] - base_off;
   HIP_TRY(hipSetDevice(c->device));
-  carve cv;
-  const size_t o_init = cv.take(shared_initial ? 208 : 0);
-  const size_t o_ts = cv.take(208 * (size_t)N);
-  const size_t o_msgs = cv.take((size_t)total);
-  const size_t o_off = cv.take(((size_t)N + 1) * 8);
-  rc = ensure_ws(c, cv.off);
+  staging st(c);
+  const size_t o_init = st.in_opt(shared_initial ? ts : nullptr, 208);               // ts is the one shared initial transcript, or all N
+  const size_t o_ts = st.inout(shared_initial ? nullptr : ts, ts, 208 * (size_t)N);
+  m.stage(st, msgs, offsets);
+  rc = st.begin();
   if (rc) return rc;
-  uint8_t* base = static_cast<uint8_t*>(c->ws);
-  HIP_TRY(hipMemcpyAsync(base + (shared_initial ? o_init : o_ts), ts, shared_initial ? 208 : 208 * (size_t)N, hipMemcpyHostToDevice, c->stream));
-  if (total) HIP_TRY(hipMemcpyAsync(base + o_msgs, msgs + base_off, (size_t)total, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(base + o_off, rebased.data(), ((size_t)N + 1) * 8, hipMemcpyHostToDevice, c->stream));
-  prof_begin(c);
-  rc = launch_strobe_append(c, N, shared_initial, base + (shared_initial ? o_init : o_ts), base + o_ts, lab, base + o_msgs, total,
-                            reinterpret_cast<const uint64_t*>(base + o_off));
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(ts, base + o_ts, 208 * (size_t)N, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return ZKP_OK;
+  return st.end(launch_strobe_append(c, N, shared_initial, st.at<uint8_t>(shared_initial ? o_init : o_ts), st.at<uint8_t>(o_ts), lab, st.at<uint8_t>(m.o_msgs), m.total,
+                                     st.at<const uint64_t>(m.o_off)));
 }
 
 int zkp_transcripts_challenge_bytes_dev(zkp_ctx* c, uint32_t N, uint8_t* d_ts, const char* label, uint32_t len, uint8_t* d_out) {
@@ -4670,20 +4557,12 @@ int zkp_transcripts_challenge_bytes(zkp_ctx* c, uint32_t N, uint8_t* ts, const c
   if (!ts || (len && !out)) return fail(ZKP_ERR_ARG, "NULL pointer");
   if (!strobe_positions_ok(ts, N)) return fail(ZKP_ERR_ARG, "a transcript's position byte is 166 or more");
   HIP_TRY(hipSetDevice(c->device));
-  carve cv;
-  const size_t o_ts = cv.take(208 * (size_t)N);
-  const size_t o_out = cv.take((size_t)N * len);
-  rc = ensure_ws(c, cv.off);
+  staging st(c);
+  const size_t o_ts = st.inout(ts, ts, 208 * (size_t)N);
+  const size_t o_out = st.out(out, (size_t)N * len);
+  rc = st.begin();
   if (rc) return rc;
-  uint8_t* base = static_cast<uint8_t*>(c->ws);
-  HIP_TRY(hipMemcpyAsync(base + o_ts, ts, 208 * (size_t)N, hipMemcpyHostToDevice, c->stream));
-  prof_begin(c);
-  rc = launch_strobe_challenge(c, N, base + o_ts, lab, len, base + o_out);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(ts, base + o_ts, 208 * (size_t)N, hipMemcpyDeviceToHost, c->stream));
-  if (len) HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)N * len, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return ZKP_OK;
+  return st.end(launch_strobe_challenge(c, N, st.at<uint8_t>(o_ts), lab, len, st.at<uint8_t>(o_out)));
 }
 
 // the witness RNG's arguments beyond strobe_call_check's; out_bytes = the size of the whole output
@@ -4723,6 +4602,7 @@ int zkp_transcripts_witness_rng(zkp_ctx* c, uint32_t N, const uint8_t* ts, const
   if (!strobe_positions_ok(ts, N)) return fail(ZKP_ERR_ARG, "a transcript's position byte is 166 or more");
   HIP_TRY(hipSetDevice(c->device));
   const size_t wit_bytes = (size_t)N * m * wlen;
+  // (Staged by hand, the one host-pointer call that is: `staging` returns at the first error, and here no way out may skip the wipe.)
   carve cv;
   const size_t o_ts = cv.take(208 * (size_t)N);
   const size_t o_secret = cv.take(32 * (size_t)N + wit_bytes);       // entropy, then the witnesses: one region, wiped below
@@ -4770,20 +4650,12 @@ int zkp_transcripts_challenge_scalars(zkp_ctx* c, uint32_t N, uint8_t* ts, const
   if (!ts || !out) return fail(ZKP_ERR_ARG, "NULL pointer");
   if (!strobe_positions_ok(ts, N)) return fail(ZKP_ERR_ARG, "a transcript's position byte is 166 or more");
   HIP_TRY(hipSetDevice(c->device));
-  carve cv;
-  const size_t o_ts = cv.take(208 * (size_t)N);
-  const size_t o_out = cv.take(32 * (size_t)N);
-  rc = ensure_ws(c, cv.off);
+  staging st(c);
+  const size_t o_ts = st.inout(ts, ts, 208 * (size_t)N);
+  const size_t o_out = st.out(out, 32 * (size_t)N);
+  rc = st.begin();
   if (rc) return rc;
-  uint8_t* base = static_cast<uint8_t*>(c->ws);
-  HIP_TRY(hipMemcpyAsync(base + o_ts, ts, 208 * (size_t)N, hipMemcpyHostToDevice, c->stream));
-  prof_begin(c);
-  rc = launch_strobe_challenge_scalars(c, N, base + o_ts, lab, base + o_out);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(ts, base + o_ts, 208 * (size_t)N, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(out, base + o_out, 32 * (size_t)N, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return ZKP_OK;
+  return st.end(launch_strobe_challenge_scalars(c, N, st.at<uint8_t>(o_ts), lab, st.at<uint8_t>(o_out)));
 }
 
 // the two labels of the point appends, checked as strobe_call_check checks its one
@@ -4817,22 +4689,13 @@ int zkp_transcripts_append_points(zkp_ctx* c, uint32_t N, uint8_t* ts, const cha
   if (!ts || !points || (validate && !status)) return fail(ZKP_ERR_ARG, "NULL pointer");
   if (!strobe_positions_ok(ts, N)) return fail(ZKP_ERR_ARG, "a transcript's position byte is 166 or more");
   HIP_TRY(hipSetDevice(c->device));
-  carve cv;
-  const size_t o_ts = cv.take(208 * (size_t)N);
-  const size_t o_pts = cv.take(32 * (size_t)N);
-  const size_t o_st = cv.take(status ? (size_t)N : 0);
-  rc = ensure_ws(c, cv.off);
+  staging st(c);
+  const size_t o_ts = st.inout(ts, ts, 208 * (size_t)N);
+  const size_t o_pts = st.in(points, 32 * (size_t)N);
+  const size_t o_st = st.out_opt(status, (size_t)N);
+  rc = st.begin();
   if (rc) return rc;
-  uint8_t* base = static_cast<uint8_t*>(c->ws);
-  HIP_TRY(hipMemcpyAsync(base + o_ts, ts, 208 * (size_t)N, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(base + o_pts, points, 32 * (size_t)N, hipMemcpyHostToDevice, c->stream));
-  prof_begin(c);
-  rc = launch_strobe_append_points(c, N, base + o_ts, k, v, base + o_pts, validate ? 1u : 0u, status ? base + o_st : nullptr);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(ts, base + o_ts, 208 * (size_t)N, hipMemcpyDeviceToHost, c->stream));
-  if (status) HIP_TRY(hipMemcpyAsync(status, base + o_st, (size_t)N, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return ZKP_OK;
+  return st.end(launch_strobe_append_points(c, N, st.at<uint8_t>(o_ts), k, v, st.at<uint8_t>(o_pts), validate ? 1u : 0u, st.at<uint8_t>(o_st)));
 }
 
 #ifdef ZKP_BUILD_TEST_HOOKS
@@ -4860,18 +4723,14 @@ int zkp_debug_quad_selftest(zkp_ctx* c, uint32_t n, const uint8_t* pairs, uint8_
   if (!c || !pairs || !out) return fail(ZKP_ERR_ARG, "NULL pointer");
   if (n == 0) return ZKP_OK;
   HIP_TRY(hipSetDevice(c->device));
-  carve cv;
-  const size_t o_in = cv.take((size_t)n * 64);
-  const size_t o_out = cv.take((size_t)n * 128);
-  const int rc = ensure_ws(c, cv.off);
+  staging st(c);
+  const size_t o_in = st.in(pairs, (size_t)n * 64);
+  const size_t o_out = st.out(out, (size_t)n * 128);
+  const int rc = st.upload();                 // (a probe, not a timed call: no prof_begin)
   if (rc) return rc;
-  char* base = static_cast<char*>(c->ws);
-  HIP_TRY(hipMemcpyAsync(base + o_in, pairs, (size_t)n * 64, hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(k_debug_quad, grid1((size_t)n * 4, 256), dim3(256), 0, c->stream, n, reinterpret_cast<uint8_t*>(base + o_in), reinterpret_cast<uint8_t*>(base + o_out));
+  hipLaunchKernelGGL(k_debug_quad, grid1((size_t)n * 4, 256), dim3(256), 0, c->stream, n, st.at<uint8_t>(o_in), st.at<uint8_t>(o_out));
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)n * 128, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return ZKP_OK;
+  return st.end(ZKP_OK);
 }
 #endif  // ZKP_BUILD_TEST_HOOKS
 
@@ -4880,18 +4739,14 @@ int zkp_debug_row_selftest(zkp_ctx* c, uint32_t n, const uint8_t* pairs, uint8_t
   if (!c || !pairs || !out) return fail(ZKP_ERR_ARG, "NULL pointer");
   if (n == 0) return ZKP_OK;
   HIP_TRY(hipSetDevice(c->device));
-  carve cv;
-  const size_t o_in = cv.take((size_t)n * 64);
-  const size_t o_out = cv.take((size_t)n * 96);
-  const int rc = ensure_ws(c, cv.off);
+  staging st(c);
+  const size_t o_in = st.in(pairs, (size_t)n * 64);
+  const size_t o_out = st.out(out, (size_t)n * 96);
+  const int rc = st.upload();                 // (as in zkp_debug_quad_selftest)
   if (rc) return rc;
-  char* base = static_cast<char*>(c->ws);
-  HIP_TRY(hipMemcpyAsync(base + o_in, pairs, (size_t)n * 64, hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(k_debug_row, dim3(n), dim3(64), 0, c->stream, n, reinterpret_cast<uint8_t*>(base + o_in), reinterpret_cast<uint8_t*>(base + o_out));
+  hipLaunchKernelGGL(k_debug_row, dim3(n), dim3(64), 0, c->stream, n, st.at<uint8_t>(o_in), st.at<uint8_t>(o_out));
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)n * 96, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return ZKP_OK;
+  return st.end(ZKP_OK);
 }
 #endif  // ZKP_BUILD_TEST_HOOKS
 
@@ -4955,20 +4810,15 @@ int zkp_encode_many(zkp_ctx* c, uint64_t n, const uint8_t* xyzt, uint8_t* out) {
   if (!xyzt || !out) return fail(ZKP_ERR_ARG, "NULL pointer");
   if (n > 0x7fffffffull) return fail(ZKP_ERR_ARG, "n too large");
   HIP_TRY(hipSetDevice(c->device));
-  carve cv;
-  const size_t o_in = cv.take((size_t)n * 128);
-  const size_t o_out = cv.take((size_t)n * 32);
-  const int rc = ensure_ws(c, cv.off);
+  staging st(c);
+  const size_t o_in = st.in(xyzt, (size_t)n * 128);
+  const size_t o_out = st.out(out, (size_t)n * 32);
+  const int rc = st.begin();
   if (rc) return rc;
-  char* base = static_cast<char*>(c->ws);
-  HIP_TRY(hipMemcpyAsync(base + o_in, xyzt, (size_t)n * 128, hipMemcpyHostToDevice, c->stream));
-  prof_begin(c);
-  hipLaunchKernelGGL(k_encode_many, grid1(n, 256), dim3(256), 0, c->stream, (uint32_t)n, reinterpret_cast<uint8_t*>(base + o_in), reinterpret_cast<uint8_t*>(base + o_out));
+  hipLaunchKernelGGL(k_encode_many, grid1(n, 256), dim3(256), 0, c->stream, (uint32_t)n, st.at<uint8_t>(o_in), st.at<uint8_t>(o_out));
   prof_mark(c, ZKP_K_REDUCE);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return ZKP_OK;
+  return st.end(ZKP_OK);
 }
 
 }  // extern "C"
