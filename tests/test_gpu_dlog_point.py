@@ -360,7 +360,7 @@ def test_dev_form_on_a_side_stream_and_recorded_into_a_graph_in_signed_mode(plan
     e.prepare_dlog_point(0, PD.base("H"), bb)
     d_pts = torch.from_numpy(pts).to("cuda:0")
     d_out = torch.zeros(n, dtype=torch.int64, device="cuda:0")
-    d_st = torch.zeros(n, dtype=torch.uint8, device="cuda:0")
+    d_st = torch.full((n,), 0xAB, dtype=torch.uint8, device="cuda:0")
     torch.cuda.synchronize()
 
     def enqueue():

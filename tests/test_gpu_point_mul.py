@@ -288,7 +288,7 @@ def test_dev_forms_on_a_side_stream_and_recorded_into_a_graph():
     d_bs = torch.from_numpy(bs).to("cuda:0")
     d_out = torch.zeros((n, 32), dtype=torch.uint8, device="cuda:0")
     d_bout = torch.zeros((n, 32), dtype=torch.uint8, device="cuda:0")
-    d_st = torch.zeros(n, dtype=torch.uint8, device="cuda:0")
+    d_st = torch.full((n,), 0xAB, dtype=torch.uint8, device="cuda:0")
     torch.cuda.synchronize()
     e.mul_base_dev(n, d_bs.data_ptr(), d_bout.data_ptr())
     e.mul_points_dev(n, d_s.data_ptr(), 1, d_p.data_ptr(), 1, ZKP_CT, d_out.data_ptr(), d_st.data_ptr())

@@ -343,9 +343,9 @@ def test_dev_forms_on_a_side_stream_and_recorded_into_a_graph(group):
     d_a = torch.from_numpy(inputs[0][0]).to("cuda:0")
     d_b = torch.from_numpy(inputs[0][1]).to("cuda:0")
     d_off = torch.from_numpy(off.view(np.int32)).to("cuda:0")
-    d_pst = torch.zeros(n, dtype=torch.uint8, device="cuda:0")
+    d_pst = torch.full((n,), 0xAB, dtype=torch.uint8, device="cuda:0")
     d_out = torch.zeros((n_sums, 32), dtype=torch.uint8, device="cuda:0")
-    d_st = torch.zeros(n_sums, dtype=torch.uint8, device="cuda:0")
+    d_st = torch.full((n_sums,), 0xAB, dtype=torch.uint8, device="cuda:0")
     torch.cuda.synchronize()
 
     def enqueue():
