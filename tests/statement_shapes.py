@@ -332,3 +332,83 @@ def _check_flows_vs_oracle(eng, shape, n, secrets, inst, common, E, routes=(("ho
         for a, b in zip(out[first], out[route]):
             assert a.shape == b.shape and (a == b).all(), "%s and %s routes leave different bytes" % (first, route)
     return out[routes[-1][0]]
+
+
+# ---- the _dev entry points on device buffers (tests/test_gpu_degenerate.py: CMZ; tests/test_gpu_random_statements.py: any shape) ----------------
+def fused_statement_of(shape):
+    """the shape as zkp_amd.engine.FusedStatement: every secret allocated before the first point, the points in the shape's order"""
+    from zkp_amd import engine as EN
+    si = {s: i for i, s in enumerate(shape.secret_names)}
+    pi = {p: i for i, (p, _) in enumerate(shape.points)}
+    return EN.FusedStatement(shape.label, [s.encode() for s in shape.secret_names], [(p.encode(), c) for p, c in shape.points],
+                             [(pi[lhs], [(si[s], pi[p]) for s, p in lc]) for lhs, lc in shape.cons])
+
+
+def _torch():
+    import torch
+    assert torch.cuda.is_available(), "torch cannot see the GPU in this process (its HIP runtime must initialise before libzkp_mi355x.so: run with -m gpu)"
+    return torch
+
+
+def dev_flows(e, fst, b, E, names=None, register=True, prove=True, after=None):
+    """zkp_fused_prove_dev / _verify_compact_dev / _verify_batchable_dev / _batch_verify_dev on device buffers against E (oracle_expectation, with
+    E.sub = (k, inst, coms, resp, w) of the proofs the oracle accepts one by one and E.rc_sub = its verdict on that batch).
+    b: shape, n, secrets, inst, common.  fst = None: built from b.shape.  names: {index: text} for messages.  register = False: the common points
+    are not registered for fixed-base tables.  prove = False: the verifiers only (E holds proofs the prover would not emit).
+    after(call name): called when each entry point has finished, e.g. to read the engine's last_schedule()."""
+    torch = _torch()
+    fst = fst or fused_statement_of(b.shape)
+    names = names or {}
+    after = after or (lambda what: None)
+    n, m, nc = b.n, len(b.shape.secret_names), len(b.shape.cons)
+    ns, ni = len(b.common), len(b.inst)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
+    z = lambda *s: torch.zeros(s, dtype=torch.uint8, device="cuda:0")
+    t0 = T.Transcript(E.tl).state
+    pos = int(t0[200]) | int(t0[201]) << 8 | int(t0[202]) << 16
+    ts0 = np.stack([t0] * n)
+    if register and len(b.common):
+        e.prepare_fixed_points(b.common)
+    table = np.concatenate([b.common, b.inst.reshape(-1, 32)])
+    d_tbl = dev(table)
+    if prove:
+        d_ts, d_sec, d_ent = dev(ts0), dev(b.secrets), dev(E.entropy)
+        d_chal, d_resp, d_coms, d_st = z(n, 32), z(n, m, 32), z(n, nc, 32), z(nc * n)
+        torch.cuda.synchronize()
+        e.fused_prove_dev(fst, n, pos, d_ts.data_ptr(), d_sec.data_ptr(), d_tbl.data_ptr(), d_ent.data_ptr(), d_chal.data_ptr(), d_resp.data_ptr(),
+                          d_coms.data_ptr(), d_st.data_ptr())
+        e.synchronize()
+        after("prove")
+        assert not d_st.cpu().numpy().any()
+        for what, got, want in (("challenge", d_chal, E.chal), ("responses", d_resp, E.resp), ("commitments", d_coms, E.coms)):
+            j = _first_diff(got.cpu().numpy(), want)
+            assert j is None, "%s of proof %d (%s) differ from the oracle's prover" % (what, j, names.get(j, "ordinary"))
+    # the verifiers on the ORACLE's proofs (equal to the device's by the lines above)
+    d_chal, d_resp, d_coms = dev(E.chal), dev(E.resp), dev(E.coms)
+    d_ts2, d_res = dev(ts0), z(n) + 7
+    torch.cuda.synchronize()
+    e.fused_verify_compact_dev(fst, n, pos, d_ts2.data_ptr(), d_tbl.data_ptr(), d_chal.data_ptr(), d_resp.data_ptr(), d_res.data_ptr())
+    e.synchronize()
+    after("verify_compact")
+    j = _first_diff(d_res.cpu().numpy(), E.vc)
+    assert j is None, "verify_compact_dev says %d for proof %d (%s), the oracle %d" % (d_res.cpu().numpy()[j], j, names.get(j, "ordinary"), E.vc[j])
+    d_tbl_each = torch.cat([d_tbl, d_coms.reshape(-1, 32)])
+    d_ts4, d_we, d_res4 = dev(ts0), dev(E.w_each), z(n) + 7
+    torch.cuda.synchronize()
+    e.fused_verify_batchable_dev(fst, n, pos, d_ts4.data_ptr(), d_tbl_each.data_ptr(), d_resp.data_ptr(), d_we.data_ptr(), d_res4.data_ptr())
+    e.synchronize()
+    after("verify_batchable")
+    j = _first_diff(d_res4.cpu().numpy(), E.vb)
+    assert j is None, "verify_batchable_dev says %d for proof %d (%s), the oracle %d" % (d_res4.cpu().numpy()[j], j, names.get(j, "ordinary"), E.vb[j])
+    # one batch verification over all n, and one over the proofs the oracle accepts one by one
+    for k, inst, coms, resp, w, want in ((n, b.inst, E.coms, E.resp, E.w, E.rc_batch),) + ((E.sub + (E.rc_sub,),) if E.sub[0] != n else ()):
+        d_pts = z(ns + (ni + nc) * k, 32)
+        d_pts[: ns + ni * k] = dev(np.concatenate([b.common, inst.reshape(-1, 32)]))
+        d_ts3, d_c, d_r, d_w, d_out = dev(ts0[:k]), dev(coms), dev(resp), dev(w), z(32) + 1
+        d_bst = torch.ones(2, dtype=torch.int32, device="cuda:0")
+        torch.cuda.synchronize()
+        e.fused_batch_verify_dev(fst, k, pos, d_ts3.data_ptr(), d_pts.data_ptr(), d_c.data_ptr(), d_r.data_ptr(), d_w.data_ptr(), d_out.data_ptr(), d_bst.data_ptr())
+        e.synchronize()
+        after("batch_verify")
+        got = int(d_out.cpu().numpy().any() or d_bst.cpu().numpy().any())
+        assert got == want, "batch_verify_dev over %d proofs: %d, the oracle %d" % (k, got, want)

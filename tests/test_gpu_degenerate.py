@@ -37,10 +37,7 @@ def eng():
     T.set_fused_min_batch(32)
 
 
-def _torch():
-    import torch
-    assert torch.cuda.is_available(), "torch cannot see the GPU in this process (its HIP runtime must initialise before libzkp_mi355x.so: run with -m gpu)"
-    return torch
+_torch = SH._torch
 
 
 def _expect(b, seed, **kw):
@@ -194,54 +191,9 @@ def _dev_case(batch_family):
 
 
 def _dev_flows(e, fst, b, E):
-    """zkp_fused_prove_dev / _verify_compact_dev / _verify_batchable_dev / _batch_verify_dev on device buffers against E"""
-    torch = _torch()
-    n, m, nc = b.n, len(b.shape.secret_names), len(b.shape.cons)
-    ns, ni = len(b.common), len(b.inst)
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
-    z = lambda *s: torch.zeros(s, dtype=torch.uint8, device="cuda:0")
-    t0 = T.Transcript(E.tl).state
-    pos = int(t0[200]) | int(t0[201]) << 8 | int(t0[202]) << 16
-    ts0 = np.stack([t0] * n)
-    e.prepare_fixed_points(b.common)
-    table = np.concatenate([b.common, b.inst.reshape(-1, 32)])
-    d_ts, d_sec, d_tbl, d_ent = dev(ts0), dev(b.secrets), dev(table), dev(E.entropy)
-    d_chal, d_resp, d_coms, d_st = z(n, 32), z(n, m, 32), z(n, nc, 32), z(nc * n)
-    torch.cuda.synchronize()
-    e.fused_prove_dev(fst, n, pos, d_ts.data_ptr(), d_sec.data_ptr(), d_tbl.data_ptr(), d_ent.data_ptr(), d_chal.data_ptr(), d_resp.data_ptr(),
-                      d_coms.data_ptr(), d_st.data_ptr())
-    e.synchronize()
-    assert not d_st.cpu().numpy().any()
-    names = _names(b)
-    for what, got, want in (("challenge", d_chal, E.chal), ("responses", d_resp, E.resp), ("commitments", d_coms, E.coms)):
-        j = SH._first_diff(got.cpu().numpy(), want)
-        assert j is None, "%s of proof %d (%s) differ from the oracle's prover" % (what, j, names.get(j, "ordinary"))
-    # the verifiers on the ORACLE's proofs (equal to the device's by the lines above)
-    d_chal, d_resp, d_coms = dev(E.chal), dev(E.resp), dev(E.coms)
-    d_ts2, d_res = dev(ts0), z(n) + 7
-    torch.cuda.synchronize()
-    e.fused_verify_compact_dev(fst, n, pos, d_ts2.data_ptr(), d_tbl.data_ptr(), d_chal.data_ptr(), d_resp.data_ptr(), d_res.data_ptr())
-    e.synchronize()
-    j = SH._first_diff(d_res.cpu().numpy(), E.vc)
-    assert j is None, "verify_compact_dev says %d for proof %d (%s), the oracle %d" % (d_res.cpu().numpy()[j], j, names.get(j, "ordinary"), E.vc[j])
-    d_tbl_each = torch.cat([d_tbl, d_coms.reshape(-1, 32)])
-    d_ts4, d_we, d_res4 = dev(ts0), dev(E.w_each), z(n) + 7
-    torch.cuda.synchronize()
-    e.fused_verify_batchable_dev(fst, n, pos, d_ts4.data_ptr(), d_tbl_each.data_ptr(), d_resp.data_ptr(), d_we.data_ptr(), d_res4.data_ptr())
-    e.synchronize()
-    j = SH._first_diff(d_res4.cpu().numpy(), E.vb)
-    assert j is None, "verify_batchable_dev says %d for proof %d (%s), the oracle %d" % (d_res4.cpu().numpy()[j], j, names.get(j, "ordinary"), E.vb[j])
-    # one batch verification over all n, and one over the proofs the oracle accepts one by one
-    for k, inst, coms, resp, w, want in ((n, b.inst, E.coms, E.resp, E.w, E.rc_batch),) + ((E.sub + (E.rc_sub,),) if E.sub[0] != n else ()):
-        d_pts = z(ns + (ni + nc) * k, 32)
-        d_pts[: ns + ni * k] = dev(np.concatenate([b.common, inst.reshape(-1, 32)]))
-        d_ts3, d_c, d_r, d_w, d_out = dev(ts0[:k]), dev(coms), dev(resp), dev(w), z(32) + 1
-        d_bst = torch.ones(2, dtype=torch.int32, device="cuda:0")
-        torch.cuda.synchronize()
-        e.fused_batch_verify_dev(fst, k, pos, d_ts3.data_ptr(), d_pts.data_ptr(), d_c.data_ptr(), d_r.data_ptr(), d_w.data_ptr(), d_out.data_ptr(), d_bst.data_ptr())
-        e.synchronize()
-        got = int(d_out.cpu().numpy().any() or d_bst.cpu().numpy().any())
-        assert got == want, "batch_verify_dev over %d proofs: %d, the oracle %d" % (k, got, want)
+    """zkp_fused_prove_dev / _verify_compact_dev / _verify_batchable_dev / _batch_verify_dev on device buffers against E (the helper is shared with
+    tests/test_gpu_random_statements.py, which runs it on other statements)"""
+    SH.dev_flows(e, fst, b, E, names=_names(b))
 
 
 @pytest.mark.parametrize("config", list(DEV_CONFIGS))
