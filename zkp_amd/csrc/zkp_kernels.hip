@@ -65,6 +65,7 @@ __device__ __forceinline__ uint32_t sel8(const uint32_t w[8], int j) {
 #include "point_scan.h"
 #include "dlog.h"
 #include "transcript_kernels.h"
+#include "or_lane.h"
 #include "sha512.h"
 
 // =============================================================================================
@@ -2038,6 +2039,7 @@ struct zkp_ctx {
   bool sync_throughput = false;        // ZKP_OPT_SYNC_SCHEDULE: the synchronous host-pointer entry points run the jobs' throughput schedule (callers with a thread per context)
   size_t ws_limit = 0;                 // ZKP_OPT_WS_LIMIT_BYTES: a call that would need a larger workspace fails with ZKP_ERR_OOM (0 = no cap)
   bool hot_registry_uploaded = false;  // the device copy of the fixed-base registry matches hot_key[]
+  std::vector<uint64_t> or_meta_keep;  // or_flows.h: the statement blob of the last OR-proof call, the source of its upload
 };
 void free_fused_plans(zkp_ctx* c);
 // frees rows, slots and walk points; the fixed-base table as well where the struct owns it (a slot), and forgets it either way
@@ -2121,7 +2123,7 @@ struct staging {
   struct copy { size_t off, bytes; const void* src; void* dst; };
   zkp_ctx* c;
   carve cv;
-  copy copies[8];                                               // (the most any call stages is six)
+  copy copies[12];                                              // (the most any call stages is nine: zkp_or_prove)
   int n_copies = 0;
   bool reserved = false;
   explicit staging(zkp_ctx* ctx) : c(ctx) {}
@@ -4827,3 +4829,4 @@ int zkp_encode_many(zkp_ctx* c, uint64_t n, const uint8_t* xyzt, uint8_t* out) {
 #include "ragged_transcripts.h"
 #include "host_jobs.h"
 #include "pip_segments.h"
+#include "or_flows.h"

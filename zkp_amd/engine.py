@@ -62,7 +62,7 @@ def load_library(test_hooks: bool = False) -> ctypes.CDLL:
     if not os.path.exists(path):
         raise ZkpError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                        "(hipcc --offload-arch=gfx950); there is no CPU fallback")
-    lib = cabi.bind(ctypes.CDLL(path), "zkp_mi355x.h", test_hooks)
+    lib = cabi.bind(cabi.bind(ctypes.CDLL(path), "zkp_mi355x.h", test_hooks), "zkp_or_mi355x.h")
     if test_hooks:
         _hooks_lib = lib
     else:
@@ -759,6 +759,46 @@ class Engine:
         _check(self._lib.zkp_transcripts_append_points_dev(self._h, n, d_ts, bytes(kind), bytes(var_label), d_points, int(bool(validate)), d_status),
                "zkp_transcripts_append_points_dev")
 
+    # ---- batched 1-of-k OR-proofs (include/zkp_or_mi355x.h) ----------------------------------------------
+    def or_prove(self, fst: "FusedStatement", transcripts, secrets, real, inst, common, entropy):
+        """N disjunctions of k instances of the statement, proved on the GPU: transcripts C-contiguous uint8 [N][208] (advanced in place),
+        secrets [N][m][32], real [N] (the branch each witness satisfies), inst [k][ni][N][32], common [ns][32], entropy [N][32]
+        -> (challenges [N][k][32], responses [N][k][m][32], status [N]: 1 = a point of that proof did not decode)"""
+        ts = _blobs(transcripts, len(transcripts))
+        n, m = len(ts), fst.c.shape.n_secrets
+        inst = np.ascontiguousarray(inst, np.uint8)
+        k = or_branches(fst, inst, n)
+        sec = np.ascontiguousarray(secrets, np.uint8).reshape(n, m, 32)
+        rl = np.ascontiguousarray(real, np.uint8).reshape(n)
+        com = np.ascontiguousarray(common, np.uint8).reshape(fst.n_static, 32)
+        ent = np.ascontiguousarray(entropy, np.uint8).reshape(n, 32)
+        chal, resp, status = np.zeros((n, k, 32), np.uint8), np.zeros((n, k, m, 32), np.uint8), np.zeros(n, np.uint8)
+        _check(self._lib.zkp_or_prove(self._h, ctypes.byref(fst.c), k, n, _ptr(ts), _ptr(sec), _ptr(rl), _ptr(inst), _ptr(com), _ptr(ent), _ptr(chal), _ptr(resp),
+                                      _ptr(status)), "zkp_or_prove")
+        return chal, resp, status
+
+    def or_verify(self, fst: "FusedStatement", transcripts, inst, common, challenges, responses) -> np.ndarray:
+        """The verifier of or_prove's proofs -> results uint8 [N]: 0 = accepted, 1 = rejected; transcripts advance in place"""
+        ts = _blobs(transcripts, len(transcripts))
+        n, m = len(ts), fst.c.shape.n_secrets
+        inst = np.ascontiguousarray(inst, np.uint8)
+        k = or_branches(fst, inst, n)
+        com = np.ascontiguousarray(common, np.uint8).reshape(fst.n_static, 32)
+        chal = np.ascontiguousarray(challenges, np.uint8).reshape(n, k, 32)
+        resp = np.ascontiguousarray(responses, np.uint8).reshape(n, k, m, 32)
+        res = np.ones(n, np.uint8)
+        _check(self._lib.zkp_or_verify(self._h, ctypes.byref(fst.c), k, n, _ptr(ts), _ptr(inst), _ptr(com), _ptr(chal), _ptr(resp), _ptr(res)), "zkp_or_verify")
+        return res
+
+    def or_prove_dev(self, fst: "FusedStatement", k, n, d_ts, d_secrets, d_real, d_inst, d_common, d_entropy, d_chal, d_resp, d_status) -> None:
+        """zkp_or_prove_dev: device pointers (16-byte aligned where they hold 32-byte rows or transcripts), queued on the context's stream"""
+        _check(self._lib.zkp_or_prove_dev(self._h, ctypes.byref(fst.c), k, n, d_ts, d_secrets, d_real, d_inst, d_common, d_entropy, d_chal, d_resp, d_status),
+               "zkp_or_prove_dev")
+
+    def or_verify_dev(self, fst: "FusedStatement", k, n, d_ts, d_inst, d_common, d_chal, d_resp, d_results) -> None:
+        """zkp_or_verify_dev: as or_prove_dev; d_results [n] bytes, 0 = accepted"""
+        _check(self._lib.zkp_or_verify_dev(self._h, ctypes.byref(fst.c), k, n, d_ts, d_inst, d_common, d_chal, d_resp, d_results), "zkp_or_verify_dev")
+
     # ---- fused statement flows on device-resident buffers (include/zkp_mi355x.h section 2c) -------------
     def fused_prove_dev(self, fst: "FusedStatement", n, strobe_pos, d_ts, d_secrets, d_table, d_entropy, d_chal, d_resp, d_coms, d_status) -> None:
         _check(self._lib.zkp_fused_prove_dev(self._h, ctypes.byref(fst.c), n, strobe_pos, d_ts, d_secrets, d_table, d_entropy, d_chal, d_resp, d_coms,
@@ -929,6 +969,13 @@ class Engine:
             if n > 0:
                 out[k] = buf.value.decode().split(";")
         return out
+
+
+def or_branches(fst: "FusedStatement", inst: np.ndarray, n: int) -> int:
+    """k of an OR-proof call, read off inst [k][ni][N][32]"""
+    if inst.ndim != 4 or inst.shape[1:] != (fst.n_instance, n, 32) or len(inst) == 0:
+        raise ValueError("inst must be uint8 [k][%d][%d][32] with k >= 1" % (fst.n_instance, n))
+    return len(inst)
 
 
 class _Capture:

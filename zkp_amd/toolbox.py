@@ -59,7 +59,7 @@ def lib() -> ctypes.CDLL:
         load_library()          # libzkp_mi355x.so must exist: no CPU fallback
         if not os.path.exists(LIB_PATH):
             raise RuntimeError(f"{LIB_PATH} is missing: run __graft_entry__.build()")
-        _lib = cabi.bind(ctypes.CDLL(LIB_PATH), "zkp_toolbox.h")
+        _lib = cabi.bind(cabi.bind(ctypes.CDLL(LIB_PATH), "zkp_toolbox.h"), "zkp_or_toolbox.h")
     return _lib
 
 
@@ -600,6 +600,65 @@ def set_append_points_min_batch(n: int) -> None:
 
 def get_append_points_min_batch() -> int:
     return int(lib().zkp_toolbox_get_append_points_min_batch())
+
+
+# ---- batched 1-of-k OR-proofs (include/zkp_or_toolbox.h) --------------------------------------------
+def _or_shapes(st, transcripts, inst, common, what: str):
+    ts = _blob_array(transcripts, what)
+    n = len(ts)
+    inst = np.ascontiguousarray(inst, np.uint8)
+    if inst.ndim != 4 or inst.shape[1:] != (st.ni, n, 32):
+        raise ValueError("%s: inst must be uint8 [k][%d][%d][32]" % (what, st.ni, n))
+    com = np.ascontiguousarray(common, np.uint8)
+    if com.size != 32 * st.ns:
+        raise ValueError("%s: common must be uint8 [%d][32]" % (what, st.ns))
+    return ts, n, len(inst), inst, com
+
+
+def or_prove(eng, st: Statement, transcripts, secrets, real, inst, common, entropy=None, threads: int = 0):
+    """N disjunctions "I know a witness of ONE of these k instances of st" (Cramer-Damgard-Schoenmakers over the reference's prover steps;
+    the protocol is stated in include/zkp_or_mi355x.h).  inst: uint8 [k][ni][N][32], branch b = st over inst[b] and the shared common points,
+    k is taken from it; secrets [N][m][32]; real [N] = the branch each witness satisfies; entropy [N][32] or None (drawn from the operating
+    system).  transcripts (C-contiguous uint8 [N][208], any mix of positions) advance in place.
+    -> (challenges [N][k][32], responses [N][k][m][32], status [N]: 1 = a point of that proof did not decode, its rows are zeros).
+    No branch, address or call sequence depends on real.  eng = None runs the host backend; with an Engine, batches of at least
+    get_or_min_batch() proofs run on the GPU.  Same bytes either way."""
+    ts, n, k, inst, com = _or_shapes(st, transcripts, inst, common, "or_prove")
+    sec = np.ascontiguousarray(secrets, np.uint8)
+    rl = np.ascontiguousarray(real, np.uint8)
+    if sec.size != 32 * n * st.m or rl.shape != (n,):
+        raise ValueError("or_prove: secrets must be uint8 [N][m][32] and real uint8 [N]")
+    ent = None if entropy is None else np.ascontiguousarray(entropy, np.uint8)
+    if ent is not None and ent.shape != (n, 32):
+        raise ValueError("or_prove: entropy must be uint8 [N][32] (or None)")
+    chal, resp, status = np.zeros((n, k, 32), np.uint8), np.zeros((n, k, st.m, 32), np.uint8), np.zeros(n, np.uint8)
+    rc = lib().zkp_or_prove_batch(None if eng is None else eng._h, st._h, k, n, _p(ts), _p(sec), _p(rl), _p(inst), _p(com), _p(ent), threads, _p(chal), _p(resp),
+                                  _p(status))
+    _raise(rc, "zkp_or_prove_batch")
+    return chal, resp, status
+
+
+def or_verify(eng, st: Statement, transcripts, inst, common, challenges, responses, threads: int = 0) -> np.ndarray:
+    """The verifier of or_prove's proofs -> results uint8 [N]: 0 = accepted, 1 = rejected.  transcripts advance in place (an accepted
+    proof's ends where the prover's ended)."""
+    ts, n, k, inst, com = _or_shapes(st, transcripts, inst, common, "or_verify")
+    chal = np.ascontiguousarray(challenges, np.uint8)
+    resp = np.ascontiguousarray(responses, np.uint8)
+    if chal.shape != (n, k, 32) or resp.size != 32 * n * k * st.m:
+        raise ValueError("or_verify: challenges must be uint8 [N][k][32] and responses uint8 [N][k][m][32]")
+    res = np.ones(n, np.uint8)
+    rc = lib().zkp_or_verify_batch(None if eng is None else eng._h, st._h, k, n, _p(ts), _p(inst), _p(com), _p(chal), _p(resp), threads, _p(res))
+    _raise(rc, "zkp_or_verify_batch")
+    return res
+
+
+def set_or_min_batch(n: int) -> None:
+    """or_prove / or_verify calls on an engine with at least n proofs run on the device (0: always; 2**32 - 1: never)"""
+    lib().zkp_toolbox_set_or_min_batch(n)
+
+
+def get_or_min_batch() -> int:
+    return int(lib().zkp_toolbox_get_or_min_batch())
 
 
 def hash_from_bytes_sha512(eng, messages, threads: int = 0) -> np.ndarray:
