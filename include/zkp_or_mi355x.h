@@ -61,7 +61,7 @@
  * all k - 1 / j mod k / random and witness all 0 / all l - 1 / random.
  * Where it does not win: the cost grows with k N (terms + constraints) multiplications of 253 bits -- every branch is a full constant-time
  * multiscalar multiplication, the real one included -- so k = 16 costs 2.5 x what k = 4 does; nothing below N = 4,096 was measured; and the
- * commitments are recomputed per proof: there is no batchable form whose verification is one random linear combination.
+ * commitments are recomputed per proof: zkp_or_batch_mi355x.h has the batchable form, whose batch verification is one multiscalar sum.
  */
 #ifndef ZKP_OR_MI355X_H
 #define ZKP_OR_MI355X_H

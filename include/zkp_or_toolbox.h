@@ -26,6 +26,7 @@
  * a position byte of 166 or more or a real[j] >= k, with nothing written; ZKP_TB_NO_ENTROPY; or the device library's negative code.
  * zkp_or_verify_batch returns ZKP_TB_OK whatever the verdicts are: results says which proofs are rejected.  N = 0 is a no-op.
  * The host backend zeroes its copies of the nonces, rows and keyed transcript states before it returns.
+ * zkp_or_batch_toolbox.h has the batchable form of these proofs, which a verifier checks as a batch with one multiscalar sum.
  */
 #ifndef ZKP_OR_TOOLBOX_H
 #define ZKP_OR_TOOLBOX_H

@@ -65,9 +65,11 @@ def build_host(force: bool = False, verbose: bool = False):
     if not srcs:
         return None
     # (host_backend.cpp compiles the kernels' point formulas, scalars, SHA-512 and the dlog plan for the host: ge25519.h and what it includes, sc25519.h, sha512.h, dlog.h;
-    # transcript_rng.cpp the one-lane STROBE: strobe_lane.h over merlin_prog.h; or_proof.cpp the OR-proof items: or_lane.h, or_meta.h)
+    # transcript_rng.cpp the one-lane STROBE: strobe_lane.h over merlin_prog.h; or_proof.cpp the OR-proof items: or_lane.h, or_meta.h;
+    # or_batch.cpp those of the batchable form: or_batch_lane.h)
     deps = _deps(host_dir, os.path.join(HERE, "..", "include"), exts=(".h", ".hpp", ".cpp", ".map")) + [os.path.join(CSRC, f) for f in (
-        "ge25519.h", "fe25519.h", "fe_constants.h", "sha512.h", "sc25519.h", "dlog.h", "strobe_lane.h", "merlin_prog.h", "or_lane.h", "or_meta.h")]
+        "ge25519.h", "fe25519.h", "fe_constants.h", "sha512.h", "sc25519.h", "dlog.h", "strobe_lane.h", "merlin_prog.h", "or_lane.h", "or_meta.h",
+        "or_batch_lane.h")]
     force = force or bool(os.environ.get("ZKP_FORCE_BUILD"))
     if force or _stale(HOST_LIB, deps):
         cmd = ["g++", "-O3", "-std=c++17", "-shared", "-fPIC", "-pthread", "-Wall", "-Wno-unknown-pragmas", "-I", os.path.join(HERE, "..", "include")] + srcs + [

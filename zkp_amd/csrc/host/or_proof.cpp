@@ -7,10 +7,8 @@
 #include <cstring>
 #include <vector>
 
-#include "../or_meta.h"
 #include "../../../include/zkp_or_toolbox.h"
-#include "host_backend.hpp"
-#include "toolbox_internal.hpp"
+#include "or_host.hpp"
 
 using namespace zkp::host;
 
@@ -26,91 +24,19 @@ inline bool on_device(const zkp_ctx* ctx, uint32_t N) {
   const uint32_t min_batch = g_or_min_batch.load();
   return ctx && min_batch != 0xffffffffu && N >= min_batch;
 }
-inline void lane_load(zkp::strobe_lane& L, const uint8_t* blob) {
-  alignas(8) uint64_t in[26];
-  std::memcpy(in, blob, TB);
-  zkp::strobe_load(L, in);
-}
-inline void lane_store(const zkp::strobe_lane& L, uint8_t* blob) {
-  alignas(8) uint64_t out[26];
-  zkp::strobe_store(L, out, zkp::strobe_tail(L));
-  std::memcpy(blob, out, TB);
-}
 inline void wipe(std::vector<uint8_t>& v) {
   if (!v.empty()) explicit_bzero(v.data(), v.size());
 }
 
-// what both calls share: the statement blob, the sizes, the table [common | inst] and the CSR arrays of the term path
-struct or_host_call {
-  zkp::or_meta M;
-  zkp::or_sizes z{};
-  zkp::or_stmt s{};
-  std::vector<uint8_t> table;
-  std::vector<uint32_t> off, pidx;
-  // ZKP_TB_OK, or ZKP_TB_BAD_STATEMENT before anything is written
-  int prepare(const zkp_statement* st, uint32_t k, uint32_t N, const uint8_t* ts, const uint8_t* inst, const uint8_t* common) {
-    if (!st) return ZKP_TB_BAD_STATEMENT;
-    FusedView fv(*st);
-    if (!zkp::or_meta_build(&fv.fs, M) || M.nc == 0 || !zkp::or_sizes_of(M, k, N, z)) return ZKP_TB_BAD_STATEMENT;
-    if (N == 0) return ZKP_TB_OK;
-    if (!ts || (M.ni && !inst) || (M.ns && !common)) return ZKP_TB_BAD_STATEMENT;
-    for (uint32_t j = 0; j < N; ++j)
-      if (ts[TB * (size_t)j + 200] >= zkp::STROBE_RATE) return ZKP_TB_BAD_STATEMENT;
-    s = M.view(M.blob.data(), k, N);
-    return ZKP_TB_OK;
-  }
-  void plan(const uint8_t* inst, const uint8_t* common, int n_threads) {
-    table.resize(32 * (size_t)z.n_points);
-    if (M.ns) std::memcpy(table.data(), common, 32 * (size_t)M.ns);
-    if (M.ni) std::memcpy(table.data() + 32 * (size_t)M.ns, inst, 32 * (size_t)z.n_blocks * M.ni);
-    off.resize((size_t)z.n_msm + 1);
-    pidx.resize(z.n_terms);
-    parallel_for(s.N, n_threads, [&](uint32_t lo, uint32_t hi) {
-      for (uint32_t j = lo; j < hi; ++j)
-        for (uint32_t b = 0; b < s.k; ++b) zkp::or_plan_item(s, j, b, off.data(), pidx.data());
-    });
-  }
-  // the MSMs of the proofs [lo, hi): rows = their [hi - lo][k][nterm][32] scalars -> coms [hi - lo][k][nc][32], status [hi - lo][k][nc]
-  int msm(uint32_t lo, uint32_t hi, const uint8_t* rows, int flags, uint8_t* coms, uint8_t* status) const {
-    const uint32_t m0 = lo * s.k * s.nc, n = (hi - lo) * s.k * s.nc;
-    std::vector<uint32_t> o(n + 1);
-    for (uint32_t i = 0; i <= n; ++i) o[i] = off[m0 + i] - off[m0];
-    return zkp::hostbk::msm_many(n, o.data(), rows, pidx.data() + off[m0], table.data(), z.n_points, flags, coms, status);
-  }
-};
-
 }  // namespace
 
-extern "C" {
-
-void zkp_toolbox_set_or_min_batch(uint32_t n) { g_or_min_batch = n; }
-uint32_t zkp_toolbox_get_or_min_batch(void) { return g_or_min_batch.load(); }
-
-int zkp_or_prove_batch(zkp_ctx* ctx, const zkp_statement* st, uint32_t k, uint32_t N, uint8_t* ts, const uint8_t* secrets, const uint8_t* real,
-                       const uint8_t* inst, const uint8_t* common, const uint8_t* entropy, int n_threads, uint8_t* challenges, uint8_t* responses,
-                       uint8_t* status) {
-  or_host_call h;
-  int rc = h.prepare(st, k, N, ts, inst, common);
-  if (rc || N == 0) return rc;
+// The prover on the host threads; commitments: NULL or [N][k][nc][32], what was appended (or_batch.cpp's batchable form)
+namespace zkp {
+namespace host {
+int or_prove_host(or_host_call& h, uint8_t* ts, const uint8_t* secrets, const uint8_t* real, const uint8_t* inst, const uint8_t* common, const uint8_t* entropy,
+                  int n_threads, uint8_t* commitments, uint8_t* challenges, uint8_t* responses, uint8_t* status) {
   const zkp::or_stmt& s = h.s;
-  if (!real || !challenges || !status || (s.m && (!secrets || !responses))) return ZKP_TB_BAD_STATEMENT;
-  for (uint32_t j = 0; j < N; ++j)
-    if (real[j] >= k) return ZKP_TB_BAD_STATEMENT;
-  std::vector<uint8_t> seed;                                           // prover.rs:82 `thread_rng()`, drawn as zkp_prove_batch draws it
-  if (!entropy) {
-    seed.resize(32 * (size_t)N);
-    if (!os_random(seed.data(), seed.size())) {
-      wipe(seed);
-      return ZKP_TB_NO_ENTROPY;
-    }
-    entropy = seed.data();
-  }
-  if (on_device(ctx, N)) {
-    FusedView fv(*st);
-    rc = zkp_or_prove(ctx, &fv.fs, k, N, ts, secrets, real, inst, common, entropy, challenges, responses, status);
-    wipe(seed);
-    return rc;
-  }
+  const uint32_t N = s.N;
   h.plan(inst, common, n_threads);
   const size_t drawn = h.z.drawn, blk_rows = (size_t)s.k * s.nterm, blk_coms = (size_t)s.k * s.nc;
   const zkp::strobe_label empty{};
@@ -146,13 +72,50 @@ int zkp_or_prove_batch(zkp_ctx* ctx, const zkp_statement* st, uint32_t k, uint32
                            responses + 32 * (size_t)s.k * s.m * j);
       status[j] = (uint8_t)bad;
     }
+    if (commitments) std::memcpy(commitments + 32 * blk_coms * lo, coms.data(), coms.size());
     explicit_bzero(col, sizeof(col));                                  // the keyed state
     wipe(nonces);
     wipe(rows);
     wipe(wit);
   });
-  wipe(seed);
   return failed.load() ? ZKP_TB_BAD_STATEMENT : ZKP_TB_OK;
+}
+}  // namespace host
+}  // namespace zkp
+
+extern "C" {
+
+void zkp_toolbox_set_or_min_batch(uint32_t n) { g_or_min_batch = n; }
+uint32_t zkp_toolbox_get_or_min_batch(void) { return g_or_min_batch.load(); }
+
+int zkp_or_prove_batch(zkp_ctx* ctx, const zkp_statement* st, uint32_t k, uint32_t N, uint8_t* ts, const uint8_t* secrets, const uint8_t* real,
+                       const uint8_t* inst, const uint8_t* common, const uint8_t* entropy, int n_threads, uint8_t* challenges, uint8_t* responses,
+                       uint8_t* status) {
+  or_host_call h;
+  int rc = h.prepare(st, k, N, ts, inst, common);
+  if (rc || N == 0) return rc;
+  const zkp::or_stmt& s = h.s;
+  if (!real || !challenges || !status || (s.m && (!secrets || !responses))) return ZKP_TB_BAD_STATEMENT;
+  for (uint32_t j = 0; j < N; ++j)
+    if (real[j] >= k) return ZKP_TB_BAD_STATEMENT;
+  std::vector<uint8_t> seed;                                           // prover.rs:82 `thread_rng()`, drawn as zkp_prove_batch draws it
+  if (!entropy) {
+    seed.resize(32 * (size_t)N);
+    if (!os_random(seed.data(), seed.size())) {
+      wipe(seed);
+      return ZKP_TB_NO_ENTROPY;
+    }
+    entropy = seed.data();
+  }
+  if (on_device(ctx, N)) {
+    FusedView fv(*st);
+    rc = zkp_or_prove(ctx, &fv.fs, k, N, ts, secrets, real, inst, common, entropy, challenges, responses, status);
+    wipe(seed);
+    return rc;
+  }
+  rc = or_prove_host(h, ts, secrets, real, inst, common, entropy, n_threads, nullptr, challenges, responses, status);
+  wipe(seed);
+  return rc;
 }
 
 int zkp_or_verify_batch(zkp_ctx* ctx, const zkp_statement* st, uint32_t k, uint32_t N, uint8_t* ts, const uint8_t* inst, const uint8_t* common,

@@ -4830,3 +4830,4 @@ int zkp_encode_many(zkp_ctx* c, uint64_t n, const uint8_t* xyzt, uint8_t* out) {
 #include "host_jobs.h"
 #include "pip_segments.h"
 #include "or_flows.h"
+#include "or_batch_flows.h"

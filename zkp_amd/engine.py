@@ -62,7 +62,7 @@ def load_library(test_hooks: bool = False) -> ctypes.CDLL:
     if not os.path.exists(path):
         raise ZkpError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                        "(hipcc --offload-arch=gfx950); there is no CPU fallback")
-    lib = cabi.bind(cabi.bind(ctypes.CDLL(path), "zkp_mi355x.h", test_hooks), "zkp_or_mi355x.h")
+    lib = cabi.bind(cabi.bind(cabi.bind(ctypes.CDLL(path), "zkp_mi355x.h", test_hooks), "zkp_or_mi355x.h"), "zkp_or_batch_mi355x.h")
     if test_hooks:
         _hooks_lib = lib
     else:
@@ -798,6 +798,69 @@ class Engine:
     def or_verify_dev(self, fst: "FusedStatement", k, n, d_ts, d_inst, d_common, d_chal, d_resp, d_results) -> None:
         """zkp_or_verify_dev: as or_prove_dev; d_results [n] bytes, 0 = accepted"""
         _check(self._lib.zkp_or_verify_dev(self._h, ctypes.byref(fst.c), k, n, d_ts, d_inst, d_common, d_chal, d_resp, d_results), "zkp_or_verify_dev")
+
+    # ---- batchable 1-of-k OR-proofs (include/zkp_or_batch_mi355x.h) --------------------------------------
+    def or_prove_batchable(self, fst: "FusedStatement", transcripts, secrets, real, inst, common, entropy):
+        """or_prove plus the commitments the prover hashed -> (commitments [N][k][nc][32], challenges, responses, status)"""
+        ts = _blobs(transcripts, len(transcripts))
+        n, m, nc = len(ts), fst.c.shape.n_secrets, fst.c.shape.n_constraints
+        inst = np.ascontiguousarray(inst, np.uint8)
+        k = or_branches(fst, inst, n)
+        sec = np.ascontiguousarray(secrets, np.uint8).reshape(n, m, 32)
+        rl = np.ascontiguousarray(real, np.uint8).reshape(n)
+        com = np.ascontiguousarray(common, np.uint8).reshape(fst.n_static, 32)
+        ent = np.ascontiguousarray(entropy, np.uint8).reshape(n, 32)
+        coms, chal = np.zeros((n, k, nc, 32), np.uint8), np.zeros((n, k, 32), np.uint8)
+        resp, status = np.zeros((n, k, m, 32), np.uint8), np.zeros(n, np.uint8)
+        _check(self._lib.zkp_or_prove_batchable(self._h, ctypes.byref(fst.c), k, n, _ptr(ts), _ptr(sec), _ptr(rl), _ptr(inst), _ptr(com), _ptr(ent), _ptr(coms),
+                                                _ptr(chal), _ptr(resp), _ptr(status)), "zkp_or_prove_batchable")
+        return coms, chal, resp, status
+
+    def _or_batchable_args(self, fst, transcripts, inst, common, commitments, challenges, responses):
+        ts = _blobs(transcripts, len(transcripts))
+        n, m, nc = len(ts), fst.c.shape.n_secrets, fst.c.shape.n_constraints
+        inst = np.ascontiguousarray(inst, np.uint8)
+        k = or_branches(fst, inst, n)
+        com = np.ascontiguousarray(common, np.uint8).reshape(fst.n_static, 32)
+        coms = np.ascontiguousarray(commitments, np.uint8).reshape(n, k, nc, 32)
+        chal = np.ascontiguousarray(challenges, np.uint8).reshape(n, k, 32)
+        resp = np.ascontiguousarray(responses, np.uint8).reshape(n, k, m, 32)
+        return ts, n, k, inst, com, coms, chal, resp
+
+    def or_verify_batchable(self, fst: "FusedStatement", transcripts, inst, common, commitments, challenges, responses) -> np.ndarray:
+        """The exact per-proof verifier of the batchable form -> results uint8 [N]: 0 = accepted; transcripts advance in place"""
+        ts, n, k, inst, com, coms, chal, resp = self._or_batchable_args(fst, transcripts, inst, common, commitments, challenges, responses)
+        res = np.ones(n, np.uint8)
+        _check(self._lib.zkp_or_verify_batchable(self._h, ctypes.byref(fst.c), k, n, _ptr(ts), _ptr(inst), _ptr(com), _ptr(coms), _ptr(chal), _ptr(resp), _ptr(res)),
+               "zkp_or_verify_batchable")
+        return res
+
+    def or_batch_verify(self, fst: "FusedStatement", transcripts, inst, common, commitments, challenges, responses, weights16, debug: bool = False):
+        """One verdict for N batchable proofs with one multiscalar sum of ns + N k (ni + nc) operands; weights16 uint8 [N][k][nc][16]
+        -> verdict (0 = every proof verifies), or (verdict, coefficient vector [ns + N k (ni + nc)][32]) with debug"""
+        ts, n, k, inst, com, coms, chal, resp = self._or_batchable_args(fst, transcripts, inst, common, commitments, challenges, responses)
+        nc = fst.c.shape.n_constraints
+        w = np.ascontiguousarray(weights16, np.uint8).reshape(n, k, nc, 16)
+        verdict = ctypes.c_int(1)
+        dbg = np.zeros((fst.n_static + n * k * (fst.c.shape.n_instance + nc), 32), np.uint8) if debug else None
+        _check(self._lib.zkp_or_batch_verify(self._h, ctypes.byref(fst.c), k, n, _ptr(ts), _ptr(inst), _ptr(com), _ptr(coms), _ptr(chal), _ptr(resp), _ptr(w),
+                                             ctypes.byref(verdict), None if dbg is None else _ptr(dbg)), "zkp_or_batch_verify")
+        return (verdict.value, dbg) if debug else verdict.value
+
+    def or_prove_batchable_dev(self, fst: "FusedStatement", k, n, d_ts, d_secrets, d_real, d_inst, d_common, d_entropy, d_coms, d_chal, d_resp, d_status) -> None:
+        """zkp_or_prove_batchable_dev: as or_prove_dev, plus d_coms [n][k][nc][32]"""
+        _check(self._lib.zkp_or_prove_batchable_dev(self._h, ctypes.byref(fst.c), k, n, d_ts, d_secrets, d_real, d_inst, d_common, d_entropy, d_coms, d_chal, d_resp,
+                                                    d_status), "zkp_or_prove_batchable_dev")
+
+    def or_verify_batchable_dev(self, fst: "FusedStatement", k, n, d_ts, d_inst, d_common, d_coms, d_chal, d_resp, d_results) -> None:
+        """zkp_or_verify_batchable_dev: d_results [n] bytes, 0 = accepted"""
+        _check(self._lib.zkp_or_verify_batchable_dev(self._h, ctypes.byref(fst.c), k, n, d_ts, d_inst, d_common, d_coms, d_chal, d_resp, d_results),
+               "zkp_or_verify_batchable_dev")
+
+    def or_batch_verify_dev(self, fst: "FusedStatement", k, n, d_ts, d_inst, d_common, d_coms, d_chal, d_resp, d_weights16, d_verdict) -> None:
+        """zkp_or_batch_verify_dev: d_weights16 [n][k][nc][16]; d_verdict one uint32 word written on the context's stream, 0 = every proof verifies"""
+        _check(self._lib.zkp_or_batch_verify_dev(self._h, ctypes.byref(fst.c), k, n, d_ts, d_inst, d_common, d_coms, d_chal, d_resp, d_weights16, d_verdict),
+               "zkp_or_batch_verify_dev")
 
     # ---- fused statement flows on device-resident buffers (include/zkp_mi355x.h section 2c) -------------
     def fused_prove_dev(self, fst: "FusedStatement", n, strobe_pos, d_ts, d_secrets, d_table, d_entropy, d_chal, d_resp, d_coms, d_status) -> None:

@@ -59,7 +59,7 @@ def lib() -> ctypes.CDLL:
         load_library()          # libzkp_mi355x.so must exist: no CPU fallback
         if not os.path.exists(LIB_PATH):
             raise RuntimeError(f"{LIB_PATH} is missing: run __graft_entry__.build()")
-        _lib = cabi.bind(cabi.bind(ctypes.CDLL(LIB_PATH), "zkp_toolbox.h"), "zkp_or_toolbox.h")
+        _lib = cabi.bind(cabi.bind(cabi.bind(ctypes.CDLL(LIB_PATH), "zkp_toolbox.h"), "zkp_or_toolbox.h"), "zkp_or_batch_toolbox.h")
     return _lib
 
 
@@ -659,6 +659,100 @@ def set_or_min_batch(n: int) -> None:
 
 def get_or_min_batch() -> int:
     return int(lib().zkp_toolbox_get_or_min_batch())
+
+
+# ---- batchable 1-of-k OR-proofs (include/zkp_or_batch_toolbox.h) -------------------------------------
+def or_prove_batchable(eng, st: Statement, transcripts, secrets, real, inst, common, entropy=None, threads: int = 0):
+    """or_prove plus the commitments the prover appended -> (commitments [N][k][nc][32], challenges [N][k][32], responses [N][k][m][32],
+    status [N]).  Challenges, responses, status and transcripts are or_prove's bytes; the commitments of a proof with status 1 are
+    unspecified."""
+    ts, n, k, inst, com = _or_shapes(st, transcripts, inst, common, "or_prove_batchable")
+    sec = np.ascontiguousarray(secrets, np.uint8)
+    rl = np.ascontiguousarray(real, np.uint8)
+    if sec.size != 32 * n * st.m or rl.shape != (n,):
+        raise ValueError("or_prove_batchable: secrets must be uint8 [N][m][32] and real uint8 [N]")
+    ent = None if entropy is None else np.ascontiguousarray(entropy, np.uint8)
+    if ent is not None and ent.shape != (n, 32):
+        raise ValueError("or_prove_batchable: entropy must be uint8 [N][32] (or None)")
+    coms, chal = np.zeros((n, k, st.nc, 32), np.uint8), np.zeros((n, k, 32), np.uint8)
+    resp, status = np.zeros((n, k, st.m, 32), np.uint8), np.zeros(n, np.uint8)
+    rc = lib().zkp_or_prove_batchable_batch(None if eng is None else eng._h, st._h, k, n, _p(ts), _p(sec), _p(rl), _p(inst), _p(com), _p(ent), threads, _p(coms),
+                                            _p(chal), _p(resp), _p(status))
+    _raise(rc, "zkp_or_prove_batchable_batch")
+    return coms, chal, resp, status
+
+
+def _or_batchable_shapes(st, transcripts, inst, common, commitments, challenges, responses, weights16, what: str):
+    ts, n, k, inst, com = _or_shapes(st, transcripts, inst, common, what)
+    coms = np.ascontiguousarray(commitments, np.uint8)
+    chal = np.ascontiguousarray(challenges, np.uint8)
+    resp = np.ascontiguousarray(responses, np.uint8)
+    if coms.shape != (n, k, st.nc, 32) or chal.shape != (n, k, 32) or resp.size != 32 * n * k * st.m:
+        raise ValueError("%s: commitments must be uint8 [N][k][nc][32], challenges [N][k][32] and responses [N][k][m][32]" % what)
+    w = None if weights16 is None else np.ascontiguousarray(weights16, np.uint8)
+    if w is not None and w.shape != (n, k, st.nc, 16):
+        raise ValueError("%s: weights16 must be uint8 [N][k][nc][16] (or None)" % what)
+    return ts, n, k, inst, com, coms, chal, resp, w
+
+
+def or_verify_batchable(eng, st: Statement, transcripts, inst, common, commitments, challenges, responses, threads: int = 0) -> np.ndarray:
+    """The exact per-proof verifier of or_prove_batchable's proofs -> results uint8 [N]: 0 = accepted, 1 = rejected.  transcripts advance
+    in place (an accepted proof's ends where the prover's ended)."""
+    ts, n, k, inst, com, coms, chal, resp, _ = _or_batchable_shapes(st, transcripts, inst, common, commitments, challenges, responses, None,
+                                                                    "or_verify_batchable")
+    res = np.ones(n, np.uint8)
+    rc = lib().zkp_or_verify_batchable_batch(None if eng is None else eng._h, st._h, k, n, _p(ts), _p(inst), _p(com), _p(coms), _p(chal), _p(resp), threads,
+                                             _p(res))
+    _raise(rc, "zkp_or_verify_batchable_batch")
+    return res
+
+
+def or_batch_verify(eng, st: Statement, transcripts, inst, common, commitments, challenges, responses, weights16=None, threads: int = 0) -> bool:
+    """One verdict for N batchable proofs: True = every proof verifies.  One multiscalar sum of ns + N k (ni + nc) operands under the
+    weights r_jbc (weights16 uint8 [N][k][nc][16], None: drawn from the operating system); a wrong proof passes with probability 2^-128.
+    eng = None, or fewer than get_or_batch_min_batch() proofs, runs the host backend: the same verdict."""
+    ts, n, k, inst, com, coms, chal, resp, w = _or_batchable_shapes(st, transcripts, inst, common, commitments, challenges, responses, weights16,
+                                                                    "or_batch_verify")
+    rc = lib().zkp_or_batch_verify_batch(None if eng is None else eng._h, st._h, k, n, _p(ts), _p(inst), _p(com), _p(coms), _p(chal), _p(resp), _p(w), threads)
+    if rc not in (0, 1):
+        _raise(rc, "zkp_or_batch_verify_batch")
+    return rc == 0
+
+
+def or_batch_verify_locate(eng, st: Statement, transcripts, inst, common, commitments, challenges, responses, weights16=None, threads: int = 0):
+    """The batch check and, only if it fails, which proofs fail -> (ok, results [N]): ok = the batch verified (results then all 0);
+    otherwise results[j] = 1 for the proofs or_verify_batchable rejects.  Never read success from results alone."""
+    ts, n, k, inst, com, coms, chal, resp, w = _or_batchable_shapes(st, transcripts, inst, common, commitments, challenges, responses, weights16,
+                                                                    "or_batch_verify_locate")
+    res = np.ones(n, np.uint8)
+    rc = lib().zkp_or_batch_verify_locate(None if eng is None else eng._h, st._h, k, n, _p(ts), _p(inst), _p(com), _p(coms), _p(chal), _p(resp), _p(w), threads,
+                                          _p(res))
+    if rc not in (0, 1):
+        _raise(rc, "zkp_or_batch_verify_locate")
+    return rc == 0, res
+
+
+def or_batch_verify_coeffs(eng, st: Statement, transcripts, inst, common, commitments, challenges, responses, weights16, threads: int = 0):
+    """or_batch_verify that also returns the coefficient vector -> (ok, coeffs [ns + N k (ni + nc)][32]) over the operands
+    [common | inst[b][v][j] | commitments [N][k][nc]]"""
+    ts, n, k, inst, com, coms, chal, resp, w = _or_batchable_shapes(st, transcripts, inst, common, commitments, challenges, responses, weights16,
+                                                                    "or_batch_verify_coeffs")
+    co = np.zeros((st.ns + n * k * (st.ni + st.nc), 32), np.uint8)
+    rc = lib().zkp_or_batch_verify_coeffs(None if eng is None else eng._h, st._h, k, n, _p(ts), _p(inst), _p(com), _p(coms), _p(chal), _p(resp), _p(w), threads,
+                                          _p(co))
+    if rc not in (0, 1):
+        _raise(rc, "zkp_or_batch_verify_coeffs")
+    return rc == 0, co
+
+
+def set_or_batch_min_batch(n: int) -> None:
+    """or_batch_verify (and _locate's and _coeffs' batch check) on an engine with at least n proofs runs on the device (0: always;
+    2**32 - 1: never)"""
+    lib().zkp_toolbox_set_or_batch_min_batch(n)
+
+
+def get_or_batch_min_batch() -> int:
+    return int(lib().zkp_toolbox_get_or_batch_min_batch())
 
 
 def hash_from_bytes_sha512(eng, messages, threads: int = 0) -> np.ndarray:
